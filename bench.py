@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — headline benchmark of the genlm-backend hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload NAME]
+    python bench.py --gpus N --steps K --warmup W [--workload NAME] [--full] [--dump-outputs DIR]
 
 One process per GPU.  `python bench.py --gpus N` with N > 1 starts the N ranks itself: the parent process (which
 never touches the GPU) runs `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1
@@ -32,11 +32,16 @@ A step is one pass of the hot path over one batch of synthetic input that is alr
   plumbing      CPU / gloo self-test of the multi-rank launch, barrier, all-gather and JSON relay (tests only; no
                 kernel is run and the line says so).
 
-Rank 0 prints ONE JSON line.  `value` = particles per second over all GPUs (weak scaling).  `roofline` prices the
-fused step: algorithmic bytes per call over the mean duration of its launch (fused_step_kernel), measured
-inside the timed region with HIP events the launch carries as its own start / stop stamps, and - reported beside it -
-with events recorded around the call.  `cpu_baseline` times the
-reference-semantics CPU port (oracle/, test infrastructure) of the same work on a bounded sample on this host.
+Rank 0 prints ONE JSON line.  `value` = particles per second over all GPUs (weak scaling), `ms_per_step` = the
+milliseconds of one of the K timed steps.  `roofline` prices the fused step: algorithmic bytes per call
+over the mean duration of its launch (fused_step_kernel), measured inside the timed region with HIP events the launch
+carries as its own start / stop stamps, and - reported beside it - with events recorded around the call.
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds what takes work of its own:
+`cpu_baseline` times the reference-semantics CPU port (oracle/, test infrastructure) of the same work on a bounded
+sample on this host, and the default sis workload times its loop twice more (value_kv: KV rows shared by equal contexts;
+value_library_gemms: the GEMM library's default solutions).  `--dump-outputs DIR` writes what the last timed step
+computed (DIR/<name>.npy); the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -234,8 +239,16 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--workload", default="sis", choices=WORKLOADS)
-    ap.add_argument("--cpu-sample", type=int, default=1024, help="rows of the CPU baseline sample (upper bound)")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements beyond the headline figure: the CPU baseline, and for the default sis workload "
+                         "the shared-KV-rows line (value_kv) and the library-GEMM line (value_library_gemms). Without it a run "
+                         "sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy "
+                         "(float32 / float64; integers as float64; at most 64 MB in all, larger outputs as a fixed seeded sample "
+                         "of rows with their indices in <name>_rows.npy); rank 0's outputs")
+    ap.add_argument("--cpu-sample", type=int, default=1024, help="rows of the CPU baseline sample (upper bound; --full)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: leave the CPU baseline out")
     ap.add_argument("--step-times", action="store_true", help="diagnostic: print the longest host-side steps of the timed region to stderr")
     ap.add_argument("--particle-kv", action="store_true",
                     help="sis workloads with device-resident per-particle KV (beyond the reference: one token per particle per step)")
@@ -283,7 +296,7 @@ def main():
     ap.add_argument("--rehearse-one-gpu", action="store_true",
                     help="--gpus N on a box with ONE GPU: every rank computes on cuda:0 and the exchange goes over gloo through "
                          "host memory (RCCL wants a GPU per rank) - a rehearsal of the multi-rank code, not a measurement")
-    ap.add_argument("--no-kv-line", action="store_true", help="default sis workload: do not also time the shared-KV-rows variant (value_kv)")
+    ap.add_argument("--no-kv-line", action="store_true", help="--full, default sis workload: do not also time the shared-KV-rows variant (value_kv)")
     ap.add_argument("--no-rccl-single", action="store_true",
                     help="N = 1 sis workloads: do NOT route the per-step exchange through a one-rank RCCL group")
     ap.add_argument("--gemms", choices=["recorded", "library", "tune"], default="recorded",
@@ -435,6 +448,8 @@ def main():
         return dt
 
     dt = timed_run(runner)
+    if args.dump_outputs and rank == 0:  # (before --full's further runs: what the headline's last timed step computed)
+        dump_outputs(runner, args.dump_outputs)
     # what a scaling curve needs to explain itself: the collectives' share of a step on rank 0 (RCCL: device
     # time between two stream events around every call, waiting for the slowest rank included; the gloo rehearsal: host time
     # of the synchronous calls), the particles that changed ranks, every rank's own step time
@@ -453,11 +468,12 @@ def main():
             coll_info["rank_ms_per_step"] = {"min": min(runner.rank_ms), "max": max(runner.rank_ms),
                                              "mean": float(np.mean(runner.rank_ms)), "ranks": runner.rank_ms}
         clock.on = False
-    # The default line also carries the same loop with KV rows shared by equal contexts (`--particle-kv`: one new token
-    # per distinct context per step instead of the reference's re-encoding; tokens proven equal to the reference's by
-    # tests/test_host_gpu.py) as value_kv / ms_per_step_kv.  `value` itself stays BASELINE config 2's algorithm.
+    # With --full the default line also carries the same loop with KV rows shared by equal contexts (`--particle-kv`: one
+    # new token per distinct context per step instead of the reference's re-encoding; tokens proven equal to the reference's
+    # by tests/test_host_gpu.py) as value_kv / ms_per_step_kv.  `value` itself stays BASELINE config 2's algorithm.
     kv_extra = None
-    if (workload == "sis" and not (args.particle_kv or args.prefix_kv or args.per_row_masks or args.resample or args.rng != "philox")
+    if (args.full and workload == "sis"
+            and not (args.particle_kv or args.prefix_kv or args.per_row_masks or args.resample or args.rng != "philox")
             and not args.no_kv_line):
         from genlm_backend_amd.sis import SisBenchWorkload
 
@@ -475,7 +491,7 @@ def main():
         del runner_kv
 
     # ... and `value` once more with the GEMM library's own choice of kernels (what AsyncAmdLM runs unless asked for the
-    # recorded solutions): the default line carries both, so that neither hides behind the other
+    # recorded solutions): the default line with --full carries both, so that neither hides behind the other
     lib_extra = None
     if workload == "sis" and kv_extra is not None and args.gemm_shapes:
         kern_first = runner.kernel_times_us()
@@ -507,7 +523,7 @@ def main():
             out["config"]["gemms"] = {
                 "recorded": f"AsyncAmdLM(gemms=\"recorded\") = load_model_by_name(name, llm_opts={{\"gemms\": \"recorded\"}}): PyTorch "
                             f"TunableOp, {args.gemm_shapes} shapes of genlm-backend_amd/tuned/<arch>.csv run by their recorded "
-                            "rocBLAS / hipBLASLt solution, the rest by the library's default; value_library_gemms = the same loop with "
+                            "rocBLAS / hipBLASLt solution, the rest by the library's default; value_library_gemms (--full) = the same loop with "
                             "the backend's default option (gemms=\"library\")" if args.gemm_shapes else
                             "the library's default solutions (no recorded file for this build of the libraries)",
                 "library": "the library's default solutions",
@@ -568,11 +584,56 @@ def main():
                 "frac_outer_events": (runner.kernel_bytes / (np.mean(outer) * 1e-6) / 1e9 / HBM_PEAK_GBS) if len(outer) else None,
                 "launches_timed": len(kern_us),
             }
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             out["cpu_baseline"] = cpu_baseline(workload, args.cpu_sample)
         print(json.dumps(out), file=_LINE_OUT, flush=True)
     if dist is not None:
         dist.destroy_process_group()
+
+
+DUMP_CAP_BYTES = 64_000_000  # 64 MB
+
+
+def step_outputs(runner):
+    """What a caller of the timed path holds after its last step, by name (device tensors or arrays)."""
+    if hasattr(runner, "outputs"):
+        return runner.outputs()
+    s = runner.sis  # genlm_backend_amd.sis.SisBenchWorkload: the device-resident population after the step
+    return {"log_weights": s.log_weights, "contexts": s.contexts, "lengths": s.lengths, "active": s.active}
+
+
+def dump_outputs(runner, out_dir):
+    """--dump-outputs: every output as <out_dir>/<name>.npy, float32 (floats) or float64 (integers, exact), within
+    DUMP_CAP_BYTES; an output too large for what is left is cut to a fixed seeded sample of its rows, whose indices go to
+    <name>_rows.npy."""
+    outs = step_outputs(runner)
+    torch.cuda.synchronize()
+    fsize = {k: v.numel() * (4 if v.is_floating_point() else 8) if torch.is_tensor(v) else np.asarray(v).size * 8
+             for k, v in outs.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    left = DUMP_CAP_BYTES
+    order = sorted(outs, key=lambda n: fsize[n])  # smallest first: only the largest ones are sampled
+    for i, k in enumerate(order):
+        v, rows = outs[k], None
+        share = left // (len(order) - i)
+        n = v.shape[0] if v.ndim >= 2 else 0
+        if fsize[k] > share and n > 1:
+            per_row = fsize[k] // n + 8
+            rows = np.sort(np.random.default_rng(0).choice(n, max(1, min(n, share // per_row)), replace=False))
+        if torch.is_tensor(v):
+            if rows is not None:
+                v = v[torch.from_numpy(rows).to(v.device)]
+            v = v.detach().float().cpu().numpy() if v.is_floating_point() else v.detach().cpu().numpy().astype(np.float64)
+        else:
+            v = np.asarray(v)
+            v = v[rows] if rows is not None else v
+            v = v.astype(np.float32 if v.dtype.kind == "f" and v.dtype.itemsize <= 4 else np.float64)
+        np.save(os.path.join(out_dir, f"{k}.npy"), v)
+        left -= v.nbytes
+        if rows is not None:
+            np.save(os.path.join(out_dir, f"{k}_rows.npy"), rows.astype(np.float64))
+            left -= rows.size * 8
+    print(f"outputs of the last timed step: {', '.join(sorted(outs))} -> {out_dir}", file=sys.stderr)
 
 
 def pmc_traffic(workload):
@@ -622,6 +683,9 @@ def plumbing(args, rank, world, dist):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
         assert gathered.view(world, 8)[:, 0].tolist() == [float(r) for r in range(world)]
+    if rank == 0 and args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "gathered.npy"), (gathered if dist is not None else lw).numpy().astype(np.float32))
     if rank == 0:
         print(json.dumps({"metric": "plumbing self-test (no kernel run; NOT a benchmark result)", "value": 8 * world * args.steps / dt,
                           "unit": "fake particles/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -695,11 +759,14 @@ class TrieWorkload:
         if timed:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-            self.trie.masses_from_logits(x, lse, **kw)
+            self.last = self.trie.masses_from_logits(x, lse, **kw)
             e1.record()
             self.outer.append((e0, e1))
         else:
-            self.trie.masses_from_logits(x, lse, **kw)
+            self.last = self.trie.masses_from_logits(x, lse, **kw)
+
+    def outputs(self):
+        return {"masses": self.last}
 
     def kernel_times_us(self):
         return np.array([a.elapsed_time(b) * 1e3 for a, b in self.outer])
@@ -840,6 +907,9 @@ class KernelWorkload:
             _gather_all(self.dist, self.gathered, self.lw)
             self.eng.normalize_weights(self.gathered)
 
+    def outputs(self):
+        return {"logZ": self.out[0], "lse": self.out[1], "tokens": self.out[2], "log_weights": self.lw}
+
     def kernel_times_us(self):
         if self.parity or self.n_changed:  # the span that holds the noise generation / the masks' update too
             return self.outer_times_us()
@@ -979,6 +1049,7 @@ class ApiWorkload:
             self.llm.clear_cache()
             rows = self.loop.run_until_complete(self.llm.batch_next_token_logprobs(self.ctx_pool))
             assert rows.shape == (self.N, self.V)
+            self.last_rows = rows
             return
         if self.t >= self.max_tokens:
             self._reset()
@@ -1013,6 +1084,20 @@ class ApiWorkload:
             lw = self.d_lw if self.device_batch else \
                 torch.tensor([p.log_weight for p in self.particles], dtype=torch.float32, device=self.dev)
             _gather_all(self.dist, self.gathered, lw)
+
+    def outputs(self):
+        if self.logprobs:
+            return {"logprobs": self.last_rows}
+        if self.device_batch:
+            return {"log_weights": self.d_lw, "contexts": self.d_ctx, "lengths": self.d_len, "active": self.d_act}
+        P = len(self.prompt)
+        ctx = np.full((self.N, P + self.max_tokens + 1), -1, np.int64)
+        for i, p in enumerate(self.particles):
+            c = self.prompt + [int(t) for t in p.context]
+            ctx[i, :len(c)] = c
+        return {"log_weights": np.array([float(p.log_weight) for p in self.particles], np.float64), "contexts": ctx,
+                "lengths": np.array([P + len(p.context) for p in self.particles], np.int64),
+                "active": np.array([int(p.active) for p in self.particles], np.int64)}
 
     def kernel_times_us(self):
         return None

@@ -9,10 +9,10 @@ export TMPDIR=/tmp
 O=$R/gpurun_out/prof
 rm -rf $O && mkdir -p $O
 for w in kernel kernel-llama; do
-  python3 $R/bench.py --workload $w --steps 200 --warmup 10 > $O/bench_$w.json 2> $O/bench_$w.err
+  python3 $R/bench.py --workload $w --steps 200 --warmup 10 --full > $O/bench_$w.json 2> $O/bench_$w.err
 done
-python3 $R/bench.py --workload sis --steps 50 --warmup 10 > $O/bench_sis.json 2> $O/bench_sis.err
-python3 $R/bench.py --workload sis-llama --steps 30 --warmup 5 > $O/bench_sis-llama.json 2> $O/bench_sis-llama.err
+python3 $R/bench.py --workload sis --steps 50 --warmup 10 --full > $O/bench_sis.json 2> $O/bench_sis.err
+python3 $R/bench.py --workload sis-llama --steps 30 --warmup 5 --full > $O/bench_sis-llama.json 2> $O/bench_sis-llama.err
 for w in "api" "api-coro" "api-logprobs"; do
   python3 $R/bench.py --workload $w --steps 20 --warmup 3 --no-cpu > $O/bench_$w.json 2> $O/bench_$w.err
 done
@@ -27,9 +27,9 @@ for w in kernel kernel-llama; do
   rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch_$w -o f -- python3 $R/bench.py --workload $w --steps 20 --warmup 2 --no-cpu > $O/pmc_f_$w.log 2>&1
   rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write_$w -o w -- python3 $R/bench.py --workload $w --steps 20 --warmup 2 --no-cpu > $O/pmc_w_$w.log 2>&1
 done
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/kstats_sis -o s -- python3 $R/bench.py --workload sis --steps 30 --warmup 3 --no-cpu > $O/kstats_sis.log 2>&1
-rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch_sis -o f -- python3 $R/bench.py --workload sis --steps 20 --warmup 0 --no-cpu > $O/pmc_f_sis.log 2>&1
-rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write_sis -o w -- python3 $R/bench.py --workload sis --steps 20 --warmup 0 --no-cpu > $O/pmc_w_sis.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/kstats_sis -o s -- python3 $R/bench.py --workload sis --steps 30 --warmup 3 --no-cpu --full > $O/kstats_sis.log 2>&1
+rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch_sis -o f -- python3 $R/bench.py --workload sis --steps 20 --warmup 0 --no-cpu --full > $O/pmc_f_sis.log 2>&1
+rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write_sis -o w -- python3 $R/bench.py --workload sis --steps 20 --warmup 0 --no-cpu --full > $O/pmc_w_sis.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kstats_sis-llama -o s -- python3 $R/bench.py --workload sis-llama --steps 20 --warmup 3 --no-cpu > $O/kstats_sis-llama.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kstats_lsm -o l -- python3 $R/tools/kbench_lsm.py > $O/kstats_lsm.log 2>&1
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch_lsm -o f -- python3 $R/tools/kbench_lsm.py > $O/pmc_f_lsm.log 2>&1
@@ -58,7 +58,7 @@ done
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch_trie -o f -- python3 $R/tools/tbench.py > $O/pmc_f_trie.log 2>&1
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write_trie -o w -- python3 $R/tools/tbench.py > $O/pmc_w_trie.log 2>&1
 for o in rows slots selected; do
-  python3 $R/bench.py --workload trie --trie-out $o --steps 50 --warmup 5 $([ $o = rows ] || echo --no-cpu) > $O/bench_trie_$o.json 2>> $O/bench_trie.err
+  python3 $R/bench.py --workload trie --trie-out $o --steps 50 --warmup 5 --full $([ $o = rows ] || echo --no-cpu) > $O/bench_trie_$o.json 2>> $O/bench_trie.err
 done
 python3 $R/tools/gbench.py > $O/gbench.log 2>&1
 # ---- round 5: per-step tables of the default lines (GEMM us / TFLOP/s / % of step) from the traces made above

@@ -10,7 +10,7 @@ export TMPDIR=/tmp
 O=$R/gpurun_out/prof2
 rm -rf $O && mkdir -p $O
 b() { n=$1; shift; timeout -k 10 400 python3 $R/bench.py "$@" > $O/bench_$n.json 2> $O/bench_$n.err; echo "$n rc=$?"; }
-b kernel_parity --workload kernel --rng parity --steps 100 --warmup 5
+b kernel_parity --workload kernel --rng parity --steps 100 --warmup 5 --full
 b kernel-llama_parity --workload kernel-llama --rng parity --steps 100 --warmup 5 --no-cpu
 b sis_parity --workload sis --rng parity --steps 30 --warmup 5 --no-cpu
 b sis_particlekv_parity --workload sis --particle-kv --rng parity --steps 30 --warmup 5 --no-cpu

@@ -7,7 +7,7 @@ R="${GRAFT_REPO_ROOT:-/root/repo}"
 cd $R
 F=$R/gpurun_out/tuned_gfx950.csv
 [ -f $R/genlm-backend_amd/tuned/gfx950.csv ] && [ ! -f $F ] && cp $R/genlm-backend_amd/tuned/gfx950.csv $F
-run() { echo "== $*"; timeout -k 10 900 python bench.py "$@" --gemms tune --gemms-file $F --no-cpu 2>/dev/null | cut -c1-160; grep -c Gemm $F; }
+run() { echo "== $*"; timeout -k 10 900 python bench.py "$@" --gemms tune --gemms-file $F --no-cpu --full 2>/dev/null | cut -c1-160; grep -c Gemm $F; }
 case "${1:-1}" in
 1)
   run
