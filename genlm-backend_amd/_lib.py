@@ -15,6 +15,7 @@ F32, BF16, F16 = 0, 1, 2
 MASK_NONE, MASK_BITS, MASK_F32, MASK_PREPARED = 0, 1, 2, 3
 RNG_NONE, RNG_PHILOX, RNG_NOISE = 0, 1, 2
 STEP_HW_EXP = 1  # glb_step_args.flags: the hardware-exponential contract of 16-bit rows
+GEMM_BIAS, GEMM_BIAS_GELU_TANH = 0, 1  # glb_gemm_args.epilogue
 
 
 class GlbError(RuntimeError):
@@ -167,6 +168,18 @@ class MtRowsArgs(C.Structure):
     ]
 
 
+class GemmArgs(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("m", C.c_int64), ("n", C.c_int64), ("k", C.c_int64),
+        ("a", C.c_void_p), ("lda", C.c_int64),
+        ("w_split", C.c_void_p),
+        ("bias", C.c_void_p),
+        ("c", C.c_void_p), ("ldc", C.c_int64),
+        ("epilogue", C.c_int32),
+    ]
+
+
 # every symbol include/glb.h declares: name -> (restype, argtypes)
 _vp, _i32, _i64, _f32, _sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_size_t
 SYMBOLS = {
@@ -226,6 +239,9 @@ SYMBOLS = {
     "glb_comm_init": (C.c_int, [_vp, _i32, _i32, C.POINTER(C.c_void_p)]),
     "glb_allgather_f32": (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
     "glb_comm_destroy": (C.c_int, [_vp]),
+    "glb_gemm_split_bytes": (_sz, [_i64, _i64]),
+    "glb_gemm_split_weights": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _sz, _vp]),
+    "glb_gemm_f32_split": (C.c_int, [C.POINTER(GemmArgs), _vp]),
     "glb_philox4x32_10": (None, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
 }
 

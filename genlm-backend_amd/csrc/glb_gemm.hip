@@ -1,0 +1,277 @@
+// glb_gemm.hip - fp32 projection GEMM on bf16 MFMA (include/glb.h: glb_gemm_split_bytes, glb_gemm_split_weights,
+// glb_gemm_f32_split): C[M, N] = A[M, K] . W[K, N] + bias, optionally followed by the tanh GELU, for GPT-2's Conv1D
+// projections (hf modeling_gpt2.py: `addmm(bias, x, weight)`).
+//
+// Numerics ("split bf16"): every fp32 operand element is written as x = hi + mid + lo, three bf16 values made by
+// round-to-nearest-even (v_cvt_pk_bf16_f32), each residual an exact fp32 subtraction; the sum is exact for every finite x
+// whose parts stay normal.  a.b is then the sum of nine exact bf16 products; the three smallest (mid.lo, lo.mid, lo.lo) are
+// below 2^-24 |a||b| together and are dropped.  The other six of one 32-deep K step go into ONE fresh fp32 accumulator,
+// smallest first:
+//   mid.mid, lo.hi, hi.lo, mid.hi, hi.mid, hi.hi
+// and that partial is added to the running sum by a round-to-nearest v_add_f32.  (Chaining every K step through the MFMA's
+// own accumulator instead measured 1.6-2.6x torch.addmm's fp32 error on random data: the MFMA's additions into a large
+// running sum cost more than 24 rounded adds.)  The result is fp32-accurate - tests/test_split_gemm_cpu.py bounds the
+// truncation against float64, tests/test_split_gemm_gpu.py the whole GEMM against torch.addmm - at 6/16 of the MFMA
+// cycles of the fp32-input MFMA.
+//
+// Layout.  W is split once per weight (glb_gemm_split_weights) into a packed image of 1 KiB pieces, one per
+// (16 columns, 32 rows of K, plane): piece ((nb * K/32 + kb) * 3 + p) holds, at byte 16 * l, the eight plane-p values
+// W[kb*32 + 8(l>>4) + j][nb*16 + (l&15)], j = 0..7 - exactly the B operand of lane l of v_mfma_f32_16x16x32_bf16, so a
+// piece is staged with one contiguous 1 KiB global_load_lds per wave and read back with one lane-linear ds_read_b128.
+// A stays fp32: its 128 x 32 tile is staged in 16 pieces of 1 KiB, piece (mf, h) holding at byte 16 * l the four values
+// A[mf*16 + (l&15)][8(l>>4) + 4h .. +3] - lane l's A operand is pieces (mf, 0) and (mf, 1) - and split in registers.
+//
+// Tiling: 128 x 128 output tile per 256-thread block, K step 32, two LDS stages (80 KiB: two blocks per CU); wave w owns
+// rows 32w .. 32w+31 and all 128 columns (2 x 8 fragments of 16 x 16): each A element is split by one wave only.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "../../include/glb.h"
+#include "glb_common.hpp"
+
+namespace {
+
+typedef __attribute__((ext_vector_type(2))) float f32x2;
+typedef __attribute__((ext_vector_type(4))) float f32x4;
+typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
+typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
+typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
+
+constexpr int BM = 128, BN = 128, BK = 32, THREADS = 256;
+constexpr int PIECE = 1024;                          // bytes of one staged piece (64 lanes x 16 B)
+constexpr int A_PIECES = (BM / 16) * 2;              // 16
+constexpr int B_PIECES = (BN / 16) * 3;              // 24
+constexpr int STAGE_BYTES = (A_PIECES + B_PIECES) * PIECE;  // 40 KiB
+constexpr int LDS_BYTES = 2 * STAGE_BYTES;                 // 80 KiB
+
+// round-to-nearest-even split of two fp32 values into packed bf16 pairs hi / mid / lo (hi + mid + lo == x)
+__device__ __forceinline__ void split2(f32x2 x, uint32_t &h, uint32_t &m, uint32_t &l) {
+  h = __builtin_bit_cast(uint32_t, __builtin_convertvector(x, bf16x2));
+  const f32x2 hf = {__builtin_bit_cast(float, h << 16), __builtin_bit_cast(float, h & 0xffff0000u)};
+  const f32x2 r1 = x - hf;
+  m = __builtin_bit_cast(uint32_t, __builtin_convertvector(r1, bf16x2));
+  const f32x2 mf = {__builtin_bit_cast(float, m << 16), __builtin_bit_cast(float, m & 0xffff0000u)};
+  const f32x2 r2 = r1 - mf;
+  l = __builtin_bit_cast(uint32_t, __builtin_convertvector(r2, bf16x2));
+}
+
+__device__ __forceinline__ void split8(f32x4 x0, f32x4 x1, bf16x8 &h, bf16x8 &m, bf16x8 &l) {
+  uint32_t h0, h1, h2, h3, m0, m1, m2, m3, l0, l1, l2, l3;
+  split2(f32x2{x0[0], x0[1]}, h0, m0, l0);
+  split2(f32x2{x0[2], x0[3]}, h1, m1, l1);
+  split2(f32x2{x1[0], x1[1]}, h2, m2, l2);
+  split2(f32x2{x1[2], x1[3]}, h3, m3, l3);
+  const u32x4 H = {h0, h1, h2, h3}, M = {m0, m1, m2, m3}, L = {l0, l1, l2, l3};
+  h = __builtin_bit_cast(bf16x8, H);
+  m = __builtin_bit_cast(bf16x8, M);
+  l = __builtin_bit_cast(bf16x8, L);
+}
+
+__device__ __forceinline__ float gelu_tanh(float x) {
+  const float kBeta = 0.7978845608028654f;  // sqrt(2 / pi)
+  const float kKappa = 0.044715f;
+  const float inner = kBeta * (x + kKappa * x * x * x);
+  return 0.5f * x * (1.0f + tanhf(inner));
+}
+
+// One thread per (16-column block, 32-row K block, lane): reads lane l's eight values of W, writes their three planes.
+__global__ __launch_bounds__(256) void split_weights_kernel(const float *__restrict__ w, int64_t k, int64_t n, int64_t ldw,
+                                                            u32x4 *__restrict__ out) {
+  const int64_t kb_count = k / BK;
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (n / 16) * kb_count * 64) return;
+  const int l = (int)(t & 63);
+  const int64_t blk = t >> 6, kb = blk % kb_count, nb = blk / kb_count;
+  const int64_t col = nb * 16 + (l & 15), row = kb * BK + 8 * (l >> 4);
+  f32x4 x0, x1;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    x0[j] = w[(row + j) * ldw + col];
+    x1[j] = w[(row + 4 + j) * ldw + col];
+  }
+  bf16x8 h, m, lo;
+  split8(x0, x1, h, m, lo);
+  u32x4 *dst = out + blk * 3 * 64 + l;
+  dst[0] = __builtin_bit_cast(u32x4, h);
+  dst[64] = __builtin_bit_cast(u32x4, m);
+  dst[128] = __builtin_bit_cast(u32x4, lo);
+}
+
+// 16-byte LDS-DMA of lane l's source to byte 16 * l of the piece at `lds` (wave-uniform)
+__device__ __forceinline__ void glds16(const void *src, char *lds) {
+  __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void *)lds, 16, 0, 0);
+}
+
+template <bool GELU>
+__global__ __launch_bounds__(THREADS, 2) void gemm_split_kernel(const float *__restrict__ a, int64_t lda,
+                                                                const char *__restrict__ wsplit, const float *__restrict__ bias,
+                                                                float *__restrict__ c, int64_t ldc, int m, int n, int k) {
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int ntn = n / BN, ntm = (m + BM - 1) / BM;
+  // bijective XCD remap: blocks that share blockIdx.x % 8 run on one XCD; give each such group a contiguous run of tiles
+  const int nwg = ntm * ntn, orig = blockIdx.x, xcd = orig & 7, q = nwg >> 3, r = nwg & 7;
+  const int wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
+  const int tm = wgid / ntn, tn = wgid % ntn;
+  const int m0 = tm * BM, n0 = tn * BN;
+  const int kt_count = k / BK;
+
+  // staging sources (per lane, advanced by one K step each iteration)
+  // A pieces of this wave: p = 4 * wave + i -> (mf = p >> 1, h = p & 1)
+  const float *a_src[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int p = 4 * wave + i, mf = p >> 1, h = p & 1;
+    int row = m0 + mf * 16 + (lane & 15);
+    row = row < m ? row : m - 1;  // rows past M read the last row; their results are never stored
+    a_src[i] = a + (int64_t)row * lda + 8 * (lane >> 4) + 4 * h;
+  }
+  // B pieces of this wave: p = 6 * wave + i -> (nf = p / 3, plane = p % 3); LDS image: plane-major (plane * 8 + nf)
+  const char *b_src[6];
+  int b_dst[6];
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+    const int p = 6 * wave + i, nf = p / 3, pl = p % 3;
+    const int64_t nb = n0 / 16 + nf;
+    b_src[i] = wsplit + ((nb * kt_count) * 3 + pl) * PIECE + lane * 16;
+    b_dst[i] = (A_PIECES + pl * 8 + nf) * PIECE;
+  }
+  const int64_t b_step = 3 * PIECE;  // one K step further in the packed image
+
+  auto stage = [&](int buf, int kt) {
+    char *base = lds + buf * STAGE_BYTES;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) glds16(a_src[i] + kt * BK, base + (4 * wave + i) * PIECE);
+#pragma unroll
+    for (int i = 0; i < 6; ++i) glds16(b_src[i] + kt * b_step, base + b_dst[i]);
+  };
+
+  f32x4 acc[2][8];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  float bcol[8];  // (loaded ahead: the loop's waits retire it)
+#pragma unroll
+  for (int nf = 0; nf < 8; ++nf) bcol[nf] = bias ? bias[n0 + nf * 16 + (lane & 15)] : 0.0f;
+
+  stage(0, 0);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+
+  for (int kt = 0; kt < kt_count; ++kt) {
+    const int cur = kt & 1;
+    if (kt + 1 < kt_count) stage(cur ^ 1, kt + 1);
+    const char *base = lds + cur * STAGE_BYTES;
+    bf16x8 ah[2], am[2], al[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int mf = 2 * wave + i;
+      const f32x4 x0 = *(const f32x4 *)(base + (2 * mf) * PIECE + lane * 16);
+      const f32x4 x1 = *(const f32x4 *)(base + (2 * mf + 1) * PIECE + lane * 16);
+      split8(x0, x1, ah[i], am[i], al[i]);
+    }
+#pragma unroll
+    for (int nf = 0; nf < 8; ++nf) {
+      const bf16x8 bh = *(const bf16x8 *)(base + (A_PIECES + 0 * 8 + nf) * PIECE + lane * 16);
+      const bf16x8 bm = *(const bf16x8 *)(base + (A_PIECES + 1 * 8 + nf) * PIECE + lane * 16);
+      const bf16x8 bl = *(const bf16x8 *)(base + (A_PIECES + 2 * 8 + nf) * PIECE + lane * 16);
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        f32x4 t = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am[i], bm, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+        t = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[i], bh, t, 0, 0, 0);
+        t = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[i], bl, t, 0, 0, 0);
+        t = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am[i], bh, t, 0, 0, 0);
+        t = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[i], bm, t, 0, 0, 0);
+        t = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[i], bh, t, 0, 0, 0);
+        acc[i][nf] += t;  // (round-to-nearest add of this K step's partial: see the header)
+      }
+    }
+    // the next stage has landed for every wave, and every wave is done reading this one (it is restaged next iteration)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+  }
+
+  // epilogue: C/D map of 16x16 MFMA - col = lane & 15, row = 4 * (lane >> 4) + reg
+#pragma unroll
+  for (int nf = 0; nf < 8; ++nf) {
+    const int col = n0 + nf * 16 + (lane & 15);
+    const float b = bcol[nf];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int row0 = m0 + wave * 32 + i * 16 + 4 * (lane >> 4);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int row = row0 + j;
+        if (row < m) {
+          float v = acc[i][nf][j] + b;
+          if (GELU) v = gelu_tanh(v);
+          c[(int64_t)row * ldc + col] = v;
+        }
+      }
+    }
+  }
+}
+
+bool shape_supported(int64_t k, int64_t n) { return k > 0 && n > 0 && n % BN == 0 && k % 64 == 0 && k <= (1 << 20) && n <= (1 << 20); }
+
+std::atomic<uint64_t> g_lds_plain{0}, g_lds_gelu{0};
+
+}  // namespace
+
+extern "C" {
+
+size_t glb_gemm_split_bytes(int64_t k, int64_t n) {
+  return shape_supported(k, n) ? (size_t)k * (size_t)n * 3 * sizeof(uint16_t) : 0;
+}
+
+int glb_gemm_split_weights(const float *w, int64_t k, int64_t n, int64_t ldw, void *out, size_t out_bytes, void *stream) {
+  if (!w || !out) return glb::api_fail(GLB_EINVAL, "null pointer");
+  if (k <= 0 || n <= 0 || ldw < n) return glb::api_fail(GLB_EINVAL, "bad shape (k %lld, n %lld, ldw %lld)", (long long)k,
+                                                          (long long)n, (long long)ldw);
+  if (!shape_supported(k, n)) return glb::api_fail(GLB_EUNSUPPORTED, "split GEMM needs n %% 128 == 0 and k %% 64 == 0");
+  if (out_bytes < glb_gemm_split_bytes(k, n) || ((uintptr_t)out) % 16)
+    return glb::api_fail(GLB_ENOSPC, "split weight buffer too small or not 16-byte aligned");
+  const int64_t threads = (n / 16) * (k / BK) * 64;
+  hipLaunchKernelGGL(split_weights_kernel, dim3(blocks_for(threads, 256)), dim3(256), 0, (hipStream_t)stream, w, k, n, ldw,
+                     (u32x4 *)out);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return glb::api_hip_fail(e, "split_weights launch");
+  return GLB_OK;
+}
+
+int glb_gemm_f32_split(const glb_gemm_args *args, void *stream) {
+  if (!args) return glb::api_fail(GLB_EINVAL, "null argument block");
+  if (args->struct_size != sizeof(glb_gemm_args))
+    return glb::api_fail(GLB_EINVAL, "glb_gemm_args.struct_size %u != %zu (ABI mismatch)", args->struct_size,
+                         sizeof(glb_gemm_args));
+  const glb_gemm_args &g = *args;
+  if (!g.a || !g.w_split || !g.c) return glb::api_fail(GLB_EINVAL, "null pointer");
+  if (g.m <= 0 || g.n <= 0 || g.k <= 0 || g.lda < g.k || g.ldc < g.n)
+    return glb::api_fail(GLB_EINVAL, "bad shape (m %lld, n %lld, k %lld, lda %lld, ldc %lld)", (long long)g.m,
+                         (long long)g.n, (long long)g.k, (long long)g.lda, (long long)g.ldc);
+  if (g.epilogue != GLB_GEMM_BIAS && g.epilogue != GLB_GEMM_BIAS_GELU_TANH)
+    return glb::api_fail(GLB_EINVAL, "bad epilogue %d", g.epilogue);
+  if (!shape_supported(g.k, g.n)) return glb::api_fail(GLB_EUNSUPPORTED, "split GEMM needs n %% 128 == 0 and k %% 64 == 0");
+  if (((uintptr_t)g.a) % 16 || g.lda % 4 || ((uintptr_t)g.w_split) % 16)
+    return glb::api_fail(GLB_EUNSUPPORTED, "split GEMM needs A and its row pitch 16-byte aligned");
+  const int64_t tiles = ((g.m + BM - 1) / BM) * (g.n / BN);
+  if (tiles > INT32_MAX / 2 || g.m > INT32_MAX / 2) return glb::api_fail(GLB_EUNSUPPORTED, "too many rows");
+  const bool gelu = g.epilogue == GLB_GEMM_BIAS_GELU_TANH;
+  const void *kern = gelu ? (const void *)gemm_split_kernel<true> : (const void *)gemm_split_kernel<false>;
+  hipError_t e = glb::allow_dynamic_lds(kern, LDS_BYTES, gelu ? g_lds_gelu : g_lds_plain);
+  if (e != hipSuccess) return glb::api_hip_fail(e, "split GEMM LDS attribute");
+  if (gelu)
+    hipLaunchKernelGGL(gemm_split_kernel<true>, dim3((unsigned)tiles), dim3(THREADS), LDS_BYTES, (hipStream_t)stream, g.a,
+                       g.lda, (const char *)g.w_split, g.bias, g.c, g.ldc, (int)g.m, (int)g.n, (int)g.k);
+  else
+    hipLaunchKernelGGL(gemm_split_kernel<false>, dim3((unsigned)tiles), dim3(THREADS), LDS_BYTES, (hipStream_t)stream, g.a,
+                       g.lda, (const char *)g.w_split, g.bias, g.c, g.ldc, (int)g.m, (int)g.n, (int)g.k);
+  e = hipGetLastError();
+  if (e != hipSuccess) return glb::api_hip_fail(e, "split GEMM launch");
+  return GLB_OK;
+}
+
+}  // extern "C"

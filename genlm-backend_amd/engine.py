@@ -597,6 +597,48 @@ class HipEngine:
         check(self.lib.glb_normalize_weights(_ptr(log_weights), n, _ptr(probs), _ptr(stats), self._stream()))
         return probs, stats
 
+    # ---- fp32 projections on bf16 MFMA (glb_gemm_*: DESIGN.md §12) ------------------------------------------------
+    def gemm_split_supports(self, k, n):
+        return self.lib.glb_gemm_split_bytes(k, n) > 0
+
+    def gemm_split_weights(self, w):
+        """The packed hi / mid / lo bf16 image of a float32 weight w [K, N] (glb_gemm_split_weights: 6 bytes per element),
+        or None when the kernel does not serve its shape."""
+        k, n = w.shape
+        nbytes = self.lib.glb_gemm_split_bytes(k, n)
+        if nbytes == 0 or w.dtype != torch.float32 or w.stride(1) != 1:
+            return None
+        if w.device != self.device:
+            raise ValueError(f"tensor on {w.device}, engine on {self.device}")
+        out =torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        check(self.lib.glb_gemm_split_weights(_ptr(w), k, n, w.stride(0), _ptr(out), nbytes, self._stream()))
+        return out
+
+    def gemm_split(self, x, w_split, n, bias=None, gelu=False, out=None):
+        """x [..., K] float32 (rows of unit inner stride) times the weight whose image is `w_split`, plus bias [N], then the
+        tanh GELU when `gelu` (glb_gemm_f32_split).  Returns [..., N] float32, or None when the kernel does not serve the
+        call (alignment, shape): the caller then runs its library GEMM."""
+        k = x.shape[-1]
+        x2 = x.reshape(-1, k)
+        m = x2.shape[0]
+        if m == 0 or x2.stride(1) != 1:
+            return None
+        if out is None:
+            out = torch.empty((m, n), dtype=torch.float32, device=self.device)
+        a = _lib.GemmArgs()
+        a.struct_size = C.sizeof(_lib.GemmArgs)
+        a.m, a.n, a.k = m, n, k
+        a.a, a.lda = x2.data_ptr(), x2.stride(0)
+        a.w_split = w_split.data_ptr()
+        a.bias = bias.data_ptr() if bias is not None else None
+        a.c, a.ldc = out.data_ptr(), n
+        a.epilogue = _lib.GEMM_BIAS_GELU_TANH if gelu else _lib.GEMM_BIAS
+        rc = self.lib.glb_gemm_f32_split(C.byref(a), self._stream())
+        if rc == _lib.GLB_EUNSUPPORTED:
+            return None
+        check(rc)
+        return out.view(*x.shape[:-1], n)
+
     # ---- device-resident particle state ------------------------------------------------------------------
     def kv_append(self, slab, new_rows, pos, rows=None):
         """slab[rows[i] (or i), h, pos[i], :] = new_rows[i, h, 0, :] (glb_kv_append).  slab [R, H, cap, Dh] contiguous;

@@ -18,9 +18,14 @@ What the shadow swaps (PyTorch ops only - no kernels of this library inside the 
                                                                 rows, rebuilt when the caller's weights change)
   * Llama's gate_proj + up_proj, for few-token forwards       -> one GEMM on a derived [gate; up] weight (a second copy of
                                                                 those two matrices: `merge_mlp=False` keeps the memory)
+  * GPT-2's Conv1D projections (float32)                     -> `SplitConv1D`: this library's split-bf16 MFMA GEMM
+                                                                (glb_gemm_f32_split, on a derived bf16 image of the weight)
+                                                                for the batches where it was measured faster; the MLP's
+                                                                tanh GELU then runs in that GEMM's epilogue
   * the attention interface                                  -> kv.py's "glb" entry (glb_short_attention /
                                                                 glb_slab_attention where they apply, SDPA otherwise)
-Same functions, different rounding (float32 inside the fused ops, one rounding at the end): the reference's goldens hold
+Same functions, different rounding (float32 inside the fused ops, one rounding at the end; the split GEMM is fp32-accurate
+but sums in another order than the library's): the reference's goldens hold
 within 1e-4 with identical tokens (tests/test_host_cpu.py, tests/test_host_gpu.py).
 """
 import copy
@@ -125,6 +130,77 @@ def _llama_mlp_forward(self, x):
     return self.down_proj(self.act_fn(self.gate_proj(x)) * self.up_proj(x))
 
 
+# The split GEMM's dispatch rule: the fewest rows (tokens of a forward) at which it runs, per (N, K) of a Conv1D, from the
+# A/B of profiles/r07/split_gemm_ab.txt (tools/split_gemm_ab.py: native kernel vs torch.addmm in one process, alternating):
+# the first measured row count from which the kernel wins at every larger one.  Shapes not listed, and smaller batches -
+# the one-token KV forwards (M ~ 1024) among them - keep the library GEMM.
+SPLIT_GEMM_MIN_ROWS = {
+    (2304, 768): 1536,  # attn.c_attn: 0.73x the library's time at 1536 rows, 0.62-0.89x above
+    (768, 768): 6144,  # attn.c_proj: 1.08x at 4096, 0.61-0.82x from 6144
+    (3072, 768): 1536,  # mlp.c_fc (with its GELU): 0.85x at 1536, 0.65-0.90x above
+    (768, 3072): 8192,  # mlp.c_proj: 1.03x at 6144 (245 us), 0.74x at 9216 (249 us: the kernel's time is flat between the
+                        # two, the library's rises with M), 0.68-0.90x above
+}
+
+
+def _is_tanh_gelu(act):
+    return isinstance(act, torch.nn.GELU) and act.approximate == "tanh"
+
+
+class SplitConv1D(torch.nn.Module):
+    """GPT-2's Conv1D (`addmm(bias, x, weight)`, weight [K, N]) sharing the original module's parameter table.  A float32
+    forward on the engine's device without autograd, of at least `min_rows` rows, runs glb_gemm_f32_split on a derived
+    image of the weight (hi / mid / lo bf16 planes, 6 bytes per element, rebuilt when the weight is replaced or changed in
+    place: `Tensor._version`, identity, address); everything else runs `torch.addmm` exactly as Conv1D does.  `act`: an
+    activation applied to the result - the tanh GELU goes into the GEMM's epilogue."""
+
+    def __init__(self, src, engine, min_rows):
+        super().__init__()
+        self._parameters = src._parameters
+        self.nf, self.nx = src.nf, src.nx
+        self.min_rows = min_rows
+        self.__dict__["_glb_engine"] = engine  # (not a submodule)
+
+    def _split(self):
+        w = self.weight
+        key = (id(w), w._version, w.data_ptr())
+        ent = self.__dict__.get("_glb_split")
+        if ent is None or ent[0] != key:
+            with torch.no_grad():
+                img = self._glb_engine.gemm_split_weights(w)
+            # (the entry holds the weight: its id cannot be handed to another tensor while it lives)
+            ent = self.__dict__["_glb_split"] = (key, img, w)
+        return ent[1]
+
+    def _native(self, x):
+        w = self.weight
+        return (x.dtype == torch.float32 and w.dtype == torch.float32 and x.is_cuda and x.device == w.device
+                and x.device == self._glb_engine.device and x.shape[:-1].numel() >= self.min_rows
+                and not (torch.is_grad_enabled() and (x.requires_grad or w.requires_grad
+                                                      or (self.bias is not None and self.bias.requires_grad))))
+
+    def forward(self, x, act=None):
+        if self._native(x):
+            img = self._split()
+            if img is not None:
+                gelu = _is_tanh_gelu(act)
+                y = self._glb_engine.gemm_split(x, img, self.nf, self.bias, gelu=gelu)
+                if y is not None:
+                    return y if gelu or act is None else act(y)
+        size_out = x.size()[:-1] + (self.nf,)
+        y = torch.addmm(self.bias, x.view(-1, x.size(-1)), self.weight).view(size_out)
+        return y if act is None else act(y)
+
+    def extra_repr(self):
+        return f"nf={self.nf}, nx={self.nx}, split-bf16 GEMM from {self.min_rows} rows"
+
+
+def _gpt2_mlp_forward(self, hidden_states):
+    """modeling_gpt2.py GPT2MLP.forward with the activation handed to c_fc (SplitConv1D: the tanh GELU in its epilogue)."""
+    h = self.c_fc(hidden_states, act=self.act)
+    return self.dropout(self.c_proj(h))
+
+
 def weights_version(net):
     """A number that changes when a weight the shadow keeps a derived copy of changes (SlabForward drops its hipGraphs then:
     a captured launch would keep reading the stale copy)."""
@@ -134,6 +210,9 @@ def weights_version(net):
         if ent is not None:
             for t in (mod.q_proj.weight, mod.k_proj.weight, mod.v_proj.weight):
                 v += t._version + (id(t) & 0xFFFF)
+        if mod.__dict__.get("_glb_split") is not None:
+            t = mod.weight
+            v += t._version + (id(t) & 0xFFFF)
     return v
 
 
@@ -182,10 +261,13 @@ def _rotary_forward_signed(self, x, position_ids):
     return cos, sin
 
 
-def fuse_shadow(shadow, activations=True, merge_mlp=True):
+def fuse_shadow(shadow, activations=True, merge_mlp=True, split_engine=None):
     """Swap the decomposed activations / norms / rotary embedding of a SHADOW tree (never call this on a caller's model).
-    Returns the names of what was swapped."""
+    split_engine: a HipEngine - GPT-2's float32 Conv1D projections of the shapes in SPLIT_GEMM_MIN_ROWS become
+    SplitConv1D (None: not swapped).  Returns the names of what was swapped."""
     done = []
+    if split_engine is not None:
+        done += _split_conv1d(shadow, split_engine)
     if not activations:
         return done
     for mod in list(shadow.modules()):
@@ -205,4 +287,20 @@ def fuse_shadow(shadow, activations=True, merge_mlp=True):
             elif kind == "LlamaMLP" and merge_mlp:
                 child.forward = types.MethodType(_llama_mlp_forward, child)
                 done.append("gate_up")
+    return done
+
+
+def _split_conv1d(shadow, engine):
+    done = []
+    for mod in list(shadow.modules()):
+        for name, child in list(mod._modules.items()):
+            if type(child).__name__ != "Conv1D" or child.weight.dtype != torch.float32:
+                continue
+            min_rows = SPLIT_GEMM_MIN_ROWS.get((child.nf, child.nx))
+            if min_rows is None or not engine.gemm_split_supports(child.nx, child.nf):
+                continue
+            mod._modules[name] = SplitConv1D(child, engine, min_rows)
+            done.append("split_gemm")
+        if type(mod).__name__ == "GPT2MLP" and isinstance(mod._modules.get("c_fc"), SplitConv1D):
+            mod.forward = types.MethodType(_gpt2_mlp_forward, mod)
     return done

@@ -289,6 +289,7 @@ class SlabForward:
                          for t in (mod.q_proj.weight, mod.k_proj.weight, mod.v_proj.weight)]
         self._watched += [t for mod in body.modules() if hasattr(mod, "gate_proj") and hasattr(mod, "up_proj")
                           for t in (mod.gate_proj.weight, mod.up_proj.weight)]
+        self._watched += [mod.weight for mod in body.modules() if type(mod).__name__ == "SplitConv1D"]  # (fuse.py)
         self._watched_version = self._weights_version()
         # glb_slab_attention instead of two appends + a mask + a dense SDPA call per layer: for models whose attention
         # goes through transformers' attention interface with plain softmax(q k^T * scale) v semantics on a HIP device

@@ -187,7 +187,8 @@ class AsyncAmdLM(AsyncLM):
     @torch.no_grad()
     def __init__(self, hf_model, hf_tokenizer, batch_size=20, timeout=0.02, engine=None, fuse_activations=True,
                  kv_budget_bytes=8 << 30, logprob_budget_bytes=16 << 30, auto_kv_rows=0, auto_kv_cap=64,
-                 logprob_dtype="float32", glb_attention=True, merge_mlp=True, contract=None, gemms="library"):
+                 logprob_dtype="float32", glb_attention=True, merge_mlp=True, contract=None, gemms="library",
+                 split_gemms=True):
         """The caller's `hf_model` is never modified (hf.py:114-140 leaves it alone too): with `fuse_activations` or
         `glb_attention` the forwards of this backend run on a private SHADOW of its module tree that shares every weight
         (fuse.shadow_model); `self.model` stays the caller's object.
@@ -210,7 +211,11 @@ class AsyncAmdLM(AsyncLM):
         shapes run by the rocBLAS / hipBLASLt solution recorded for them in tuned/<arch>.csv (gemm_tuning: PyTorch TunableOp,
         a PROCESS-WIDE switch that also reaches the caller's other GEMMs; 8-10 % of a step at 1024 particles; silently the
         library's defaults when the file was made by another build of the libraries - `self.gemm_shapes` says how many
-        shapes were taken over).  `close()` gives the switch back."""
+        shapes were taken over).  `close()` gives the switch back.
+        split_gemms: in the shadow, GPT-2's float32 Conv1D projections run this library's split-bf16 MFMA GEMM (fuse.py
+        SplitConv1D: fp32-accurate, the MLP's tanh GELU in its epilogue) for the batch sizes where it was measured faster
+        than the library; it keeps a derived bf16 image of each such weight (6 bytes per element: 510 MB for GPT-2 small).
+        `gemms` still decides every GEMM this path does not take.  False: not swapped."""
         self.model = hf_model
         self.tokenizer = hf_tokenizer
         self.device = hf_model.device
@@ -249,7 +254,9 @@ class AsyncAmdLM(AsyncLM):
             from .fuse import fuse_shadow, shadow_model
 
             self._net = shadow_model(self.model)
-            self.fused = fuse_shadow(self._net, activations=bool(fuse_activations), merge_mlp=bool(merge_mlp))
+            split_engine = self.engine if split_gemms and self.device.type == "cuda" else None
+            self.fused = fuse_shadow(self._net, activations=bool(fuse_activations), merge_mlp=bool(merge_mlp),
+                                     split_engine=split_engine)
             if want_attention:
                 from .kv import use_glb_attention
 
@@ -290,7 +297,7 @@ class AsyncAmdLM(AsyncLM):
 
     def refresh_weights(self):
         """Call after changing the model's weights in a way PyTorch's version counters do not see.  The shadow keeps derived
-        copies of some weights ([q; k; v] and [gate; up] as one matrix each: fuse.py) and captured hipGraphs of the
+        copies of some weights ([q; k; v] and [gate; up] as one matrix each, the split GEMM's bf16 images: fuse.py) and captured hipGraphs of the
         one-token forward read the copies they were captured with; both notice `param.copy_()` / `param.mul_()` and replaced
         parameters by themselves (`Tensor._version`, identity, address), but NOT writes through `param.data` (EMA and
         weight-merging code does that: `p.data.copy_(...)` bumps no counter and moves no address).  This drops every
@@ -299,6 +306,7 @@ class AsyncAmdLM(AsyncLM):
         for mod in self._net.modules():
             mod.__dict__.pop("_glb_qkv", None)
             mod.__dict__.pop("_glb_gate_up", None)
+            mod.__dict__.pop("_glb_split", None)
         self.weights_epoch = getattr(self, "weights_epoch", 0) + 1  # SlabForward drops its graphs when this moves
         self.clear_cache()
 

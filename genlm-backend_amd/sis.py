@@ -959,7 +959,7 @@ class SisBenchWorkload:
         # GEMM work of a step, analytically: 2 x (weights of the body's linear layers) per token fed + 2 x d x V per row
         # through the output embedding (tools/gemm_table.py divides by the Tensile kernels' time in a rocprofv3 trace)
         body = self.llm._body
-        self._lin_w = sum(m.weight.numel() for m in body.modules() if type(m).__name__ in ("Linear", "Conv1D"))
+        self._lin_w = sum(m.weight.numel() for m in body.modules() if type(m).__name__ in ("Linear", "Conv1D", "SplitConv1D"))
         self._head_w = self.llm._head.weight.numel()
         # set-up, not measurement: one untimed pass over the loop's ten batch shapes (context lengths 8..17) so that
         # GEMM algorithm selection and allocator growth happen before bench.py's own warm-up / timed steps

@@ -665,6 +665,35 @@ int glb_comm_init(const void *id, int32_t rank, int32_t world, void **out_comm);
 int glb_allgather_f32(void *comm, const float *send, int64_t n, float *recv, void *hip_stream);
 int glb_comm_destroy(void *comm);
 
+/*
+ * fp32 projection GEMM on bf16 MFMA ("split bf16"): C[m, n] = A[m, k] . W[k, n] + bias, optionally followed by
+ * the tanh GELU (torch.nn.GELU(approximate="tanh") in fp32) - GPT-2's Conv1D, `addmm(bias, x, weight)` (hf
+ * modeling_gpt2.py).  Every operand element is split into three bf16 values by round-to-nearest (hi + mid + lo == x) and
+ * six of the nine products (mid.mid, lo.hi, hi.lo, mid.hi, hi.mid, hi.hi, in that order) go into one fp32 accumulator:
+ * fp32-accurate at 6/16 of the fp32 MFMA's cycles.
+ * W is split once per weight into a packed image of glb_gemm_split_bytes(k, n) bytes (6 per element; 0 when the shape is
+ * not served: the build serves n % 128 == 0 and k % 64 == 0), rebuilt by the caller whenever W changes.  A row-major with
+ * row pitch lda (elements; A and lda * 4 16-byte aligned), C row-major with pitch ldc, bias [n] or null.
+ * Argument errors return GLB_EINVAL before any GPU work, shapes and alignments the kernel does not serve
+ * GLB_EUNSUPPORTED (the caller then runs its library GEMM).  Launches go on the given stream, allocate nothing and may be
+ * captured into a hipGraph.
+ */
+enum { GLB_GEMM_BIAS = 0, GLB_GEMM_BIAS_GELU_TANH = 1 };
+typedef struct glb_gemm_args {
+  uint32_t struct_size; /* sizeof(glb_gemm_args) - ABI guard */
+  int64_t m, n, k;
+  const float *a;
+  int64_t lda;
+  const void *w_split; /* glb_gemm_split_weights' image of W */
+  const float *bias;   /* [n], nullable */
+  float *c;
+  int64_t ldc;
+  int32_t epilogue; /* GLB_GEMM_BIAS or GLB_GEMM_BIAS_GELU_TANH */
+} glb_gemm_args;
+size_t glb_gemm_split_bytes(int64_t k, int64_t n);
+int glb_gemm_split_weights(const float *w, int64_t k, int64_t n, int64_t ldw, void *out, size_t out_bytes, void *hip_stream);
+int glb_gemm_f32_split(const glb_gemm_args *args, void *hip_stream);
+
 /* Philox4x32-10 block function, exposed so hosts can reproduce the device draws. */
 void glb_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 

@@ -2,8 +2,8 @@
 
     python3 tools/gemm_table.py <kernel_trace.csv> <bench line .json> [steps-marker kernel substring]
 
-GEMM = every Tensile kernel (`Cijk_*` / `Custom_Cijk_*`: the transformer body's linear layers and the output embedding - the only
-MFMA work on the path).  Their FLOPs are not in the trace; the bench line carries them (`config.gemm_flops_per_step`: 2 x the
+GEMM = every Tensile kernel (`Cijk_*` / `Custom_Cijk_*`) and this library's split-bf16 GEMM (`gemm_split_kernel`, with the tanh GELU
+of mlp.c_fc in its epilogue): the transformer body's linear layers and the output embedding - the only MFMA work on the path.  Their FLOPs are not in the trace; the bench line carries them (`config.gemm_flops_per_step`: 2 x the
 linear layers' weights x the tokens fed + 2 x d x V x the rows through the output embedding, summed analytically per step).
 A "step" in the trace = one fused call (`fused_step_kernel`, or `chunk_stats_small_kernel` for the calls too small for it):
 set-up and warm-up steps run the same mix, so the per-step means hold for the timed region."""
@@ -16,7 +16,7 @@ bench = {}
 for ln in open(line):
     if ln.startswith("{"):
         bench = json.loads(ln)
-groups = {"GEMM (Tensile)": lambda n: n.startswith("Cijk_") or n.startswith("Custom_Cijk_"),
+groups = {"GEMM (Tensile + split bf16)": lambda n: n.startswith("Cijk_") or n.startswith("Custom_Cijk_") or "gemm_split_kernel" in n,
           "glb attention": lambda n: "short_attention" in n or "slab_attention" in n,
           "library attention (attn_fwd / SDPA)": lambda n: "attn_fwd" in n or "fmha" in n.lower(),
           "fused step (glb)": lambda n: "fused_step_kernel" in n or "chunk_stats" in n or "finish_kernel" in n,
@@ -51,5 +51,5 @@ for k, (cnt, us) in sorted(tot.items(), key=lambda kv: -kv[1][1]):
     print(f"{k:40s} {cnt / steps:14.1f} {us / steps:10.1f} {us / busy * 100:13.1f}% {wall}")
 print(f"{'sum of kernel durations':40s} {'':14s} {busy / steps:10.1f}")
 if flops:
-    g = tot["GEMM (Tensile)"][1] / steps
+    g = tot["GEMM (Tensile + split bf16)"][1] / steps
     print(f"GEMM: {flops / 1e9:.1f} GFLOP per step (analytic, bench line) / {g:.1f} us = {flops / (g * 1e-6) / 1e12:.1f} TFLOP/s")
