@@ -180,6 +180,19 @@ class GemmArgs(C.Structure):
     ]
 
 
+class LoraJob(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("w_dtype", C.c_int32), ("ab_dtype", C.c_int32), ("w_transposed", C.c_int32),
+        ("n_out", C.c_int64), ("k_in", C.c_int64), ("r", C.c_int64),
+        ("w", C.c_void_p), ("ldw", C.c_int64),
+        ("a", C.c_void_p), ("lda", C.c_int64),
+        ("b", C.c_void_p), ("ldb", C.c_int64),
+        ("scale", C.c_float),
+        ("out", C.c_void_p), ("ldo", C.c_int64),
+    ]
+
+
 # every symbol include/glb.h declares: name -> (restype, argtypes)
 _vp, _i32, _i64, _f32, _sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_size_t
 SYMBOLS = {
@@ -242,6 +255,8 @@ SYMBOLS = {
     "glb_gemm_split_bytes": (_sz, [_i64, _i64]),
     "glb_gemm_split_weights": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _sz, _vp]),
     "glb_gemm_f32_split": (C.c_int, [C.POINTER(GemmArgs), _vp]),
+    "glb_lora_merge_workspace_bytes": (_sz, [_i32]),
+    "glb_lora_merge": (C.c_int, [C.POINTER(LoraJob), _i32, _vp, _sz, _vp]),
     "glb_philox4x32_10": (None, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
 }
 

@@ -75,7 +75,8 @@ class AutoKV:
                 pos_d = torch.where(is_a, plan["pos_of_row"], torch.where(idle, self.row_len.clamp(max=cap - 1), zero))
                 at = st_d[ctx_r.clamp_min(0).long()] + torch.where(is_a, pos_d, zero).long()
                 ids = tok_d[at].view(-1, 1).long()
-                if self._slab_fwd is None or self._slab_fwd.pkv is not self.pkv:
+                # (a new body: set_lora made the backend's shadow after this forward was built over the caller's model)
+                if self._slab_fwd is None or self._slab_fwd.pkv is not self.pkv or self._slab_fwd.body is not llm._body:
                     from .kv import SlabForward
 
                     self._slab_fwd = SlabForward(self.pkv, llm._body, graph=self.graph, owner=llm)

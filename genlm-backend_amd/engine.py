@@ -639,6 +639,43 @@ class HipEngine:
         check(rc)
         return out.view(*x.shape[:-1], n)
 
+    # ---- LoRA merge (glb_lora_merge: DESIGN.md §13) ------------------------------------------------------------------
+    def lora_merge(self, jobs):
+        """out = w + scale * b @ a for every job, in ONE library call (one launch per weight dtype among the jobs).  A job is
+        a dict: `w` [n_out, k_in] (or [k_in, n_out] with `transposed`: GPT-2's Conv1D), `a` = lora_A [r, k_in], `b` = lora_B
+        [n_out, r], `scale` (float), `transposed` (bool), `out` (w's dtype and layout; must not overlap w, a or b).  Every
+        matrix has unit inner stride; rows may be padded.  Arithmetic: include/glb.h glb_lora_merge (bit-exact contract)."""
+        n = len(jobs)
+        if n == 0:
+            return
+        table = (_lib.LoraJob * n)()
+        for q, j in zip(table, jobs):
+            w, a, b, out = j["w"], j["a"], j["b"], j["out"]
+            for t in (w, a, b, out):
+                if t.device != self.device:
+                    raise ValueError(f"tensor on {t.device}, engine on {self.device}")
+                if t.dim() != 2 or t.stride(1) != 1:
+                    raise ValueError("lora_merge: every matrix must be 2-D with unit inner stride")
+                if t.dtype not in _DT:
+                    raise ValueError(f"lora_merge: unsupported dtype {t.dtype}")
+            if a.dtype != b.dtype or out.dtype != w.dtype or out.shape != w.shape:
+                raise ValueError("lora_merge: a / b must share a dtype, out must match w's dtype and shape")
+            tr = bool(j.get("transposed", False))
+            q.struct_size = C.sizeof(_lib.LoraJob)
+            q.w_dtype, q.ab_dtype, q.w_transposed = _DT[w.dtype], _DT[a.dtype], int(tr)
+            q.k_in, q.n_out = (w.shape[0], w.shape[1]) if tr else (w.shape[1], w.shape[0])
+            q.r = a.shape[0]
+            if tuple(a.shape) != (q.r, q.k_in) or tuple(b.shape) != (q.n_out, q.r):
+                raise ValueError(f"lora_merge: a {tuple(a.shape)} / b {tuple(b.shape)} do not fit w {tuple(w.shape)}")
+            q.w, q.ldw = w.data_ptr(), w.stride(0)
+            q.a, q.lda = a.data_ptr(), a.stride(0)
+            q.b, q.ldb = b.data_ptr(), b.stride(0)
+            q.scale = float(j["scale"])
+            q.out, q.ldo = out.data_ptr(), out.stride(0)
+        nbytes = self.lib.glb_lora_merge_workspace_bytes(n)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)  # (freed in stream order: the launch reads it first)
+        check(self.lib.glb_lora_merge(table, n, _ptr(ws), nbytes, self._stream()))
+
     # ---- device-resident particle state ------------------------------------------------------------------
     def kv_append(self, slab, new_rows, pos, rows=None):
         """slab[rows[i] (or i), h, pos[i], :] = new_rows[i, h, 0, :] (glb_kv_append).  slab [R, H, cap, Dh] contiguous;

@@ -9,6 +9,7 @@
 * `PrefixLRU` — byte-budgeted least-recently-used store for the prompt prefixes `cache_kv` pins (hf.py:155-164);
   the eviction policy of cache.py:103-191 (`DynamicTokenTrie`), applied to whole prefix slabs.
 """
+import gc
 from collections import OrderedDict
 
 import torch
@@ -352,6 +353,12 @@ class SlabForward:
                 return self._run(ids, pos)
             s_ids, s_pos = ids.clone(), pos.clone()
             g = torch.cuda.CUDAGraph()
+            # No cyclic garbage collection inside the capture: a collection there can destroy a dead object that holds a
+            # captured graph or device memory (an earlier population's SlabForward), whose release is not allowed while a
+            # stream is being captured and aborts the process.  What is dead already goes first, outside the capture.
+            gc.collect()
+            gc_was_on = gc.isenabled()
+            gc.disable()
             try:
                 with torch.cuda.graph(g, capture_error_mode="thread_local"):  # (a collective's watchdog thread may be about)
                     hidden = self._run(s_ids, s_pos)
@@ -367,6 +374,9 @@ class SlabForward:
                 self.capture_error = e
                 torch.cuda.synchronize()
                 return self._run(ids, pos)
+            finally:
+                if gc_was_on:
+                    gc.enable()
             ent = self.graphs[key] = (g, s_ids, s_pos, hidden, slabs)
         g, s_ids, s_pos, hidden, _held = ent
         s_ids.copy_(ids)

@@ -290,6 +290,9 @@ class AsyncAmdLM(AsyncLM):
         self._noise_src = None  # "torch" draws: the CPU generator's stream on the device, made at the first evaluation
         self._batch_counter = 0
         self.stats = {"batches": 0, "queries": 0, "unique": 0, "rows": 0}
+        self._loras = {}  # name -> lora.LoraAdapter (loaded, validated)
+        self._lora = None  # lora.MergedLora of the active adapter
+        self.lora_epoch = 0  # moves at every set_lora / clear_lora
         if hf_tokenizer is not None:
             super().__init__(tokenizer=self.tokenizer)
         else:  # model-only use (synthetic benchmarks): no vocabulary to decode
@@ -301,12 +304,17 @@ class AsyncAmdLM(AsyncLM):
         one-token forward read the copies they were captured with; both notice `param.copy_()` / `param.mul_()` and replaced
         parameters by themselves (`Tensor._version`, identity, address), but NOT writes through `param.data` (EMA and
         weight-merging code does that: `p.data.copy_(...)` bumps no counter and moves no address).  This drops every
-        derived copy and every captured graph - they are rebuilt from the current weights at the next forward - and the
-        cached log-prob rows and KV (made with the old weights: clear_cache())."""
+        derived copy and every captured graph - they are rebuilt from the current weights at the next forward -, merges an
+        active LoRA adapter again, and drops the cached log-prob rows and KV (made with the old weights: clear_cache())."""
         for mod in self._net.modules():
             mod.__dict__.pop("_glb_qkv", None)
             mod.__dict__.pop("_glb_gate_up", None)
             mod.__dict__.pop("_glb_split", None)
+        if self._lora is not None:  # an active adapter is merged again from the current base weights
+            self._lora.uninstall()
+            from .lora import MergedLora
+
+            self._lora = MergedLora(self._lora.adapter, self._net, self.engine)
         self.weights_epoch = getattr(self, "weights_epoch", 0) + 1  # SlabForward drops its graphs when this moves
         self.clear_cache()
 
@@ -353,6 +361,7 @@ class AsyncAmdLM(AsyncLM):
     def cache_kv(self, prompt_tokens):
         """hf.py:155-164: run the prompt once, cache every position's log-probs and keep the KV states
         on the prompt's last node so later queries only feed their new tokens."""
+        self._lora_sync()
         key = tuple(int(t) for t in prompt_tokens)
         # extend_cache makes fresh nodes, so caching the same prompt again (or one that shares leading tokens) orphans
         # the node that held the KV so far: its entry leaves the store instead of lingering under the budget
@@ -382,15 +391,80 @@ class AsyncAmdLM(AsyncLM):
         self._kv_tokens[id(node)] = key
         self._ptab = None
 
-    # ---- LoRA hooks (hf.py:166-200): weight management is outside the hot path ---------------------
+    # ---- LoRA adapters (hf.py:166-200): merged into private weights of the shadow (lora.py) ----------
     def add_new_lora(self, lora_path, lora_name="lora_1"):
-        raise NotImplementedError("LoRA adapters are out of scope for the MI355X hot-path backend")
+        """Load a peft LoRA adapter (a local directory or a hub id) and check it against the model; it is not activated
+        (`set_lora` does that).  A name that is already loaded raises ValueError, as transformers' load_adapter does."""
+        from .lora import load_adapter
+
+        if lora_name in self._loras:
+            raise ValueError(f"Adapter with name {lora_name} already exists. Please use a different name.")
+        self._loras[lora_name] = load_adapter(lora_path, self.model, lora_name)
+        self._lora_stats()
 
     def set_lora(self, lora_path=None, lora_name="lora_1"):
-        raise NotImplementedError("LoRA adapters are out of scope for the MI355X hot-path backend")
+        """Activate a loaded adapter: its targeted weights become W + s * B . A (one glb_lora_merge call into private
+        tensors of the shadow; the caller's model is not touched), every cache made with other weights is dropped, and
+        DeviceSIS / DeviceSampler objects made before refuse to step."""
+        if lora_name not in self._loras:
+            raise ValueError(
+                f"A LoRA adapter named '{lora_name}' has not been loaded yet. Please call add_new_lora() first to load and "
+                "name your LoRA adapters."
+            )
+        try:
+            self._drop_lora()
+            if self._net is self.model:  # no shadow yet (fuse_activations=False, glb_attention=False): one to merge into
+                from .fuse import shadow_model
+
+                self._net = shadow_model(self.model)
+                self._head = self._net.get_output_embeddings()
+                self._body = self._net.base_model
+            from .lora import MergedLora
+
+            self._lora = MergedLora(self._loras[lora_name], self._net, self.engine)
+        finally:  # (also when the merge fails: the old adapter is gone, and what was made with it must go too)
+            self._weights_switched()
 
     def clear_lora(self):
-        raise NotImplementedError("LoRA adapters are out of scope for the MI355X hot-path backend")
+        """Back to the base weights: the shared parameter tables return and the merged tensors are freed, so results are
+        bit-identical to a backend that never saw an adapter.  Clears the caches also when no adapter is active."""
+        self._drop_lora()
+        self._weights_switched()
+
+    @property
+    def active_lora(self):
+        """Name of the active adapter, or None."""
+        return None if self._lora is None else self._lora.adapter.name
+
+    def _drop_lora(self):
+        if self._lora is not None:
+            self._lora.uninstall()
+            self._lora = None
+            for mod in self._net.modules():  # derived copies of merged weights go with them (rebuilt from the base)
+                mod.__dict__.pop("_glb_qkv", None)
+                mod.__dict__.pop("_glb_gate_up", None)
+                mod.__dict__.pop("_glb_split", None)
+
+    def _weights_switched(self):
+        self.lora_epoch += 1  # DeviceSIS objects made before refuse to step
+        self.weights_epoch = getattr(self, "weights_epoch", 0) + 1  # SlabForward drops its graphs
+        self.clear_kv_cache()
+        self.clear_cache()
+        self._lora_stats()
+
+    def _lora_stats(self):
+        self.stats["lora_merged_bytes"] = 0 if self._lora is None else self._lora.nbytes()
+        self.stats["lora_adapter_bytes"] = sum(a.nbytes() for a in self._loras.values())
+
+    def _lora_sync(self, epoch=None):
+        """Before a batch evaluates: an object made under other weights (`epoch`: the lora_epoch it was made at) raises;
+        an active adapter whose base weights changed since the merge is merged again (SlabForward's graphs are dropped)."""
+        if epoch is not None and epoch != self.lora_epoch:
+            raise RuntimeError("the LoRA adapter changed (set_lora / clear_lora) after this object was made: its KV was "
+                               "computed with other weights - make a new one")
+        if self._lora is not None and self._lora.sync():
+            self.weights_epoch = getattr(self, "weights_epoch", 0) + 1
+            self._lora_stats()
 
     # ---- fused-step configuration -------------------------------------------------------------------
     def register_masks(self, masks):
@@ -455,6 +529,7 @@ class AsyncAmdLM(AsyncLM):
 
     def _evaluate(self, queries):
         eng, dev = self.engine, self.device
+        self._lora_sync()
         n = len(queries)
         if all(q.kind == "step" and q.past is None for q in queries):
             # a population of README particles (README.md:82-91) and no cached prefix: the whole batch goes through the
@@ -740,6 +815,7 @@ class AsyncAmdLM(AsyncLM):
         """hf.py:404-422: no KV, no output cache, no batching."""
         if not token_ids:
             raise ValueError("Token ids must not be empty")
+        self._lora_sync()
         ids = torch.tensor([token_ids], device=self.device)
         h = self._body(input_ids=ids, use_cache=False).last_hidden_state[0, -1:]
         return self._log_softmax(self._lm_head(h))[0]  # (a single row: the three-launch form, no waits inside)
@@ -955,6 +1031,7 @@ class AsyncAmdLM(AsyncLM):
         """The batched step on a ragged batch that is on the device already.  l_max: the longest context if the host
         knows it (else it rides on the call's D2H copy).  Returns device tensors."""
         eng, dev = self.engine, self.device
+        self._lora_sync()
         group_of, rep, ng = eng.group_contexts(tok_d, st_d, ln_d)
         P = self._prefix_table()
         base, pref = None, None

@@ -204,6 +204,10 @@ class DeviceSIS:
                  dist=None, use_prefix_kv=False, use_particle_kv=False, resample_ess=None, force_collectives=False,
                  share_kv=True, kv_rows=None, kv_in_place=0.75, kv_graph=True, particle_masks=None, migrate_kv=True):
         self.llm, self.eng, self.dev = llm, llm.engine, llm.device
+        # the LoRA adapter this population's KV is made with: a step after set_lora / clear_lora raises (llm._lora_sync)
+        self._lora_epoch = getattr(llm, "lora_epoch", 0)
+        if hasattr(llm, "_lora_sync"):
+            llm._lora_sync(self._lora_epoch)
         self.N, self.max_tokens, self.eos_id = n_particles, max_tokens, eos_id
         self.rank, self.world, self.dist = rank, world, dist
         self.collective = world > 1 or (bool(force_collectives) and dist is not None)
@@ -587,6 +591,8 @@ class DeviceSIS:
     def step(self, time_kernel=False):
         """One SIS step for every active particle.  Returns (n_unique, particles active over ALL ranks before it)."""
         eng, llm, dev, N = self.eng, self.llm, self.dev, self.N
+        if hasattr(llm, "_lora_sync"):
+            llm._lora_sync(self._lora_epoch)
         if self.share_kv:
             return self._step_shared_kv(time_kernel)
         if self.particle_kv and self.t > 0:

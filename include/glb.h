@@ -694,6 +694,43 @@ size_t glb_gemm_split_bytes(int64_t k, int64_t n);
 int glb_gemm_split_weights(const float *w, int64_t k, int64_t n, int64_t ldw, void *out, size_t out_bytes, void *hip_stream);
 int glb_gemm_f32_split(const glb_gemm_args *args, void *hip_stream);
 
+/*
+ * LoRA merge: out = W + scale * B . A for every matrix of an adapter in one call - what peft's merged
+ * weights are (peft lora/layer.py get_delta_weight), made once per adapter switch so the forward runs the base model's
+ * kernels.  Per job: W and out [n_out, k_in] (nn.Linear) or [k_in, n_out] (w_transposed: GPT-2's Conv1D, peft's
+ * fan_in_fan_out), row pitches ldw / ldo; A = lora_A [r, k_in] (pitch lda), B = lora_B [n_out, r] (pitch ldb); all device
+ * pointers aligned to their element.  Arithmetic contract, for every element (i output feature, j input feature):
+ *     acc = +0.0f;  for t = 0 .. r-1 ascending: acc = fmaf(f32(B[i, t]), f32(A[t, j]), acc)
+ *     out[i, j] = round_to_w_dtype(fmaf(scale, acc, f32(W[i, j])))      (round to nearest even)
+ * f32() is exact for every element type; the bits depend on nothing else (no atomics, no launch-geometry dependence),
+ * so the result is restated bit for bit on the CPU (tests/lora_engine.py).  r 1 .. 256 and any n_out, k_in >= 1 up to
+ * 2^30 are served (GLB_EUNSUPPORTED otherwise).  No job's out may overlap any job's w, a or b, nor another job's out
+(GLB_EINVAL: the blocks of one call run in any order).  The job table is copied into the
+ * caller's device `workspace` (glb_lora_merge_workspace_bytes(n_jobs) bytes, 16-byte aligned) before the call returns;
+ * argument errors return GLB_EINVAL before any GPU work.  One launch per W dtype among the jobs (split when its grid
+exceeds 2^24 - 1 blocks), on the given stream;
+ * not for stream capture (the table copy reads host memory).
+ */
+typedef struct glb_lora_job {
+  uint32_t struct_size; /* sizeof(glb_lora_job) - ABI guard */
+  int32_t w_dtype;      /* GLB_F32 / GLB_BF16 / GLB_F16: W and out */
+  int32_t ab_dtype;     /* GLB_F32 / GLB_BF16 / GLB_F16: A and B */
+  int32_t w_transposed; /* 0: W is [n_out, k_in] (nn.Linear); 1: W is [k_in, n_out] (GPT-2 Conv1D) */
+  int64_t n_out, k_in, r;
+  const void *w;
+  int64_t ldw; /* row pitches in elements */
+  const void *a;
+  int64_t lda; /* lora_A [r, k_in] */
+  const void *b;
+  int64_t ldb; /* lora_B [n_out, r] */
+  float scale;
+  void *out;
+  int64_t ldo; /* same dtype and layout as w */
+} glb_lora_job;
+size_t glb_lora_merge_workspace_bytes(int32_t n_jobs);
+int glb_lora_merge(const glb_lora_job *jobs /* host */, int32_t n_jobs, void *workspace /* device */, size_t workspace_bytes,
+                   void *hip_stream);
+
 /* Philox4x32-10 block function, exposed so hosts can reproduce the device draws. */
 void glb_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 
