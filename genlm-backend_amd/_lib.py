@@ -193,6 +193,31 @@ class LoraJob(C.Structure):
     ]
 
 
+class W4Args(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("dtype", C.c_int32), ("transposed", C.c_int32),
+        ("n", C.c_int64), ("k", C.c_int64),
+        ("w", C.c_void_p), ("ldw", C.c_int64),
+        ("codebook", C.POINTER(C.c_float)),
+        ("image", C.c_void_p), ("image_bytes", C.c_size_t),
+    ]
+
+
+class W4GemmArgs(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("dtype", C.c_int32),
+        ("m", C.c_int64), ("n", C.c_int64), ("k", C.c_int64),
+        ("x", C.c_void_p), ("ldx", C.c_int64),
+        ("image", C.c_void_p),
+        ("codebook", C.POINTER(C.c_float)),
+        ("bias", C.c_void_p),
+        ("y", C.c_void_p), ("ldy", C.c_int64),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+    ]
+
+
 # every symbol include/glb.h declares: name -> (restype, argtypes)
 _vp, _i32, _i64, _f32, _sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_size_t
 SYMBOLS = {
@@ -257,6 +282,12 @@ SYMBOLS = {
     "glb_gemm_f32_split": (C.c_int, [C.POINTER(GemmArgs), _vp]),
     "glb_lora_merge_workspace_bytes": (_sz, [_i32]),
     "glb_lora_merge": (C.c_int, [C.POINTER(LoraJob), _i32, _vp, _sz, _vp]),
+    "glb_w4_bytes": (_sz, [_i64, _i64]),
+    "glb_w4_quantize": (C.c_int, [C.POINTER(W4Args), _vp]),
+    "glb_w4_dequantize": (C.c_int, [C.POINTER(W4Args), _vp]),
+    "glb_w4_gemm_max_rows": (C.c_int, []),
+    "glb_w4_gemm_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "glb_w4_gemm": (C.c_int, [C.POINTER(W4GemmArgs), _vp]),
     "glb_philox4x32_10": (None, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
 }
 

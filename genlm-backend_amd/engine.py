@@ -676,6 +676,94 @@ class HipEngine:
         ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)  # (freed in stream order: the launch reads it first)
         check(self.lib.glb_lora_merge(table, n, _ptr(ws), nbytes, self._stream()))
 
+    # ---- 4-bit block-quantised weights (glb_w4_*: DESIGN.md §14) --------------------------------------------------------
+    @staticmethod
+    def _codebook(codebook):
+        cb = (C.c_float * 16)(*[float(v) for v in codebook])
+        if len(codebook) != 16:
+            raise ValueError("a 4-bit codebook has 16 entries")
+        return cb
+
+    def w4_bytes(self, n, k):
+        return self.lib.glb_w4_bytes(n, k)
+
+    def w4_gemm_max_rows(self):
+        return self.lib.glb_w4_gemm_max_rows()
+
+    def _w4_args(self, w, n, k, transposed, codebook, image):
+        if w.device != self.device or image.device != self.device:
+            raise ValueError(f"tensor on {w.device} / {image.device}, engine on {self.device}")
+        if w.dim() != 2 or w.stride(1) != 1 or w.dtype not in _DT:
+            raise ValueError("w4: the weight must be 2-D float32 / bfloat16 / float16 with unit inner stride")
+        if tuple(w.shape) != ((k, n) if transposed else (n, k)):
+            raise ValueError(f"w4: weight {tuple(w.shape)} does not fit n {n}, k {k}, transposed {transposed}")
+        a = _lib.W4Args()
+        a.struct_size = C.sizeof(_lib.W4Args)
+        a.dtype, a.transposed = _DT[w.dtype], int(bool(transposed))
+        a.n, a.k = n, k
+        a.w, a.ldw = w.data_ptr(), w.stride(0)
+        a.codebook = self._codebook(codebook)
+        a.image, a.image_bytes = image.data_ptr(), image.numel()
+        return a
+
+    def w4_quantize(self, w, codebook, transposed=False, out=None):
+        """The packed 4-bit image (uint8 [glb_w4_bytes(n, k)]) of a weight w [n, k] (or [k, n] with `transposed`: GPT-2's
+        Conv1D) in float32 / bfloat16 / float16, rows of unit inner stride (glb_w4_quantize: one pass over w), or None
+        when the shape is not served (k % 64 != 0)."""
+        n, k = (w.shape[1], w.shape[0]) if transposed else (w.shape[0], w.shape[1])
+        nbytes = self.lib.glb_w4_bytes(n, k)
+        if nbytes == 0:
+            return None
+        if out is None:
+            out = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        a = self._w4_args(w, n, k, transposed, codebook, out)
+        check(self.lib.glb_w4_quantize(C.byref(a), self._stream()))
+        return out
+
+    def w4_dequantize(self, image, n, k, codebook, dtype=torch.float32, transposed=False, out=None):
+        """W' [n, k] (or [k, n] with `transposed`) of a packed image, in `dtype` (glb_w4_dequantize); `out`: a 2-D tensor of
+        that shape with unit inner stride (rows may be padded).  None when the shape is not served."""
+        if self.lib.glb_w4_bytes(n, k) == 0:
+            return None
+        if out is None:
+            out = torch.empty((k, n) if transposed else (n, k), dtype=dtype, device=self.device)
+        a = self._w4_args(out, n, k, transposed, codebook, image)
+        check(self.lib.glb_w4_dequantize(C.byref(a), self._stream()))
+        return out
+
+    def w4_gemm(self, x, image, n, codebook, bias=None, out=None):
+        """x [..., K] bfloat16 / float16 (rows of unit inner stride) times the dequantised weight of `image`, transposed,
+        plus bias [N] of x's dtype (glb_w4_gemm: codes expanded in registers).  Returns [..., N] in x's dtype, or None
+        when the kernel does not serve the call (more rows than glb_w4_gemm_max_rows(), shape, alignment): the caller then
+        dequantises and runs its library GEMM."""
+        k = x.shape[-1]
+        x2 = x.reshape(-1, k)
+        m = x2.shape[0]
+        if m == 0 or x2.stride(1) != 1 or x.dtype not in (torch.bfloat16, torch.float16):
+            return None
+        if bias is not None and bias.dtype != x.dtype:
+            return None
+        ws_bytes = self.lib.glb_w4_gemm_workspace_bytes(m, n, k)
+        if ws_bytes == 0:
+            return None
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)  # (freed in stream order)
+        y = out if out is not None else torch.empty((m, n), dtype=x.dtype, device=self.device)
+        a = _lib.W4GemmArgs()
+        a.struct_size = C.sizeof(_lib.W4GemmArgs)
+        a.dtype = _DT[x.dtype]
+        a.m, a.n, a.k = m, n, k
+        a.x, a.ldx = x2.data_ptr(), x2.stride(0)
+        a.image = image.data_ptr()
+        a.codebook = self._codebook(codebook)
+        a.bias = bias.data_ptr() if bias is not None else None
+        a.y, a.ldy = y.data_ptr(), y.stride(0)
+        a.workspace, a.workspace_bytes = ws.data_ptr(), ws_bytes
+        rc = self.lib.glb_w4_gemm(C.byref(a), self._stream())
+        if rc == _lib.GLB_EUNSUPPORTED:
+            return None
+        check(rc)
+        return y if out is not None else y.view(*x.shape[:-1], n)
+
     # ---- device-resident particle state ------------------------------------------------------------------
     def kv_append(self, slab, new_rows, pos, rows=None):
         """slab[rows[i] (or i), h, pos[i], :] = new_rows[i, h, 0, :] (glb_kv_append).  slab [R, H, cap, Dh] contiguous;

@@ -121,7 +121,7 @@ def _llama_mlp_forward(self, x):
     up_proj are ONE GEMM on a derived [gate; up] weight - at M = 512 two GEMMs of N = 8192 leave three quarters of the chip's
     CUs without a tile (65.6 -> 48.3 us a layer at Llama-3.2-1B's shape, 135 -> 114 at Llama-3-8B's); the big re-encoding
     batches keep two GEMMs (the strided halves cost the elementwise ops more than the GEMM gains there)."""
-    if (x.shape[:-1].numel() <= MERGE_MLP_MAX_TOKENS
+    if (hasattr(self.gate_proj, "weight") and x.shape[:-1].numel() <= MERGE_MLP_MAX_TOKENS  # (no .weight: quant.W4Linear)
             and not (torch.is_grad_enabled() and (x.requires_grad or self.gate_proj.weight.requires_grad))):
         w, b = _merged_gate_up(self)
         n = self.gate_proj.weight.shape[0]
@@ -207,7 +207,7 @@ def weights_version(net):
     v = 0
     for mod in net.modules():
         ent = mod.__dict__.get("_glb_qkv")
-        if ent is not None:
+        if ent is not None and hasattr(mod.q_proj, "weight"):
             for t in (mod.q_proj.weight, mod.k_proj.weight, mod.v_proj.weight):
                 v += t._version + (id(t) & 0xFFFF)
         if mod.__dict__.get("_glb_split") is not None:
@@ -223,14 +223,20 @@ def _llama_attention_forward(self, hidden_states, position_embeddings=None, atte
     from transformers.modeling_utils import ALL_ATTENTION_FUNCTIONS
     from transformers.models.llama.modeling_llama import eager_attention_forward
 
-    if torch.is_grad_enabled() and (hidden_states.requires_grad or self.q_proj.weight.requires_grad):
+    w4 = not hasattr(self.q_proj, "weight")  # quant.W4Linear: 4-bit images, nothing to concatenate or differentiate
+    if torch.is_grad_enabled() and (hidden_states.requires_grad or (not w4 and self.q_proj.weight.requires_grad)):
         return type(self).forward(self, hidden_states, position_embeddings=position_embeddings, attention_mask=attention_mask,
                                   past_key_values=past_key_values, **kwargs)
     input_shape = hidden_states.shape[:-1]
     D = self.head_dim
-    w, b = _merged_qkv(self)
-    qkv = torch.nn.functional.linear(hidden_states, w, b).view(*input_shape, -1, D)  # [B, T, Hq + 2 Hkv, D]
-    n_kv = self.k_proj.weight.shape[0] // D
+    if w4:  # three projections, one joint tensor: the rotary pass below stays the fused one
+        qkv = torch.cat((self.q_proj(hidden_states), self.k_proj(hidden_states), self.v_proj(hidden_states)), -1)
+        qkv = qkv.view(*input_shape, -1, D)
+        n_kv = self.k_proj.out_features // D
+    else:
+        w, b = _merged_qkv(self)
+        qkv = torch.nn.functional.linear(hidden_states, w, b).view(*input_shape, -1, D)  # [B, T, Hq + 2 Hkv, D]
+        n_kv = self.k_proj.weight.shape[0] // D
     n_q = qkv.shape[-2] - 2 * n_kv
     cos, sin = position_embeddings
     ss = getattr(sin, "_glb_signed", None)

@@ -286,10 +286,11 @@ class SlabForward:
         self.graphs = {}  # identity of the slab set -> (graph, ids, pos, hidden, the slab tensors themselves)
         # weights the shadow keeps derived copies of (fuse._merged_qkv): a captured graph reads the copy it was captured
         # with, so the graphs are dropped when one of the sources changes
-        self._watched = [t for mod in body.modules() if hasattr(mod, "q_proj") and hasattr(mod, "k_proj") and hasattr(mod, "v_proj")
-                         for t in (mod.q_proj.weight, mod.k_proj.weight, mod.v_proj.weight)]
-        self._watched += [t for mod in body.modules() if hasattr(mod, "gate_proj") and hasattr(mod, "up_proj")
-                          for t in (mod.gate_proj.weight, mod.up_proj.weight)]
+        # (a 4-bit projection - quant.W4Linear - has no .weight and no derived copy)
+        self._watched = [p.weight for mod in body.modules() if hasattr(mod, "q_proj") and hasattr(mod, "k_proj") and hasattr(mod, "v_proj")
+                         for p in (mod.q_proj, mod.k_proj, mod.v_proj) if hasattr(p, "weight")]
+        self._watched += [p.weight for mod in body.modules() if hasattr(mod, "gate_proj") and hasattr(mod, "up_proj")
+                          for p in (mod.gate_proj, mod.up_proj) if hasattr(p, "weight")]
         self._watched += [mod.weight for mod in body.modules() if type(mod).__name__ == "SplitConv1D"]  # (fuse.py)
         self._watched_version = self._weights_version()
         # glb_slab_attention instead of two appends + a mask + a dense SDPA call per layer: for models whose attention

@@ -118,11 +118,18 @@ class AsyncAmdLM(AsyncLM):
 
     @classmethod
     def from_name(cls, model_id, bitsandbytes_opts=None, hf_opts=None, **kwargs):
-        """hf.py:80-112.  bitsandbytes is a CUDA-only dependency and is rejected."""
+        """hf.py:80-112.  bitsandbytes_opts: the dict the reference hands to transformers.BitsAndBytesConfig; the model is
+        loaded as without it and its linear layers are then quantised to 4-bit NF4 / FP4 blocks by this library's own
+        kernels (quant.py, DESIGN.md §14: `bitsandbytes` is not needed).  Served: load_in_4bit, bnb_4bit_quant_type "fp4"
+        (default) / "nf4", bnb_4bit_compute_dtype, llm_int8_skip_modules; load_in_8bit, double quantisation, another
+        quant storage and pre-quantised checkpoints raise NotImplementedError.  `self.quantization` holds the report."""
         from transformers import AutoModelForCausalLM, AutoTokenizer
 
+        w4 = None
         if bitsandbytes_opts:
-            raise NotImplementedError("bitsandbytes quantisation is CUDA-only; not available on MI355X")
+            from .quant import parse_opts
+
+            w4 = parse_opts(bitsandbytes_opts)
         _hf_opts = {"torch_dtype": "auto"}
         if hf_opts:
             _hf_opts.update(hf_opts)
@@ -131,12 +138,37 @@ class AsyncAmdLM(AsyncLM):
             device = "cuda:0"
         tok = AutoTokenizer.from_pretrained(model_id)
         mod = AutoModelForCausalLM.from_pretrained(model_id, **_hf_opts).to(device)
+        if w4 is not None:
+            kwargs = cls._quantize_own(mod, w4, kwargs)
         return cls(mod, tok, **kwargs)
 
+    @staticmethod
+    def _quantize_own(mod, w4, kwargs):
+        """4-bit weights for a model this backend has just made (a model handed to the constructor is never rewritten)."""
+        from .quant import quantize_model
+
+        if getattr(mod.config, "quantization_config", None) is not None:
+            raise NotImplementedError("a pre-quantised checkpoint (quantization_config in its config.json) is not served")
+        kwargs = dict(kwargs)
+        if kwargs.get("engine") is None:
+            from .engine import HipEngine  # raises without the library / a HIP device
+
+            kwargs["engine"] = HipEngine(mod.device, contract=kwargs.get("contract") or "auto")
+        mod.eval()
+        quantize_model(mod, w4, kwargs["engine"])
+        return kwargs
+
     @classmethod
-    def from_config(cls, config, tokenizer, device="cuda:0", dtype=torch.float32, seed=0, **kwargs):
-        """Random-init model of a given architecture (no hub access needed; synthetic benchmarks/tests)."""
+    def from_config(cls, config, tokenizer, device="cuda:0", dtype=torch.float32, seed=0, bitsandbytes_opts=None, **kwargs):
+        """Random-init model of a given architecture (no hub access needed; synthetic benchmarks/tests).
+        bitsandbytes_opts: as `from_name` (the model is quantised after it is made)."""
         from transformers import AutoModelForCausalLM
+
+        w4 = None
+        if bitsandbytes_opts:
+            from .quant import parse_opts
+
+            w4 = parse_opts(bitsandbytes_opts)
 
         torch.manual_seed(seed)
         n_params = getattr(config, "num_hidden_layers", 0) * getattr(config, "hidden_size", 0) ** 2 * 12
@@ -153,6 +185,8 @@ class AsyncAmdLM(AsyncLM):
             mod = mod.to(dtype)
         else:
             mod = AutoModelForCausalLM.from_config(config).to(dtype).to(device)
+        if w4 is not None:
+            kwargs = cls._quantize_own(mod, w4, kwargs)
         return cls(mod, tokenizer, **kwargs)
 
     @staticmethod
@@ -188,7 +222,7 @@ class AsyncAmdLM(AsyncLM):
     def __init__(self, hf_model, hf_tokenizer, batch_size=20, timeout=0.02, engine=None, fuse_activations=True,
                  kv_budget_bytes=8 << 30, logprob_budget_bytes=16 << 30, auto_kv_rows=0, auto_kv_cap=64,
                  logprob_dtype="float32", glb_attention=True, merge_mlp=True, contract=None, gemms="library",
-                 split_gemms=True):
+                 split_gemms=True, w4_gemm="auto"):
         """The caller's `hf_model` is never modified (hf.py:114-140 leaves it alone too): with `fuse_activations` or
         `glb_attention` the forwards of this backend run on a private SHADOW of its module tree that shares every weight
         (fuse.shadow_model); `self.model` stays the caller's object.
@@ -215,7 +249,10 @@ class AsyncAmdLM(AsyncLM):
         split_gemms: in the shadow, GPT-2's float32 Conv1D projections run this library's split-bf16 MFMA GEMM (fuse.py
         SplitConv1D: fp32-accurate, the MLP's tanh GELU in its epilogue) for the batch sizes where it was measured faster
         than the library; it keeps a derived bf16 image of each such weight (6 bytes per element: 510 MB for GPT-2 small).
-        `gemms` still decides every GEMM this path does not take.  False: not swapped."""
+        `gemms` still decides every GEMM this path does not take.  False: not swapped.
+        w4_gemm: how the 4-bit layers of a quantised model (quant.W4Linear) multiply - "auto": glb_w4_gemm on the 4-bit image
+        for the row counts where it was measured faster (quant.MIN_ROWS_FUSED), dequantise + library GEMM otherwise;
+        "fused" / "dequant": one path wherever it is able to serve the call (tests, A/Bs)."""
         self.model = hf_model
         self.tokenizer = hf_tokenizer
         self.device = hf_model.device
@@ -236,6 +273,12 @@ class AsyncAmdLM(AsyncLM):
                 raise ValueError(f"contract must be one of {engine.CONTRACTS}, got {contract!r}")
             engine.contract = contract
         self.engine = engine
+        from .quant import W4_GEMM_MODES
+
+        if w4_gemm not in W4_GEMM_MODES:
+            raise ValueError(f"w4_gemm must be one of {W4_GEMM_MODES}, got {w4_gemm!r}")
+        self.w4_gemm = w4_gemm
+        self.quantization = hf_model.__dict__.get("_glb_quantization")  # quantize_model's report; None: not quantised
         if logprob_dtype not in ("float32", "model"):
             raise ValueError(f"logprob_dtype must be 'float32' or 'model', got {logprob_dtype!r}")
         self._lp_model_dtype = logprob_dtype == "model"
@@ -261,6 +304,9 @@ class AsyncAmdLM(AsyncLM):
                 from .kv import use_glb_attention
 
                 self.glb_attention = use_glb_attention(self._net, self.engine)
+        from .quant import bind as _bind_w4
+
+        _bind_w4(self._net, self.engine, w4_gemm)
         self._head = self._net.get_output_embeddings()
         if self._head is None:
             raise NotImplementedError(f"{type(hf_model).__name__} has no output embedding (get_output_embeddings() is None)")

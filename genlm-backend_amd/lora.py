@@ -41,6 +41,8 @@ def _module_kind(mod):
         return "linear"
     if type(mod).__name__ in ("Conv1D", "SplitConv1D") and hasattr(mod, "nf"):
         return "conv1d"
+    if type(mod).__name__ == "W4Linear":
+        return "w4"  # (quant.py: loadable and checked for shape, but `set_lora` cannot merge into 4-bit codes)
     return None
 
 
@@ -129,8 +131,12 @@ def load_adapter(lora_path, model, name):
         kind = _module_kind(mod)
         if kind is None:
             raise ValueError(f"adapter {path}: {mpath} is a {type(mod).__name__}, not nn.Linear or Conv1D")
-        w = mod.weight
-        k_in, n_out = (w.shape[0], w.shape[1]) if kind == "conv1d" else (w.shape[1], w.shape[0])
+        if kind == "w4":
+            k_in, n_out = mod.in_features, mod.out_features
+            w = torch.empty((n_out, k_in), device="meta")  # (for the messages below: a 4-bit module has no weight)
+        else:
+            w = mod.weight
+            k_in, n_out = (w.shape[0], w.shape[1]) if kind == "conv1d" else (w.shape[1], w.shape[0])
         a, b = ab["lora_A"], ab["lora_B"]
         r = int(_pattern_value(rank_pattern, mpath, r0))
         alpha = float(_pattern_value(alpha_pattern, mpath, alpha0))
@@ -160,6 +166,11 @@ class MergedLora:
     def __init__(self, adapter, net, engine):
         self.adapter, self.net, self.engine = adapter, net, engine
         self.slots = {}  # path -> [module, shared dict, private dict, base key]
+        quantised = [p for p in adapter.modules if type(net.get_submodule(p)).__name__ == "W4Linear"]
+        if quantised:
+            raise ValueError(f"adapter {adapter.name}: {quantised[0]} (and {len(quantised) - 1} more) are 4-bit quantised "
+                             "modules (W4Linear); LoRA is served by merging into the weight, which a quantised base does not "
+                             "allow - load the model without bitsandbytes_opts")
         for p in adapter.modules:
             mod = net.get_submodule(p)
             self.slots[p] = [mod, mod._parameters, None, None]

@@ -966,6 +966,7 @@ class SisBenchWorkload:
         # through the output embedding (tools/gemm_table.py divides by the Tensile kernels' time in a rocprofv3 trace)
         body = self.llm._body
         self._lin_w = sum(m.weight.numel() for m in body.modules() if type(m).__name__ in ("Linear", "Conv1D", "SplitConv1D"))
+        self._lin_w += sum(m.in_features * m.out_features for m in body.modules() if type(m).__name__ == "W4Linear")
         self._head_w = self.llm._head.weight.numel()
         # set-up, not measurement: one untimed pass over the loop's ten batch shapes (context lengths 8..17) so that
         # GEMM algorithm selection and allocator growth happen before bench.py's own warm-up / timed steps

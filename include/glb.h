@@ -731,6 +731,60 @@ size_t glb_lora_merge_workspace_bytes(int32_t n_jobs);
 int glb_lora_merge(const glb_lora_job *jobs /* host */, int32_t n_jobs, void *workspace /* device */, size_t workspace_bytes,
                    void *hip_stream);
 
+/*
+ * 4-bit block-quantised weights: the block format bitsandbytes uses for Linear4bit, without double
+ * quantisation.  A weight W[n, k] (nn.Linear layout; `transposed`: the memory holds W^T [k, n], GPT-2's Conv1D) is cut into
+ * blocks of 64 consecutive elements along k; a block stores absmax = max |w| as float32 and 64 four-bit codes into a
+ * 16-entry float32 codebook that the caller passes as data (`codebook`: HOST pointer, 16 finite floats, copied into the
+ * launch; NF4 and FP4 are two tables).  Arithmetic contract, restated bit for bit in tests/quant4_engine.py:
+ *     quantise:   sort the codebook ascending (c_0 .. c_15), m_i = (c_i + c_{i+1}) * 0.5f in float32; the code of w is the
+ *                 sorted entry whose index is the number of float32 products m_i * absmax strictly below f32(w)
+ *     dequantise: w' = codebook[code] * absmax, one float32 multiplication, then one round-to-nearest-even to the dtype
+ * Weights must be finite.  glb_w4_bytes(n, k) = n k / 2 + 4 n k / 64 bytes of image (16-byte aligned), 0 for a shape that
+ * is not served (k % 64 != 0, more than 2^34 elements); the order inside the image is private to the library
+ * (glb_w4_dequantize inverts glb_w4_quantize).  `dtype` / `w` / `ldw` (row pitch in elements): the source of quantize,
+ * the destination of dequantize.  glb_w4_gemm: Y[m, n] = X[m, k] . W'^T (+ bias), X, Y and bias of one 16-bit dtype
+ * (GLB_BF16 / GLB_F16), rows of unit inner stride with pitches ldx / ldy, reading the image directly: codes are expanded
+ * in registers to exactly glb_w4_dequantize's 16-bit element, multiplied on v_mfma_f32_16x16x32, summed in float32 -
+ * K is split over workgroups by a rule that depends on (n, k) only, the slices are added in ascending order by a second
+ * launch (no atomics: same bits every run) - and rounded once.  It is the few-row kernel: 1 <= m <=
+ * glb_w4_gemm_max_rows(), n % 16 == 0, X and ldx 16-byte aligned; everything else returns GLB_EUNSUPPORTED (the caller
+ * dequantises and runs its library GEMM).  `workspace`: glb_w4_gemm_workspace_bytes(m, n, k) bytes of device memory,
+ * 16-byte aligned (0: the call is not served).  Argument errors return GLB_EINVAL before any GPU work; launches go on
+ * the given stream, allocate nothing and may be captured into a hipGraph.
+ */
+typedef struct glb_w4_args {
+  uint32_t struct_size; /* sizeof(glb_w4_args) - ABI guard */
+  int32_t dtype;        /* GLB_F32 / GLB_BF16 / GLB_F16 of w */
+  int32_t transposed;   /* 0: w is [n, k]; 1: w is [k, n] */
+  int64_t n, k;
+  void *w; /* read by quantize, written by dequantize */
+  int64_t ldw;
+  const float *codebook; /* host, 16 entries */
+  void *image;
+  size_t image_bytes;
+} glb_w4_args;
+typedef struct glb_w4_gemm_args {
+  uint32_t struct_size; /* sizeof(glb_w4_gemm_args) - ABI guard */
+  int32_t dtype;        /* GLB_BF16 / GLB_F16: x, bias and y */
+  int64_t m, n, k;
+  const void *x;
+  int64_t ldx;
+  const void *image;
+  const float *codebook; /* host, 16 entries */
+  const void *bias;      /* [n], nullable */
+  void *y;
+  int64_t ldy;
+  void *workspace;
+  size_t workspace_bytes;
+} glb_w4_gemm_args;
+size_t glb_w4_bytes(int64_t n, int64_t k);
+int glb_w4_quantize(const glb_w4_args *args, void *hip_stream);
+int glb_w4_dequantize(const glb_w4_args *args, void *hip_stream);
+int glb_w4_gemm_max_rows(void);
+size_t glb_w4_gemm_workspace_bytes(int64_t m, int64_t n, int64_t k);
+int glb_w4_gemm(const glb_w4_gemm_args *args, void *hip_stream);
+
 /* Philox4x32-10 block function, exposed so hosts can reproduce the device draws. */
 void glb_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 
