@@ -14,18 +14,23 @@ trie's nodes instead (mlx.py:177-318, cache.py:103-191).  `AutoKV` is that idea 
   * the table rows of everything that now holds a context are rewritten.
 
 Lookup and block table run on the device (glb_match_rows, glb_kv_plan: one launch each), like `DeviceSIS._step_shared_kv`;
-the host reads the numbers of rows of each kind from the call's one D2H copy and launches the forwards.
+the host reads the numbers of rows of each kind from the call's one D2H copy and launches the forwards (kv.SlabRunner).
 """
 import torch
+
+from .kv import SlabRunner
 
 
 class AutoKV:
     def __init__(self, llm, rows, cap=64, in_place=0.75, graph=True):
         self.llm, self.eng, self.dev = llm, llm.engine, llm.device
-        self.R, self.cap, self.in_place, self.graph = int(rows), int(cap), in_place, graph
-        self.pkv = None
-        self._slab_fwd = None
+        self.R, self.cap = int(rows), int(cap)
+        self.kv = SlabRunner(llm, rows, cap, in_place, graph)  # the slabs (they outlive a reset) and the forwards over them
         self.reset()
+
+    pkv = property(lambda self: self.kv.pkv)
+    _slab_fwd = property(lambda self: self.kv._slab_fwd)
+    in_place = property(lambda self: self.kv.in_place, lambda self, v: setattr(self.kv, "in_place", v))
 
     def reset(self):
         dev, R, cap = self.dev, self.R, self.cap
@@ -43,7 +48,7 @@ class AutoKV:
         group_of, rep, ng: glb_group_contexts' output.  Returns (logits [U, V], row_of_group int32 [n] device: the
         logits row of dedup group g, group_of_row int64 [U]: its inverse, U, extra: the host values of `extra_head`'s
         device scalars - they ride on the call's one D2H copy)."""
-        eng, llm, dev, R, cap = self.eng, self.llm, self.dev, self.R, self.cap
+        eng, dev, R, cap = self.eng, self.dev, self.R, self.cap
         # the row that holds every distinct context, or its first L - 1 tokens (every candidate's tokens are compared:
         # a hash never decides alone), then the block table - both on the device, one launch each
         old, gh = eng.match_rows(tok_d, st_d, ln_d, rep, ng, self.row_tok, self.row_len, self.row_hash)
@@ -51,8 +56,8 @@ class AutoKV:
         plan = eng.kv_plan(group_of, rep, ng, old, ln_d, R, cap, stamps=self.stamp, call_no=self.t,
                            table=(self.row_tok, self.row_len, self.row_hash, gh, tok_d, st_d))
         head = torch.cat([plan["head"][:6], *[e.to(torch.int32).view(1) for e in extra_head]]).cpu().tolist()  # the one D2H copy
-        U, nA, nB, n_copied, n_unkept, l_max_b = head[:6]
-        extra = head[6:]
+        counts, extra = head[:6], head[6:]
+        U, nA, nB, n_copied, n_unkept, _ = counts
         st = self.stats
         st["calls"] += 1
         st["forward_rows"] += U
@@ -60,59 +65,10 @@ class AutoKV:
         st["encoded_rows"] += nB
         st["copied_rows"] += n_copied
         st["unkept_rows"] += n_unkept
-        parts = []
-        if nA:
-            if n_copied:
-                self.pkv.copy_rows(plan["copy_src"], plan["copy_len"])
-            if self.in_place is not None and nA >= self.in_place * R:
-                # rows outside this forward still hold contexts the table knows: their dummy token is appended BEHIND what
-                # they hold (a full row has no such place: the table forgets it); rows being filled from an encoding take
-                # theirs at position 0, which the fill overwrites
-                ctx_r = plan["ctx_of_row"]
-                is_a, idle = ctx_r >= 0, ctx_r == -1
-                self.row_len.masked_fill_(idle & (self.row_len >= cap), 0)
-                zero = torch.zeros_like(ctx_r)
-                pos_d = torch.where(is_a, plan["pos_of_row"], torch.where(idle, self.row_len.clamp(max=cap - 1), zero))
-                at = st_d[ctx_r.clamp_min(0).long()] + torch.where(is_a, pos_d, zero).long()
-                ids = tok_d[at].view(-1, 1).long()
-                # (a new body: set_lora made the backend's shadow after this forward was built over the caller's model)
-                if self._slab_fwd is None or self._slab_fwd.pkv is not self.pkv or self._slab_fwd.body is not llm._body:
-                    from .kv import SlabForward
-
-                    self._slab_fwd = SlabForward(self.pkv, llm._body, graph=self.graph, owner=llm)
-                hidden = self._slab_fwd(ids, pos_d)
-                parts.append(llm._lm_head(hidden.index_select(0, plan["rows_a"][:nA].long())))
-                st["in_place_calls"] += 1
-            else:
-                pos_a = plan["pos_a"][:nA].contiguous()
-                ids = tok_d[st_d[plan["ctx_a"][:nA].long()] + pos_a.long()].view(-1, 1).long()
-                self.pkv.set_forward(plan["rows_a"][:nA].contiguous(), pos_a)
-                out = llm._body(input_ids=ids, position_ids=pos_a.view(-1, 1).long(),
-                                attention_mask=self.pkv.attention_mask(pos_a), past_key_values=self.pkv, use_cache=True)
-                parts.append(llm._lm_head(out.last_hidden_state[:, 0]))
-        if nB:
-            sel = plan["ctx_b"][:nB].contiguous()
-            pad_id = getattr(llm.tokenizer, "pad_token_id", None) if llm.tokenizer is not None else None
-            ids, am, pos, last = eng.gather_padded(tok_d, st_d, ln_d, sel, nB, None, 0 if pad_id is None else pad_id, 0,
-                                                   l_max_b)
-            stored = nB > n_unkept
-            out = llm._body(input_ids=ids, attention_mask=am, position_ids=pos, use_cache=stored)
-            parts.append(llm._lm_head(out.last_hidden_state[torch.arange(nB, device=dev), last.long()]))
-            if stored:
-                srcs = [(ly.keys.contiguous(), ly.values.contiguous()) for ly in out.past_key_values.layers]
-                if self.pkv is None:
-                    from .kv import SharedSlabKV
-
-                    self.pkv = SharedSlabKV(eng, R, cap, len(srcs))
-                rows_b = plan["rows_b"][:nB].long()
-                slot = torch.where(rows_b >= 0, rows_b, torch.full_like(rows_b, R))  # (rows nobody keeps: a slot past the end)
-                src_full = torch.full((R + 1,), -1, dtype=torch.int32, device=dev)
-                len_full = torch.zeros(R + 1, dtype=torch.int32, device=dev)
-                src_full[slot] = torch.arange(nB, dtype=torch.int32, device=dev)
-                len_full[slot] = ln_d[sel.long()]
-                src_full[R] = -1
-                self.pkv.fill_rows(srcs, src_full[:R].contiguous(), len_full[:R].contiguous())
-        logits = parts[0] if len(parts) == 1 else torch.cat(parts)
+        # rows outside an in-place forward still hold contexts the table knows: hence row_len (SlabRunner.run)
+        logits, _, in_place = self.kv.run(plan, counts, lambda ctx, pos: tok_d[st_d[ctx] + pos], (tok_d, st_d, ln_d),
+                                          pad_id=self.llm._pad_id, row_len=self.row_len)
+        st["in_place_calls"] += int(in_place)
         row_of_group = plan["logits_row"]
         group_of_row = torch.empty(U, dtype=torch.int64, device=dev)
         group_of_row[row_of_group[:U].long()] = torch.arange(U, device=dev)

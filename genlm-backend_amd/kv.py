@@ -6,14 +6,19 @@
   particle owns row i of every slab, the new token's K/V is written in place at its own position (glb_kv_append:
   ragged lengths, no torch.cat regrow) and a resampling step is one gather launch over all layers
   (glb_kv_gather_rows) into the second slab set.
+* `SlabRunner` — the slabs of one population and the forwards over them: executes the block table glb_kv_plan decided
+  (`DeviceSIS._step_shared_kv`, `autokv.AutoKV`).
+* `PrefixTable` — the device table of cached prompt prefixes and the `DynamicCache` a batch that uses them is run with.
 * `PrefixLRU` — byte-budgeted least-recently-used store for the prompt prefixes `cache_kv` pins (hf.py:155-164);
   the eviction policy of cache.py:103-191 (`DynamicTokenTrie`), applied to whole prefix slabs.
 """
 import gc
+import itertools
 from collections import OrderedDict
 
+import numpy as np
 import torch
-from transformers.cache_utils import Cache, CacheLayerMixin
+from transformers.cache_utils import Cache, CacheLayerMixin, DynamicCache
 
 
 # ---- the attention kernels of the path behind transformers' attention interface -----------------------------------------
@@ -385,6 +390,129 @@ class SlabForward:
         self.pkv.set_forward_in_place(s_pos)  # (the captured launches read the static buffers)
         g.replay()
         return hidden
+
+
+class SlabRunner:
+    """The KV slabs of one population (`pkv`: a `SharedSlabKV` made by the first encoding that keeps its KV, or the private
+    `SlabKV` its owner puts here), the in-place forward over them, and `run`: the forwards of one glb_kv_plan block table.
+    R rows of `cap` positions; `in_place`: the fraction of the R rows from which the one-token forward runs on the slab
+    where the rows lie (None: never); `graph`: that forward is replayed from a hipGraph (`SlabForward`)."""
+
+    def __init__(self, llm, rows, cap, in_place=0.75, graph=True):
+        self.llm, self.R, self.cap, self.in_place, self.graph = llm, int(rows), int(cap), in_place, graph
+        self.pkv = None
+        self._slab_fwd = None
+
+    def slab_forward(self):
+        """The in-place forward over the slabs as they are now: made again when the slabs were replaced, or the body (set_lora
+        makes the backend's shadow after a forward was built over the caller's model)."""
+        fwd, body = self._slab_fwd, self.llm._body
+        if fwd is None or fwd.pkv is not self.pkv or fwd.body is not body:
+            fwd = self._slab_fwd = SlabForward(self.pkv, body, graph=self.graph, owner=self.llm)
+        return fwd
+
+    @torch.no_grad()
+    def run(self, plan, counts, token_at, batch, pad_id=0, row_len=None):
+        """The forwards of the block table `plan` (engine.kv_plan).  counts: (U, nA, nB, n_copied, n_unkept, l_max_b), the
+        head words the caller read with its one D2H copy (nothing is read back here).  Rows of kind A - their prefix sits
+        in a slab row - are fed ONE token, `token_at(ctx, pos)` (int64 index tensors -> the tokens at position pos of
+        contexts ctx), after the copy-on-append copies; rows of kind B are encoded from the ragged `batch` = (tokens,
+        starts, lengths), padded with `pad_id`, and their KV kept where the plan names a row.  row_len: int32 [R], what
+        every slab row holds according to the caller's table - given, a row outside an in-place forward takes its dummy
+        token BEHIND what it holds (a full row has no such place: its length is zeroed, the table forgets it) and a row
+        being filled from an encoding at position 0, which the fill overwrites; absent, `pos_of_row` is taken as it is.
+        Returns (logits [U, V]: A rows, then B rows; tokens fed to the body; whether the A part ran in place)."""
+        llm, R, cap = self.llm, self.R, self.cap
+        eng, dev = llm.engine, llm.device
+        U, nA, nB, n_copied, n_unkept, l_max_b = counts
+        parts, fed, in_place = [], nB * l_max_b, False
+        if nA:
+            if n_copied:
+                self.pkv.copy_rows(plan["copy_src"], plan["copy_len"])
+            in_place = self.in_place is not None and nA >= self.in_place * R
+            if in_place:
+                # most rows are live: the forward runs on the slab rows where they lie (rows outside it ride along with a
+                # dummy token) instead of gathering the live rows' prefixes into batch order
+                ctx_r, pos_d = plan["ctx_of_row"], plan["pos_of_row"]
+                at = pos_d
+                if row_len is not None:
+                    is_a, idle = ctx_r >= 0, ctx_r == -1
+                    row_len.masked_fill_(idle & (row_len >= cap), 0)
+                    zero = torch.zeros_like(ctx_r)
+                    pos_d = torch.where(is_a, pos_d, torch.where(idle, row_len.clamp(max=cap - 1), zero))
+                    at = torch.where(is_a, pos_d, zero)
+                ids = token_at(ctx_r.clamp_min(0).long(), at.long()).view(-1, 1).long()
+                hidden = self.slab_forward()(ids, pos_d)
+                parts.append(llm._lm_head(hidden.index_select(0, plan["rows_a"][:nA].long())))
+                fed += R
+            else:
+                pos_a = plan["pos_a"][:nA].contiguous()
+                ids = token_at(plan["ctx_a"][:nA].long(), pos_a.long()).view(-1, 1).long()
+                self.pkv.set_forward(plan["rows_a"][:nA].contiguous(), pos_a)
+                out = llm._body(input_ids=ids, position_ids=pos_a.view(-1, 1).long(),
+                                attention_mask=self.pkv.attention_mask(pos_a), past_key_values=self.pkv, use_cache=True)
+                parts.append(llm._lm_head(out.last_hidden_state[:, 0]))
+                fed += nA
+        if nB:
+            tok_d, st_d, ln_d = batch
+            sel = plan["ctx_b"][:nB].contiguous()
+            ids, am, pos, last = eng.gather_padded(tok_d, st_d, ln_d, sel, nB, None, pad_id, 0, l_max_b)
+            stored = nB > n_unkept  # some row keeps the KV of what is encoded here
+            out = llm._body(input_ids=ids, attention_mask=am, position_ids=pos, use_cache=stored)
+            parts.append(llm._lm_head(out.last_hidden_state[torch.arange(nB, device=dev), last.long()]))
+            if stored:
+                srcs = [(ly.keys.contiguous(), ly.values.contiguous()) for ly in out.past_key_values.layers]
+                if self.pkv is None:
+                    self.pkv = SharedSlabKV(eng, R, cap, len(srcs))
+                rows_b = plan["rows_b"][:nB].long()
+                slot = torch.where(rows_b >= 0, rows_b, torch.full_like(rows_b, R))  # (rows nobody keeps: a slot past the end)
+                src_full = torch.full((R + 1,), -1, dtype=torch.int32, device=dev)
+                len_full = torch.zeros(R + 1, dtype=torch.int32, device=dev)
+                src_full[slot] = torch.arange(nB, dtype=torch.int32, device=dev)
+                len_full[slot] = ln_d[sel.long()]
+                src_full[R] = -1
+                self.pkv.fill_rows(srcs, src_full[:R].contiguous(), len_full[:R].contiguous())
+        return (parts[0] if len(parts) == 1 else torch.cat(parts)), fed, in_place
+
+
+def ragged(seqs):
+    """Host arrays of a ragged batch of token sequences: (tokens int32 [total], starts int64 [n], lengths int32 [n])."""
+    n = len(seqs)
+    lens = np.fromiter(map(len, seqs), np.int32, n)
+    starts = np.zeros(n, np.int64)
+    starts[1:] = np.cumsum(lens[:-1])
+    return np.fromiter(itertools.chain.from_iterable(seqs), np.int32, int(lens.sum())), starts, lens
+
+
+class PrefixTable:
+    """Device table of cached prompt prefixes (hf.py:155-164), from [(KVPrefix, its token ids)]: `tokens` / `starts` /
+    `lengths` for glb_match_prefixes (left out when the ids are None: a batch that names its prefixes itself) and
+    per-layer pointer tables for glb_gather_kv_padded.  Holds the prefixes: the pointers stay valid while it lives."""
+
+    def __init__(self, entries, device):
+        self.kvs = kvs = [kv for kv, _ in entries]
+        p0 = kvs[0]
+        for p in kvs[1:]:  # one gather launch per layer serves every prefix: they must come from one model
+            if (p.heads, p.head_dim, p.dtype, len(p.layers)) != (p0.heads, p0.head_dim, p0.dtype, len(p0.layers)):
+                raise ValueError("cached prefixes of different KV shapes in one batch")
+        self.n = len(kvs)
+        self.tokens = self.starts = None
+        if entries[0][1] is not None:
+            flat, starts, lens = ragged([t for _, t in entries])
+            self.tokens, self.starts = torch.from_numpy(flat).to(device), torch.from_numpy(starts).to(device)
+        else:
+            lens = np.array([len(kv) for kv in kvs], np.int32)
+        self.lengths, self.p_max = torch.from_numpy(lens).to(device), int(lens.max())
+        self.ptrs = [[torch.tensor([kv.layers[l][j].data_ptr() for kv in kvs], dtype=torch.int64, device=device)
+                      for j in range(2)] for l in range(len(p0.layers))]
+
+    def cache_for(self, engine, pref_u):
+        """The `DynamicCache` of a batch whose row u continues prefix pref_u[u] (int32 device; -1: none): every layer's K
+        and V padded to `p_max` positions, one launch each (glb_gather_kv_padded)."""
+        p0 = self.kvs[0]
+        return DynamicCache(ddp_cache_data=[tuple(engine.gather_kv_padded(self.ptrs[l][j], self.lengths, pref_u, p0.heads,
+                                                                           p0.head_dim, self.p_max, p0.dtype)
+                                                  for j in range(2)) for l in range(len(p0.layers))])
 
 
 class PrefixLRU:

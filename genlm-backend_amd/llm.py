@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from .cache import KVPrefix, RowLRU, TokenTrie
+from .kv import PrefixLRU, PrefixTable, ragged
 from .tokenization import decode_vocab
 
 MASK_NONE, MASK_BITS, MASK_F32 = 0, 1, 2
@@ -111,6 +112,27 @@ class Query:
         self.first_new = first_new  # first prompt position whose next-token row the caller needs
         self.kind = kind            # "logprobs" | "step"
         self.mask_id = mask_id
+
+
+class _Slot:
+    """Stand-in for a query's future on the synchronous paths.  reraise: an exception handed over is raised where it is
+    set instead of being kept in `exc`."""
+
+    __slots__ = ("value", "exc", "reraise")
+
+    def __init__(self, reraise=False):
+        self.value, self.exc, self.reraise = None, None, reraise
+
+    def done(self):
+        return self.value is not None or self.exc is not None
+
+    def set_result(self, v):
+        self.value = v
+
+    def set_exception(self, e):
+        if self.reraise:
+            raise e
+        self.exc = e
 
 
 class AsyncAmdLM(AsyncLM):
@@ -312,8 +334,6 @@ class AsyncAmdLM(AsyncLM):
             raise NotImplementedError(f"{type(hf_model).__name__} has no output embedding (get_output_embeddings() is None)")
         self._head_mult, self._head_cap = self._post_head(self.model.config)
         self._body = self._net.base_model
-        from .kv import PrefixLRU
-
         self._kv_tokens = {}  # id(trie node) -> the prefix's token ids (for the device prefix table)
         self._ptab = None
         # prompt prefixes pinned by cache_kv, least recently used out first; an entry that leaves the store takes its
@@ -379,6 +399,11 @@ class AsyncAmdLM(AsyncLM):
             self.close()
         except Exception:  # interpreter shutdown
             pass
+
+    @property
+    def _pad_id(self):
+        pad_id = getattr(self.tokenizer, "pad_token_id", None) if self.tokenizer is not None else None
+        return 0 if pad_id is None else pad_id
 
     def _forget_prefix(self, node):
         self._kv_tokens.pop(id(node), None)
@@ -589,13 +614,7 @@ class AsyncAmdLM(AsyncLM):
                 and all(q.kind == "logprobs" and q.past is None and q.first_new == len(q.prompt) - 1 for q in queries)):
             # every request wants the row after its LAST token only (its shorter prefixes are in the trie - a population
             # that grew by one token): the contexts find their KV rows (autokv.AutoKV) and one token each is fed
-            import itertools
-
-            lens = np.fromiter((len(q.prompt) for q in queries), np.int32, n)
-            flat = np.fromiter(itertools.chain.from_iterable(q.prompt for q in queries), np.int32, int(lens.sum()))
-            starts = np.zeros(n, np.int64)
-            starts[1:] = np.cumsum(lens[:-1])
-            tok_d, st_d, ln_d = (torch.from_numpy(a).to(dev) for a in (flat, starts, lens))
+            tok_d, st_d, ln_d = (torch.from_numpy(a).to(dev) for a in ragged([q.prompt for q in queries]))
             group_of, rep, ng = eng.group_contexts(tok_d, st_d, ln_d)
             logits, row_of_group, _, U, _ = self._auto_kv.logits(tok_d, st_d, ln_d, group_of, rep, ng)
             lp = self._log_softmax(logits)
@@ -648,8 +667,6 @@ class AsyncAmdLM(AsyncLM):
 
         p_max = max(q.past_len for q in uniq)
         l_max = max(len(q.prompt) for q in uniq)
-        pad_id = getattr(self.tokenizer, "pad_token_id", None) if self.tokenizer is not None else None
-        pad_id = 0 if pad_id is None else pad_id
 
         # -- ragged -> padded gather (glb_gather_padded).  starts/lengths are shifted so that
         #    tokens[start + base + t] is prompt token t, with base = past_len.
@@ -657,28 +674,15 @@ class AsyncAmdLM(AsyncLM):
         base_d = torch.from_numpy(past_len).to(dev)
         st_adj = st_d + 2 - base_d.to(torch.int64)
         ln_adj = ln_d - 2 + base_d
-        ids, am, pos, _last = eng.gather_padded(tok_d, st_adj, ln_adj, rep_d, U, base_d, pad_id, p_max, l_max)
+        ids, am, pos, _last = eng.gather_padded(tok_d, st_adj, ln_adj, rep_d, U, base_d, self._pad_id, p_max, l_max)
 
         # -- batched prefix KV (glb_gather_kv_padded), one launch per layer and K/V
         cache = None
         if p_max > 0:
-            from transformers import DynamicCache
-
             slot_of_u = np.array([prefix_slot[id(q.past)] - 1 if q.past is not None else -1 for q in uniq], np.int32)
-            slot_d = torch.from_numpy(slot_of_u).to(dev)
-            plen_d = torch.tensor([len(p) for p in prefixes], dtype=torch.int32, device=dev)
-            p0 = prefixes[0]
-            for p in prefixes[1:]:  # one gather launch per layer serves every prefix: they must come from one model
-                if (p.heads, p.head_dim, p.dtype, len(p.layers)) != (p0.heads, p0.head_dim, p0.dtype, len(p0.layers)):
-                    raise ValueError("cached prefixes of different KV shapes in one batch")
-            data = []
-            for layer in range(len(p0.layers)):
-                kv = []
-                for j in range(2):
-                    ptrs = torch.tensor([p.layers[layer][j].data_ptr() for p in prefixes], dtype=torch.int64, device=dev)
-                    kv.append(eng.gather_kv_padded(ptrs, plen_d, slot_d, p0.heads, p0.head_dim, p_max, p0.dtype))
-                data.append(tuple(kv))
-            cache = DynamicCache(ddp_cache_data=data)
+            # (a table of this batch's prefixes alone; it checks that they share one KV shape.  Every prefix is some
+            # unique query's: the table's longest is p_max)
+            cache = PrefixTable([(p, None) for p in prefixes], dev).cache_for(eng, torch.from_numpy(slot_of_u).to(dev))
 
         # -- transformer body (PyTorch-ROCm; the only MFMA work on the path)
         hidden = self._body(input_ids=ids, attention_mask=am, position_ids=pos, past_key_values=cache,
@@ -825,21 +829,6 @@ class AsyncAmdLM(AsyncLM):
 
     def _evaluate_one(self, prompt, past, first_new):
         """Synchronous single-query evaluation through the same batched machinery."""
-
-        class _Slot:
-            def __init__(self):
-                self.value = None
-                self.exc = None
-
-            def done(self):
-                return self.value is not None or self.exc is not None
-
-            def set_result(self, v):
-                self.value = v
-
-            def set_exception(self, e):
-                self.exc = e
-
         slot = _Slot()
         self._evaluate([Query(prompt, slot, past, first_new=first_new)])
         return slot.value
@@ -995,27 +984,15 @@ class AsyncAmdLM(AsyncLM):
 
     # ---- batched submit: a whole population per call (no per-query futures, no per-query Python) ----------------------
     def _prefix_table(self):
-        """Device table of the prompts whose KV `cache_kv` holds (tokens / starts / lengths for glb_match_prefixes and
-        per-layer pointer tables for glb_gather_kv_padded); rebuilt when the set of cached prefixes changed."""
+        """The prompts whose KV `cache_kv` holds: their device table (kv.PrefixTable; None when there are none), their
+        trie nodes and their number; rebuilt when the set of cached prefixes changed."""
         entries = [(node, self._kv_tokens.get(id(node))) for node, _ in self._kv_lru._od.values()]
         entries = [(n, t) for n, t in entries if t is not None and n.past_key_values is not None]
         key = tuple(id(n) for n, _ in entries)
         if self._ptab is not None and self._ptab["key"] == key:
             return self._ptab
-        if not entries:
-            self._ptab = dict(key=key, n=0)
-            return self._ptab
-        dev = self.device
-        kvs = [n.past_key_values for n, _ in entries]
-        lens = np.array([len(t) for _, t in entries], np.int32)
-        starts = np.zeros(len(entries), np.int64)
-        starts[1:] = np.cumsum(lens[:-1])
-        flat = np.concatenate([np.asarray(t, np.int32) for _, t in entries])
-        ptrs = [[torch.tensor([kv.layers[l][j].data_ptr() for kv in kvs], dtype=torch.int64, device=dev)
-                 for j in range(2)] for l in range(len(kvs[0].layers))]
-        self._ptab = dict(key=key, n=len(entries), kvs=kvs, nodes=[n for n, _ in entries], tokens=torch.from_numpy(flat).to(dev),
-                          starts=torch.from_numpy(starts).to(dev), lengths=torch.from_numpy(lens).to(dev), ptrs=ptrs,
-                          p_max=int(lens.max()))
+        table = PrefixTable([(n.past_key_values, t) for n, t in entries], self.device) if entries else None
+        self._ptab = dict(key=key, n=len(entries), nodes=[n for n, _ in entries], table=table)
         return self._ptab
 
     @torch.no_grad()
@@ -1026,19 +1003,13 @@ class AsyncAmdLM(AsyncLM):
         ragged-to-padded gather, forward, lm_head on the last position, fused step - but the ragged batch is built
         once (three host arrays) and nothing is done per query in Python.  Returns (logZ float32 [n], token int32 [n])
         as NumPy arrays."""
-        import itertools
-
         dev = self.device
         n = len(contexts)
         if n == 0:
             return np.zeros(0, np.float32), np.zeros(0, np.int32)
-        lens = np.fromiter(map(len, contexts), np.int32, n)
+        flat, starts, lens = ragged(contexts)
         if int(lens.min()) == 0:
             raise ValueError("Token ids must not be empty")
-        total = int(lens.sum())
-        flat = np.fromiter(itertools.chain.from_iterable(contexts), np.int32, total)
-        starts = np.zeros(n, np.int64)
-        starts[1:] = np.cumsum(lens[:-1])
         mid_d = None
         if self._mask_kind != MASK_NONE:
             mid = np.zeros(n, np.int32) if mask_ids is None else np.ascontiguousarray(mask_ids, dtype=np.int32)
@@ -1080,12 +1051,13 @@ class AsyncAmdLM(AsyncLM):
         self._lora_sync()
         group_of, rep, ng = eng.group_contexts(tok_d, st_d, ln_d)
         P = self._prefix_table()
+        T = P["table"]
         base, pref = None, None
         head = [ng[0]]
         used_d = None
         auto = self._auto_kv if (self._auto_kv is not None and not P["n"]) else None
         if P["n"]:
-            pref, base = eng.match_prefixes(tok_d, st_d, ln_d, P["tokens"], P["starts"], P["lengths"])
+            pref, base = eng.match_prefixes(tok_d, st_d, ln_d, T.tokens, T.starts, T.lengths)
             head.append((ln_d - base).max().to(torch.int32))
             # which cached prefixes this call uses (they count as recently used, like walk_cache's touch)
             used_d = torch.zeros(P["n"] + 1, dtype=torch.int32, device=dev).index_fill_(0, (pref + 1).long(), 1)[1:]
@@ -1116,18 +1088,9 @@ class AsyncAmdLM(AsyncLM):
         U = head[0]
         l_max = head[1] if (P["n"] or l_max is None) else l_max
         by_row = bool(head[-1]) if mid_d is not None else False
-        p_max = P["p_max"] if P["n"] else 0
-        pad_id = getattr(self.tokenizer, "pad_token_id", None) if self.tokenizer is not None else None
-        ids, am, pos, last = eng.gather_padded(tok_d, st_d, ln_d, rep, U, base, 0 if pad_id is None else pad_id, p_max, l_max)
-        cache = None
-        if P["n"]:
-            from transformers import DynamicCache
-
-            kv0 = P["kvs"][0]
-            pref_u = pref[rep[:U].long()].contiguous()
-            data = [tuple(eng.gather_kv_padded(P["ptrs"][l][j], P["lengths"], pref_u, kv0.heads, kv0.head_dim, p_max,
-                                               kv0.dtype) for j in range(2)) for l in range(len(kv0.layers))]
-            cache = DynamicCache(ddp_cache_data=data)
+        p_max = T.p_max if P["n"] else 0
+        ids, am, pos, last = eng.gather_padded(tok_d, st_d, ln_d, rep, U, base, self._pad_id, p_max, l_max)
+        cache = T.cache_for(eng, pref[rep[:U].long()].contiguous()) if P["n"] else None
         hidden = self._body(input_ids=ids, attention_mask=am, position_ids=pos, past_key_values=cache,
                             use_cache=cache is not None).last_hidden_state
         logits = self._lm_head(hidden[torch.arange(U, device=dev), last.long()])  # [U, V]
@@ -1168,22 +1131,6 @@ class AsyncAmdLM(AsyncLM):
     def _batch_logprobs(self, token_ids_list):
         """`batch_next_token_logprobs` without one coroutine / future per context: cache walk per context, ONE batched
         evaluation of the misses, trie update, rows stacked on the device."""
-
-        class _Slot:
-            __slots__ = ("value",)
-
-            def __init__(self):
-                self.value = None
-
-            def done(self):
-                return self.value is not None
-
-            def set_result(self, v):
-                self.value = v
-
-            def set_exception(self, e):
-                raise e
-
         pending, refs = [], [None] * len(token_ids_list)  # refs[i]: (tensor, index) of context i's row (held: the budget may evict)
         for i, token_ids in enumerate(token_ids_list):
             if not token_ids:
@@ -1192,7 +1139,7 @@ class AsyncAmdLM(AsyncLM):
             if nti == len(token_ids):
                 refs[i] = node.row_ref()
             else:
-                pending.append((i, node, nti, base, Query(token_ids[base:], _Slot(), past, first_new=nti - base)))
+                pending.append((i, node, nti, base, Query(token_ids[base:], _Slot(reraise=True), past, first_new=nti - base)))
         if pending:
             self._evaluate([q for *_, q in pending])
             for i, node, nti, base, q in pending:

@@ -21,6 +21,7 @@ import torch
 
 from ._lib import MASK_BITS
 from .cache import KVPrefix
+from .kv import PrefixTable, SlabKV, SlabRunner
 
 RNG_PHILOX, RNG_NOISE = 1, 2
 
@@ -268,11 +269,9 @@ class DeviceSIS:
         self.share_kv = bool(share_kv) and self.particle_kv
         self.kv_rows = int(kv_rows) if kv_rows is not None else n_particles
         self.kv_stats = dict(forward_rows=0, encoded_rows=0, copied_rows=0, unkept_rows=0, steps=0, in_place_steps=0)
-        # a forward runs on the KV slab rows where they lie when at least this fraction of them is live (None: always
-        # gather the live rows into batch order)
-        self.kv_in_place = kv_in_place
-        self.kv_graph = kv_graph
-        self._slab_fwd = None
+        # the KV slabs and the forwards over them: one runs on the slab rows where they lie when at least the fraction
+        # kv_in_place of them is live (None: always gather the live rows into batch order)
+        self._kv = SlabRunner(llm, self.kv_rows, self.cap, kv_in_place, kv_graph)
         if self.particle_kv:
             assert not use_prefix_kv
         self.particle_masks = particle_masks
@@ -283,25 +282,19 @@ class DeviceSIS:
         self.resample_ess = resample_ess
         self.n_resamples = 0
         self.sync_every = 1  # per-particle-KV steps: how often the active counts are read back (one small D2H copy)
-        self.pkv = None
         self.reset()
+
+    pkv = property(lambda self: self._kv.pkv)
+    _slab_fwd = property(lambda self: self._kv._slab_fwd)
 
     @torch.no_grad()
     def _build_prefixes(self, distinct):
         llm, dev = self.llm, self.dev
-        kvs = []
+        entries = []
         for p in distinct:
             out = llm._body(input_ids=torch.tensor([list(p)], device=dev), use_cache=True)
-            kvs.append(KVPrefix.from_hf_cache(out.past_key_values))
-        lens = np.array([len(p) for p in distinct], np.int32)
-        starts = np.zeros(len(distinct), np.int64)
-        if len(distinct) > 1:
-            starts[1:] = np.cumsum(lens[:-1])
-        flat = np.concatenate([np.array(p, np.int32) for p in distinct])
-        ptrs = [[torch.tensor([kv.layers[l][j].data_ptr() for kv in kvs], dtype=torch.int64, device=dev)
-                 for j in range(2)] for l in range(len(kvs[0].layers))]
-        self.prefixes = dict(kvs=kvs, tokens=torch.from_numpy(flat).to(dev), starts=torch.from_numpy(starts).to(dev),
-                             lengths=torch.from_numpy(lens).to(dev), ptrs=ptrs, p_max=int(lens.max()))
+            entries.append((KVPrefix.from_hf_cache(out.past_key_values), p))
+        self.prefixes = PrefixTable(entries, dev)
 
     def reset(self):
         if self.noise_src is not None:  # a run starts its seeded noise stream over
@@ -360,9 +353,7 @@ class DeviceSIS:
         out = llm._body(input_ids=ids, attention_mask=am, position_ids=pos, use_cache=True)
         src = [(ly.keys.contiguous(), ly.values.contiguous()) for ly in out.past_key_values.layers]
         if self.pkv is None:
-            from .kv import SlabKV
-
-            self.pkv = SlabKV(eng, N, self.cap, len(src))
+            self._kv.pkv = SlabKV(eng, N, self.cap, len(src))
         src_row = torch.where(want, group_of, torch.full_like(group_of, -1))
         self.pkv.fill_rows(src, src_row, lens_eff)
         return out, group_of, rep, U
@@ -383,11 +374,7 @@ class DeviceSIS:
         pos = (self.lengths - 1).clamp_min(0)  # tokens already in the row's KV = index of the newest token
         newest = self.contexts[rows, pos.long()]
         ids = torch.where(self.active > 0, newest, torch.zeros_like(newest)).view(N, 1).long()
-        if self._slab_fwd is None or self._slab_fwd.pkv is not self.pkv:
-            from .kv import SlabForward
-
-            self._slab_fwd = SlabForward(self.pkv, llm._body, graph=self.kv_graph, owner=llm)
-        logits = llm._lm_head(self._slab_fwd(ids, pos))  # [N, V]
+        logits = llm._lm_head(self._kv.slab_forward()(ids, pos))  # [N, V]
         self._noise_groups = None
         if self.rng_mode == RNG_NOISE:  # parity draws follow the reference's resolution order: by dedup group
             lengths_eff = torch.where(self.active > 0, self.lengths, torch.ones_like(self.lengths))
@@ -402,7 +389,7 @@ class DeviceSIS:
         (B) a context without a row (step 0, an ancestor from another rank, a spent row budget) - encoded from its tokens
         like the reference does every step, its KV kept if a row is free.  The block table is decided on the device
         (glb_kv_plan, one launch); the host reads nine words - how many rows of which kind - and launches the forwards."""
-        eng, llm, dev, N, R = self.eng, self.llm, self.dev, self.N, self.kv_rows
+        eng, N, R = self.eng, self.N, self.kv_rows
         ctx_flat = self.contexts.view(-1)
         lengths_eff = torch.where(self.active > 0, self.lengths, torch.ones_like(self.lengths))
         hashes_eff = torch.where(self.active > 0, self.hashes, self._hash_stub)
@@ -419,54 +406,10 @@ class DeviceSIS:
         st["copied_rows"] += n_copied
         st["unkept_rows"] += n_unkept
         st["steps"] += 1
-        logits_parts = []
-        fed_a = 0  # tokens the one-token forward is fed: its live rows, or every slab row when it runs in place
-        if nA:
-            if n_copied:
-                self.pkv.copy_rows(plan["copy_src"], plan["copy_len"])
-            if self.kv_in_place is not None and nA >= self.kv_in_place * R:
-                # most rows are live: the forward runs on the slab rows where they lie (rows outside it ride along with a
-                # dummy token at position 0) instead of gathering the live rows' prefixes into batch order
-                pos_d = plan["pos_of_row"]
-                ids = self.contexts[plan["ctx_of_row"].clamp_min(0).long(), pos_d.long()].view(-1, 1).long()
-                if self._slab_fwd is None or self._slab_fwd.pkv is not self.pkv:
-                    from .kv import SlabForward
-
-                    self._slab_fwd = SlabForward(self.pkv, llm._body, graph=self.kv_graph, owner=llm)
-                hidden = self._slab_fwd(ids, pos_d)
-                logits_parts.append(llm._lm_head(hidden.index_select(0, plan["rows_a"][:nA].long())))
-                st["in_place_steps"] += 1
-                fed_a = R
-            else:
-                pos_a = plan["pos_a"][:nA].contiguous()
-                ids = self.contexts[plan["ctx_a"][:nA].long(), pos_a.long()].view(-1, 1).long()
-                self.pkv.set_forward(plan["rows_a"][:nA].contiguous(), pos_a)
-                out = llm._body(input_ids=ids, position_ids=pos_a.view(-1, 1).long(),
-                                attention_mask=self.pkv.attention_mask(pos_a), past_key_values=self.pkv, use_cache=True)
-                logits_parts.append(llm._lm_head(out.last_hidden_state[:, 0]))
-                fed_a = nA
-        if nB:
-            sel = plan["ctx_b"][:nB].contiguous()
-            ids, am, pos, last = eng.gather_padded(ctx_flat, self.starts, lengths_eff, sel, nB, None, 0, 0, l_max_b)
-            out = llm._body(input_ids=ids, attention_mask=am, position_ids=pos, use_cache=True)
-            h_last = out.last_hidden_state[torch.arange(nB, device=dev), last.long()]
-            logits_parts.append(llm._lm_head(h_last))
-            if nB > n_unkept:  # rows that keep the KV of what was just encoded
-                src = [(ly.keys.contiguous(), ly.values.contiguous()) for ly in out.past_key_values.layers]
-                if self.pkv is None:
-                    from .kv import SharedSlabKV
-
-                    self.pkv = SharedSlabKV(eng, R, self.cap, len(src))
-                rows_b = plan["rows_b"][:nB].long()
-                slot = torch.where(rows_b >= 0, rows_b, torch.full_like(rows_b, R))  # (rows nobody keeps: a slot past the end)
-                src_full = torch.full((R + 1,), -1, dtype=torch.int32, device=dev)
-                len_full = torch.zeros(R + 1, dtype=torch.int32, device=dev)
-                src_full[slot] = torch.arange(nB, dtype=torch.int32, device=dev)
-                len_full[slot] = lengths_eff[sel.long()]
-                src_full[R] = -1
-                self.pkv.fill_rows(src, src_full[:R].contiguous(), len_full[:R].contiguous())
-        self._fwd_tokens = fed_a + nB * l_max_b
-        logits = logits_parts[0] if len(logits_parts) == 1 else torch.cat(logits_parts)
+        # (tokens the body is fed: its live rows, or every slab row when the one-token forward runs in place)
+        logits, self._fwd_tokens, in_place = self._kv.run(plan, head[:6], lambda ctx, pos: self.contexts[ctx, pos],
+                                                          (ctx_flat, self.starts, lengths_eff))
+        st["in_place_steps"] += int(in_place)
         self._rep = torch.cat([plan["ctx_a"][:nA], plan["ctx_b"][:nB]])  # the context behind every logits row
         self._noise_groups = group_of  # parity draws follow the reference's resolution order: by dedup group
         row_of = plan["logits_row"][group_of.long()]
@@ -622,19 +565,12 @@ class DeviceSIS:
         l_max = self.max_len_now
         if use_kv:
             P = self.prefixes
-            pref, base = eng.match_prefixes(ctx_flat, self.starts, lengths_eff, P["tokens"], P["starts"], P["lengths"])
-            p_max = P["p_max"]
+            pref, base = eng.match_prefixes(ctx_flat, self.starts, lengths_eff, P.tokens, P.starts, P.lengths)
+            p_max = P.p_max
             l_max = max(self.t, 1)  # every prompt is cached: only the generated tokens (<= t) are fed
         ids, am, pos, last = eng.gather_padded(ctx_flat, self.starts, lengths_eff, rep, U, base, 0, p_max, l_max)
         if use_kv:
-            from transformers import DynamicCache
-
-            P = self.prefixes
-            kv0 = P["kvs"][0]
-            pref_u = pref[rep[:U].long()].contiguous()
-            data = [tuple(eng.gather_kv_padded(P["ptrs"][l][j], P["lengths"], pref_u, kv0.heads, kv0.head_dim, p_max,
-                                               kv0.dtype) for j in range(2)) for l in range(len(kv0.layers))]
-            cache = DynamicCache(ddp_cache_data=data)
+            cache = self.prefixes.cache_for(eng, pref[rep[:U].long()].contiguous())
         out = llm._body(input_ids=ids, attention_mask=am, position_ids=pos, past_key_values=cache,
                         use_cache=cache is not None)
         h_last = out.last_hidden_state[torch.arange(U, device=dev), last.long()]
