@@ -193,6 +193,31 @@ class LoraJob(C.Structure):
     ]
 
 
+class LoraRowsEntry(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("ab_dtype", C.c_int32),
+        ("n_out", C.c_int64), ("k_in", C.c_int64), ("r", C.c_int64),
+        ("a", C.c_void_p), ("lda", C.c_int64),
+        ("b", C.c_void_p), ("ldb", C.c_int64),
+        ("scale", C.c_float),
+    ]
+
+
+class LoraRowsArgs(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("dtype", C.c_int32),
+        ("m", C.c_int64), ("n", C.c_int64), ("k", C.c_int64),
+        ("x", C.c_void_p), ("ldx", C.c_int64),
+        ("y", C.c_void_p), ("ldy", C.c_int64),
+        ("row_slot", C.c_void_p),
+        ("table", C.c_void_p),
+        ("n_slots", C.c_int32), ("n_modules", C.c_int32), ("module", C.c_int32), ("r_max", C.c_int32),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+    ]
+
+
 class W4Args(C.Structure):
     _fields_ = [
         ("struct_size", C.c_uint32),
@@ -282,6 +307,10 @@ SYMBOLS = {
     "glb_gemm_f32_split": (C.c_int, [C.POINTER(GemmArgs), _vp]),
     "glb_lora_merge_workspace_bytes": (_sz, [_i32]),
     "glb_lora_merge": (C.c_int, [C.POINTER(LoraJob), _i32, _vp, _sz, _vp]),
+    "glb_lora_rows_table_bytes": (_sz, [_i32, _i32]),
+    "glb_lora_rows_table_upload": (C.c_int, [C.POINTER(LoraRowsEntry), _i32, _i32, _vp, _sz, _vp]),
+    "glb_lora_rows_workspace_bytes": (_sz, [_i64, _i32]),
+    "glb_lora_rows": (C.c_int, [C.POINTER(LoraRowsArgs), _vp]),
     "glb_w4_bytes": (_sz, [_i64, _i64]),
     "glb_w4_quantize": (C.c_int, [C.POINTER(W4Args), _vp]),
     "glb_w4_dequantize": (C.c_int, [C.POINTER(W4Args), _vp]),

@@ -20,6 +20,14 @@ def _ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+class LoraRowsTable:
+    """The uploaded adapter table of glb_lora_rows (HipEngine.lora_rows_table): device bytes, its shape, the largest rank,
+    and the adapter tensors it points into."""
+
+    def __init__(self, dev, n_slots, n_modules, r_max, keep):
+        self.dev, self.n_slots, self.n_modules, self.r_max, self.keep = dev, n_slots, n_modules, r_max, keep
+
+
 class HostRng:
     """torch-CPU-compatible MT19937 stream for GLB_RNG_NOISE (parity mode).
 
@@ -254,6 +262,7 @@ class HipEngine:
         self._ws = None
         self._step_ws = None
         self._trie_ws = None
+        self._lora_rows_ws = None
         self._mt_polys = {}
         self._ptr_tables = {}
 
@@ -675,6 +684,101 @@ class HipEngine:
         nbytes = self.lib.glb_lora_merge_workspace_bytes(n)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)  # (freed in stream order: the launch reads it first)
         check(self.lib.glb_lora_merge(table, n, _ptr(ws), nbytes, self._stream()))
+
+    # ---- LoRA per row (glb_lora_rows: DESIGN.md §15) -----------------------------------------------------------------
+    def lora_rows_table(self, slots):
+        """The device table of glb_lora_rows for `slots`: a list (one item per adapter slot) of equally long lists (one item
+        per module index) holding None - the adapter does not target the module - or a dict `a` = lora_A [r, k_in], `b` =
+        lora_B [n_out, r] (2-D, unit inner stride, one dtype), `scale`.  Uploaded once; the returned object keeps the
+        tensors alive and goes to `lora_rows`."""
+        n_slots = len(slots)
+        n_modules = len(slots[0]) if n_slots else 0
+        nbytes = self.lib.glb_lora_rows_table_bytes(n_slots, n_modules)
+        if nbytes == 0:
+            raise ValueError(f"lora_rows_table: {n_slots} slots x {n_modules} modules is not served")
+        host = (_lib.LoraRowsEntry * (n_slots * n_modules))()
+        keep, r_max = [], 0
+        for si, mods in enumerate(slots):
+            if len(mods) != n_modules:
+                raise ValueError("lora_rows_table: every slot lists every module")
+            for mi, j in enumerate(mods):
+                q = host[si * n_modules + mi]
+                q.struct_size = C.sizeof(_lib.LoraRowsEntry)
+                if j is None:
+                    continue
+                a, b = j["a"], j["b"]
+                for t in (a, b):
+                    if t.device != self.device:
+                        raise ValueError(f"tensor on {t.device}, engine on {self.device}")
+                    if t.dim() != 2 or t.stride(1) != 1 or t.dtype not in _DT:
+                        raise ValueError("lora_rows_table: a / b must be 2-D float32 / bfloat16 / float16 with unit inner stride")
+                if a.dtype != b.dtype or a.shape[0] != b.shape[1]:
+                    raise ValueError("lora_rows_table: a / b must share a dtype and the rank")
+                q.ab_dtype = _DT[a.dtype]
+                q.n_out, q.k_in, q.r = b.shape[0], a.shape[1], a.shape[0]
+                q.a, q.lda = a.data_ptr(), a.stride(0)
+                q.b, q.ldb = b.data_ptr(), b.stride(0)
+                q.scale = float(j["scale"])
+                keep += [a, b]
+                r_max = max(r_max, int(a.shape[0]))
+        dev = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        check(self.lib.glb_lora_rows_table_upload(host, n_slots, n_modules, _ptr(dev), nbytes, self._stream()))
+        return LoraRowsTable(dev, n_slots, n_modules, max(r_max, 1), keep)
+
+    @staticmethod
+    def _rows_2d(t, what):
+        """(rows, row pitch) of a tensor [..., C] read as a matrix of rows with one pitch (a column slice of a contiguous
+        tensor qualifies).  The pitch is the stride of the innermost row dimension of size > 1 (the stride of a dimension
+        of size 1 means nothing); with one row it is C."""
+        if t.dim() < 1 or t.stride(-1) != 1:
+            raise ValueError(f"lora_rows: {what} must have unit inner stride")
+        rows, pitch = 1, None
+        for d in range(t.dim() - 2, -1, -1):
+            if t.shape[d] == 1:
+                continue
+            if pitch is None:  # (rows == 1 so far)
+                pitch = t.stride(d)
+            elif t.stride(d) != pitch * rows:
+                raise ValueError(f"lora_rows: {what} is not a matrix of rows with one pitch")
+            rows *= t.shape[d]
+        return rows, (t.shape[-1] if pitch is None else pitch)
+
+    def lora_rows(self, x, y, row_slot, table, module_index):
+        """In place on y [..., N], the output of a projection whose input was x [..., K] (same dtype, same rows): for every
+        row with row_slot >= 0 (int32, device, one per row) y += scale * (x A^T) B^T with that slot's entry of module
+        `module_index`; other rows, and rows whose slot has no entry for the module, are not written (glb_lora_rows)."""
+        if x.dtype != y.dtype or x.dtype not in _DT:
+            raise ValueError(f"lora_rows: x {x.dtype} / y {y.dtype} must be one of float32, bfloat16, float16")
+        for t in (x, y, row_slot, table.dev):  # (y may be a column slice: not contiguous)
+            if t.device != self.device:
+                raise ValueError(f"tensor on {t.device}, engine on {self.device}")
+        try:
+            m, ldx = self._rows_2d(x, "x")
+        except ValueError:  # (x is only read: an input that is no matrix of rows is COPIED, on every such call)
+            x = x.contiguous()
+            m, ldx = self._rows_2d(x, "x")
+        my, ldy = self._rows_2d(y, "y")
+        if m != my or m == 0 or row_slot.dtype != torch.int32 or row_slot.numel() != m or not row_slot.is_contiguous():
+            raise ValueError(f"lora_rows: x has {m} rows, y {my}, row_slot {tuple(row_slot.shape)} {row_slot.dtype}")
+        need = self.lib.glb_lora_rows_workspace_bytes(m, table.r_max)
+        ws = self._lora_rows_ws
+        if ws is None or ws.numel() < need:  # (grown, never shrunk)
+            if torch.cuda.is_current_stream_capturing():
+                # the buffer it replaces may be held by a captured graph, and one made now would belong to this capture
+                raise RuntimeError(f"lora_rows: the workspace must grow to {need} bytes while a stream is capturing; run the "
+                                   "call once at this size before the capture")
+            ws = self._lora_rows_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        a = _lib.LoraRowsArgs()
+        a.struct_size = C.sizeof(_lib.LoraRowsArgs)
+        a.dtype = _DT[x.dtype]
+        a.m, a.n, a.k = m, y.shape[-1], x.shape[-1]
+        a.x, a.ldx = x.data_ptr(), ldx
+        a.y, a.ldy = y.data_ptr(), ldy
+        a.row_slot, a.table = row_slot.data_ptr(), table.dev.data_ptr()
+        a.n_slots, a.n_modules, a.module, a.r_max = table.n_slots, table.n_modules, int(module_index), table.r_max
+        a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+        check(self.lib.glb_lora_rows(C.byref(a), self._stream()))
+        return y
 
     # ---- 4-bit block-quantised weights (glb_w4_*: DESIGN.md §14) --------------------------------------------------------
     @staticmethod

@@ -98,6 +98,15 @@ def _merged_qkv(attn):
     return ent[1], ent[2]
 
 
+def _row_deltas(x, joint, parts):
+    """A call that names adapters per context (lora.RowLora) wraps its targeted projections: the output of a joint GEMM gets
+    each wrapped projection's per-row delta on that projection's column slice (module, first column, columns), in place."""
+    for mod, first, cols in parts:
+        add = getattr(mod, "add_delta", None)
+        if add is not None:
+            add(x, joint[..., first:first + cols])
+
+
 MERGE_MLP_MAX_TOKENS = 2048  # up to here one GEMM for gate + up wins (tools/dbg/gemm_merge_probe.py); beyond, two do
 
 
@@ -126,6 +135,7 @@ def _llama_mlp_forward(self, x):
         w, b = _merged_gate_up(self)
         n = self.gate_proj.weight.shape[0]
         h = torch.nn.functional.linear(x, w, b)
+        _row_deltas(x, h, ((self.gate_proj, 0, n), (self.up_proj, n, h.shape[-1] - n)))  # (before the activation)
         return self.down_proj(self.act_fn(h[..., :n]) * h[..., n:])
     return self.down_proj(self.act_fn(self.gate_proj(x)) * self.up_proj(x))
 
@@ -235,8 +245,12 @@ def _llama_attention_forward(self, hidden_states, position_embeddings=None, atte
         n_kv = self.k_proj.out_features // D
     else:
         w, b = _merged_qkv(self)
-        qkv = torch.nn.functional.linear(hidden_states, w, b).view(*input_shape, -1, D)  # [B, T, Hq + 2 Hkv, D]
-        n_kv = self.k_proj.weight.shape[0] // D
+        qkv = torch.nn.functional.linear(hidden_states, w, b)
+        nq, nk = self.q_proj.weight.shape[0], self.k_proj.weight.shape[0]
+        _row_deltas(hidden_states, qkv, ((self.q_proj, 0, nq), (self.k_proj, nq, nk),
+                                         (self.v_proj, nq + nk, qkv.shape[-1] - nq - nk)))  # (before the rotary pass)
+        qkv = qkv.view(*input_shape, -1, D)  # [B, T, Hq + 2 Hkv, D]
+        n_kv = nk // D
     n_q = qkv.shape[-2] - 2 * n_kv
     cos, sin = position_embeddings
     ss = getattr(sin, "_glb_signed", None)

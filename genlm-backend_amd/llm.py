@@ -355,8 +355,9 @@ class AsyncAmdLM(AsyncLM):
         self._rng_seed = 0
         self._noise_src = None  # "torch" draws: the CPU generator's stream on the device, made at the first evaluation
         self._batch_counter = 0
-        self.stats = {"batches": 0, "queries": 0, "unique": 0, "rows": 0}
+        self.stats = {"batches": 0, "queries": 0, "unique": 0, "rows": 0, "lora_rows_calls": 0}
         self._loras = {}  # name -> lora.LoraAdapter (loaded, validated)
+        self._row_lora = None  # lora.RowLora over the loaded adapters (made at the first call that names adapters per context)
         self._lora = None  # lora.MergedLora of the active adapter
         self.lora_epoch = 0  # moves at every set_lora / clear_lora
         if hf_tokenizer is not None:
@@ -471,6 +472,7 @@ class AsyncAmdLM(AsyncLM):
         if lora_name in self._loras:
             raise ValueError(f"Adapter with name {lora_name} already exists. Please use a different name.")
         self._loras[lora_name] = load_adapter(lora_path, self.model, lora_name)
+        self._row_lora = None  # (its table lists the loaded adapters)
         self._lora_stats()
 
     def set_lora(self, lora_path=None, lora_name="lora_1"):
@@ -484,17 +486,21 @@ class AsyncAmdLM(AsyncLM):
             )
         try:
             self._drop_lora()
-            if self._net is self.model:  # no shadow yet (fuse_activations=False, glb_attention=False): one to merge into
-                from .fuse import shadow_model
-
-                self._net = shadow_model(self.model)
-                self._head = self._net.get_output_embeddings()
-                self._body = self._net.base_model
+            self._ensure_shadow()  # (fuse_activations=False, glb_attention=False: one to merge into)
             from .lora import MergedLora
 
             self._lora = MergedLora(self._loras[lora_name], self._net, self.engine)
         finally:  # (also when the merge fails: the old adapter is gone, and what was made with it must go too)
             self._weights_switched()
+
+    def _ensure_shadow(self):
+        if self._net is self.model:
+            from .fuse import shadow_model
+
+            self._net = shadow_model(self.model)
+            self._head = self._net.get_output_embeddings()
+            self._body = self._net.base_model
+            self._row_lora = None
 
     def clear_lora(self):
         """Back to the base weights: the shared parameter tables return and the merged tensors are freed, so results are
@@ -996,17 +1002,34 @@ class AsyncAmdLM(AsyncLM):
         return self._ptab
 
     @torch.no_grad()
-    def batch_next_token_step_sync(self, contexts, mask_ids=None):
+    def batch_next_token_step_sync(self, contexts, mask_ids=None, lora_names=None):
         """README.md:82-87 for a whole population in ONE call: for every context, logZ = logsumexp(next-token
         log-probs + mask[mask_id]) and a draw from the masked, renormalised distribution (-1 if nothing is allowed).
         Same pipeline as the queued `next_token_step` - dedup (hf.py:214-220), cached-prefix match (hf.py:334-342),
         ragged-to-padded gather, forward, lm_head on the last position, fused step - but the ragged batch is built
         once (three host arrays) and nothing is done per query in Python.  Returns (logZ float32 [n], token int32 [n])
-        as NumPy arrays."""
+        as NumPy arrays.
+        lora_names: one entry per context - a name given to `add_new_lora`, or None for the base model; the contexts are
+        then evaluated in ONE forward with each context's adapter applied unmerged (`_lora_rows_logits`)."""
         dev = self.device
         n = len(contexts)
+        if lora_names is not None:
+            slots = self._lora_slots(lora_names, n)
         if n == 0:
             return np.zeros(0, np.float32), np.zeros(0, np.int32)
+        if lora_names is not None:
+            if any(len(c) == 0 for c in contexts):
+                raise ValueError("Token ids must not be empty")
+            mid_d = None
+            if self._mask_kind != MASK_NONE:
+                mid = np.zeros(n, np.int32) if mask_ids is None else np.ascontiguousarray(mask_ids, dtype=np.int32)
+                mid_d = torch.from_numpy(mid).to(dev)
+            logits, group_of, U, row_mid, by_row = self._lora_rows_logits(contexts, slots, mid_d)
+            logZ, tok = self._finish_batch_step(logits, group_of, group_of, U, n, mid_d, row_mid, by_row)
+            out = torch.stack([logZ, tok.to(torch.float32)]).cpu().numpy()
+            toks = out[1].astype(np.int32)
+            self.engine.raise_if_failed(tokens=toks)
+            return out[0], toks
         flat, starts, lens = ragged(contexts)
         if int(lens.min()) == 0:
             raise ValueError("Token ids must not be empty")
@@ -1122,10 +1145,90 @@ class AsyncAmdLM(AsyncLM):
         self.stats["rows"] += U
         return logZ, tok
 
-    async def batch_next_token_step(self, contexts, mask_ids=None):
+    async def batch_next_token_step(self, contexts, mask_ids=None, lora_names=None):
         """Awaitable form of `batch_next_token_step_sync` (the evaluation itself blocks the loop, like
         `batch_evaluate_queries` does in the reference, hf.py:307-308)."""
-        return self.batch_next_token_step_sync(contexts, mask_ids)
+        return self.batch_next_token_step_sync(contexts, mask_ids, lora_names=lora_names)
+
+    # ---- one adapter per context in one forward (lora.RowLora, glb_lora_rows: DESIGN.md §15) --------------------------------
+    def _lora_slots(self, lora_names, n):
+        """The table slot of every context (-1: the base model) for a call's `lora_names`; ValueError for a wrong length,
+        an unknown name, an active merged adapter (the shadow's weights are then not the base's) or too many adapters."""
+        from .lora import MAX_ROW_SLOTS
+
+        names = list(lora_names)
+        if len(names) != n:
+            raise ValueError(f"lora_names has {len(names)} entries for {n} contexts")
+        if self._lora is not None:
+            raise ValueError(f"lora_names cannot be used while the merged adapter {self.active_lora!r} is active: "
+                             "call clear_lora() first")
+        order = {name: i for i, name in enumerate(self._loras)}  # (`add_new_lora` order)
+        for name in names:
+            if name is not None and name not in order:
+                raise ValueError(f"A LoRA adapter named '{name}' has not been loaded yet. Please call add_new_lora() first "
+                                 "to load and name your LoRA adapters.")
+        if len(order) > MAX_ROW_SLOTS:
+            raise ValueError(f"{len(order)} adapters are loaded; a call with lora_names serves at most {MAX_ROW_SLOTS}")
+        return np.fromiter((-1 if name is None else order[name] for name in names), np.int32, n)
+
+    def _lora_rows_logits(self, contexts, slots, mid_d=None):
+        """The last-position logits of `contexts` under their adapters (`slots`: int32 [n], -1 the base), in one forward on
+        the re-encoding path: dedup on (adapter, context) - every context is grouped with a leading pseudo-token V + 1 + slot
+        -, ragged-to-padded gather without it, the body and the head with every targeted module wrapped for this call
+        (lora.RowLora).  Neither reads nor writes the output trie, the prefix KV or the auto-KV rows (keyed by tokens alone).
+        Returns (logits [U, V'], group_of, U, row mask ids, mask ids go per row)."""
+        from .lora import RowLora
+
+        eng, dev = self.engine, self.device
+        n = len(contexts)
+        self._ensure_shadow()
+        if self._row_lora is None:
+            self._row_lora = RowLora(list(self._loras.values()), self._net, eng)
+        vocab = int(self.model.config.vocab_size)
+        flat, starts, lens = ragged([[vocab + 1 + int(s)] + list(c) for s, c in zip(slots, contexts)])
+        tok_d, st_d, ln_d = (torch.from_numpy(a).to(dev) for a in (flat, starts, lens))
+        slots_d = torch.from_numpy(slots).to(dev)
+        group_of, rep, ng = eng.group_contexts(tok_d, st_d, ln_d)
+        head = [ng[0]]
+        row_mid = None
+        if mid_d is not None:
+            row_mid = mid_d[rep.long().clamp(0, n - 1)]
+            head.append((row_mid[group_of.long()] == mid_d).all().to(torch.int32))
+        head = torch.stack(head).cpu().tolist()
+        U = head[0]
+        by_row = bool(head[-1]) if mid_d is not None else False
+        ids, am, pos, last = eng.gather_padded(tok_d, st_d + 1, ln_d - 1, rep, U, None, self._pad_id, 0, int(lens.max()) - 1)
+        seq_slots = slots_d[rep[:U].long()].contiguous()
+        head_was, body_was = self._head, self._body
+        with self._row_lora(seq_slots) as rl:
+            try:
+                self._head, self._body = self._net.get_output_embeddings(), self._net.base_model
+                hidden = self._body(input_ids=ids, attention_mask=am, position_ids=pos, past_key_values=None,
+                                    use_cache=False).last_hidden_state
+                logits = self._lm_head(hidden[torch.arange(U, device=dev), last.long()])  # [U, V]: per-sequence slots
+            finally:
+                self._head, self._body = head_was, body_was
+            self.stats["lora_rows_calls"] += rl.calls
+        return logits, group_of, U, row_mid, by_row
+
+    @torch.no_grad()
+    def _batch_lora_logprobs(self, token_ids_list, lora_names):
+        n = len(token_ids_list)
+        slots = self._lora_slots(lora_names, n)
+        if any(len(c) == 0 for c in token_ids_list):
+            raise ValueError("Token ids must not be empty")
+        if n == 0:
+            return torch.zeros((0, int(self.model.config.vocab_size)), device=self.device)
+        logits, group_of, U, _, _ = self._lora_rows_logits(token_ids_list, slots)
+        lp = self._log_softmax(logits)
+        out = lp.index_select(0, group_of.long())
+        self.engine.raise_if_failed(int(self.engine.error_word().item()), what="glb_log_softmax_rows")
+        self._batch_counter += 1
+        self.stats["batches"] += 1
+        self.stats["queries"] += n
+        self.stats["unique"] += U
+        self.stats["rows"] += U
+        return out
 
     @torch.no_grad()
     def _batch_logprobs(self, token_ids_list):
@@ -1167,12 +1270,19 @@ class AsyncAmdLM(AsyncLM):
             out[torch.from_numpy(np.asarray(pos, np.int64)).to(dev)] = got
         return out
 
-    async def batch_next_token_logprobs(self, token_ids_list):
-        """base.py:47-60 (one batched evaluation instead of a gather over per-context coroutines)"""
+    async def batch_next_token_logprobs(self, token_ids_list, lora_names=None):
+        """base.py:47-60 (one batched evaluation instead of a gather over per-context coroutines).  lora_names: as
+        `batch_next_token_step_sync`."""
+        if lora_names is not None:
+            return self._batch_lora_logprobs(token_ids_list, lora_names)
         return self._batch_logprobs(token_ids_list)
 
-    def batch_next_token_logprobs_sync(self, token_ids_list):
-        """base.py:62-73"""
+    def batch_next_token_logprobs_sync(self, token_ids_list, lora_names=None):
+        """base.py:62-73.  lora_names: one entry per context - a name given to `add_new_lora`, or None for the base model;
+        all contexts are evaluated in one forward, each under its adapter (unmerged: DESIGN.md §15).  Such a call leaves
+        the output trie and the KV caches alone."""
+        if lora_names is not None:
+            return self._batch_lora_logprobs(token_ids_list, lora_names)
         return self._batch_logprobs(token_ids_list)
 
     # ---- sampling (base.py:110-179): a device-resident multi-token loop -----------------------------------------------

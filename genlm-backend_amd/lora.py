@@ -13,6 +13,10 @@ forward then runs exactly the kernels (and the tuned shapes) of the base model.
     weight plus the caller's other parameters).  Shadow modules share their `_parameters` dict with the caller's module,
     so the shared dict is never written; `uninstall` puts the shared dicts back and lets the merged tensors go.  `sync`
     re-merges the modules whose base weight changed since the merge (`Tensor._version`, identity, address).
+  * `RowLora` serves SEVERAL adapters in one forward, one per context, UNMERGED: every loaded adapter is a
+    slot of a device table, and for the duration of one call each targeted shadow module is wrapped by a `RowLoraModule`
+    that runs the base module and then glb_lora_rows on its output with the call's row slots.  It reads only a module's
+    input and output, so the base may be a 4-bit `W4Linear`.
 """
 import json
 import math
@@ -22,7 +26,8 @@ import re
 import numpy as np
 import torch
 
-MAX_RANK = 256  # glb_lora_merge serves r = 1 .. 256
+MAX_RANK = 256  # glb_lora_merge and glb_lora_rows serve r = 1 .. 256
+MAX_ROW_SLOTS = 64  # adapters that may be loaded when a call names adapters per context (glb_lora_rows' table)
 _KEY = re.compile(r"^(?:base_model\.model\.)?(?P<path>.+)\.(?P<which>lora_A|lora_B)(?:\.(?P<name>[^.]+))?\.weight$")
 _SERVED = (torch.float32, torch.bfloat16, torch.float16)
 
@@ -217,3 +222,101 @@ class MergedLora:
 
     def nbytes(self):
         return sum(s[2]["weight"].numel() * s[2]["weight"].element_size() for s in self.slots.values())
+
+
+class RowLoraModule(torch.nn.Module):
+    """A targeted shadow module for the duration of one call that names adapters per context: the base module's output plus,
+    per row, its adapter's s (x A^T) B^T (HipEngine.lora_rows, in place).  Everything else about the module (`weight`,
+    `out_features`, `nf`, ...) is the base module's."""
+
+    def __init__(self, base, owner, index):
+        super().__init__()
+        self.__dict__["_glb_base"] = base  # (not a submodule: the shadow's parameter walk must not see it twice)
+        self.__dict__["_glb_owner"] = owner
+        self.__dict__["_glb_index"] = index
+
+    def __getattr__(self, name):
+        try:
+            return super().__getattr__(name)
+        except AttributeError:
+            return getattr(self.__dict__["_glb_base"], name)
+
+    def add_delta(self, x, y):
+        """y (this module's output for input x, or the column slice of a joint GEMM's output that is) += the rows' deltas."""
+        return self._glb_owner.apply(self._glb_index, x, y)
+
+    def forward(self, x, act=None):
+        y = self._glb_base(x)  # (a SplitConv1D runs without its GELU epilogue: the activation follows the delta)
+        self.add_delta(x, y)
+        return y if act is None else act(y)
+
+
+class RowLora:
+    """The loaded adapters as slots (in `add_new_lora` order) over the shadow `net`: the device table of glb_lora_rows and
+    the per-call wrappers."""
+
+    def __init__(self, adapters, net, engine):
+        if len(adapters) > MAX_ROW_SLOTS:
+            raise ValueError(f"{len(adapters)} adapters are loaded; a call with lora_names serves at most {MAX_ROW_SLOTS}")
+        self.net, self.engine = net, engine
+        self.slot_of = {ad.name: i for i, ad in enumerate(adapters)}
+        self.paths = sorted({p for ad in adapters for p in ad.modules})
+        self.index_of = {p: i for i, p in enumerate(self.paths)}
+        slots = []
+        for ad in adapters:
+            row = []
+            for p in self.paths:
+                lm = ad.modules.get(p)
+                row.append(None if lm is None else dict(a=lm.a, b=lm.b, scale=lm.scale))
+            slots.append(row)
+        self.table = engine.lora_rows_table(slots) if self.paths else None
+        self._seq = None      # int32 [U] device: the slot of every sequence of the running call
+        self._by_rows = {}    # rows of a module's input -> its row slots
+        self.calls = 0        # lora_rows launches of the running call
+
+    def apply(self, index, x, y):
+        seq = self._seq
+        if seq is None:
+            raise RuntimeError("RowLoraModule outside a call with lora_names")
+        k = x.shape[-1]
+        rows = x.numel() // k
+        slots = self._by_rows.get(rows)
+        if slots is None:
+            u = seq.numel()
+            if rows % u:
+                raise RuntimeError(f"a targeted module saw {rows} rows for {u} sequences")
+            # body modules see [U, L] tokens: a sequence's slot for each of its L positions
+            slots = self._by_rows[rows] = seq.repeat_interleave(rows // u).contiguous()
+        self.engine.lora_rows(x, y, slots, self.table, index)
+        self.calls += 1
+        return y
+
+    def __call__(self, seq_slots):
+        return _RowLoraCall(self, seq_slots)
+
+
+class _RowLoraCall:
+    """Context of one call: wrappers installed on entry and gone on exit (base results stay bit-identical)."""
+
+    def __init__(self, owner, seq_slots):
+        self.owner, self.seq = owner, seq_slots
+        self.saved = []
+
+    def __enter__(self):
+        o = self.owner
+        o._seq, o._by_rows, o.calls = self.seq.to(torch.int32).contiguous(), {}, 0
+        o._by_rows[o._seq.numel()] = o._seq
+        for p, i in o.index_of.items():
+            parent_path, _, name = p.rpartition(".")
+            parent = o.net.get_submodule(parent_path) if parent_path else o.net
+            base = parent._modules[name]
+            self.saved.append((parent, name, base))
+            parent._modules[name] = RowLoraModule(base, o, i)
+        return o
+
+    def __exit__(self, *exc):
+        for parent, name, base in self.saved:
+            parent._modules[name] = base
+        self.saved = []
+        self.owner._seq, self.owner._by_rows = None, {}
+        return False

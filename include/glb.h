@@ -732,6 +732,65 @@ int glb_lora_merge(const glb_lora_job *jobs /* host */, int32_t n_jobs, void *wo
                    void *hip_stream);
 
 /*
+ * LoRA per row: peft's unmerged form with the adapter chosen per row of one projection, in place on the
+ * projection's output.  X [m, k] is the module's input, Y [m, n] its output (one dtype, GLB_F32 / GLB_BF16 / GLB_F16, row
+ * pitches ldx / ldy in elements; ldy > n serves a column slice of a joint [q; k; v] or [gate; up] output):
+ *     slot = row_slot[i]                (int32, device; negative: the base model)
+ *     slot < 0, slot >= n_slots, or no entry for `module` in that slot: Y[i, :] is not written (its bits are untouched,
+ *                                        as are the columns beyond n of every row)
+ *     else  T[i, t] = sum_k A[t, k] * X[i, k];   Y[i, j] = round_to_y_dtype(fmaf(scale, sum_t B[j, t] * T[i, t], f32(Y[i, j])))
+ * The table (device memory, glb_lora_rows_table_bytes bytes, 16-byte aligned) holds one entry per (slot, module), made from
+ * a host array entries[slot * n_modules + module] by glb_lora_rows_table_upload when the set of adapters changes: A =
+ * lora_A [r, k_in] (pitch lda), B = lora_B [n_out, r] (pitch ldb) in their stored dtype (independent of X's; slots may
+ * differ in dtype and rank), r 1 .. 256, r == 0: the slot does not target the module.  At most 64 slots and 4096 modules
+ * (GLB_EUNSUPPORTED beyond, as for r > 256).  An entry whose n_out / k_in are not the call's n / k, or whose rank exceeds
+ * the call's r_max, leaves its rows untouched.
+ * Numerics: both sums run on MFMA with float32 accumulation.  X and A / B of ONE 16-bit dtype: v_mfma_f32_16x16x32 of that
+ * dtype, and T is rounded once to it (round to nearest even) between the two sums; every other combination widens the
+ * operands to float32 (exact), runs v_mfma_f32_16x16x4_f32 and keeps T in float32.  k is summed in chunks of 32 dealt to
+ * four partial sums (chunk c to sum c % 4, each ascending), added as ((s0 + s1) + s2) + s3; t ascending; one rounding of Y.
+ * Row independence: the bits of row i depend on X[i, :], Y[i, :] and its slot's A, B and scale only - not on m, on other
+ * rows' slots or values (rows of different slots may be in any order), or on replay from a hipGraph.  No atomics.
+ * Alignment: x, y, a, b to their element, row_slot to 4 bytes, table and workspace to 16 bytes; 16-byte vector accesses
+ * are used where a pointer and its pitch are multiples of 16 bytes and element accesses elsewhere, so every n, k >= 1 is
+ * served.  x and y must not overlap.  `workspace`: glb_lora_rows_workspace_bytes(m, r_max) bytes of device memory (T).
+ * Argument errors return GLB_EINVAL before any GPU work; glb_lora_rows launches twice on the given stream, allocates
+ * nothing, reads no host memory besides its argument block and may be captured into a hipGraph (the upload may not: it
+ * copies from host memory).
+ */
+typedef struct glb_lora_rows_entry {
+  uint32_t struct_size; /* sizeof(glb_lora_rows_entry) - ABI guard */
+  int32_t ab_dtype;     /* GLB_F32 / GLB_BF16 / GLB_F16: A and B */
+  int64_t n_out, k_in, r; /* r == 0: absent (the other fields are ignored) */
+  const void *a;
+  int64_t lda; /* lora_A [r, k_in] */
+  const void *b;
+  int64_t ldb; /* lora_B [n_out, r] */
+  float scale;
+} glb_lora_rows_entry;
+typedef struct glb_lora_rows_args {
+  uint32_t struct_size; /* sizeof(glb_lora_rows_args) - ABI guard */
+  int32_t dtype;        /* GLB_F32 / GLB_BF16 / GLB_F16: x and y */
+  int64_t m, n, k;
+  const void *x;
+  int64_t ldx;
+  void *y;
+  int64_t ldy;
+  const void *row_slot; /* int32 [m] */
+  const void *table;    /* device table of glb_lora_rows_table_upload */
+  int32_t n_slots, n_modules;
+  int32_t module; /* which module of the table this projection is */
+  int32_t r_max;  /* >= the rank of every entry that is to be applied; sizes the workspace */
+  void *workspace;
+  size_t workspace_bytes;
+} glb_lora_rows_args;
+size_t glb_lora_rows_table_bytes(int32_t n_slots, int32_t n_modules);
+int glb_lora_rows_table_upload(const glb_lora_rows_entry *entries /* host */, int32_t n_slots, int32_t n_modules,
+                               void *table /* device */, size_t table_bytes, void *hip_stream);
+size_t glb_lora_rows_workspace_bytes(int64_t m, int32_t r_max);
+int glb_lora_rows(const glb_lora_rows_args *args, void *hip_stream);
+
+/*
  * 4-bit block-quantised weights: the block format bitsandbytes uses for Linear4bit, without double
  * quantisation.  A weight W[n, k] (nn.Linear layout; `transposed`: the memory holds W^T [k, n], GPT-2's Conv1D) is cut into
  * blocks of 64 consecutive elements along k; a block stores absmax = max |w| as float32 and 64 four-bit codes into a
