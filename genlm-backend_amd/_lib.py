@@ -146,6 +146,18 @@ class KvPlanArgs(C.Structure):
     ]
 
 
+class KvPlanChunkArgs(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("plan", KvPlanArgs),
+        ("old_keep", C.c_void_p),
+        ("out_n_new_a", C.c_void_p), ("out_n_new_of_row", C.c_void_p),
+    ]
+
+
+KV_CHUNK_MAX = 16  # GLB_KV_CHUNK_MAX
+
+
 class MT19937(C.Structure):
     _fields_ = [("mt", C.c_uint32 * 624), ("idx", C.c_int32)]
 
@@ -282,6 +294,10 @@ SYMBOLS = {
                                       _i64, _i64, _i64, _i64, _i64, _i64, _f32, _i32, _vp, _vp]),
     "glb_kv_plan_workspace": (_sz, [_i64, _i64]),
     "glb_kv_plan": (C.c_int, [C.POINTER(KvPlanArgs), _vp]),
+    "glb_match_prefix_rows": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp]),
+    "glb_kv_plan_chunk": (C.c_int, [C.POINTER(KvPlanChunkArgs), _vp]),
+    "glb_slab_attention_chunk": (C.c_int, [_vp, C.POINTER(C.c_int64), _vp, C.POINTER(C.c_int64), _vp, C.POINTER(C.c_int64), _vp, _vp,
+                                           _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _i32, _vp, _vp]),
     "glb_trie_workspace": (_sz, [_i64, _i64]),
     "glb_trie_reduce": (C.c_int, [_vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _sz,
                                   _vp]),

@@ -69,9 +69,63 @@ __global__ __launch_bounds__(64) void match_rows_kernel(const int32_t *tok, cons
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// glb_match_prefix_rows: one wave per dedup group, the lanes walk the table rows r = lane, lane + 64, ... and COMPARE
+// TOKENS with every row that holds something (no hash selects here: a row of any length may share a prefix, and the
+// first unequal token - for most rows the very first - ends the comparison).  c = the common prefix of row and context,
+// keep = min(c, L - 1); a row is a candidate when keep >= 1 and the L - keep tokens behind it fit one forward (max_new).
+// The order is one 64-bit key per lane - keep, then "holds exactly the context", then the smaller row index - and a
+// maximum over the wave: whichever lane sees which row, the same row wins.
+// ---------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void match_prefix_rows_kernel(const int32_t *tok, const int64_t *st, const int32_t *len,
+                                                               const int32_t *rep, const int32_t *n_groups,
+                                                               const int32_t *row_tok, const int32_t *row_len, int32_t R,
+                                                               int32_t cap, int32_t max_new, int32_t *out_old,
+                                                               int32_t *out_keep, uint64_t *out_hash) {
+  const int u = blockIdx.x, lane = threadIdx.x;
+  if (u >= *n_groups) return;
+  const int i = rep[u];
+  const int32_t L = len[i];
+  const int32_t *t = tok + st[i];
+  if (out_hash) {
+    uint64_t h = 0xcbf29ce484222325ull;
+    for (int j = 0; j < L; ++j) h = ctx_hash_step(h, (uint32_t)t[j]);
+    if (lane == 0) out_hash[u] = h;
+  }
+  unsigned long long best = 0;  // (keep * 2 + exact) << 32 | (INT_MAX - row); 0: no candidate (keep >= 1 makes a key > 0)
+  if (L <= cap && L > 1) {
+    for (int r = lane; r < R; r += 64) {
+      int32_t rl = row_len[r];
+      if (rl <= 0) continue;  // the row holds nothing
+      rl = rl < cap ? rl : cap;
+      const int32_t *q = row_tok + (int64_t)r * cap;
+      const int lim = rl < L ? rl : L;
+      int c = 0;
+      while (c < lim && q[c] == t[c]) ++c;
+      const int keep = c < L - 1 ? c : L - 1;
+      if (keep < 1 || L - keep > max_new) continue;
+      const unsigned long long exact = rl == L && c == L ? 1ull : 0ull;
+      const unsigned long long key = (((unsigned long long)keep * 2ull + exact) << 32) | (unsigned long long)(INT_MAX - r);
+      best = key > best ? key : best;
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long other = __shfl_xor(best, o, 64);
+    best = other > best ? other : best;
+  }
+  if (lane == 0) {
+    out_old[u] = best ? INT_MAX - (int)(best & 0xffffffffull) : -1;
+    out_keep[u] = best ? (int)(best >> 33) : 0;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // glb_kv_plan: one workgroup.  Exclusive scans over the groups / rows run in strides of the workgroup with a carry.
+// glb_kv_plan_chunk is the same kernel with a kept length per group (old_keep): a row with a prefix is fed the tokens
+// keep .. L - 1 instead of the last one; without old_keep every group keeps L - 1 and nothing below differs.
 // ---------------------------------------------------------------------------------------------------------------------
 constexpr int kT = 1024;
+constexpr int kPinned = INT_MAX - 1;  // keeper[] of a matched row nobody may keep in place: not free, not anybody's
 
 struct Scan {
   int *s_wave;  // [17] in LDS
@@ -119,16 +173,23 @@ struct PlanArgs {
   const int64_t *st;
   // scratch: keeper[R], free_by_rank[R], flags[n]
   int32_t *keeper, *free_by_rank, *flags;
+  // glb_kv_plan_chunk (all null for glb_kv_plan): tokens of the context the matched row already holds, per group (by the
+  // index old_src is read with); tokens fed per forward row / per slab row
+  const int32_t *old_keep;
+  int32_t *n_new_a, *n_new_row;
 };
 
 __global__ __launch_bounds__(kT) void kv_plan_kernel(const PlanArgs a) {
   __shared__ int s_wave[17];
-  __shared__ int s_lmax, s_unkept, s_copied;
+  __shared__ int s_lmax, s_unkept, s_copied, s_nmax;
   Scan scan{s_wave};
   const int tid = threadIdx.x, n = a.n, R = a.R;
   const int U = *a.n_groups < n ? (*a.n_groups < 0 ? 0 : *a.n_groups) : n;  // (never past the scratch sized for n groups)
-  if (tid == 0) s_lmax = 0, s_unkept = 0, s_copied = 0;
+  if (tid == 0) s_lmax = 0, s_unkept = 0, s_copied = 0, s_nmax = 0;
+  // tokens of group u's context that its matched row holds: all but the last one, or what the prefix matcher found
+  auto keep_of = [&](int u, int L) { return a.old_keep ? a.old_keep[a.old_sel ? a.old_sel[u] : u] : L - 1; };
   for (int r = tid; r < R; r += kT) {
+    if (a.n_new_row) a.n_new_row[r] = 0;
     a.keeper[r] = INT_MAX;
     a.copy_src[r] = -1;
     a.copy_len[r] = 0;
@@ -141,9 +202,18 @@ __global__ __launch_bounds__(kT) void kv_plan_kernel(const PlanArgs a) {
     int o = a.old_src[a.old_sel ? a.old_sel[u] : u];
     // (a row index outside the table reads as "no row"; so does the row of a context that has outgrown a row's cap
     // positions: it is encoded from its tokens and its row goes back to the free ones - never a position past the row)
-    o = o >= 0 && o < R && a.lengths[a.rep[u]] <= a.cap ? o : -1;
+    const int L = a.lengths[a.rep[u]];
+    o = o >= 0 && o < R && L <= a.cap ? o : -1;
+    int claim = u;
+    if (a.old_keep && o >= 0) {
+      const int keep = keep_of(u, L);
+      if (keep < 0 || keep > L - 1 || L - keep > GLB_KV_CHUNK_MAX) o = -1;  // (not a prefix of this context, or more tokens behind it than one forward feeds: encoded)
+      // a row that holds more than keep + 1 tokens is never truncated in place: it stays as it is - pinned, so that it
+      // is not handed out as a free row either - and the group takes a copy of its keep tokens
+      else if (a.row_len[o] > keep + 1) claim = kPinned;
+    }
     a.flags[u] = o;
-    if (o >= 0) atomicMin(&a.keeper[o], u);
+    if (o >= 0) atomicMin(&a.keeper[o], claim);
   }
   __syncthreads();
   // ---- free rows in the order they are handed out: by (stamp, row) - longest unused first - or by row
@@ -246,48 +316,71 @@ __global__ __launch_bounds__(kT) void kv_plan_kernel(const PlanArgs a) {
   }
   __syncthreads();
   // ---- the forward's rows: groups with a prefix in a row (kept or copied) first, the ones to encode behind them
-  int n_a = 0;
+  //      (glb_kv_plan_chunk: among the rows with a prefix, the ones fed one token first, the ones fed a chunk behind them)
+  int n_a = 0, n_ac = 0;
   {
-    int carry = 0;
+    int carry = 0, carry_k = 0;
     for (int u0 = 0; u0 < U; u0 += kT) {
       const int u = u0 + tid;
-      int in_a = 0;
+      int in_a = 0, in_c = 0;
       if (u < U) {
         const int o = a.flags[u];
         in_a = o >= 0 && a.grp_row[u] >= 0 ? 1 : 0;
+        if (in_a && a.old_keep) {
+          const int L = a.lengths[a.rep[u]];
+          in_c = L - keep_of(u, L) > 1 ? 1 : 0;
+        }
       }
       int tot;
       scan.excl(in_a, tot);
       carry += tot;
+      if (a.old_keep) {  // (the same for every thread)
+        scan.excl(in_c, tot);
+        carry_k += tot;
+      }
     }
     n_a = carry;
+    n_ac = carry_k;
   }
-  int carry_a = 0;
+  const int n_a1 = n_a - n_ac;
+  int carry_a = 0, carry_k = 0;
   for (int u0 = 0; u0 < U; u0 += kT) {
     const int u = u0 + tid;
-    int in_a = 0, o = -1, row = -1, L = 0, ctx = 0;
+    int in_a = 0, in_c = 0, o = -1, row = -1, L = 0, ctx = 0, keep = 0;
     if (u < U) {
       o = a.flags[u];
       row = a.grp_row[u];
       ctx = a.rep[u];
       L = a.lengths[ctx];
       in_a = o >= 0 && row >= 0 ? 1 : 0;
+      if (in_a) {
+        keep = keep_of(u, L);
+        in_c = L - keep > 1 ? 1 : 0;
+      }
     }
-    int tot;
+    int tot, tot_k = 0, ex_k = 0;
     const int ex = scan.excl(in_a, tot);
+    if (a.old_keep) ex_k = scan.excl(in_c, tot_k);
     if (u < U) {
       if (in_a) {
-        const int k = carry_a + ex;
+        const int chunks_before = carry_k + ex_k;
+        const int k = in_c ? n_a1 + chunks_before : carry_a + ex - chunks_before;
         a.inv[u] = k;
         a.rows_a[k] = row;
         a.reps_a[k] = ctx;
-        a.pos_a[k] = L - 1;
-        a.ctx_of_row[row] = ctx;
-        a.pos_full[row] = L - 1;
+        a.pos_a[k] = keep;
+        // (a chunk row is not part of a one-token forward over all rows: -3, and its first new position - what such a
+        // forward writes there is overwritten by the chunk's own forward)
+        a.ctx_of_row[row] = in_c ? -3 : ctx;
+        a.pos_full[row] = keep;
+        if (a.n_new_a) a.n_new_a[k] = L - keep;
+        if (a.n_new_row) a.n_new_row[row] = L - keep;
+        if (a.old_keep) atomicMax(&s_nmax, L - keep);
         if (row != o) {  // a copy of the prefix into a free row
           a.copy_src[row] = o;
-          a.copy_len[row] = L - 1;
+          a.copy_len[row] = keep;
           atomicAdd(&s_copied, 1);
+          if (a.old_keep && a.stamps) a.stamps[o] = a.call_no;  // (a pinned source has no keeper to stamp it: used in this call)
         }
       } else {
         const int k = u - (carry_a + ex);  // rank among the groups to encode
@@ -310,6 +403,7 @@ __global__ __launch_bounds__(kT) void kv_plan_kernel(const PlanArgs a) {
       }
     }
     carry_a += tot;
+    carry_k += tot_k;
   }
   __syncthreads();
   // ---- every context's row from now on
@@ -324,6 +418,10 @@ __global__ __launch_bounds__(kT) void kv_plan_kernel(const PlanArgs a) {
     a.head[5] = s_lmax;
     a.head[6] = n_free;
     a.head[7] = 0;
+    if (a.old_keep) {
+      a.head[8] = n_ac;
+      a.head[9] = s_nmax;
+    }
   }
 }
 
@@ -464,6 +562,118 @@ hipError_t launch_attention(const AttnArgs &a, int head_dim, hipStream_t s) {
   else if (head_dim == 128) hipLaunchKernelGGL((slab_attention_kernel<DT, 128>), grid, block, 0, s, a);
   else if (head_dim == 32) hipLaunchKernelGGL((slab_attention_kernel<DT, 32>), grid, block, 0, s, a);
   else if (head_dim == 16) hipLaunchKernelGGL((slab_attention_kernel<DT, 16>), grid, block, 0, s, a);
+  else return hipErrorInvalidValue;
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// glb_slab_attention_chunk: up to 16 new tokens per row in one forward.  One wave per (row, query head, new token t): the
+// wave is the one-token kernel above for the query at position pos + t - the same LP lanes a position, PP positions a
+// load, the same position -> slot deal (p = p0 + j), the same online softmax per slot and the same slot merge - so its
+// output carries the bits the t + 1'th of successive glb_slab_attention calls would leave.  Positions below pos come from
+// the slab; positions pos .. pos + t from k_new / v_new where the projection left them, NEVER from the slab (no wave
+// reads what another wave of the launch writes: no hand-off inside the launch); the wave of the group's first query head
+// writes its own token's K / V to slab position pos + t.  The T waves of a (row, head) read the same slab positions: the
+// first brings them into the L2, the others find them there (sharing the loads inside one wave - T queries' sums in
+// registers - is not built: DESIGN.md §16).  row_of: the slab row of forward row r (null: r), so that rows anywhere in the
+// slab are served without gathering their prefixes.
+// ---------------------------------------------------------------------------------------------------------------------
+struct ChunkAttnArgs {
+  const char *q, *k_new, *v_new;
+  char *k_slab, *v_slab, *out;
+  const int32_t *pos, *n_new, *row_of;
+  int64_t q_sr, q_sh, q_sp, k_sr, k_sh, k_sp, v_sr, v_sh, v_sp;  // element strides: row, head, position
+  int32_t n, H, Hkv, cap, T, n_slab_rows;
+  float scale;
+};
+
+template <int DT, int DH>
+__global__ __launch_bounds__(64) void slab_attention_chunk_kernel(const ChunkAttnArgs a) {
+  constexpr int ES = DT == GLB_F32 ? 4 : 2, EPV = 16 / ES, LP = DH / EPV, PP = 64 / LP;
+  static_assert(LP >= 1 && LP <= 64 && PP * LP == 64, "head_dim / vector width must divide the wave");
+  const int lane = threadIdx.x, j = lane / LP, i = lane - j * LP;
+  const int t = blockIdx.x % a.T, rh = blockIdx.x / a.T;
+  const int r = rh / a.H, h = rh - r * a.H;
+  const int G = a.H / a.Hkv, hk = h / G;
+  const int p0_new = a.pos[r], nn = a.n_new[r];
+  const int64_t sr = a.row_of ? (int64_t)a.row_of[r] : (int64_t)r;
+  char *out = a.out + ((((int64_t)r * a.T + t) * a.H + h) * DH + i * EPV) * ES;
+  // a chunk that does not lie inside the row (or a row outside the slab): the caller's bug - no fault, no plausible
+  // answer: NaN for the whole row, nothing appended
+  const bool bad = p0_new < 0 || nn < 1 || nn > a.T || (int64_t)p0_new + nn > a.cap || sr < 0 || sr >= a.n_slab_rows;
+  if (bad || t >= nn) {  // (wave-uniform)
+    if (j == 0) {
+      float z[EPV];
+#pragma unroll
+      for (int k = 0; k < EPV; ++k) z[k] = bad ? __builtin_nanf("") : 0.0f;
+      *reinterpret_cast<u32x4 *>(out) = pack16v<DT>(z);
+    }
+    return;
+  }
+  const int p_new = p0_new + t;  // this wave's token sits at p_new; positions 0 .. p_new are attended to
+  float qf[EPV];
+  unpack16<DT>(*reinterpret_cast<const u32x4 *>(a.q + ((int64_t)r * a.q_sr + (int64_t)h * a.q_sh + (int64_t)t * a.q_sp + i * EPV) * ES), qf);
+  const char *kb = a.k_new + ((int64_t)r * a.k_sr + (int64_t)hk * a.k_sh + i * EPV) * ES;
+  const char *vb = a.v_new + ((int64_t)r * a.v_sr + (int64_t)hk * a.v_sh + i * EPV) * ES;
+  const int64_t slab_row = (sr * a.Hkv + hk) * a.cap;
+  if (h == hk * G && j == 0) {  // the append of this wave's token: once per (row, KV head, token)
+    *reinterpret_cast<u32x4 *>(a.k_slab + ((slab_row + p_new) * DH + i * EPV) * ES) = *reinterpret_cast<const u32x4 *>(kb + (int64_t)t * a.k_sp * ES);
+    *reinterpret_cast<u32x4 *>(a.v_slab + ((slab_row + p_new) * DH + i * EPV) * ES) = *reinterpret_cast<const u32x4 *>(vb + (int64_t)t * a.v_sp * ES);
+  }
+  float m = -__builtin_huge_valf(), l = 0.0f, acc[EPV];
+#pragma unroll
+  for (int k = 0; k < EPV; ++k) acc[k] = 0.0f;
+  for (int p0 = 0; p0 <= p_new; p0 += PP) {
+    const int p = p0 + j;
+    float kf[EPV], vf[EPV];
+    if (p < p0_new) {
+      unpack16<DT>(*reinterpret_cast<const u32x4 *>(a.k_slab + ((slab_row + p) * DH + i * EPV) * ES), kf);
+      unpack16<DT>(*reinterpret_cast<const u32x4 *>(a.v_slab + ((slab_row + p) * DH + i * EPV) * ES), vf);
+    } else {
+      const int tn = p <= p_new ? p - p0_new : t;  // (slots past the query's own position read its token and ignore it)
+      unpack16<DT>(*reinterpret_cast<const u32x4 *>(kb + (int64_t)tn * a.k_sp * ES), kf);
+      unpack16<DT>(*reinterpret_cast<const u32x4 *>(vb + (int64_t)tn * a.v_sp * ES), vf);
+    }
+    float s = 0.0f;
+#pragma unroll
+    for (int k = 0; k < EPV; ++k) s = __builtin_fmaf(qf[k], kf[k], s);
+#pragma unroll
+    for (int o = 1; o < LP; o <<= 1) s += __shfl_xor(s, o, 64);  // the LP lanes of a position end up with its score
+    if (p <= p_new) {
+      s *= a.scale;
+      const float m2 = fmaxf(m, s), c = __expf(m - m2), w = __expf(s - m2);
+      l = l * c + w;
+#pragma unroll
+      for (int k = 0; k < EPV; ++k) acc[k] = __builtin_fmaf(acc[k], c, w * vf[k]);
+      m = m2;
+    }
+  }
+  // merge the PP position slots (lanes i, i + LP, i + 2 LP, ...)
+#pragma unroll
+  for (int o = LP; o < 64; o <<= 1) {
+    const float mo = __shfl_xor(m, o, 64), lo = __shfl_xor(l, o, 64);
+    const float m2 = fmaxf(m, mo);
+    const float c = m == m2 ? 1.0f : __expf(m - m2), co = mo == m2 ? 1.0f : __expf(mo - m2);  // (-inf - -inf: an empty slot)
+    l = l * c + lo * co;
+#pragma unroll
+    for (int k = 0; k < EPV; ++k) acc[k] = acc[k] * c + __shfl_xor(acc[k], o, 64) * co;
+    m = m2;
+  }
+  if (j == 0) {
+    const float inv = 1.0f / l;
+#pragma unroll
+    for (int k = 0; k < EPV; ++k) acc[k] *= inv;
+    *reinterpret_cast<u32x4 *>(out) = pack16v<DT>(acc);
+  }
+}
+
+template <int DT>
+hipError_t launch_attention_chunk(const ChunkAttnArgs &a, int head_dim, hipStream_t s) {
+  const dim3 grid((unsigned)((int64_t)a.n * a.H * a.T)), block(64);
+  if (head_dim == 64) hipLaunchKernelGGL((slab_attention_chunk_kernel<DT, 64>), grid, block, 0, s, a);
+  else if (head_dim == 128) hipLaunchKernelGGL((slab_attention_chunk_kernel<DT, 128>), grid, block, 0, s, a);
+  else if (head_dim == 32) hipLaunchKernelGGL((slab_attention_chunk_kernel<DT, 32>), grid, block, 0, s, a);
+  else if (head_dim == 16) hipLaunchKernelGGL((slab_attention_chunk_kernel<DT, 16>), grid, block, 0, s, a);
   else return hipErrorInvalidValue;
   return hipGetLastError();
 }
@@ -870,6 +1080,55 @@ int glb_slab_attention(const void *q, int64_t q_stride_row, int64_t q_stride_hea
   return GLB_OK;
 }
 
+int glb_slab_attention_chunk(const void *q, const int64_t q_strides[3], const void *k_new, const int64_t k_strides[3],
+                             const void *v_new, const int64_t v_strides[3], void *k_slab, void *v_slab, const int32_t *pos,
+                             const int32_t *n_new, const int32_t *row_of, int64_t n_rows, int64_t n_slab_rows, int64_t heads,
+                             int64_t kv_heads, int64_t cap, int64_t head_dim, int64_t max_new, float scale, int32_t dtype,
+                             void *out, void *stream) {
+  if (!q || !k_new || !v_new || !k_slab || !v_slab || !pos || !n_new || !out || !q_strides || !k_strides || !v_strides)
+    return glb::api_fail(GLB_EINVAL, "glb_slab_attention_chunk: null pointer");
+  if (dtype < GLB_F32 || dtype > GLB_F16) return glb::api_fail(GLB_EINVAL, "bad dtype %d", dtype);
+  if (max_new < 1 || max_new > GLB_KV_CHUNK_MAX)
+    return glb::api_fail(GLB_EINVAL, "glb_slab_attention_chunk: %lld query positions per row (1 .. %d)", (long long)max_new, GLB_KV_CHUNK_MAX);
+  if (n_rows <= 0 || n_slab_rows <= 0 || heads <= 0 || kv_heads <= 0 || cap <= 0 || heads % kv_heads || cap > 0x7fffffffll ||
+      n_slab_rows > 0x7fffffffll || n_rows * heads * max_new > 0x7fffffffll)
+    return glb::api_fail(GLB_EINVAL, "glb_slab_attention_chunk: bad sizes");
+  if (head_dim != 16 && head_dim != 32 && head_dim != 64 && head_dim != 128)
+    return glb::api_fail(GLB_EUNSUPPORTED, "glb_slab_attention_chunk: head_dim %lld (16, 32, 64 and 128 are built)", (long long)head_dim);
+  const int es = dtype == GLB_F32 ? 4 : 2;
+  bool aligned = (((uintptr_t)q | (uintptr_t)k_new | (uintptr_t)v_new | (uintptr_t)k_slab | (uintptr_t)v_slab | (uintptr_t)out) % 16) == 0;
+  for (int d = 0; d < 3; ++d) aligned = aligned && (q_strides[d] * es) % 16 == 0 && (k_strides[d] * es) % 16 == 0 && (v_strides[d] * es) % 16 == 0;
+  if (!aligned) return glb::api_fail(GLB_EINVAL, "glb_slab_attention_chunk: pointers and strides must be 16-byte aligned");
+  ChunkAttnArgs a{};
+  a.q = (const char *)q;
+  a.k_new = (const char *)k_new;
+  a.v_new = (const char *)v_new;
+  a.k_slab = (char *)k_slab;
+  a.v_slab = (char *)v_slab;
+  a.out = (char *)out;
+  a.pos = pos;
+  a.n_new = n_new;
+  a.row_of = row_of;
+  a.q_sr = q_strides[0], a.q_sh = q_strides[1], a.q_sp = q_strides[2];
+  a.k_sr = k_strides[0], a.k_sh = k_strides[1], a.k_sp = k_strides[2];
+  a.v_sr = v_strides[0], a.v_sh = v_strides[1], a.v_sp = v_strides[2];
+  a.n = (int32_t)n_rows;
+  a.H = (int32_t)heads;
+  a.Hkv = (int32_t)kv_heads;
+  a.cap = (int32_t)cap;
+  a.T = (int32_t)max_new;
+  a.n_slab_rows = (int32_t)n_slab_rows;
+  a.scale = scale;
+  hipError_t e;
+  switch (dtype) {
+    case GLB_F32: e = launch_attention_chunk<GLB_F32>(a, (int)head_dim, (hipStream_t)stream); break;
+    case GLB_BF16: e = launch_attention_chunk<GLB_BF16>(a, (int)head_dim, (hipStream_t)stream); break;
+    default: e = launch_attention_chunk<GLB_F16>(a, (int)head_dim, (hipStream_t)stream); break;
+  }
+  if (e != hipSuccess) return glb::api_hip_fail(e, "slab_attention_chunk launch");
+  return GLB_OK;
+}
+
 int glb_match_rows(const int32_t *tokens, const int64_t *starts, const int32_t *lengths, const int32_t *rep,
                    const int32_t *n_groups, int64_t n, const int32_t *row_tok, const int32_t *row_len,
                    const uint64_t *row_hash, int64_t n_rows, int64_t cap, int32_t *out_old, uint64_t *out_hash,
@@ -885,12 +1144,47 @@ int glb_match_rows(const int32_t *tokens, const int64_t *starts, const int32_t *
   return GLB_OK;
 }
 
+int glb_match_prefix_rows(const int32_t *tokens, const int64_t *starts, const int32_t *lengths, const int32_t *rep,
+                          const int32_t *n_groups, int64_t n, const int32_t *row_tok, const int32_t *row_len,
+                          const uint64_t *row_hash, int64_t n_rows, int64_t cap, int32_t max_new, int32_t *out_old,
+                          int32_t *out_keep, uint64_t *out_hash, void *stream) {
+  (void)row_hash;  // (part of the table: a row of any length may share a prefix, so no hash selects - tokens decide)
+  if (!tokens || !starts || !lengths || !rep || !n_groups || !row_tok || !row_len || !out_old || !out_keep)
+    return glb::api_fail(GLB_EINVAL, "glb_match_prefix_rows: null pointer");
+  if (n <= 0 || n_rows <= 0 || cap <= 0 || n > 0x7fffffffll || n_rows > 0x3fffffffll || cap > 0x3fffffffll)
+    return glb::api_fail(GLB_EINVAL, "glb_match_prefix_rows: bad sizes");
+  if (max_new < 1 || max_new > GLB_KV_CHUNK_MAX)
+    return glb::api_fail(GLB_EINVAL, "glb_match_prefix_rows: max_new %d outside 1 .. %d", max_new, GLB_KV_CHUNK_MAX);
+  hipLaunchKernelGGL(match_prefix_rows_kernel, dim3((unsigned)n), dim3(64), 0, (hipStream_t)stream, tokens, starts, lengths,
+                     rep, n_groups, row_tok, row_len, (int32_t)n_rows, (int32_t)cap, max_new, out_old, out_keep, out_hash);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return glb::api_hip_fail(e, "match_prefix_rows launch");
+  return GLB_OK;
+}
+
 size_t glb_kv_plan_workspace(int64_t n, int64_t n_rows) {
   if (n <= 0 || n_rows <= 0) return 0;
   return (size_t)(2 * n_rows + n) * sizeof(int32_t) + 256;
 }
 
-int glb_kv_plan(const glb_kv_plan_args *a, void *stream) {
+static int kv_plan_launch(const glb_kv_plan_args *a, const int32_t *old_keep, int32_t *n_new_a, int32_t *n_new_row,
+                          void *stream);
+
+int glb_kv_plan(const glb_kv_plan_args *a, void *stream) { return kv_plan_launch(a, nullptr, nullptr, nullptr, stream); }
+
+int glb_kv_plan_chunk(const glb_kv_plan_chunk_args *c, void *stream) {
+  if (!c) return glb::api_fail(GLB_EINVAL, "glb_kv_plan_chunk: null args");
+  if (c->struct_size != sizeof(glb_kv_plan_chunk_args))
+    return glb::api_fail(GLB_EINVAL, "glb_kv_plan_chunk_args.struct_size %u != %zu (ABI mismatch)", c->struct_size,
+                         sizeof(glb_kv_plan_chunk_args));
+  if (!c->old_keep || !c->out_n_new_a || !c->out_n_new_of_row)
+    return glb::api_fail(GLB_EINVAL, "glb_kv_plan_chunk: null old_keep / out_n_new_a / out_n_new_of_row");
+  if (!c->plan.row_tok) return glb::api_fail(GLB_EINVAL, "glb_kv_plan_chunk: the row table is required (row lengths decide who keeps a row in place)");
+  return kv_plan_launch(&c->plan, c->old_keep, c->out_n_new_a, c->out_n_new_of_row, stream);
+}
+
+static int kv_plan_launch(const glb_kv_plan_args *a, const int32_t *old_keep, int32_t *n_new_a, int32_t *n_new_row,
+                          void *stream) {
   if (!a) return glb::api_fail(GLB_EINVAL, "glb_kv_plan: null args");
   if (a->struct_size != sizeof(glb_kv_plan_args))
     return glb::api_fail(GLB_EINVAL, "glb_kv_plan_args.struct_size %u != %zu (ABI mismatch)", a->struct_size, sizeof(glb_kv_plan_args));
@@ -936,6 +1230,9 @@ int glb_kv_plan(const glb_kv_plan_args *a, void *stream) {
   p.grp_hash = a->group_hash;
   p.tok = a->tokens;
   p.st = a->starts;
+  p.old_keep = old_keep;
+  p.n_new_a = n_new_a;
+  p.n_new_row = n_new_row;
   int32_t *ws = (int32_t *)a->workspace;
   p.keeper = ws;
   p.free_by_rank = ws + a->n_rows;

@@ -11,7 +11,7 @@ import torch
 from . import _lib
 from ._lib import GLB_EHIP, GlbError
 from ._lib import (F32, BF16, F16, MASK_NONE, MASK_BITS, MASK_F32, MASK_PREPARED, RNG_NONE, RNG_PHILOX, RNG_NOISE,
-                   STEP_HW_EXP, KvPlanArgs, MtRowsArgs, StepArgs, TrieArgs, TriePlan, TrieRowsArgs, MT19937, MT_POLY_WORDS, check)
+                   STEP_HW_EXP, KvPlanArgs, KvPlanChunkArgs, MtRowsArgs, StepArgs, TrieArgs, TriePlan, TrieRowsArgs, MT19937, MT_POLY_WORDS, check)
 
 _DT = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16}
 
@@ -976,30 +976,39 @@ class HipEngine:
         return old, gh
 
     def kv_plan(self, group_of, rep, n_groups, old_row, lengths, n_rows, cap, by_context=False, stamps=None, call_no=0,
-                table=None):
+                table=None, old_keep=None):
         """The block table of one step (glb_kv_plan).  `old_row`: the row every group's prefix sits in (match_rows'
         output), or with `by_context` every CONTEXT's row (the previous plan's `row_of_context`).  `stamps`: int64
         [n_rows], free rows are handed out longest unused first (and stamped `call_no`).  `table`: (row_tok, row_len,
         row_hash, group_hash, tokens, starts) - the rows' contents, rewritten for every group that holds a row.
         Returns a dict of int32 device tensors (include/glb.h names without the out_ prefix); `head` (8 words) is all
-        the host has to read."""
+        the host has to read.  `old_keep`: see `kv_plan_chunk`."""
         n = group_of.numel()
-        self._check_dev(group_of, rep, n_groups, old_row, lengths, stamps)
-        buf = torch.empty(8 * n + 4 * n_rows + 8, dtype=torch.int32, device=self.device)
+        self._check_dev(group_of, rep, n_groups, old_row, lengths, stamps, old_keep)
+        chunk = old_keep is not None
+        buf = torch.empty(9 * n + 5 * n_rows + 10 if chunk else 8 * n + 4 * n_rows + 8, dtype=torch.int32, device=self.device)
         names_n = ("group_row", "logits_row", "rows_a", "ctx_a", "pos_a", "ctx_b", "rows_b", "row_of_context")
         names_r = ("copy_src", "copy_len", "ctx_of_row", "pos_of_row")
         out, o = {}, 0
+        if chunk:
+            out["n_new_a"], out["n_new_of_row"], o = buf[:n], buf[n:n + n_rows], n + n_rows
         for k in names_n:
             out[k] = buf[o:o + n]
             o += n
         for k in names_r:
             out[k] = buf[o:o + n_rows]
             o += n_rows
-        out["head"] = buf[o:o + 8]
+        out["head"] = buf[o:o + (10 if chunk else 8)]
         need = self.lib.glb_kv_plan_workspace(n, n_rows)
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty(max(need, 1 << 16), dtype=torch.uint8, device=self.device)
-        a = KvPlanArgs()
+        if chunk:
+            c = KvPlanChunkArgs()
+            c.struct_size = C.sizeof(KvPlanChunkArgs)
+            c.old_keep, c.out_n_new_a, c.out_n_new_of_row = old_keep.data_ptr(), out["n_new_a"].data_ptr(), out["n_new_of_row"].data_ptr()
+            a = c.plan
+        else:
+            a = KvPlanArgs()
         a.struct_size = C.sizeof(KvPlanArgs)
         a.n, a.n_rows, a.cap = n, n_rows, cap
         a.group_of, a.rep, a.n_groups = group_of.data_ptr(), rep.data_ptr(), n_groups.data_ptr()
@@ -1015,8 +1024,60 @@ class HipEngine:
         for k in names_n + names_r + ("head",):
             setattr(a, "out_" + k, out[k].data_ptr())
         a.workspace, a.workspace_bytes = self._ws.data_ptr(), self._ws.numel()
-        check(self.lib.glb_kv_plan(C.byref(a), self._stream()))
+        if chunk:
+            check(self.lib.glb_kv_plan_chunk(C.byref(c), self._stream()))
+        else:
+            check(self.lib.glb_kv_plan(C.byref(a), self._stream()))
         return out
+
+    def match_prefix_rows(self, tokens, starts, lengths, rep, n_groups, row_tok, row_len, row_hash, max_new):
+        """For every dedup group the table row that shares the longest prefix with its context - `keep` tokens, at most
+        L - 1, with the L - keep tokens behind them no more than `max_new` - else -1 (glb_match_prefix_rows; ties: a row that
+        holds exactly the context, then the smallest row).  Returns (old_row int32 [n], keep int32 [n], group_hash int64
+        [n]); entries past the group count are unspecified."""
+        n = lengths.numel()
+        R, cap = row_tok.shape
+        self._check_dev(tokens, starts, lengths, rep, n_groups, row_tok, row_len, row_hash)
+        old, keep = self._i32(n), self._i32(n)
+        gh = torch.empty(n, dtype=torch.int64, device=self.device)
+        check(self.lib.glb_match_prefix_rows(_ptr(tokens), _ptr(starts), _ptr(lengths), _ptr(rep), _ptr(n_groups), n,
+                                             _ptr(row_tok), _ptr(row_len), _ptr(row_hash), R, cap, int(max_new), _ptr(old),
+                                             _ptr(keep), _ptr(gh), self._stream()))
+        return old, keep, gh
+
+    def kv_plan_chunk(self, group_of, rep, n_groups, old_row, old_keep, lengths, n_rows, cap, stamps=None, call_no=0,
+                      table=None):
+        """The block table of one step whose rows with a prefix are fed the tokens keep .. L - 1 (glb_kv_plan_chunk):
+        `kv_plan` with `old_keep` (match_prefix_rows' output) and the row table, which is required.  The dict has
+        `kv_plan`'s entries - `pos_a` / `pos_of_row`: the first new position; forward rows: one-token rows, chunk rows,
+        rows to encode - plus `n_new_a` [n], `n_new_of_row` [n_rows]; `head` has ten words (8: chunk rows, 9: the largest
+        number of tokens fed to a row)."""
+        if table is None:
+            raise ValueError("kv_plan_chunk needs the row table: the rows' lengths decide who keeps a row in place")
+        return self.kv_plan(group_of, rep, n_groups, old_row, lengths, n_rows, cap, stamps=stamps, call_no=call_no,
+                            table=table, old_keep=old_keep)
+
+    def slab_attention_chunk(self, query, k_new, v_new, k_slab, v_slab, pos, n_new, scale, rows=None):
+        """Attention of a forward with up to 16 new tokens per row over slab rows where they lie, the new K / V appended on
+        the way (glb_slab_attention_chunk).  query [n, H, T, Dh], k_new / v_new [n, H_kv, T, Dh] (unit inner stride), slabs
+        [R, H_kv, cap, Dh] contiguous, pos / n_new int32 [n]: first new position and number of new tokens of every row,
+        rows: int32 [n] slab row of forward row i (None: i).  Returns [n, T, H, Dh]; queries t >= n_new[i] give zeros."""
+        n, H, T, Dh = query.shape
+        R, Hkv, cap = k_slab.shape[0], k_slab.shape[1], k_slab.shape[2]
+        assert query.stride(3) == 1 and k_new.stride(3) == 1 and v_new.stride(3) == 1 and k_slab.is_contiguous() and v_slab.is_contiguous()
+        assert k_new.dtype == v_new.dtype == query.dtype == k_slab.dtype == v_slab.dtype
+        assert k_new.shape == v_new.shape == (n, Hkv, T, Dh) and (rows is not None or n == R)
+        out = torch.empty((n, T, H, Dh), dtype=query.dtype, device=self.device)
+        i64x3 = C.c_int64 * 3
+        check(self.lib.glb_slab_attention_chunk(_ptr(query), i64x3(*query.stride()[:3]), _ptr(k_new), i64x3(*k_new.stride()[:3]),
+                                                _ptr(v_new), i64x3(*v_new.stride()[:3]), _ptr(k_slab), _ptr(v_slab), _ptr(pos),
+                                                _ptr(n_new), _ptr(rows), n, R, H, Hkv, cap, Dh, T, float(scale), _DT[query.dtype],
+                                                _ptr(out), self._stream()))
+        return out
+
+    @staticmethod
+    def slab_attention_chunk_supports(dtype, head_dim):
+        return dtype in _DT and head_dim in (16, 32, 64, 128)
 
     def resample_systematic(self, log_weights, seed, offset):
         """Ancestors of a systematic resampling step over `log_weights` (the gathered population), int32 [n]

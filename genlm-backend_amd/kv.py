@@ -37,6 +37,15 @@ def _glb_attention_forward(module, query, key, value, attention_mask, dropout=0.
     from transformers.integrations.sdpa_attention import sdpa_attention_forward
 
     layer = getattr(key, "_glb_layer", None)
+    if layer is not None and layer._new_k is not None and getattr(layer.owner, "n_new", None) is not None:
+        # a chunk forward over slab rows (SharedSlabKV.set_forward_chunk): up to 16 new tokens per row, appended by the kernel
+        if key is not layer.keys or value is not layer.values:
+            raise RuntimeError("glb_slab_attention_chunk: the attention module changed the key / value tensors the KV slab "
+                               "handed out: the new tokens were never appended")
+        k_new, v_new, layer._new_k, layer._new_v = layer._new_k, layer._new_v, None, None
+        o = layer.owner
+        scale = scaling if scaling is not None else query.shape[-1] ** -0.5
+        return o.engine.slab_attention_chunk(query, k_new, v_new, layer.keys, layer.values, o.pos, o.n_new, scale, rows=o.rows), None
     if layer is not None and layer._new_k is not None:
         # an in-place forward whose append is this kernel's job: the new token's K / V are only in the stash
         if key is not layer.keys or value is not layer.values or query.shape[2] != 1:
@@ -212,6 +221,20 @@ class _SharedLayer(_SlabLayer):
             eng.kv_append(self.values, value_states, o.pos)
             return self.keys, self.values
         U = o.rows.numel()
+        if o.n_new is not None:  # a chunk forward: row u's tokens t < n_new[u] go to positions pos[u] + t of slab row rows[u]
+            T = key_states.shape[-2]
+            if key_states.shape[0] != U:
+                raise ValueError("a chunk forward takes the rows SharedSlabKV.set_forward_chunk named")
+            if o.fused_attention:  # glb_slab_attention_chunk appends and reads the rows where they lie
+                self._new_k, self._new_v = key_states, value_states
+                self.keys._glb_layer = self
+                return self.keys, self.values
+            for t in range(T):  # (a position of -1 appends nothing: the padding behind a row's last new token)
+                at = torch.where(o.n_new > t, o.pos + t, torch.full_like(o.pos, -1))
+                for slab, stage, new in ((self.keys, self.stage_keys, key_states), (self.values, self.stage_values, value_states)):
+                    eng.kv_append(slab, new[:, :, t:t + 1], at, rows=o.rows)
+                    eng.kv_append(stage, new[:, :, t:t + 1], at, rows=o.ident[:U])
+            return self.stage_keys[:U], self.stage_values[:U]
         if key_states.shape[0] != U or key_states.shape[-2] != 1:
             raise ValueError("SharedSlabKV takes one new token for every row of the forward")
         # the new token's K / V: into the row that keeps it, and beside the gathered prefix the attention reads
@@ -240,12 +263,37 @@ class SharedSlabKV(SlabKV):
         self.rows = None   # int32 [U]: slab row of every forward row
         self.ident = None  # int32 arange(n)
         self.in_place = False
+        self.n_new = None  # int32 [U]: tokens per row of a chunk forward (None: a one-token forward)
         self._alt = None
         self._ptrs = None
 
+    def set_forward_chunk(self, rows, pos, n_new, fused):
+        """The next forward feeds row u the n_new[u] <= T tokens at positions pos[u] .. of slab row rows[u] (int32 [U]
+        device, batch [U, T], right-padded).  fused: glb_slab_attention_chunk serves it on the rows where they lie; else the
+        prefixes are gathered into the staging slabs for the SDPA path (`attention_mask(pos, n_new, T)`)."""
+        if fused:
+            self.rows, self.pos, self.in_place = rows, pos, False
+        else:
+            self.set_forward(rows, pos)
+        self.n_new = n_new
+
+    def attention_mask(self, pos, n_new=None, T=None, additive_dtype=None):
+        """One-token forward: SlabKV's [n, cap] 0/1 mask.  Chunk forward: [U, 1, T, cap], query t of row u sees positions
+        0 .. pos[u] + min(t, n_new[u] - 1) (a padded query sees what the row's last token sees: never an empty row) - bool,
+        or with `additive_dtype` 0 / most-negative (attention code that adds its mask)."""
+        if n_new is None:
+            return super().attention_mask(pos)
+        t = torch.minimum(torch.arange(T, device=pos.device, dtype=pos.dtype)[None, :], n_new[:, None] - 1)
+        last = pos[:, None] + t  # [U, T]
+        ar = torch.arange(self.cap, device=pos.device, dtype=pos.dtype)
+        see = (ar[None, None, :] <= last[:, :, None])[:, None]
+        if additive_dtype is None:
+            return see
+        return torch.zeros(see.shape, dtype=additive_dtype, device=pos.device).masked_fill_(~see, torch.finfo(additive_dtype).min)
+
     def set_forward(self, rows, pos):
         """rows, pos: int32 [U] device.  Gathers the U prefixes (pos[u] positions of row rows[u]) into the staging slabs."""
-        self.rows, self.pos, self.in_place = rows, pos, False
+        self.rows, self.pos, self.in_place, self.n_new = rows, pos, False, None
         U = rows.numel()
         if self.ident is None:
             self.ident = torch.arange(self.n, dtype=torch.int32, device=rows.device)
@@ -261,7 +309,7 @@ class SharedSlabKV(SlabKV):
         """The next forward runs on ALL slab rows where they lie (batch row b = slab row b, pos: int32 [n] device, the
         position row b's token is appended at): no gather.  Worth it when most rows are live - a free row costs a
         forward row whose result nobody reads, the gather costs every live row's whole prefix, read and written."""
-        self.rows, self.pos, self.in_place = None, pos, True
+        self.rows, self.pos, self.in_place, self.n_new = None, pos, True, None
 
     def copy_rows(self, src_row_of, len_of):
         """Row r with src_row_of[r] >= 0 takes the first len_of[r] positions of row src_row_of[r] (in place: sources
@@ -412,7 +460,54 @@ class SlabRunner:
         return fwd
 
     @torch.no_grad()
-    def run(self, plan, counts, token_at, batch, pad_id=0, row_len=None):
+    def _chunk_fused(self):
+        """Whether glb_slab_attention_chunk serves a chunk forward over these slabs (SlabForward.fused's conditions)."""
+        pkv, cfg, eng = self.pkv, getattr(self.llm._body, "config", None), self.llm.engine
+        k0 = pkv.layers[0].keys if pkv.layers and getattr(pkv.layers[0], "is_initialized", False) else None
+        return bool(cfg is not None and k0 is not None and k0.is_cuda and hasattr(eng, "slab_attention_chunk")
+                    and eng.slab_attention_chunk_supports(k0.dtype, k0.shape[-1])
+                    and getattr(cfg, "_attn_implementation", None) == _ATTN_NAME and getattr(cfg, "_glb_engine", None) is eng)
+
+    def _run_chunk(self, plan, lo, hi, t_max, token_at, pad_id):
+        """Forward rows lo .. hi - 1 of the plan, fed up to t_max tokens each (right-padded with pad_id) over the slab rows
+        where they lie: never part of the one-token forward, never captured.  Returns the hidden states of every row's last
+        new token."""
+        llm, pkv, dev = self.llm, self.pkv, self.llm.device
+        rows = plan["rows_a"][lo:hi].contiguous()
+        pos = plan["pos_a"][lo:hi].contiguous()
+        nn = plan["n_new_a"][lo:hi].contiguous()
+        ctx = plan["ctx_a"][lo:hi].long()
+        ar = torch.arange(t_max, device=dev, dtype=torch.int32)
+        valid = ar[None, :] < nn[:, None]
+        at = torch.where(valid, pos[:, None] + ar[None, :], pos[:, None]).long()  # (padding: a position the row has, its token unused)
+        ids = token_at(ctx[:, None].expand(-1, t_max), at).long()
+        ids = torch.where(valid, ids, torch.full_like(ids, pad_id))
+        fused = self._chunk_fused()
+        pkv.set_forward_chunk(rows, pos, nn, fused)
+        try:
+            if fused:
+                pkv.fused_attention = True
+                try:  # (no mask: the kernel attends to positions 0 .. pos + t and nothing else)
+                    out = llm._body(input_ids=ids, position_ids=at, attention_mask=None, past_key_values=pkv, use_cache=True)
+                finally:
+                    pkv.fused_attention = False
+                    stale = [i for i, ly in enumerate(pkv.layers) if ly._new_k is not None]
+                    for i in stale:
+                        pkv.layers[i]._new_k = pkv.layers[i]._new_v = None
+                if stale:
+                    raise RuntimeError(f"glb_slab_attention_chunk was not reached in layers {stale}: the new tokens' K / V "
+                                       "were not appended")
+            else:
+                impl = getattr(getattr(llm._body, "config", None), "_attn_implementation", None)
+                add = None if impl in ("sdpa", _ATTN_NAME) else pkv.layers[0].keys.dtype
+                out = llm._body(input_ids=ids, position_ids=at, attention_mask=pkv.attention_mask(pos, nn, t_max, add),
+                                past_key_values=pkv, use_cache=True)
+        finally:
+            pkv.n_new = None
+        return out.last_hidden_state[torch.arange(hi - lo, device=dev), (nn - 1).long()]
+
+    @torch.no_grad()
+    def run(self, plan, counts, token_at, batch, pad_id=0, row_len=None, chunk=(0, 0)):
         """The forwards of the block table `plan` (engine.kv_plan).  counts: (U, nA, nB, n_copied, n_unkept, l_max_b), the
         head words the caller read with its one D2H copy (nothing is read back here).  Rows of kind A - their prefix sits
         in a slab row - are fed ONE token, `token_at(ctx, pos)` (int64 index tensors -> the tokens at position pos of
@@ -421,14 +516,18 @@ class SlabRunner:
         every slab row holds according to the caller's table - given, a row outside an in-place forward takes its dummy
         token BEHIND what it holds (a full row has no such place: its length is zeroed, the table forgets it) and a row
         being filled from an encoding at position 0, which the fill overwrites; absent, `pos_of_row` is taken as it is.
+        chunk: (rows fed more than one token, the most tokens fed to a row) of a glb_kv_plan_chunk table - the last `chunk[0]`
+        of the nA rows; they run after the copies and the one-token forward, gathered (`_run_chunk`).
         Returns (logits [U, V]: A rows, then B rows; tokens fed to the body; whether the A part ran in place)."""
         llm, R, cap = self.llm, self.R, self.cap
         eng, dev = llm.engine, llm.device
-        U, nA, nB, n_copied, n_unkept, l_max_b = counts
+        U, nA_all, nB, n_copied, n_unkept, l_max_b = counts
+        n_chunk, t_max = chunk
+        nA = nA_all - n_chunk  # rows fed one token
         parts, fed, in_place = [], nB * l_max_b, False
+        if nA_all and n_copied:
+            self.pkv.copy_rows(plan["copy_src"], plan["copy_len"])
         if nA:
-            if n_copied:
-                self.pkv.copy_rows(plan["copy_src"], plan["copy_len"])
             in_place = self.in_place is not None and nA >= self.in_place * R
             if in_place:
                 # most rows are live: the forward runs on the slab rows where they lie (rows outside it ride along with a
@@ -436,10 +535,11 @@ class SlabRunner:
                 ctx_r, pos_d = plan["ctx_of_row"], plan["pos_of_row"]
                 at = pos_d
                 if row_len is not None:
+                    # (a row that is fed a chunk after this forward - ctx -3 - takes its dummy token at its first new position)
                     is_a, idle = ctx_r >= 0, ctx_r == -1
                     row_len.masked_fill_(idle & (row_len >= cap), 0)
                     zero = torch.zeros_like(ctx_r)
-                    pos_d = torch.where(is_a, pos_d, torch.where(idle, row_len.clamp(max=cap - 1), zero))
+                    pos_d = torch.where(is_a | (ctx_r == -3), pos_d, torch.where(idle, row_len.clamp(max=cap - 1), zero))
                     at = torch.where(is_a, pos_d, zero)
                 ids = token_at(ctx_r.clamp_min(0).long(), at.long()).view(-1, 1).long()
                 hidden = self.slab_forward()(ids, pos_d)
@@ -453,6 +553,9 @@ class SlabRunner:
                                 attention_mask=self.pkv.attention_mask(pos_a), past_key_values=self.pkv, use_cache=True)
                 parts.append(llm._lm_head(out.last_hidden_state[:, 0]))
                 fed += nA
+        if n_chunk:
+            parts.append(llm._lm_head(self._run_chunk(plan, nA, nA_all, t_max, token_at, pad_id)))
+            fed += n_chunk * t_max
         if nB:
             tok_d, st_d, ln_d = batch
             sel = plan["ctx_b"][:nB].contiguous()

@@ -243,7 +243,7 @@ class AsyncAmdLM(AsyncLM):
     @torch.no_grad()
     def __init__(self, hf_model, hf_tokenizer, batch_size=20, timeout=0.02, engine=None, fuse_activations=True,
                  kv_budget_bytes=8 << 30, logprob_budget_bytes=16 << 30, auto_kv_rows=0, auto_kv_cap=64,
-                 logprob_dtype="float32", glb_attention=True, merge_mlp=True, contract=None, gemms="library",
+                 auto_kv_chunk=1, logprob_dtype="float32", glb_attention=True, merge_mlp=True, contract=None, gemms="library",
                  split_gemms=True, w4_gemm="auto"):
         """The caller's `hf_model` is never modified (hf.py:114-140 leaves it alone too): with `fuse_activations` or
         `glb_attention` the forwards of this backend run on a private SHADOW of its module tree that shares every weight
@@ -261,6 +261,11 @@ class AsyncAmdLM(AsyncLM):
         auto_kv_rows > 0: `batch_next_token_step` keeps the KV of the contexts it evaluates in that many slab rows of
         `auto_kv_cap` positions and feeds one token to every context whose first L - 1 tokens it finds there
         (autokv.AutoKV; off by default: the reference re-encodes, hf.py:202-288).
+        auto_kv_chunk = K, 1 .. 16 (needs auto_kv_rows): with K > 1 a context is served by ANY row it shares a prefix of
+        `keep` >= 1 tokens with, provided the L - keep tokens behind it are at most K - they are fed in ONE forward and the
+        row ends up holding the whole context (contexts that grew by several tokens, shrank and grew, or fork off a longer
+        one; the reference's per-token KV, cache.py:103-191).  Everything else is encoded as before; 1 (default) is the
+        one-token behaviour in every respect.  `_auto_kv.stats` counts `chunk_rows` / `chunk_tokens`.
         contract: "poly" / "hw" / "auto" - the arithmetic of the fused step's terms (HipEngine; None: the engine's own, "auto"
         for an engine made here: the hardware exponential for 16-bit logits, the polynomial for float32).
         gemms: "library" (default: PyTorch picks the GEMM kernels as it always does) or "recorded" - the forward's GEMM
@@ -343,10 +348,14 @@ class AsyncAmdLM(AsyncLM):
         self._rows = RowLRU(logprob_budget_bytes)
         # KV rows that follow the contexts handed to batch_next_token_step (off unless auto_kv_rows > 0)
         self._auto_kv = None
+        if isinstance(auto_kv_chunk, bool) or not isinstance(auto_kv_chunk, int) or not 1 <= auto_kv_chunk <= 16:
+            raise ValueError(f"auto_kv_chunk must be an integer from 1 to 16, got {auto_kv_chunk!r}")
+        if auto_kv_chunk > 1 and not auto_kv_rows:
+            raise ValueError("auto_kv_chunk > 1 needs auto_kv_rows: there are no KV rows to share prefixes in")
         if auto_kv_rows:
             from .autokv import AutoKV
 
-            self._auto_kv = AutoKV(self, auto_kv_rows, auto_kv_cap)
+            self._auto_kv = AutoKV(self, auto_kv_rows, auto_kv_cap, chunk=auto_kv_chunk)
         # fused-step state
         self._mask_kind = MASK_NONE
         self._masks = None

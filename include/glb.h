@@ -397,6 +397,63 @@ size_t glb_kv_plan_workspace(int64_t n, int64_t n_rows);
 int glb_kv_plan(const glb_kv_plan_args *args, void *hip_stream);
 
 /*
+ * KV rows that serve ANY shared prefix (the reference's DynamicTokenTrie keeps per-token KV, cache.py:103-191:
+ * a context finds the longest prefix it shares with anything cached).  Three additions; the entry points above keep their
+ * outputs bit for bit.
+ *
+ * glb_match_prefix_rows: glb_match_rows' inputs plus max_new (1 .. GLB_KV_CHUNK_MAX).  For a group's context of L tokens and a
+ *   row r with row_len[r] > 0, let c be the length of the common prefix of the row's tokens and the context's and
+ *   keep = min(c, L - 1).  r is a candidate when keep >= 1, L - keep <= max_new and L <= cap.  out_old_row[g]: the candidate
+ *   with the largest keep - among equals a row that holds exactly the context, then the smallest row index - or -1;
+ *   out_keep[g]: its keep (0 without a row); out_hash[g] (nullable): the group's hash, as glb_match_rows gives it.  Tokens
+ *   are always compared (row_hash is not consulted: rows of every length are candidates).
+ *
+ * glb_kv_plan_chunk: glb_kv_plan with a kept length per group, old_keep (indexed as old_row is).  A row with a prefix is
+ *   fed the tokens at positions keep .. L - 1 in one forward: out_pos_a / out_pos_of_row give the FIRST new position,
+ *   out_n_new_a [n] / out_n_new_of_row [n_rows] the number of tokens (0: the row is not fed), out_copy_len the group's own
+ *   keep.  Forward rows: the ones fed one token first, the ones fed more behind them (head[8] of them), then the rows to
+ *   encode; out_ctx_of_row is -3 for a row that is fed a chunk (it is not part of a one-token forward over all rows).
+ *   The claim rule of glb_kv_plan with one addition: a group may keep its matched row in place only if that row holds at
+ *   most keep + 1 tokens (the parent, the context itself, a sibling).  A longer row is never truncated in place - the
+ *   group takes a copy of its keep tokens into a free row and the long row stays as it is, not free in this call (its stamp
+ *   is renewed).  The first group (by id) that may keep a row in place keeps it.  A group whose keep is outside
+ *   0 .. L - 1, or with more than GLB_KV_CHUNK_MAX tokens behind it, reads as a group without a row.  The row table (plan.row_tok ...) is required.  plan.out_head has TEN words:
+ *   the eight of glb_kv_plan (head[1] counts every row with a prefix), head[8] the rows fed more than one token, head[9]
+ *   the largest number of tokens fed to a row.  With old_keep[g] == L - 1 for every group and matched rows of L - 1 or L
+ *   tokens every output shared with glb_kv_plan equals it (one kernel serves both entries).
+ *
+ * glb_slab_attention_chunk: attention of a forward with up to max_new <= GLB_KV_CHUNK_MAX new tokens per row over slab rows
+ *   where they lie.  q [n_rows, heads, max_new, head_dim], k_new / v_new [n_rows, kv_heads, max_new, head_dim] by element
+ *   strides {row, head, position}, unit inner stride; slabs [n_slab_rows, kv_heads, cap, head_dim] contiguous; forward row r
+ *   lives in slab row row_of[r] (null: r; the rows of one call are distinct); pos[r]: its first new position, n_new[r] in
+ *   1 .. max_new.  Query t < n_new[r] attends positions 0 .. pos[r] + t: below pos[r] from the slab, from pos[r] on from
+ *   k_new / v_new, never from what the slab held there; the n_new[r] new K / V are written to slab positions pos[r] ..
+ *   once per (row, KV head).  out [n_rows, max_new, heads, head_dim] contiguous; outputs of t >= n_new[r] are zeros.  A
+ *   chunk outside its row (pos < 0, pos + n_new > cap, n_new outside 1 .. max_new, a slab row outside the slab): nothing
+ *   appended, the row's outputs NaN - glb_slab_attention's rule.  Output (r, h, t) and the slab afterwards carry the bits
+ *   that t + 1 successive glb_slab_attention calls on that row leave.  float32 / bfloat16 / float16, head_dim 16 / 32 / 64 / 128
+ *   (glb_slab_attention's),
+ *   pointers and strides multiples of 16 bytes.  No atomics, no allocation: fit for a captured graph.
+ */
+#define GLB_KV_CHUNK_MAX 16
+int glb_match_prefix_rows(const int32_t *tokens, const int64_t *starts, const int32_t *lengths, const int32_t *rep,
+                          const int32_t *n_groups, int64_t n, const int32_t *row_tok, const int32_t *row_len,
+                          const uint64_t *row_hash, int64_t n_rows, int64_t cap, int32_t max_new, int32_t *out_old_row,
+                          int32_t *out_keep, uint64_t *out_hash, void *hip_stream);
+typedef struct glb_kv_plan_chunk_args {
+  uint32_t struct_size; /* sizeof(glb_kv_plan_chunk_args) - ABI guard */
+  glb_kv_plan_args plan; /* as for the one-token entry (its own struct_size set); out_head: 10 words */
+  const int32_t *old_keep;
+  int32_t *out_n_new_a, *out_n_new_of_row;
+} glb_kv_plan_chunk_args;
+int glb_kv_plan_chunk(const glb_kv_plan_chunk_args *args, void *hip_stream);
+int glb_slab_attention_chunk(const void *q, const int64_t q_strides[3], const void *k_new, const int64_t k_strides[3],
+                             const void *v_new, const int64_t v_strides[3], void *k_slab, void *v_slab, const int32_t *pos,
+                             const int32_t *n_new, const int32_t *row_of, int64_t n_rows, int64_t n_slab_rows, int64_t heads,
+                             int64_t kv_heads, int64_t cap, int64_t head_dim, int64_t max_new, float scale, int32_t dtype,
+                             void *out, void *hip_stream);
+
+/*
  * Attention of a one-token forward over KV slab rows where they lie (the read side of the device-resident KV, SURVEY.md
  * §8 f1; the reference hands zero-padded per-query KV to the model's own attention, hf.py:247-281): for every row r and
  * query head h, softmax(q . K[r, h / G, 0 .. pos[r]] * scale) . V[r, h / G, 0 .. pos[r]], where position pos[r] is the token
