@@ -626,21 +626,37 @@ class HipEngine:
     def gemm_split(self, x, w_split, n, bias=None, gelu=False, out=None):
         """x [..., K] float32 (rows of unit inner stride) times the weight whose image is `w_split`, plus bias [N], then the
         tanh GELU when `gelu` (glb_gemm_f32_split).  Returns [..., N] float32, or None when the kernel does not serve the
-        call (alignment, shape): the caller then runs its library GEMM."""
+        call (alignment, shape, a bias that is not contiguous float32): the caller then runs its library GEMM.  `out`: a
+        float32 [M, N] tensor on the engine's device with unit inner stride (rows may be padded); ValueError otherwise, and
+        for a bias of the wrong length or device.  Non-finite and out-of-range operands: include/glb.h."""
         k = x.shape[-1]
         x2 = x.reshape(-1, k)
         m = x2.shape[0]
         if m == 0 or x2.stride(1) != 1:
             return None
+        if bias is not None:
+            if bias.device != self.device:
+                raise ValueError(f"bias on {bias.device}, engine on {self.device}")
+            if bias.dim() != 1 or bias.numel() != n:
+                raise ValueError(f"bias of shape {tuple(bias.shape)}, expected ({n},)")
+            if bias.dtype != torch.float32 or bias.stride(0) != 1:
+                return None
         if out is None:
             out = torch.empty((m, n), dtype=torch.float32, device=self.device)
+        else:
+            if out.device != self.device:
+                raise ValueError(f"out on {out.device}, engine on {self.device}")
+            if out.dtype != torch.float32 or tuple(out.shape) != (m, n):
+                raise ValueError(f"out is {out.dtype} {tuple(out.shape)}, expected torch.float32 {(m, n)}")
+            if out.stride(1) != 1 or (m > 1 and out.stride(0) < n):
+                raise ValueError(f"out has strides {out.stride()}: rows of unit inner stride, at least {n} apart, are needed")
         a = _lib.GemmArgs()
         a.struct_size = C.sizeof(_lib.GemmArgs)
         a.m, a.n, a.k = m, n, k
         a.a, a.lda = x2.data_ptr(), x2.stride(0)
         a.w_split = w_split.data_ptr()
         a.bias = bias.data_ptr() if bias is not None else None
-        a.c, a.ldc = out.data_ptr(), n
+        a.c, a.ldc = out.data_ptr(), max(out.stride(0), n)  # (a one-row tensor's stride is arbitrary)
         a.epilogue = _lib.GEMM_BIAS_GELU_TANH if gelu else _lib.GEMM_BIAS
         rc = self.lib.glb_gemm_f32_split(C.byref(a), self._stream())
         if rc == _lib.GLB_EUNSUPPORTED:

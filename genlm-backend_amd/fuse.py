@@ -161,8 +161,14 @@ class SplitConv1D(torch.nn.Module):
     """GPT-2's Conv1D (`addmm(bias, x, weight)`, weight [K, N]) sharing the original module's parameter table.  A float32
     forward on the engine's device without autograd, of at least `min_rows` rows, runs glb_gemm_f32_split on a derived
     image of the weight (hi / mid / lo bf16 planes, 6 bytes per element, rebuilt when the weight is replaced or changed in
-    place: `Tensor._version`, identity, address); everything else runs `torch.addmm` exactly as Conv1D does.  `act`: an
-    activation applied to the result - the tanh GELU goes into the GEMM's epilogue."""
+    place: `Tensor._version`, identity, address); everything else - other dtypes, fewer rows, autograd, a bias that is not
+    contiguous float32 - runs `torch.addmm` exactly as Conv1D does.  `act`: an activation applied to the result - the tanh
+    GELU goes into the GEMM's epilogue.
+
+    On the kernel's path the result is Conv1D's to float32 accuracy for finite operands below 0x1.ffp127 (3.3961775e38), not
+    beyond: a NaN, an infinity or a finite value at or above that threshold (+-FLT_MAX included) in x makes its whole output
+    row non-finite, in the weight its whole output column, where Conv1D gives +-inf or a finite number; the other rows and
+    columns are unaffected (include/glb.h, glb_gemm_f32_split)."""
 
     def __init__(self, src, engine, min_rows):
         super().__init__()

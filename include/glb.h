@@ -731,6 +731,15 @@ int glb_comm_destroy(void *comm);
  * W is split once per weight into a packed image of glb_gemm_split_bytes(k, n) bytes (6 per element; 0 when the shape is
  * not served: the build serves n % 128 == 0 and k % 64 == 0), rebuilt by the caller whenever W changes.  A row-major with
  * row pitch lda (elements; A and lda * 4 16-byte aligned), C row-major with pitch ldc, bias [n] or null.
+ * Only A[0 .. m-1][0 .. k-1] is read and only C[0 .. m-1][0 .. n-1] written, whatever lda and ldc are; the bits of one
+ * element of C depend on its row of A, its column of W and its bias alone - not on m, on the row's position or on the
+ * other rows and columns (tests/test_split_gemm_exact_gpu.py).
+ * Non-finite and out-of-range operands - this is NOT addmm's behaviour: an element of A or W that is NaN, +-inf, or finite
+ * with |x| >= 0x1.ffp127 (3.3961775e38, +-FLT_MAX included: such a value rounds to a bf16 infinity and its residual is
+ * inf - inf) makes every element of its row of C (an element of A) or of its column of C (an element of W) non-finite,
+ * where addmm gives +-inf or, for the finite ones, a number.  Every other row and column keeps the bits of the call
+ * without that element.  Finite |x| below that threshold are served as numbers.  Below 2^-109 the split is exact to
+ * 2^-134 only (lo falls among bf16's subnormals).  A caller that needs IEEE results for such operands runs its library GEMM.
  * Argument errors return GLB_EINVAL before any GPU work, shapes and alignments the kernel does not serve
  * GLB_EUNSUPPORTED (the caller then runs its library GEMM).  Launches go on the given stream, allocate nothing and may be
  * captured into a hipGraph.
