@@ -9,6 +9,8 @@
 * `SlabRunner` — the slabs of one population and the forwards over them: executes the block table glb_kv_plan decided
   (`DeviceSIS._step_shared_kv`, `autokv.AutoKV`).
 * `PrefixTable` — the device table of cached prompt prefixes and the `DynamicCache` a batch that uses them is run with.
+* `encode_ragged` — the one forward that ENCODES a selection of a ragged batch (padded gather, body, last rows, K / V):
+  every re-encoding path of `AsyncAmdLM`, `DeviceSIS` and `SlabRunner.run`'s rows of kind B goes through it.
 * `PrefixLRU` — byte-budgeted least-recently-used store for the prompt prefixes `cache_kv` pins (hf.py:155-164);
   the eviction policy of cache.py:103-191 (`DynamicTokenTrie`), applied to whole prefix slabs.
 """
@@ -520,7 +522,7 @@ class SlabRunner:
         of the nA rows; they run after the copies and the one-token forward, gathered (`_run_chunk`).
         Returns (logits [U, V]: A rows, then B rows; tokens fed to the body; whether the A part ran in place)."""
         llm, R, cap = self.llm, self.R, self.cap
-        eng, dev = llm.engine, llm.device
+        dev = llm.device
         U, nA_all, nB, n_copied, n_unkept, l_max_b = counts
         n_chunk, t_max = chunk
         nA = nA_all - n_chunk  # rows fed one token
@@ -557,22 +559,20 @@ class SlabRunner:
             parts.append(llm._lm_head(self._run_chunk(plan, nA, nA_all, t_max, token_at, pad_id)))
             fed += n_chunk * t_max
         if nB:
-            tok_d, st_d, ln_d = batch
             sel = plan["ctx_b"][:nB].contiguous()
-            ids, am, pos, last = eng.gather_padded(tok_d, st_d, ln_d, sel, nB, None, pad_id, 0, l_max_b)
             stored = nB > n_unkept  # some row keeps the KV of what is encoded here
-            out = llm._body(input_ids=ids, attention_mask=am, position_ids=pos, use_cache=stored)
-            parts.append(llm._lm_head(out.last_hidden_state[torch.arange(nB, device=dev), last.long()]))
+            enc = encode_ragged(llm, batch, sel, nB, l_max_b, pad_id=pad_id, keep_kv=stored)
+            parts.append(llm._lm_head(enc.last_rows()))
             if stored:
-                srcs = [(ly.keys.contiguous(), ly.values.contiguous()) for ly in out.past_key_values.layers]
+                srcs = enc.kv_layers()
                 if self.pkv is None:
-                    self.pkv = SharedSlabKV(eng, R, cap, len(srcs))
+                    self.pkv = SharedSlabKV(llm.engine, R, cap, len(srcs))
                 rows_b = plan["rows_b"][:nB].long()
                 slot = torch.where(rows_b >= 0, rows_b, torch.full_like(rows_b, R))  # (rows nobody keeps: a slot past the end)
                 src_full = torch.full((R + 1,), -1, dtype=torch.int32, device=dev)
                 len_full = torch.zeros(R + 1, dtype=torch.int32, device=dev)
                 src_full[slot] = torch.arange(nB, dtype=torch.int32, device=dev)
-                len_full[slot] = ln_d[sel.long()]
+                len_full[slot] = batch[2][sel.long()]
                 src_full[R] = -1
                 self.pkv.fill_rows(srcs, src_full[:R].contiguous(), len_full[:R].contiguous())
         return (parts[0] if len(parts) == 1 else torch.cat(parts)), fed, in_place
@@ -616,6 +616,36 @@ class PrefixTable:
         return DynamicCache(ddp_cache_data=[tuple(engine.gather_kv_padded(self.ptrs[l][j], self.lengths, pref_u, p0.heads,
                                                                            p0.head_dim, self.p_max, p0.dtype)
                                                   for j in range(2)) for l in range(len(p0.layers))])
+
+
+class RaggedEncoding:
+    """What `encode_ragged` ran: the body's output `out`, `hidden` [n_sel, l_max, d] and every row's `last` position."""
+
+    def __init__(self, out, last):
+        self.out, self.hidden, self.last = out, out.last_hidden_state, last
+
+    def last_rows(self):
+        """[n_sel, d]: the hidden state at every row's last token."""
+        return self.hidden[torch.arange(self.last.numel(), device=self.last.device), self.last.long()]
+
+    def kv_layers(self):
+        """[(K, V)] per layer, contiguous [n_sel, heads, p_max + l_max, head_dim] (an encoding with `keep_kv`)."""
+        return [(ly.keys.contiguous(), ly.values.contiguous()) for ly in self.out.past_key_values.layers]
+
+
+def encode_ragged(llm, batch, sel, n_sel, l_max, pad_id=0, base=None, prefixes=None, keep_kv=False):
+    """Encode contexts `sel` (int32 device, its first n_sel entries) of the ragged `batch` = (tokens, starts, lengths) in one
+    forward of `llm._body` (read here: a call may have swapped it): ragged -> padded gather (glb_gather_padded: masks and
+    position ids for the whole batch, hf.py:232-246), then the transformer body (PyTorch-ROCm; the only MFMA work on the
+    path).  base: int32 [n] device, the leading tokens of every context that are not fed; prefixes = (PrefixTable, int32
+    [n_sel] device: the cached prefix of every selected row, -1 none) serves them from the prefixes' KV (hf.py:247-271,
+    glb_gather_kv_padded per layer and K / V).  keep_kv: the layers' K / V are wanted.  Nothing is read back here."""
+    table, pref = prefixes or (None, None)
+    eng = llm.engine
+    ids, am, pos, last = eng.gather_padded(*batch, sel, n_sel, base, pad_id, 0 if table is None else table.p_max, l_max)
+    cache = None if table is None else table.cache_for(eng, pref)
+    return RaggedEncoding(llm._body(input_ids=ids, attention_mask=am, position_ids=pos, past_key_values=cache,
+                                    use_cache=keep_kv or cache is not None), last)
 
 
 class PrefixLRU:

@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from .cache import KVPrefix, RowLRU, TokenTrie
-from .kv import PrefixLRU, PrefixTable, ragged
+from .kv import PrefixLRU, PrefixTable, encode_ragged, ragged
 from .tokenization import decode_vocab
 
 MASK_NONE, MASK_BITS, MASK_F32 = 0, 1, 2
@@ -614,45 +614,55 @@ class AsyncAmdLM(AsyncLM):
                 raise
 
     def _evaluate(self, queries):
-        eng, dev = self.engine, self.device
         self._lora_sync()
-        n = len(queries)
         if all(q.kind == "step" and q.past is None for q in queries):
-            # a population of README particles (README.md:82-91) and no cached prefix: the whole batch goes through the
-            # vectorised pipeline of batch_next_token_step_sync - three host arrays in, two out, one loop to resolve
-            logZ, tok = self.batch_next_token_step_sync([q.prompt for q in queries], [q.mask_id for q in queries])
-            for q, z, t in zip(queries, logZ.tolist(), tok.tolist()):
-                if q.future is not None and not q.future.done():
-                    q.future.set_result((z, t))
-            return
+            return self._evaluate_steps(queries)
         if (self._auto_kv is not None and not self._kv_tokens
                 and all(q.kind == "logprobs" and q.past is None and q.first_new == len(q.prompt) - 1 for q in queries)):
-            # every request wants the row after its LAST token only (its shorter prefixes are in the trie - a population
-            # that grew by one token): the contexts find their KV rows (autokv.AutoKV) and one token each is fed
-            tok_d, st_d, ln_d = (torch.from_numpy(a).to(dev) for a in ragged([q.prompt for q in queries]))
-            group_of, rep, ng = eng.group_contexts(tok_d, st_d, ln_d)
-            logits, row_of_group, _, U, _ = self._auto_kv.logits(tok_d, st_d, ln_d, group_of, rep, ng)
-            lp = self._log_softmax(logits)
-            rows = torch.cat([row_of_group[group_of.long()], eng.error_word()]).cpu().tolist()
-            eng.raise_if_failed(rows.pop(), what="glb_log_softmax_rows")  # no NaN row may reach the trie
-            self._batch_counter += 1
-            self.stats["batches"] += 1
-            self.stats["queries"] += n
-            self.stats["unique"] += U
-            self.stats["rows"] += U
-            for q, r in zip(queries, rows):
-                if q.future is not None and not q.future.done():
-                    q.future.set_result((lp, r, q.first_new))
-            return
+            return self._evaluate_last_rows(queries)
+        return self._evaluate_encoded(queries)
+
+    def _count(self, n, unique, rows):
+        """One evaluated batch of n requests in `stats`; the fused step's draws move on with it (`_batch_counter`)."""
+        self._batch_counter += 1
+        self.stats["batches"] += 1
+        self.stats["queries"] += n
+        self.stats["unique"] += unique
+        self.stats["rows"] += rows
+
+    def _evaluate_steps(self, queries):
+        # a population of README particles (README.md:82-91) and no cached prefix: the whole batch goes through the
+        # vectorised pipeline of batch_next_token_step_sync - three host arrays in, two out, one loop to resolve
+        logZ, tok = self.batch_next_token_step_sync([q.prompt for q in queries], [q.mask_id for q in queries])
+        for q, z, t in zip(queries, logZ.tolist(), tok.tolist()):
+            if q.future is not None and not q.future.done():
+                q.future.set_result((z, t))
+
+    def _evaluate_last_rows(self, queries):
+        # every request wants the row after its LAST token only (its shorter prefixes are in the trie - a population
+        # that grew by one token): the contexts find their KV rows (autokv.AutoKV) and one token each is fed
+        eng, dev = self.engine, self.device
+        tok_d, st_d, ln_d = (torch.from_numpy(a).to(dev) for a in ragged([q.prompt for q in queries]))
+        group_of, rep, ng = eng.group_contexts(tok_d, st_d, ln_d)
+        logits, row_of_group, _, U, _ = self._auto_kv.logits(tok_d, st_d, ln_d, group_of, rep, ng)
+        lp = self._log_softmax(logits)
+        rows = torch.cat([row_of_group[group_of.long()], eng.error_word()]).cpu().tolist()
+        eng.raise_if_failed(rows.pop(), what="glb_log_softmax_rows")  # no NaN row may reach the trie
+        self._count(len(queries), U, U)
+        for q, r in zip(queries, rows):
+            if q.future is not None and not q.future.done():
+                q.future.set_result((lp, r, q.first_new))
+
+    def _evaluate_encoded(self, queries):
+        """The re-encoding path (hf.py:202-288): requests of both kinds, with or without a `cache_kv` prefix."""
+        eng, dev = self.engine, self.device
+        n = len(queries)
         # -- flatten: context i = [prefix slot, past_len, prompt...]; two header words make the dedup key
         #    (hf.py:216 keys on the prompt only; adding the prefix identity cannot merge unequal requests)
         prefixes, prefix_slot = [], {}
-        lens = np.empty(n, np.int32)
-        for i, q in enumerate(queries):
-            lens[i] = len(q.prompt) + 2
+        lens = np.fromiter((len(q.prompt) + 2 for q in queries), np.int32, n)
         starts = np.zeros(n, np.int64)
-        if n > 1:
-            starts[1:] = np.cumsum(lens[:-1])
+        starts[1:] = np.cumsum(lens[:-1])
         flat = np.empty(int(lens.sum()), np.int32)
         for i, q in enumerate(queries):
             slot = 0
@@ -666,9 +676,7 @@ class AsyncAmdLM(AsyncLM):
             flat[s] = slot
             flat[s + 1] = q.past_len
             flat[s + 2:s + lens[i]] = q.prompt
-        tok_d = torch.from_numpy(flat).to(dev)
-        st_d = torch.from_numpy(starts).to(dev)
-        ln_d = torch.from_numpy(lens).to(dev)
+        tok_d, st_d, ln_d = (torch.from_numpy(a).to(dev) for a in (flat, starts, lens))
 
         # -- shared-prefix dedup on the device, first-appearance order (glb_group_contexts)
         group_of_d, rep_d, ng_d = eng.group_contexts(tok_d, st_d, ln_d)
@@ -683,25 +691,23 @@ class AsyncAmdLM(AsyncLM):
         p_max = max(q.past_len for q in uniq)
         l_max = max(len(q.prompt) for q in uniq)
 
-        # -- ragged -> padded gather (glb_gather_padded).  starts/lengths are shifted so that
+        # -- the ragged batch as the gather takes it: starts/lengths are shifted so that
         #    tokens[start + base + t] is prompt token t, with base = past_len.
         past_len = np.array([q.past_len for q in queries], np.int32)
         base_d = torch.from_numpy(past_len).to(dev)
         st_adj = st_d + 2 - base_d.to(torch.int64)
         ln_adj = ln_d - 2 + base_d
-        ids, am, pos, _last = eng.gather_padded(tok_d, st_adj, ln_adj, rep_d, U, base_d, self._pad_id, p_max, l_max)
 
-        # -- batched prefix KV (glb_gather_kv_padded), one launch per layer and K/V
-        cache = None
+        # -- batched prefix KV: a table of this batch's prefixes alone (it checks that they share one KV shape).  Every
+        #    prefix is some unique query's: the table's longest is p_max
+        prefixes_u = None
         if p_max > 0:
             slot_of_u = np.array([prefix_slot[id(q.past)] - 1 if q.past is not None else -1 for q in uniq], np.int32)
-            # (a table of this batch's prefixes alone; it checks that they share one KV shape.  Every prefix is some
-            # unique query's: the table's longest is p_max)
-            cache = PrefixTable([(p, None) for p in prefixes], dev).cache_for(eng, torch.from_numpy(slot_of_u).to(dev))
+            prefixes_u = (PrefixTable([(p, None) for p in prefixes], dev), torch.from_numpy(slot_of_u).to(dev))
 
-        # -- transformer body (PyTorch-ROCm; the only MFMA work on the path)
-        hidden = self._body(input_ids=ids, attention_mask=am, position_ids=pos, past_key_values=cache,
-                            use_cache=cache is not None).last_hidden_state  # [U, l_max, d]
+        # -- padded gather, prefix KV, transformer body (kv.encode_ragged)
+        hidden = encode_ragged(self, (tok_d, st_adj, ln_adj), rep_d, U, l_max, pad_id=self._pad_id, base=base_d,
+                               prefixes=prefixes_u).hidden  # [U, l_max, d]
 
         # -- which (unique, position) rows are needed: log-prob queries want every new position,
         #    step queries only the last one
@@ -722,8 +728,7 @@ class AsyncAmdLM(AsyncLM):
         ru = torch.from_numpy(np.asarray(row_u, np.int64)).to(dev)
         rt = torch.from_numpy(np.asarray(row_t, np.int64)).to(dev)
         logits = self._lm_head(hidden[ru, rt])  # [R, V] plain library GEMM on the gathered rows
-        V = logits.shape[-1]
-        R = logits.shape[0]
+        R, V = logits.shape
 
         # -- log-prob rows in one launch (glb_log_softmax_rows; replaces cache.py:93-98)
         lp_slab, slab_row = None, None
@@ -753,11 +758,7 @@ class AsyncAmdLM(AsyncLM):
             eng.raise_if_failed(tokens=step_out[1])
         if lp_slab is not None:  # no NaN row may reach the trie: the error word of the log-softmax launch (one small copy)
             eng.raise_if_failed(int(eng.error_word().item()), what="glb_log_softmax_rows")
-        self._batch_counter += 1
-        self.stats["batches"] += 1
-        self.stats["queries"] += n
-        self.stats["unique"] += U
-        self.stats["rows"] += R
+        self._count(n, U, R)
 
         # -- fan out (hf.py:285-288 order)
         si = 0
@@ -765,7 +766,6 @@ class AsyncAmdLM(AsyncLM):
             rows = None
             if u in lp_rows:
                 r0, first = lp_rows[u]
-                cnt = len(uniq[u].prompt) - first
                 # (slab, index of the row of position `first`, first): no view per query
                 rows = (lp_slab, r0 if slab_row is None else slab_row[r0], first)
             for m in members[u]:
@@ -1029,25 +1029,35 @@ class AsyncAmdLM(AsyncLM):
         if lora_names is not None:
             if any(len(c) == 0 for c in contexts):
                 raise ValueError("Token ids must not be empty")
-            mid_d = None
-            if self._mask_kind != MASK_NONE:
-                mid = np.zeros(n, np.int32) if mask_ids is None else np.ascontiguousarray(mask_ids, dtype=np.int32)
-                mid_d = torch.from_numpy(mid).to(dev)
+            mid_d = self._mask_ids_device(mask_ids, n)
             logits, group_of, U, row_mid, by_row = self._lora_rows_logits(contexts, slots, mid_d)
-            logZ, tok = self._finish_batch_step(logits, group_of, group_of, U, n, mid_d, row_mid, by_row)
-            out = torch.stack([logZ, tok.to(torch.float32)]).cpu().numpy()
-            toks = out[1].astype(np.int32)
-            self.engine.raise_if_failed(tokens=toks)
-            return out[0], toks
+            return self._step_to_host(*self._finish_batch_step(logits, group_of, group_of, U, n, mid_d, row_mid, by_row))
         flat, starts, lens = ragged(contexts)
         if int(lens.min()) == 0:
             raise ValueError("Token ids must not be empty")
-        mid_d = None
-        if self._mask_kind != MASK_NONE:
-            mid = np.zeros(n, np.int32) if mask_ids is None else np.ascontiguousarray(mask_ids, dtype=np.int32)
-            mid_d = torch.from_numpy(mid).to(dev)
-        logZ, tok = self._batch_step(torch.from_numpy(flat).to(dev), torch.from_numpy(starts).to(dev),
-                                     torch.from_numpy(lens).to(dev), n, mid_d, l_max=int(lens.max()))
+        mid_d = self._mask_ids_device(mask_ids, n)
+        return self._step_to_host(*self._batch_step(torch.from_numpy(flat).to(dev), torch.from_numpy(starts).to(dev),
+                                                    torch.from_numpy(lens).to(dev), n, mid_d, l_max=int(lens.max())))
+
+    def _mask_ids_device(self, mask_ids, n):
+        """The mask ids of a call's n contexts as an int32 device tensor (absent: mask 0); None when no masks are registered."""
+        if self._mask_kind == MASK_NONE:
+            return None
+        mid = np.zeros(n, np.int32) if mask_ids is None else np.ascontiguousarray(mask_ids, dtype=np.int32)
+        return torch.from_numpy(mid).to(self.device)
+
+    @staticmethod
+    def _row_mask_ids(mid_d, rep, group_of, n, head):
+        """The mask id of every dedup group's representative (None without masks); `head`, the words of the call's D2H copy,
+        gets one more: may the mask ids go per logits row? (they do when the mask is a function of the context)."""
+        if mid_d is None:
+            return None
+        row_mid = mid_d[rep.long().clamp(0, n - 1)]  # entries of `rep` past the group count are unspecified
+        head.append((row_mid[group_of.long()] == mid_d).all().to(torch.int32))
+        return row_mid
+
+    def _step_to_host(self, logZ, tok):
+        """(logZ float32 [n], token int32 [n]) as NumPy arrays, in one D2H copy; raises if a step launch failed."""
         out = torch.stack([logZ, tok.to(torch.float32)]).cpu().numpy()  # token ids < 2^24: exact in float32
         toks = out[1].astype(np.int32)
         self.engine.raise_if_failed(tokens=toks)  # a finishing wave of the one-launch step gave up waiting (include/glb.h)
@@ -1084,9 +1094,8 @@ class AsyncAmdLM(AsyncLM):
         group_of, rep, ng = eng.group_contexts(tok_d, st_d, ln_d)
         P = self._prefix_table()
         T = P["table"]
-        base, pref = None, None
+        base, pref, used_d = None, None, None
         head = [ng[0]]
-        used_d = None
         auto = self._auto_kv if (self._auto_kv is not None and not P["n"]) else None
         if P["n"]:
             pref, base = eng.match_prefixes(tok_d, st_d, ln_d, T.tokens, T.starts, T.lengths)
@@ -1095,9 +1104,7 @@ class AsyncAmdLM(AsyncLM):
             used_d = torch.zeros(P["n"] + 1, dtype=torch.int32, device=dev).index_fill_(0, (pref + 1).long(), 1)[1:]
         elif l_max is None and auto is None:
             head.append(ln_d.max().to(torch.int32))
-        if mid_d is not None:  # may the mask ids go per logits row? (they do when the mask is a function of the context)
-            row_mid = mid_d[rep.long().clamp(0, n - 1)]  # entries of `rep` past the group count are unspecified
-            head.append((row_mid[group_of.long()] == mid_d).all().to(torch.int32))
+        row_mid = self._row_mask_ids(mid_d, rep, group_of, n, head)
         if auto is not None:
             # contexts find the KV rows of their first L - 1 tokens (autokv.AutoKV): one token per context is fed; the error
             # word of the calls so far rides on the call's one D2H copy
@@ -1107,8 +1114,7 @@ class AsyncAmdLM(AsyncLM):
             by_row = bool(extra[-2]) if mid_d is not None else False
             if mid_d is not None:
                 row_mid = row_mid[group_of_row]
-            return self._finish_batch_step(logits, row_of_group[group_of.long()], group_of, U, n, mid_d,
-                                           row_mid if mid_d is not None else None, by_row)
+            return self._finish_batch_step(logits, row_of_group[group_of.long()], group_of, U, n, mid_d, row_mid, by_row)
         n_head = len(head)
         head = torch.stack(head) if used_d is None else torch.cat([torch.stack(head), used_d])
         head = head.cpu().tolist()  # the call's one D2H copy before the forward
@@ -1120,13 +1126,10 @@ class AsyncAmdLM(AsyncLM):
         U = head[0]
         l_max = head[1] if (P["n"] or l_max is None) else l_max
         by_row = bool(head[-1]) if mid_d is not None else False
-        p_max = T.p_max if P["n"] else 0
-        ids, am, pos, last = eng.gather_padded(tok_d, st_d, ln_d, rep, U, base, self._pad_id, p_max, l_max)
-        cache = T.cache_for(eng, pref[rep[:U].long()].contiguous()) if P["n"] else None
-        hidden = self._body(input_ids=ids, attention_mask=am, position_ids=pos, past_key_values=cache,
-                            use_cache=cache is not None).last_hidden_state
-        logits = self._lm_head(hidden[torch.arange(U, device=dev), last.long()])  # [U, V]
-        return self._finish_batch_step(logits, group_of, group_of, U, n, mid_d, row_mid if mid_d is not None else None, by_row)
+        prefixes = (T, pref[rep[:U].long()].contiguous()) if P["n"] else None
+        enc = encode_ragged(self, (tok_d, st_d, ln_d), rep, U, l_max, pad_id=self._pad_id, base=base, prefixes=prefixes)
+        logits = self._lm_head(enc.last_rows())  # [U, V]
+        return self._finish_batch_step(logits, group_of, group_of, U, n, mid_d, row_mid, by_row)
 
     def _finish_batch_step(self, logits, row_of, group_of, U, n, mid_d, row_mid, by_row):
         """The fused step over a batch's logits rows (row_of: logits row of every context; group_of: its dedup group -
@@ -1147,11 +1150,7 @@ class AsyncAmdLM(AsyncLM):
             kw["noise"] = self._noise_rows(V).rows(n, row_slot=slot)
         logZ, _, tok = eng.step(logits, vocab=V, row_of=row_of, rng_mode=self._rng_mode, seed=self._rng_seed,
                                 offset=self._batch_counter, want_lse=False, **kw)
-        self._batch_counter += 1
-        self.stats["batches"] += 1
-        self.stats["queries"] += n
-        self.stats["unique"] += U
-        self.stats["rows"] += U
+        self._count(n, U, U)
         return logZ, tok
 
     async def batch_next_token_step(self, contexts, mask_ids=None, lora_names=None):
@@ -1199,22 +1198,18 @@ class AsyncAmdLM(AsyncLM):
         slots_d = torch.from_numpy(slots).to(dev)
         group_of, rep, ng = eng.group_contexts(tok_d, st_d, ln_d)
         head = [ng[0]]
-        row_mid = None
-        if mid_d is not None:
-            row_mid = mid_d[rep.long().clamp(0, n - 1)]
-            head.append((row_mid[group_of.long()] == mid_d).all().to(torch.int32))
+        row_mid = self._row_mask_ids(mid_d, rep, group_of, n, head)
         head = torch.stack(head).cpu().tolist()
         U = head[0]
         by_row = bool(head[-1]) if mid_d is not None else False
-        ids, am, pos, last = eng.gather_padded(tok_d, st_d + 1, ln_d - 1, rep, U, None, self._pad_id, 0, int(lens.max()) - 1)
         seq_slots = slots_d[rep[:U].long()].contiguous()
         head_was, body_was = self._head, self._body
         with self._row_lora(seq_slots) as rl:
             try:
                 self._head, self._body = self._net.get_output_embeddings(), self._net.base_model
-                hidden = self._body(input_ids=ids, attention_mask=am, position_ids=pos, past_key_values=None,
-                                    use_cache=False).last_hidden_state
-                logits = self._lm_head(hidden[torch.arange(U, device=dev), last.long()])  # [U, V]: per-sequence slots
+                # (the gather leaves the pseudo-token out)
+                enc = encode_ragged(self, (tok_d, st_d + 1, ln_d - 1), rep, U, int(lens.max()) - 1, pad_id=self._pad_id)
+                logits = self._lm_head(enc.last_rows())  # [U, V]: per-sequence slots
             finally:
                 self._head, self._body = head_was, body_was
             self.stats["lora_rows_calls"] += rl.calls
@@ -1232,11 +1227,7 @@ class AsyncAmdLM(AsyncLM):
         lp = self._log_softmax(logits)
         out = lp.index_select(0, group_of.long())
         self.engine.raise_if_failed(int(self.engine.error_word().item()), what="glb_log_softmax_rows")
-        self._batch_counter += 1
-        self.stats["batches"] += 1
-        self.stats["queries"] += n
-        self.stats["unique"] += U
-        self.stats["rows"] += U
+        self._count(n, U, U)
         return out
 
     @torch.no_grad()

@@ -21,7 +21,7 @@ import torch
 
 from ._lib import MASK_BITS
 from .cache import KVPrefix
-from .kv import PrefixTable, SlabKV, SlabRunner
+from .kv import PrefixTable, SlabKV, SlabRunner, encode_ragged
 
 RNG_PHILOX, RNG_NOISE = 1, 2
 
@@ -349,14 +349,13 @@ class DeviceSIS:
         group_of, rep, ng = eng.group_contexts(ctx_flat, self.starts, lens_eff)
         U = int(ng.item())
         l_max = int(lens_eff.max().item())
-        ids, am, pos, _ = eng.gather_padded(ctx_flat, self.starts, lens_eff, rep, U, None, 0, 0, l_max)
-        out = llm._body(input_ids=ids, attention_mask=am, position_ids=pos, use_cache=True)
-        src = [(ly.keys.contiguous(), ly.values.contiguous()) for ly in out.past_key_values.layers]
+        enc = encode_ragged(llm, (ctx_flat, self.starts, lens_eff), rep, U, l_max, keep_kv=True)
+        src = enc.kv_layers()
         if self.pkv is None:
             self._kv.pkv = SlabKV(eng, N, self.cap, len(src))
         src_row = torch.where(want, group_of, torch.full_like(group_of, -1))
         self.pkv.fill_rows(src, src_row, lens_eff)
-        return out, group_of, rep, U
+        return enc, group_of, rep, U
 
     @torch.no_grad()
     def _step_particle_kv(self, time_kernel):
@@ -547,34 +546,26 @@ class DeviceSIS:
             head = torch.stack([self.active.sum().to(torch.int32), self._global_active, eng.error_word()[0]]).cpu()
             n_active, n_global = int(head[0]), int(head[1])
             eng.raise_if_failed(int(head[2]))
-            out, group_of, rep, U = self._encode_into_slabs(None)
+            enc, group_of, rep, U = self._encode_into_slabs(None)
             self._rep = rep
             self._noise_groups = None
-            last = (self.lengths[rep[:U].long()] - 1).long()
-            h_last = out.last_hidden_state[torch.arange(U, device=dev), last]
-            return self._finish_step(llm._lm_head(h_last), group_of, U, n_active, n_global, time_kernel, self.max_len_now)
+            return self._finish_step(llm._lm_head(enc.last_rows()), group_of, U, n_active, n_global, time_kernel, self.max_len_now)
         hashes_eff = torch.where(self.active > 0, self.hashes, self._hash_stub)
         group_of, rep, ng = eng.group_contexts(ctx_flat, self.starts, lengths_eff, hashes=hashes_eff)
         self._rep = rep
         head = torch.stack([ng[0], self.active.sum().to(torch.int32), self._global_active, eng.error_word()[0]]).cpu()  # the step's one D2H copy
         U, n_active, n_global = int(head[0]), int(head[1]), int(head[2])
         eng.raise_if_failed(int(head[3]))  # a fused call of an earlier step that did not complete
-        base, p_max, cache = None, 0, None
+        base, prefixes = None, None
         # at t == 0 every context *is* its prompt, so no cached prefix is a proper prefix yet (hf.py:334-342)
-        use_kv = self.prefixes is not None and self.t > 0
         l_max = self.max_len_now
-        if use_kv:
+        if self.prefixes is not None and self.t > 0:
             P = self.prefixes
             pref, base = eng.match_prefixes(ctx_flat, self.starts, lengths_eff, P.tokens, P.starts, P.lengths)
-            p_max = P.p_max
+            prefixes = (P, pref[rep[:U].long()].contiguous())
             l_max = max(self.t, 1)  # every prompt is cached: only the generated tokens (<= t) are fed
-        ids, am, pos, last = eng.gather_padded(ctx_flat, self.starts, lengths_eff, rep, U, base, 0, p_max, l_max)
-        if use_kv:
-            cache = self.prefixes.cache_for(eng, pref[rep[:U].long()].contiguous())
-        out = llm._body(input_ids=ids, attention_mask=am, position_ids=pos, past_key_values=cache,
-                        use_cache=cache is not None)
-        h_last = out.last_hidden_state[torch.arange(U, device=dev), last.long()]
-        logits = llm._lm_head(h_last)  # [U, V]
+        enc = encode_ragged(llm, (ctx_flat, self.starts, lengths_eff), rep, U, l_max, base=base, prefixes=prefixes)
+        logits = llm._lm_head(enc.last_rows())  # [U, V]
         self._noise_groups = None
         return self._finish_step(logits, group_of, U, n_active, n_global, time_kernel, l_max)
 
