@@ -877,6 +877,12 @@ int glb_lora_rows(const glb_lora_rows_args *args, void *hip_stream);
  * dequantises and runs its library GEMM).  `workspace`: glb_w4_gemm_workspace_bytes(m, n, k) bytes of device memory,
  * 16-byte aligned (0: the call is not served).  Argument errors return GLB_EINVAL before any GPU work; launches go on
  * the given stream, allocate nothing and may be captured into a hipGraph.
+ * Containment (tests/test_w4_gemm_exact_gpu.py): only X[0 .. m-1][0 .. k-1] is read and only Y[0 .. m-1][0 .. n-1] written,
+ * whatever ldx and ldy are; the bits of one element of Y depend on its row of X, its row of W' and its bias alone - not on
+ * m (every row count runs the same additions in the same order), on the row's position or on the other rows and columns.
+ * A NaN or an infinity in X makes only its own row of Y non-finite; a block whose W' is infinite in the 16-bit dtype (a
+ * float32 absmax beyond the dtype's range) or zero touches only its own column; finite operands whose sum leaves the
+ * dtype's range give +-inf as IEEE addition does.  A -0 of W' reaches Y as +0 (the sums start at +0).
  */
 typedef struct glb_w4_args {
   uint32_t struct_size; /* sizeof(glb_w4_args) - ABI guard */
