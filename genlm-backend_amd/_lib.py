@@ -321,6 +321,7 @@ SYMBOLS = {
     "glb_gemm_split_bytes": (_sz, [_i64, _i64]),
     "glb_gemm_split_weights": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _sz, _vp]),
     "glb_gemm_f32_split": (C.c_int, [C.POINTER(GemmArgs), _vp]),
+    "glb_gemm_split_blocks_per_cu": (C.c_int, [C.c_int, C.POINTER(C.c_int)]),
     "glb_lora_merge_workspace_bytes": (_sz, [_i32]),
     "glb_lora_merge": (C.c_int, [C.POINTER(LoraJob), _i32, _vp, _sz, _vp]),
     "glb_lora_rows_table_bytes": (_sz, [_i32, _i32]),

@@ -18,11 +18,13 @@
 // (16 columns, 32 rows of K, plane): piece ((nb * K/32 + kb) * 3 + p) holds, at byte 16 * l, the eight plane-p values
 // W[kb*32 + 8(l>>4) + j][nb*16 + (l&15)], j = 0..7 - exactly the B operand of lane l of v_mfma_f32_16x16x32_bf16, so a
 // piece is staged with one contiguous 1 KiB global_load_lds per wave and read back with one lane-linear ds_read_b128.
-// A stays fp32: its 128 x 32 tile is staged in 16 pieces of 1 KiB, piece (mf, h) holding at byte 16 * l the four values
-// A[mf*16 + (l&15)][8(l>>4) + 4h .. +3] - lane l's A operand is pieces (mf, 0) and (mf, 1) - and split in registers.
+// A stays fp32 and never passes through LDS: each of its elements is used by one wave only, so lane l loads its own operand
+// of row fragment mf - the eight floats A[mf*16 + (l&15)][8(l>>4) .. +7], two float4 - straight from global memory into
+// registers, one K step ahead of its use, and splits it there.  (The four lanes that share l & 15 read 128 contiguous bytes
+// of one row.)
 //
-// Tiling: 128 x 128 output tile per 256-thread block, K step 32, two LDS stages (80 KiB: two blocks per CU); wave w owns
-// rows 32w .. 32w+31 and all 128 columns (2 x 8 fragments of 16 x 16): each A element is split by one wave only.
+// Tiling: 128 x 128 output tile per 256-thread block, K step 32, two LDS stages of the B pieces (48 KiB: three blocks per CU,
+// within 168 VGPRs); wave w owns rows 32w .. 32w+31 and all 128 columns (2 x 8 fragments of 16 x 16).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -40,10 +42,10 @@ typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 
 constexpr int BM = 128, BN = 128, BK = 32, THREADS = 256;
 constexpr int PIECE = 1024;                          // bytes of one staged piece (64 lanes x 16 B)
-constexpr int A_PIECES = (BM / 16) * 2;              // 16
 constexpr int B_PIECES = (BN / 16) * 3;              // 24
-constexpr int STAGE_BYTES = (A_PIECES + B_PIECES) * PIECE;  // 40 KiB
-constexpr int LDS_BYTES = 2 * STAGE_BYTES;                 // 80 KiB
+constexpr int STAGE_BYTES = B_PIECES * PIECE;        // 24 KiB
+constexpr int LDS_BYTES = 2 * STAGE_BYTES;           // 48 KiB
+constexpr int BLOCKS_PER_CU = 3;                     // 144 of the CU's 160 KiB of LDS
 
 // round-to-nearest-even split of two fp32 values into packed bf16 pairs hi / mid / lo (hi + mid + lo == x)
 __device__ __forceinline__ void split2(f32x2 x, uint32_t &h, uint32_t &m, uint32_t &l) {
@@ -104,7 +106,7 @@ __device__ __forceinline__ void glds16(const void *src, char *lds) {
 }
 
 template <bool GELU>
-__global__ __launch_bounds__(THREADS, 2) void gemm_split_kernel(const float *__restrict__ a, int64_t lda,
+__global__ __launch_bounds__(THREADS, BLOCKS_PER_CU) void gemm_split_kernel(const float *__restrict__ a, int64_t lda,
                                                                 const char *__restrict__ wsplit, const float *__restrict__ bias,
                                                                 float *__restrict__ c, int64_t ldc, int m, int n, int k) {
   extern __shared__ __attribute__((aligned(16))) char lds[];
@@ -117,15 +119,14 @@ __global__ __launch_bounds__(THREADS, 2) void gemm_split_kernel(const float *__r
   const int m0 = tm * BM, n0 = tn * BN;
   const int kt_count = k / BK;
 
-  // staging sources (per lane, advanced by one K step each iteration)
-  // A pieces of this wave: p = 4 * wave + i -> (mf = p >> 1, h = p & 1)
-  const float *a_src[4];
+  // sources (per lane, advanced by one K step each iteration)
+  // A operand of this lane for the wave's two row fragments mf = 2 * wave + i: eight floats of one row
+  const float *a_src[2];
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int p = 4 * wave + i, mf = p >> 1, h = p & 1;
-    int row = m0 + mf * 16 + (lane & 15);
+  for (int i = 0; i < 2; ++i) {
+    int row = m0 + (2 * wave + i) * 16 + (lane & 15);
     row = row < m ? row : m - 1;  // rows past M read the last row; their results are never stored
-    a_src[i] = a + (int64_t)row * lda + 8 * (lane >> 4) + 4 * h;
+    a_src[i] = a + (int64_t)row * lda + 8 * (lane >> 4);
   }
   // B pieces of this wave: p = 6 * wave + i -> (nf = p / 3, plane = p % 3); LDS image: plane-major (plane * 8 + nf)
   const char *b_src[6];
@@ -135,14 +136,20 @@ __global__ __launch_bounds__(THREADS, 2) void gemm_split_kernel(const float *__r
     const int p = 6 * wave + i, nf = p / 3, pl = p % 3;
     const int64_t nb = n0 / 16 + nf;
     b_src[i] = wsplit + ((nb * kt_count) * 3 + pl) * PIECE + lane * 16;
-    b_dst[i] = (A_PIECES + pl * 8 + nf) * PIECE;
+    b_dst[i] = (pl * 8 + nf) * PIECE;
   }
   const int64_t b_step = 3 * PIECE;  // one K step further in the packed image
 
-  auto stage = [&](int buf, int kt) {
-    char *base = lds + buf * STAGE_BYTES;
+  f32x4 ax[2][2];  // this lane's A operand of the next K step (prefetched: the loop's closing wait retires it)
+  auto load_a = [&](int kt) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) glds16(a_src[i] + kt * BK, base + (4 * wave + i) * PIECE);
+    for (int i = 0; i < 2; ++i) {
+      ax[i][0] = *(const f32x4 *)(a_src[i] + kt * BK);
+      ax[i][1] = *(const f32x4 *)(a_src[i] + kt * BK + 4);
+    }
+  };
+  auto stage_b = [&](int buf, int kt) {
+    char *base = lds + buf * STAGE_BYTES;
 #pragma unroll
     for (int i = 0; i < 6; ++i) glds16(b_src[i] + kt * b_step, base + b_dst[i]);
   };
@@ -157,27 +164,27 @@ __global__ __launch_bounds__(THREADS, 2) void gemm_split_kernel(const float *__r
 #pragma unroll
   for (int nf = 0; nf < 8; ++nf) bcol[nf] = bias ? bias[n0 + nf * 16 + (lane & 15)] : 0.0f;
 
-  stage(0, 0);
+  load_a(0);
+  stage_b(0, 0);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 
   for (int kt = 0; kt < kt_count; ++kt) {
     const int cur = kt & 1;
-    if (kt + 1 < kt_count) stage(cur ^ 1, kt + 1);
     const char *base = lds + cur * STAGE_BYTES;
     bf16x8 ah[2], am[2], al[2];
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int mf = 2 * wave + i;
-      const f32x4 x0 = *(const f32x4 *)(base + (2 * mf) * PIECE + lane * 16);
-      const f32x4 x1 = *(const f32x4 *)(base + (2 * mf + 1) * PIECE + lane * 16);
-      split8(x0, x1, ah[i], am[i], al[i]);
+    for (int i = 0; i < 2; ++i) split8(ax[i][0], ax[i][1], ah[i], am[i], al[i]);
+    // (after the split: the prefetch registers are free, and nothing beyond column K of a row is ever addressed)
+    if (kt + 1 < kt_count) {
+      load_a(kt + 1);
+      stage_b(cur ^ 1, kt + 1);
     }
 #pragma unroll
     for (int nf = 0; nf < 8; ++nf) {
-      const bf16x8 bh = *(const bf16x8 *)(base + (A_PIECES + 0 * 8 + nf) * PIECE + lane * 16);
-      const bf16x8 bm = *(const bf16x8 *)(base + (A_PIECES + 1 * 8 + nf) * PIECE + lane * 16);
-      const bf16x8 bl = *(const bf16x8 *)(base + (A_PIECES + 2 * 8 + nf) * PIECE + lane * 16);
+      const bf16x8 bh = *(const bf16x8 *)(base + (0 * 8 + nf) * PIECE + lane * 16);
+      const bf16x8 bm = *(const bf16x8 *)(base + (1 * 8 + nf) * PIECE + lane * 16);
+      const bf16x8 bl = *(const bf16x8 *)(base + (2 * 8 + nf) * PIECE + lane * 16);
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
         f32x4 t = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am[i], bm, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
@@ -189,7 +196,8 @@ __global__ __launch_bounds__(THREADS, 2) void gemm_split_kernel(const float *__r
         acc[i][nf] += t;  // (round-to-nearest add of this K step's partial: see the header)
       }
     }
-    // the next stage has landed for every wave, and every wave is done reading this one (it is restaged next iteration)
+    // the next stage and this lane's next A operand have landed, and every wave is done reading this stage (it is restaged
+    // next iteration)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
   }
@@ -271,6 +279,17 @@ int glb_gemm_f32_split(const glb_gemm_args *args, void *stream) {
                        g.lda, (const char *)g.w_split, g.bias, g.c, g.ldc, (int)g.m, (int)g.n, (int)g.k);
   e = hipGetLastError();
   if (e != hipSuccess) return glb::api_hip_fail(e, "split GEMM launch");
+  return GLB_OK;
+}
+
+int glb_gemm_split_blocks_per_cu(int gelu, int *blocks) {
+  if (!blocks) return glb::api_fail(GLB_EINVAL, "null pointer");
+  const void *kern = gelu ? (const void *)gemm_split_kernel<true> : (const void *)gemm_split_kernel<false>;
+  hipError_t e = glb::allow_dynamic_lds(kern, LDS_BYTES, gelu ? g_lds_gelu : g_lds_plain);
+  if (e != hipSuccess) return glb::api_hip_fail(e, "split GEMM LDS attribute");
+  e = gelu ? hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, gemm_split_kernel<true>, THREADS, LDS_BYTES)
+           : hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, gemm_split_kernel<false>, THREADS, LDS_BYTES);
+  if (e != hipSuccess) return glb::api_hip_fail(e, "split GEMM occupancy query");
   return GLB_OK;
 }
 

@@ -610,6 +610,13 @@ class HipEngine:
     def gemm_split_supports(self, k, n):
         return self.lib.glb_gemm_split_bytes(k, n) > 0
 
+    def gemm_split_blocks_per_cu(self, gelu=False):
+        """Blocks of the split GEMM's kernel (with the GELU epilogue when `gelu`) resident on one CU of this device."""
+        blocks = C.c_int(0)
+        with torch.cuda.device(self.device):
+            check(self.lib.glb_gemm_split_blocks_per_cu(int(bool(gelu)), C.byref(blocks)))
+        return blocks.value
+
     def gemm_split_weights(self, w):
         """The packed hi / mid / lo bf16 image of a float32 weight w [K, N] (glb_gemm_split_weights: 6 bytes per element),
         or None when the kernel does not serve its shape."""

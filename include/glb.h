@@ -759,6 +759,10 @@ typedef struct glb_gemm_args {
 size_t glb_gemm_split_bytes(int64_t k, int64_t n);
 int glb_gemm_split_weights(const float *w, int64_t k, int64_t n, int64_t ldw, void *out, size_t out_bytes, void *hip_stream);
 int glb_gemm_f32_split(const glb_gemm_args *args, void *hip_stream);
+/* How many blocks of the split GEMM's kernel (gelu != 0: the instantiation with the GELU epilogue) the runtime keeps resident
+ * on one CU of the current device, given the kernel's registers and its dynamic LDS (hipOccupancyMaxActiveBlocksPerMultiprocessor).
+ * The kernel is built for three; no GPU work. */
+int glb_gemm_split_blocks_per_cu(int gelu, int *blocks);
 
 /*
  * LoRA merge: out = W + scale * B . A for every matrix of an adapter in one call - what peft's merged
