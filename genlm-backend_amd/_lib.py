@@ -255,6 +255,26 @@ class W4GemmArgs(C.Structure):
     ]
 
 
+DFA_COUNTERS = 4  # GLB_DFA_COUNTERS: rows in use, work entries filled, overflow (sticky), private
+
+
+class DfaArgs(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("n_states", C.c_int32), ("start", C.c_int32), ("eos_id", C.c_int32),
+        ("delta", C.c_void_p), ("accepting", C.c_void_p), ("live", C.c_void_p),
+        ("vocab", C.c_int64),
+        ("tok_bytes", C.c_void_p), ("n_bytes", C.c_int64), ("tok_ptr", C.c_void_p), ("skip", C.c_void_p),
+        ("n", C.c_int64),
+        ("tokens", C.c_void_p), ("ld", C.c_int64), ("from_", C.c_void_p), ("to", C.c_void_p),
+        ("state_in", C.c_void_p), ("state_out", C.c_void_p),
+        ("bank", C.c_void_p), ("bank_ld", C.c_int64), ("capacity", C.c_int64),
+        ("row_of_state", C.c_void_p), ("work", C.c_void_p), ("counters", C.c_void_p),
+        ("max_work", C.c_int64),
+        ("done", C.c_void_p), ("out_rows", C.c_void_p),
+    ]
+
+
 # every symbol include/glb.h declares: name -> (restype, argtypes)
 _vp, _i32, _i64, _f32, _sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_size_t
 SYMBOLS = {
@@ -334,6 +354,12 @@ SYMBOLS = {
     "glb_w4_gemm_max_rows": (C.c_int, []),
     "glb_w4_gemm_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "glb_w4_gemm": (C.c_int, [C.POINTER(W4GemmArgs), _vp]),
+    "glb_dfa_bank_init": (C.c_int, [C.POINTER(DfaArgs), _vp]),
+    "glb_dfa_advance": (C.c_int, [C.POINTER(DfaArgs), _vp]),
+    "glb_dfa_claim_rows": (C.c_int, [C.POINTER(DfaArgs), _vp]),
+    "glb_dfa_fill_masks": (C.c_int, [C.POINTER(DfaArgs), _vp]),
+    "glb_dfa_mask_ids": (C.c_int, [C.POINTER(DfaArgs), _vp]),
+    "glb_dfa_bank_rows": (_i64, [_sz, _i64, _i64]),
     "glb_philox4x32_10": (None, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
 }
 

@@ -1,0 +1,291 @@
+"""Byte-level DFA constraints on the device (include/glb.h glb_dfa_*).
+
+`ByteDFA` is the automaton a user brings (a compiled regex, a literal set, a schema: a transition table over bytes);
+`DeviceConstraint` keeps it on the GPU beside the vocabulary's byte strings and produces what the fused step consumes:
+a bank of token bit masks, one row per automaton state that some particle has reached, and every particle's row.  States
+advance on the device from the tokens drawn; nothing crosses the host per step.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+
+
+class ByteDFA:
+    """delta int32 [S, 256] (-1: no transition), accepting bool [S], start in [0, S).  `live[s]`: some accepting state is
+    reachable from s (s included)."""
+
+    def __init__(self, delta, accepting, start):
+        delta = np.asarray(delta)
+        accepting = np.asarray(accepting)
+        if delta.ndim != 2 or delta.shape[1] != 256 or delta.shape[0] == 0:
+            raise ValueError(f"delta must be [S, 256] with S >= 1, got {delta.shape}")
+        if not np.issubdtype(delta.dtype, np.integer):
+            raise ValueError("delta must hold integers")
+        S = delta.shape[0]
+        if S > 0x7fffff00:
+            raise ValueError("too many states")
+        if delta.min() < -1 or delta.max() >= S:
+            raise ValueError(f"delta entries must be -1 or a state in [0, {S})")
+        if accepting.shape != (S,):
+            raise ValueError(f"accepting must be [{S}], got {accepting.shape}")
+        if accepting.dtype != np.bool_ and not np.isin(accepting, (0, 1)).all():
+            raise ValueError("accepting must be boolean")
+        if isinstance(start, bool) or not isinstance(start, (int, np.integer)) or not 0 <= int(start) < S:
+            raise ValueError(f"start must be an int in [0, {S})")
+        self.delta = np.ascontiguousarray(delta, dtype=np.int32)
+        self.accepting = np.ascontiguousarray(accepting.astype(np.bool_))
+        self.start = int(start)
+        self.n_states = S
+        self.live = self._live()
+
+    def _live(self):
+        """Backwards reachability from the accepting states over the reversed transition graph."""
+        S = self.n_states
+        src = np.repeat(np.arange(S, dtype=np.int64), 256)
+        dst = self.delta.reshape(-1).astype(np.int64)
+        keep = dst >= 0
+        src, dst = src[keep], dst[keep]
+        order = np.argsort(dst, kind="stable")
+        src, dst = src[order], dst[order]
+        first = np.searchsorted(dst, np.arange(S + 1))
+        live = self.accepting.copy()
+        todo = list(np.nonzero(live)[0])
+        while todo:
+            s = todo.pop()
+            for p in src[first[s]:first[s + 1]]:
+                if not live[p]:
+                    live[p] = True
+                    todo.append(int(p))
+        return live
+
+    @classmethod
+    def from_strings(cls, strings):
+        """The trie automaton of a finite language: accepts exactly the given byte strings."""
+        strings = [bytes(s) for s in strings]
+        if not strings:
+            raise ValueError("from_strings needs at least one string")
+        rows, acc = [np.full(256, -1, np.int32)], [False]
+        for s in strings:
+            cur = 0
+            for b in s:
+                if rows[cur][b] < 0:
+                    rows[cur][b] = len(rows)
+                    rows.append(np.full(256, -1, np.int32))
+                    acc.append(False)
+                cur = int(rows[cur][b])
+            acc[cur] = True
+        return cls(np.stack(rows), np.array(acc, np.bool_), 0)
+
+    def accepts(self, data):
+        s = self.start
+        for b in bytes(data):
+            s = int(self.delta[s, b])
+            if s < 0:
+                return False
+        return bool(self.accepting[s])
+
+
+class DeviceConstraint:
+    """A `ByteDFA` over a vocabulary's byte strings, resident on the device.
+
+    llm_or_engine    an `AsyncAmdLM` (its engine and, for the default `skip_ids`, its tokenizer's `all_special_ids`) or a
+                     `HipEngine`
+    byte_vocab       the byte string of every token id (`llm.byte_vocab`); objects with a `byte_string` are accepted
+    eos_id           allowed exactly in accepting states
+    skip_ids         tokens never allowed (special tokens)
+    mask_bank_bytes  budget of the mask bank: one row of ceil(V / 32) words per distinct state reached, plus two.  A bank
+                     that cannot hold a state a particle reaches is an error (`check()`), not an eviction.
+    """
+
+    def __init__(self, llm_or_engine, dfa, byte_vocab, eos_id, skip_ids=None, mask_bank_bytes=256 << 20):
+        import torch
+
+        eng = getattr(llm_or_engine, "engine", llm_or_engine)
+        self.eng, self.dev, self.dfa = eng, eng.device, dfa
+        toks = [bytes(getattr(t, "byte_string", t)) for t in byte_vocab]
+        V = len(toks)
+        if V == 0:
+            raise ValueError("empty vocabulary")
+        if skip_ids is None:
+            skip_ids = getattr(getattr(llm_or_engine, "tokenizer", None), "all_special_ids", None) or ()
+        skip = np.zeros(V, np.uint8)
+        for t in skip_ids:
+            if 0 <= int(t) < V:
+                skip[int(t)] = 1
+        ptr = np.zeros(V + 1, np.int64)
+        np.cumsum([len(t) for t in toks], out=ptr[1:])
+        if ptr[-1] > 0x7fffffff:
+            raise ValueError("the vocabulary's byte strings exceed 2^31 bytes")
+        flat = np.frombuffer(b"".join(toks) or b"\0", np.uint8).copy()
+        self.vocab, self.eos_id, self.words = V, int(eos_id), (V + 31) // 32
+        self.n_bytes = int(ptr[-1])
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.dev)
+        self._delta, self._acc, self._live = up(dfa.delta), up(dfa.accepting.astype(np.uint8)), up(dfa.live.astype(np.uint8))
+        self._bytes, self._ptr, self._skip = up(flat), up(ptr.astype(np.int32)), up(skip)
+        self.mask_bank_bytes = int(mask_bank_bytes)
+        self._gathered, self._cus = None, None
+        rows = int(eng.lib.glb_dfa_bank_rows(self.mask_bank_bytes, V, dfa.n_states))
+        if rows < 3:
+            raise ValueError(f"mask_bank_bytes={mask_bank_bytes} holds no state's mask: a row of this vocabulary takes "
+                             f"{self.words * 4} bytes and the bank needs at least three")
+        self._row_of_state = torch.empty(dfa.n_states, dtype=torch.int32, device=self.dev)
+        self._counters = torch.zeros(_lib.DFA_COUNTERS, dtype=torch.int32, device=self.dev)
+        self._set_bank(torch.zeros((rows, self.words), dtype=torch.int32, device=self.dev))
+
+    # ---- the bank ------------------------------------------------------------------------------------------------------
+    def _set_bank(self, bank):
+        """Use `bank` (int32 [rows, >= ceil(V / 32)], unit inner stride; rows may be padded) and start it over."""
+        import torch
+
+        if bank.dtype != torch.int32 or bank.dim() != 2 or bank.stride(1) != 1 or bank.shape[0] < 3 or bank.shape[1] < self.words \
+                or bank.device != self.dev:
+            raise ValueError("bank must be an int32 [rows >= 3, >= ceil(V / 32)] device tensor with unit inner stride")
+        self.bank = bank
+        self._work = torch.zeros((bank.shape[0], 2), dtype=torch.int32, device=self.dev)
+        self._reset_bank()
+
+    def _reset_bank(self):
+        """Forget every state's row (rows 0 and 1 are written again, the overflow word cleared)."""
+        self._warm = False
+        self._call("glb_dfa_bank_init", self._args())
+
+    capacity = property(lambda self: self.bank.shape[0])
+
+    def _args(self):
+        a = _lib.DfaArgs()
+        a.struct_size = C.sizeof(_lib.DfaArgs)
+        a.n_states, a.start, a.eos_id = self.dfa.n_states, self.dfa.start, self.eos_id
+        a.delta, a.accepting, a.live = self._delta.data_ptr(), self._acc.data_ptr(), self._live.data_ptr()
+        a.vocab, a.tok_bytes, a.n_bytes = self.vocab, self._bytes.data_ptr(), self.n_bytes
+        a.tok_ptr, a.skip = self._ptr.data_ptr(), self._skip.data_ptr()
+        a.bank, a.bank_ld, a.capacity = self.bank.data_ptr(), self.bank.stride(0), self.bank.shape[0]
+        a.row_of_state, a.work, a.counters = self._row_of_state.data_ptr(), self._work.data_ptr(), self._counters.data_ptr()
+        return a
+
+    def _call(self, name, a):
+        self.eng.dfa_call(name, a)
+
+    def _states(self, states):
+        import torch
+
+        if states.dtype != torch.int32 or states.dim() != 1 or states.device != self.dev or not states.is_contiguous():
+            raise ValueError("states must be a contiguous int32 [n] tensor on the engine's device")
+        return states
+
+    # ---- states --------------------------------------------------------------------------------------------------------
+    def states0(self, n):
+        import torch
+
+        return torch.full((n,), self.dfa.start, dtype=torch.int32, device=self.dev)
+
+    def advance(self, states, tokens, frm, to, out=None):
+        """The states after tokens[i, frm[i] .. to[i]) (int32 [n, ld], unit inner stride), from states[i] (None: the start
+        state); -1 once dead.  One launch (glb_dfa_advance)."""
+        import torch
+
+        if tokens.dtype != torch.int32 or tokens.dim() != 2 or tokens.device != self.dev:
+            raise ValueError("tokens must be an int32 [n, ld] tensor on the engine's device")
+        tokens = tokens.contiguous()
+        n = tokens.shape[0]
+        if out is None:
+            out = torch.empty(n, dtype=torch.int32, device=self.dev)
+        if n == 0:
+            return out
+        for t in (frm, to):
+            if t.dtype != torch.int32 or t.shape != (n,) or t.device != self.dev or not t.is_contiguous():
+                raise ValueError("frm / to must be contiguous int32 [n] tensors on the engine's device")
+        a = self._args()
+        a.n, a.tokens, a.ld = n, tokens.data_ptr(), tokens.shape[1]
+        if tokens.shape[1] == 0:  # nothing to walk: from == to == 0 is the only range inside
+            a.tokens, a.ld = self._ptr.data_ptr(), 1
+            to = torch.minimum(to, frm)
+        a.from_, a.to = frm.data_ptr(), to.data_ptr()
+        a.state_in = None if states is None else self._states(states).data_ptr()
+        a.state_out = out.data_ptr()
+        self._call("glb_dfa_advance", a)
+        return out
+
+    def _claim_and_fill(self, states):
+        """Every state of `states` that has no bank row yet gets one, and the new rows are filled (two launches)."""
+        n = states.numel()
+        if n == 0:
+            return
+        a = self._args()
+        a.n, a.state_in = n, self._states(states).data_ptr()
+        self._call("glb_dfa_claim_rows", a)
+        a.max_work = min(n, self.dfa.n_states, self.capacity)
+        self._call("glb_dfa_fill_masks", a)
+
+    def mask_rows(self, states, done=None):
+        """int32 [n]: the bank row of every state - 0 (nothing allowed) for a dead one; where `done` (int32 [n]) is set, row
+        1 (EOS only) if the state is accepting, else 0.  Claims and fills what is missing first; no host synchronisation."""
+        import torch
+
+        n = states.numel()
+        out = torch.empty(n, dtype=torch.int32, device=self.dev)
+        if n == 0:
+            return out
+        if not self._warm:
+            self._claim_and_fill(states)
+        a = self._args()
+        a.n, a.state_in, a.out_rows = n, self._states(states).data_ptr(), out.data_ptr()
+        if done is not None:
+            if done.dtype != torch.int32 or done.shape != (n,) or not done.is_contiguous() or done.device != self.dev:
+                raise ValueError("done must be a contiguous int32 [n] tensor on the engine's device")
+            a.done = done.data_ptr()
+        self._call("glb_dfa_mask_ids", a)
+        return out
+
+    def step_masks(self, ids, by_row, n_particles, parity=False):
+        """The fused step's mask arguments for bank rows `ids` (int32 [n_units]: per logits row when `by_row`, else per
+        particle), and whether the bank itself is handed over.  `GLB_MASK_BITS` rows are read as they are only by the
+        step's one-launch form; its two-launch form first brings ALL rows of the table it is given into the kernels'
+        layout.  So the bank is handed over where glb_logprob_mask_sample takes the one-launch form (csrc/glb_api.hip,
+        `fused`: no parity draw, more than 512 (unit, 4096-token chunk) items, at most 16 x 8 x CUs particles), and
+        otherwise only the units' rows, gathered into a buffer of this object.  This is the one place the rule is
+        restated; where it guesses wrong (a stream being captured, a workspace nobody registered) the step still computes
+        the same results from the whole bank, only slower."""
+        import torch
+
+        key = "row_mask_id" if by_row else "mask_id"
+        n_units = ids.numel()
+        if self._cus is None:
+            self._cus = torch.cuda.get_device_properties(self.dev).multi_processor_count
+        if not parity and n_units * ((self.vocab + 4095) // 4096) > 512 and n_particles <= 16 * 8 * self._cus:
+            return {"mask_kind": _lib.MASK_BITS, "mask": self.bank, key: ids}, True
+        if self._gathered is None or self._gathered[0].shape[0] != n_units:
+            self._gathered = (torch.empty((n_units, self.words), dtype=torch.int32, device=self.dev),
+                              torch.arange(n_units, dtype=torch.int32, device=self.dev))
+        buf, own = self._gathered
+        self.eng.gather_rows_i32(self.bank[:, :self.words], ids, out=buf)
+        return {"mask_kind": _lib.MASK_BITS, "mask": buf, key: own}, False
+
+    def warm(self):
+        """Fill the rows of ALL states when the bank holds them (later `mask_rows` calls are then one small launch).
+        Returns whether it did."""
+        import torch
+
+        if self.dfa.n_states + 2 > self.capacity:
+            return False
+        if not self._warm:
+            self._claim_and_fill(torch.arange(self.dfa.n_states, dtype=torch.int32, device=self.dev))
+            self._warm = True
+        return True
+
+    def _overflow_word(self):
+        """int32 [1] device view of the sticky overflow word, for hosts that let it ride on a copy they make anyway."""
+        return self._counters[2:3]
+
+    def _rows_in_use(self):
+        """(synchronises)"""
+        return int(self._counters[0].item())
+
+    def check(self, word=None):
+        """Raises when a state found no row in the bank (synchronises unless `word`, the overflow word's value already on
+        the host, is given)."""
+        if int(self._counters[2].item()) if word is None else int(word):
+            raise RuntimeError(f"the constraint's mask bank is full: {self.capacity} rows of {self.words * 4} bytes "
+                               f"(mask_bank_bytes={self.mask_bank_bytes}) do not hold the automaton states the particles "
+                               "reached; their masks were empty.  Raise mask_bank_bytes.")

@@ -1,0 +1,238 @@
+// glb_dfa.hip — byte-level DFA constraints on the device (include/glb.h: glb_dfa_*): automaton states advance
+// token by token, every distinct state claims one row of a mask bank, and the rows are filled from the automaton - a wave
+// per (state, 64 consecutive tokens), the 64 bits by one ballot.  Everything read from device memory is range-checked.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/glb.h"
+#include "glb_common.hpp"
+
+namespace {
+
+enum { C_ROWS = 0, C_FILLED = 1, C_OVERFLOW = 2, C_RESERVED = 3 };
+constexpr int FILL_THREADS = 256;    // four waves: 256 consecutive tokens of one state
+constexpr int FILL_MAX_ENTRIES = 64; // grid.y: work entries served side by side (a block loops over the rest)
+
+struct Dfa {
+  const int32_t *delta;
+  const uint8_t *accepting, *live;
+  int32_t n_states, start, eos_id;
+  const uint8_t *bytes;
+  int64_t n_bytes;
+  const int32_t *ptr;
+  const uint8_t *skip;
+  int64_t vocab;
+};
+
+// next(s, t) of include/glb.h
+__device__ inline int32_t dfa_next(const Dfa &d, int32_t s, int64_t t) {
+  if (s < 0 || s >= d.n_states || t < 0 || t >= d.vocab) return -1;
+  if (d.skip[t]) return -1;
+  const int64_t p0 = d.ptr[t], p1 = d.ptr[t + 1];
+  if (p0 < 0 || p1 <= p0 || p1 > d.n_bytes) return -1;  // an empty token, or offsets that are not the vocabulary's
+  int32_t cur = s;
+  for (int64_t p = p0; p < p1; ++p) {
+    cur = d.delta[(int64_t)cur * 256 + d.bytes[p]];
+    if (cur < 0 || cur >= d.n_states) return -1;
+  }
+  return d.live[cur] ? cur : -1;
+}
+
+__global__ void dfa_bank_init_kernel(Dfa d, int32_t *bank, int64_t bank_ld, int64_t words, int32_t *row_of_state,
+                                     int32_t *counters) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < d.n_states) row_of_state[i] = -1;
+  if (i < words) {
+    bank[i] = 0;
+    const bool eos_here = d.eos_id >= 0 && d.eos_id < d.vocab && (d.eos_id >> 5) == i;
+    bank[bank_ld + i] = eos_here ? (int32_t)(1u << (d.eos_id & 31)) : 0;
+  }
+  if (i == 0) {
+    counters[C_ROWS] = 2;
+    counters[C_FILLED] = 0;
+    counters[C_OVERFLOW] = 0;
+    counters[C_RESERVED] = 0;
+  }
+}
+
+__global__ void dfa_advance_kernel(Dfa d, int64_t n, const int32_t *tokens, int64_t ld, const int32_t *from, const int32_t *to,
+                                   const int32_t *state_in, int32_t *state_out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  int32_t cur = state_in ? state_in[i] : d.start;
+  if (cur < 0 || cur >= d.n_states) cur = -1;
+  const int64_t f = from[i], t = to[i];
+  if (f < 0 || t > ld || f > t) cur = -1;
+  for (int64_t j = f; j < t && cur >= 0; ++j) cur = dfa_next(d, cur, tokens[i * ld + j]);
+  state_out[i] = cur;
+}
+
+__global__ void dfa_claim_kernel(int32_t n_states, int64_t n, const int32_t *states, int32_t capacity, int32_t *row_of_state,
+                                 int32_t *work, int32_t *counters) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int32_t s = states[i];
+  if (s < 0 || s >= n_states) return;
+  if (__hip_atomic_load(&row_of_state[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != -1) return;
+  if (atomicCAS(&row_of_state[s], -1, -2) != -1) return;  // somebody else claims for this state
+  const int32_t r = atomicAdd(&counters[C_ROWS], 1);
+  if (r >= 2 && r < capacity) {
+    work[2 * (int64_t)(r - 2)] = s;
+    work[2 * (int64_t)(r - 2) + 1] = r;
+    atomicExch(&row_of_state[s], r);
+  } else {  // the bank is full: the state stays without a row, the counter where it was
+    atomicSub(&counters[C_ROWS], 1);
+    atomicExch(&row_of_state[s], -1);
+    atomicOr(&counters[C_OVERFLOW], 1);
+  }
+}
+
+__global__ __launch_bounds__(FILL_THREADS) void dfa_fill_kernel(Dfa d, int32_t *bank, int64_t bank_ld, int32_t capacity,
+                                                               const int32_t *work, const int32_t *counters) {
+  __shared__ int32_t range[2];
+  if (threadIdx.x == 0) {
+    int32_t begin = __hip_atomic_load(&counters[C_FILLED], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    int32_t end = __hip_atomic_load(&counters[C_ROWS], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    end = (end > capacity ? capacity : end) - 2;
+    if (begin < 0) begin = 0;
+    range[0] = begin;
+    range[1] = end;
+  }
+  __syncthreads();
+  const int32_t begin = range[0], end = range[1];
+  const int64_t words = (d.vocab + 31) / 32;
+  const int64_t t = (int64_t)blockIdx.x * FILL_THREADS + threadIdx.x;  // (a wave: 64 consecutive tokens, two words)
+  const int64_t w0 = (t >> 6) * 2;
+  const int lane = threadIdx.x & 63;
+  if (w0 < words) {
+    for (int32_t e = begin + (int32_t)blockIdx.y; e < end; e += (int32_t)gridDim.y) {
+      const int32_t s = work[2 * (int64_t)e], r = work[2 * (int64_t)e + 1];
+      if (s < 0 || s >= d.n_states || r < 2 || r >= capacity) continue;  // (uniform over the block)
+      bool bit = false;
+      if (t < d.vocab) bit = t == d.eos_id ? d.accepting[s] != 0 : dfa_next(d, s, t) >= 0;
+      const uint64_t b = __ballot(bit);
+      if (lane == 0) {
+        int32_t *row = bank + (int64_t)r * bank_ld;
+        row[w0] = (int32_t)(uint32_t)b;
+        if (w0 + 1 < words) row[w0 + 1] = (int32_t)(uint32_t)(b >> 32);
+      }
+    }
+  }
+}
+
+// after the fill (same stream): the filled mark moves up.  A launch of its own: a count of arrived workgroups on one word
+// costs more than this once the grid has thousands of them
+__global__ void dfa_commit_kernel(int32_t capacity, int32_t *counters) {
+  const int32_t rows = counters[C_ROWS];
+  const int32_t end = (rows > capacity ? capacity : rows) - 2;
+  if (end > counters[C_FILLED]) counters[C_FILLED] = end;
+}
+
+__global__ void dfa_mask_ids_kernel(int32_t n_states, const uint8_t *accepting, int64_t n, const int32_t *states,
+                                    const int32_t *done, const int32_t *row_of_state, int32_t capacity, int32_t *out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int32_t s = states[i];
+  const bool ok = s >= 0 && s < n_states;
+  int32_t r = 0;
+  if (done && done[i]) {
+    r = ok && accepting[s] ? 1 : 0;
+  } else if (ok) {
+    r = row_of_state[s];
+    if (r < 2 || r >= capacity) r = 0;
+  }
+  out[i] = r;
+}
+
+constexpr int NEED_VOCAB = 1, NEED_BANK = 2, NEED_N = 4;
+
+int dfa_check(const glb_dfa_args *a, const char *what, int need) {
+  if (!a) return glb::api_fail(GLB_EINVAL, "%s: null argument block", what);
+  if (a->struct_size != sizeof(glb_dfa_args))
+    return glb::api_fail(GLB_EINVAL, "glb_dfa_args.struct_size %u != %zu (ABI mismatch)", a->struct_size, sizeof(glb_dfa_args));
+  if (a->n_states <= 0) return glb::api_fail(GLB_EINVAL, "%s: n_states %d <= 0", what, a->n_states);
+  if (a->start < 0 || a->start >= a->n_states)
+    return glb::api_fail(GLB_EINVAL, "%s: start %d outside [0, %d)", what, a->start, a->n_states);
+  if (a->vocab <= 0 || a->vocab > 0x7fffff00ll) return glb::api_fail(GLB_EINVAL, "%s: vocab %lld", what, (long long)a->vocab);
+  if (need & NEED_BANK) {
+    if (a->bank_ld < (a->vocab + 31) / 32)
+      return glb::api_fail(GLB_EINVAL, "%s: bank_ld %lld < %lld words", what, (long long)a->bank_ld, (long long)((a->vocab + 31) / 32));
+    if (a->capacity < 2 || a->capacity > 0x7fffffffll)
+      return glb::api_fail(GLB_EINVAL, "%s: capacity %lld (rows 0 and 1 are the bank's own)", what, (long long)a->capacity);
+    if (!a->bank || !a->row_of_state || !a->work || !a->counters) return glb::api_fail(GLB_EINVAL, "%s: null bank pointer", what);
+  }
+  if (!a->delta || !a->accepting || !a->live) return glb::api_fail(GLB_EINVAL, "%s: null automaton pointer", what);
+  if (need & NEED_VOCAB) {
+    if (!a->tok_bytes || !a->tok_ptr || !a->skip || a->n_bytes < 0 || a->n_bytes > 0x7fffffffll)
+      return glb::api_fail(GLB_EINVAL, "%s: vocabulary bytes missing", what);
+  }
+  if (need & NEED_N) {
+    if (a->n <= 0) return glb::api_fail(GLB_EINVAL, "%s: n %lld <= 0", what, (long long)a->n);
+  }
+  return GLB_OK;
+}
+
+Dfa dfa_of(const glb_dfa_args *a) {
+  return Dfa{a->delta, a->accepting, a->live, a->n_states, a->start, a->eos_id, a->tok_bytes, a->n_bytes, a->tok_ptr, a->skip, a->vocab};
+}
+
+int launched(const char *what) {
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? GLB_OK : glb::api_hip_fail(e, what);
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t glb_dfa_bank_rows(size_t bank_bytes, int64_t vocab, int64_t n_states) {
+  if (vocab <= 0 || n_states <= 0) return 0;
+  const size_t row = (size_t)((vocab + 31) / 32) * sizeof(int32_t);
+  int64_t rows = (int64_t)(bank_bytes / row);
+  if (rows > n_states + 2) rows = n_states + 2;
+  return rows > 65535 ? 65535 : rows;
+}
+
+int glb_dfa_bank_init(const glb_dfa_args *a, void *stream) {
+  if (const int rc = dfa_check(a, "glb_dfa_bank_init", NEED_BANK)) return rc;
+  const int64_t words = (a->vocab + 31) / 32, items = words > a->n_states ? words : a->n_states;
+  hipLaunchKernelGGL(dfa_bank_init_kernel, dim3(blocks_for(items, 256)), dim3(256), 0, (hipStream_t)stream, dfa_of(a), a->bank,
+                     a->bank_ld, words, a->row_of_state, a->counters);
+  return launched("dfa_bank_init launch");
+}
+
+int glb_dfa_advance(const glb_dfa_args *a, void *stream) {
+  if (const int rc = dfa_check(a, "glb_dfa_advance", NEED_VOCAB | NEED_N)) return rc;
+  if (!a->tokens || !a->from || !a->to || !a->state_out || a->ld <= 0) return glb::api_fail(GLB_EINVAL, "glb_dfa_advance: null pointer or ld <= 0");
+  hipLaunchKernelGGL(dfa_advance_kernel, dim3(blocks_for(a->n, 128)), dim3(128), 0, (hipStream_t)stream, dfa_of(a), a->n, a->tokens,
+                     a->ld, a->from, a->to, a->state_in, a->state_out);
+  return launched("dfa_advance launch");
+}
+
+int glb_dfa_claim_rows(const glb_dfa_args *a, void *stream) {
+  if (const int rc = dfa_check(a, "glb_dfa_claim_rows", NEED_BANK | NEED_N)) return rc;
+  if (!a->state_in) return glb::api_fail(GLB_EINVAL, "glb_dfa_claim_rows: state_in is null");
+  hipLaunchKernelGGL(dfa_claim_kernel, dim3(blocks_for(a->n, 256)), dim3(256), 0, (hipStream_t)stream, a->n_states, a->n, a->state_in,
+                     (int32_t)a->capacity, a->row_of_state, a->work, a->counters);
+  return launched("dfa_claim launch");
+}
+
+int glb_dfa_fill_masks(const glb_dfa_args *a, void *stream) {
+  if (const int rc = dfa_check(a, "glb_dfa_fill_masks", NEED_BANK | NEED_VOCAB)) return rc;
+  if (a->max_work <= 0) return glb::api_fail(GLB_EINVAL, "glb_dfa_fill_masks: max_work %lld <= 0", (long long)a->max_work);
+  const unsigned gy = (unsigned)(a->max_work < FILL_MAX_ENTRIES ? a->max_work : FILL_MAX_ENTRIES);
+  hipLaunchKernelGGL(dfa_fill_kernel, dim3(blocks_for(a->vocab, FILL_THREADS), gy), dim3(FILL_THREADS), 0, (hipStream_t)stream,
+                     dfa_of(a), a->bank, a->bank_ld, (int32_t)a->capacity, a->work, a->counters);
+  hipLaunchKernelGGL(dfa_commit_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (int32_t)a->capacity, a->counters);
+  return launched("dfa_fill launch");
+}
+
+int glb_dfa_mask_ids(const glb_dfa_args *a, void *stream) {
+  if (const int rc = dfa_check(a, "glb_dfa_mask_ids", NEED_BANK | NEED_N)) return rc;
+  if (!a->state_in || !a->out_rows) return glb::api_fail(GLB_EINVAL, "glb_dfa_mask_ids: null pointer");
+  hipLaunchKernelGGL(dfa_mask_ids_kernel, dim3(blocks_for(a->n, 256)), dim3(256), 0, (hipStream_t)stream, a->n_states, a->accepting,
+                     a->n, a->state_in, a->done, a->row_of_state, (int32_t)a->capacity, a->out_rows);
+  return launched("dfa_mask_ids launch");
+}
+
+}  // extern "C"

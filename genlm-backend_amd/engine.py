@@ -891,6 +891,13 @@ class HipEngine:
         check(rc)
         return y if out is not None else y.view(*x.shape[:-1], n)
 
+    # ---- byte-level DFA constraints (glb_dfa_*: DESIGN.md §17; constraints.DeviceConstraint fills the argument block) ---------
+    def dfa_call(self, name, args):
+        """One of glb_dfa_bank_init / advance / claim_rows / fill_masks / mask_ids on the current stream."""
+        if name not in ("glb_dfa_bank_init", "glb_dfa_advance", "glb_dfa_claim_rows", "glb_dfa_fill_masks", "glb_dfa_mask_ids"):
+            raise ValueError(name)
+        check(getattr(self.lib, name)(C.byref(args), self._stream()))
+
     # ---- device-resident particle state ------------------------------------------------------------------
     def kv_append(self, slab, new_rows, pos, rows=None):
         """slab[rows[i] (or i), h, pos[i], :] = new_rows[i, h, 0, :] (glb_kv_append).  slab [R, H, cap, Dh] contiguous;

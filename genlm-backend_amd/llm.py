@@ -1064,13 +1064,18 @@ class AsyncAmdLM(AsyncLM):
         return out[0], toks
 
     @torch.no_grad()
-    def batch_next_token_step_device(self, tokens, lengths, mask_ids=None):
+    def batch_next_token_step_device(self, tokens, lengths, mask_ids=None, constraint=None, prompt_lengths=None):
         """`batch_next_token_step` for a population that LIVES ON THE DEVICE: `tokens` int32 [n, cap] (row i's first
         lengths[i] entries are context i - the padded particle matrix a device-resident loop keeps), `lengths` int32 [n],
         `mask_ids` int32 [n] or None, all device tensors.  Returns (logZ float32 [n], token int32 [n]) as device tensors:
         nothing of the population crosses the host in either direction (the call's only D2H copy is the handful of counts
         the host needs to size the forward; a failed launch shows as token -2 and raises at the next call / `engine.check()`).
-        No counterpart in the reference (its API takes Python lists, hf.py:346-373); this is the same evaluation."""
+        No counterpart in the reference (its API takes Python lists, hf.py:346-373); this is the same evaluation.
+        `constraint` (a `constraints.DeviceConstraint`, exclusive with `mask_ids`): context i's mask is that of the automaton
+        state after tokens[i, prompt_lengths[i]:lengths[i]) (`prompt_lengths` int32 [n], None: zeros), recomputed here - the
+        call keeps no state; the registered masks are not used."""
+        if constraint is not None and mask_ids is not None:
+            raise ValueError("give mask_ids (registered masks) or constraint (masks made on the device), not both")
         if tokens.dim() != 2 or tokens.dtype != torch.int32 or lengths.dtype != torch.int32 or lengths.numel() != tokens.shape[0]:
             raise ValueError("tokens must be int32 [n, cap] and lengths int32 [n]")
         if not tokens.is_contiguous():
@@ -1082,11 +1087,14 @@ class AsyncAmdLM(AsyncLM):
         if getattr(self, "_row_starts", (None,))[0] != key:
             self._row_starts = (key, torch.arange(n, device=self.device, dtype=torch.int64) * cap)
         mid_d = None
-        if self._mask_kind != MASK_NONE:
+        if constraint is not None:
+            frm = torch.zeros_like(lengths) if prompt_lengths is None else prompt_lengths
+            mid_d = constraint.mask_rows(constraint.advance(None, tokens, frm, lengths))
+        elif self._mask_kind != MASK_NONE:
             mid_d = torch.zeros(n, dtype=torch.int32, device=self.device) if mask_ids is None else mask_ids
-        return self._batch_step(tokens.view(-1), self._row_starts[1], lengths, n, mid_d, l_max=None)
+        return self._batch_step(tokens.view(-1), self._row_starts[1], lengths, n, mid_d, l_max=None, constraint=constraint)
 
-    def _batch_step(self, tok_d, st_d, ln_d, n, mid_d, l_max):
+    def _batch_step(self, tok_d, st_d, ln_d, n, mid_d, l_max, constraint=None):
         """The batched step on a ragged batch that is on the device already.  l_max: the longest context if the host
         knows it (else it rides on the call's D2H copy).  Returns device tensors."""
         eng, dev = self.engine, self.device
@@ -1114,7 +1122,7 @@ class AsyncAmdLM(AsyncLM):
             by_row = bool(extra[-2]) if mid_d is not None else False
             if mid_d is not None:
                 row_mid = row_mid[group_of_row]
-            return self._finish_batch_step(logits, row_of_group[group_of.long()], group_of, U, n, mid_d, row_mid, by_row)
+            return self._finish_batch_step(logits, row_of_group[group_of.long()], group_of, U, n, mid_d, row_mid, by_row, constraint)
         n_head = len(head)
         head = torch.stack(head) if used_d is None else torch.cat([torch.stack(head), used_d])
         head = head.cpu().tolist()  # the call's one D2H copy before the forward
@@ -1129,15 +1137,19 @@ class AsyncAmdLM(AsyncLM):
         prefixes = (T, pref[rep[:U].long()].contiguous()) if P["n"] else None
         enc = encode_ragged(self, (tok_d, st_d, ln_d), rep, U, l_max, pad_id=self._pad_id, base=base, prefixes=prefixes)
         logits = self._lm_head(enc.last_rows())  # [U, V]
-        return self._finish_batch_step(logits, group_of, group_of, U, n, mid_d, row_mid, by_row)
+        return self._finish_batch_step(logits, group_of, group_of, U, n, mid_d, row_mid, by_row, constraint)
 
-    def _finish_batch_step(self, logits, row_of, group_of, U, n, mid_d, row_mid, by_row):
+    def _finish_batch_step(self, logits, row_of, group_of, U, n, mid_d, row_mid, by_row, constraint=None):
         """The fused step over a batch's logits rows (row_of: logits row of every context; group_of: its dedup group -
         the order parity-mode noise is dealt in).  Returns (logZ, token) device tensors."""
         eng, dev = self.engine, self.device
         V = logits.shape[-1]
-        kw = self.step_masks(logits.dtype)
-        if kw:
+        kw = self.step_masks(logits.dtype) if constraint is None else {}
+        if constraint is not None:
+            # the bank rows as mask ids: the bank itself or the units' rows gathered out of it (DeviceConstraint.step_masks)
+            kw, _ = constraint.step_masks(row_mid[:U].contiguous() if by_row else mid_d, by_row, n,
+                                          parity=self._rng_mode == RNG_NOISE)
+        elif kw:
             if by_row:
                 kw["row_mask_id"] = row_mid[:U].contiguous()
             else:

@@ -196,6 +196,11 @@ class DeviceSIS:
                      grammar gives: README.md:57-70 generalised) while it generates, row n_particles once
                      `max_tokens` are out.  Prepared for the kernels once; `update_particle_masks(rows, bit_rows)` changes
                      some of them and only those are prepared again; every particle is its own reduction unit.
+    constraint       a `constraints.DeviceConstraint`: every particle's mask comes from its automaton state (the state after
+                     the bytes of the tokens it generated), which advances on the device with the token drawn and is
+                     recomputed from the contexts after a resampling; a particle that has generated `max_tokens` may only
+                     end (EOS if its state is accepting, nothing otherwise).  Exclusive with `particle_masks`; the
+                     backend's registered masks are not used.
     force_collectives  run the collectives of the multi-rank path (all-gather of log-weights / token matrices, the
                      set-up reductions) through `dist` even when world == 1: a one-rank "nccl" group exercises the RCCL
                      code of an 8-GPU run on a single GPU.
@@ -203,7 +208,11 @@ class DeviceSIS:
 
     def __init__(self, llm, n_particles, prompt_ids, max_tokens, eos_id, seed=0, rng="philox", rank=0, world=1,
                  dist=None, use_prefix_kv=False, use_particle_kv=False, resample_ess=None, force_collectives=False,
-                 share_kv=True, kv_rows=None, kv_in_place=0.75, kv_graph=True, particle_masks=None, migrate_kv=True):
+                 share_kv=True, kv_rows=None, kv_in_place=0.75, kv_graph=True, particle_masks=None, migrate_kv=True,
+                 constraint=None):
+        if constraint is not None and particle_masks is not None:
+            raise ValueError("give particle_masks (the caller's bit rows) or constraint (masks made on the device), not both")
+        self.constraint = constraint
         self.llm, self.eng, self.dev = llm, llm.engine, llm.device
         # the LoRA adapter this population's KV is made with: a step after set_lora / clear_lora raises (llm._lora_sync)
         self._lora_epoch = getattr(llm, "lora_epoch", 0)
@@ -278,6 +287,7 @@ class DeviceSIS:
         self._pm_prepared, self._pm_dirty, self._pm_seen, self._pm_moved = None, None, None, False
         self.pm_raw_above = None  # fraction of changed rows above which a step hands the bit rows over raw (None: by dtype)
         self.pm_raw_steps = 0
+        self.constraint_raw_steps = 0  # steps under a constraint that were handed the mask bank itself
         self.rows_moved = 0  # particles that changed ranks in the last resampling step (over all ranks)
         self.resample_ess = resample_ess
         self.n_resamples = 0
@@ -305,6 +315,7 @@ class DeviceSIS:
         self.lengths = self.prompt_len.clone()
         self.active = torch.ones(self.N, dtype=torch.int32, device=self.dev)
         self.log_weights = torch.zeros(self.N, dtype=torch.float32, device=self.dev)
+        self.states = self.constraint.states0(self.N) if self.constraint is not None else None  # automaton state per particle
         self.t = 0
         self.max_len_now = self.max_prompt
         self.last_stats = None
@@ -418,8 +429,10 @@ class DeviceSIS:
         eng, llm, N = self.eng, self.llm, self.N
         V = logits.shape[-1]
         mask_id = ((self.lengths - self.prompt_len) >= self.max_tokens).to(torch.int32)
-        kw = llm.step_masks(logits.dtype) if self.particle_masks is None else {}
-        if self.particle_masks is not None:  # one mask per particle: per-particle ids, no dedup of the math
+        kw = llm.step_masks(logits.dtype) if self.particle_masks is None and self.constraint is None else {}
+        if self.constraint is not None:
+            kw = self._constraint_masks(logits, group_of, mask_id)
+        elif self.particle_masks is not None:  # one mask per particle: per-particle ids, no dedup of the math
             # Two ways to hand the bit rows over.  RAW: the fused launch's stats waves read the caller's rows themselves
             # (kMaskRaw: + 2 us a step on float32 rows, + 5 us on 16-bit ones, nothing to prepare).  PREPARED: the rows
             # transposed into the kernels' layout (glb_mask_prepare: 11 us for 1025 rows of 50257), afterwards only the rows
@@ -479,8 +492,11 @@ class DeviceSIS:
             self.outer_events.append((e0, e1))
         if self.rng_mode == RNG_NOISE:  # the next step's rows set out on a side stream, under the next forward
             self.noise_src.prefetch()
+        len_was = self.lengths.clone() if self.constraint is not None else None
         eng.particles_advance(self.contexts, self.lengths, self.active, self.log_weights, logZ, tok, self.eos_id,
                               self.cap, hashes=self.hashes)
+        if self.constraint is not None:  # the states follow the tokens that were appended (none: the state stays)
+            self.constraint.advance(self.states, self.contexts, len_was, self.lengths, out=self.states)
         self.t += 1
         self.max_len_now = min(self.max_len_now + 1, self.cap)
         ft = self._fwd_tokens if self._fwd_tokens is not None else U * l_max
@@ -490,6 +506,28 @@ class DeviceSIS:
         if self.resample_ess is not None:
             self._maybe_resample()
         return U, n_global
+
+    def _constraint_masks(self, logits, group_of, done):
+        """The step's mask arguments under a constraint: the particles' bank rows (glb_dfa_claim_rows / fill_masks / mask_ids;
+        a warmed constraint: the last alone) and the bank handed over raw - per logits row when the state is a function of
+        the context (prompts of one length), so that a shared row is reduced once.  Bank or gathered rows: `DeviceConstraint.step_masks`
+        (`constraint_raw_steps` counts the steps that were handed the bank)."""
+        c = self.constraint
+        rows = c.mask_rows(self.states, done=done)
+        by_row = self._mask_by_row
+        if by_row and group_of is not None:
+            ids = rows[self._rep[:logits.shape[0]].long()].contiguous()
+        else:
+            ids = rows
+        kw, raw = c.step_masks(ids, by_row, self.N, parity=self.rng_mode == RNG_NOISE)
+        self.constraint_raw_steps += int(raw)
+        return kw
+
+    def _recompute_states(self):
+        """The automaton states from the contexts' generated suffixes (one launch): after the particles moved between
+        slots or ranks."""
+        if self.constraint is not None:
+            self.states = self.constraint.advance(None, self.contexts, self.prompt_len, self.lengths)
 
     def update_particle_masks(self, rows, bit_rows):
         """Particles `rows` (int32 device tensor) get new masks `bit_rows` (int32 [len(rows), ceil(V / 32)]): only these are
@@ -711,6 +749,7 @@ class DeviceSIS:
             else:  # rebuilt from the context in the next step
                 self._kv_stale = stale if bool(stale.any().item()) else None
         self._rehash()  # contexts moved between slots (and ranks): one launch, once per resampling step
+        self._recompute_states()
         self.n_resamples += 1
         self._exchange()
 
@@ -750,6 +789,8 @@ class DeviceSIS:
 
     def results(self):
         self.eng.check()  # the last steps' fused calls completed (glb_workspace_check; synchronises like the copies below)
+        if self.constraint is not None:
+            self.constraint.check()
         ctx = self.contexts.cpu().numpy()
         ln = self.lengths.cpu().numpy()
         pl = self.prompt_len.cpu().numpy()

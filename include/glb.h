@@ -920,6 +920,73 @@ int glb_w4_gemm_max_rows(void);
 size_t glb_w4_gemm_workspace_bytes(int64_t m, int64_t n, int64_t k);
 int glb_w4_gemm(const glb_w4_gemm_args *args, void *hip_stream);
 
+/*
+ * Byte-level DFA constraints: token masks made on the device from an automaton over bytes.
+ * The automaton: `delta` int32 [n_states, 256] (-1: no transition), `accepting` / `live` one byte per state (live[s]: an
+ * accepting state is reachable from s, s included - computed by the caller), `start`.  The vocabulary: the tokens' byte
+ * strings back to back in `tok_bytes` [n_bytes], token t owning [tok_ptr[t], tok_ptr[t + 1]), and `skip` [vocab] (nonzero:
+ * never allowed - special tokens).  next(s, t) = the state after walking t's bytes from s, or -1 (dead) when a transition
+ * is missing, the state reached is not live, the token is empty, skipped or outside [0, vocab), or s < 0.  The mask of
+ * state s (GLB_MASK_BITS layout): bit t = next(s, t) >= 0 for t != eos_id, bit eos_id = accepting[s], bits >= vocab zero.
+ *
+ * The mask bank: int32 [capacity, bank_ld] bit rows the fused step reads raw (mask_kind GLB_MASK_BITS, ids = rows).  Row 0
+ * is all zeros (a dead particle), row 1 EOS only, rows 2 .. hold one state each: row_of_state [n_states] (-1: none yet),
+ * `work` [capacity] pairs (state, row) in the order rows were claimed, `counters` [GLB_DFA_COUNTERS] int32:
+ *   [0] rows in use   [1] work entries filled so far   [2] overflow (sticky)   [3] reserved
+ *   glb_dfa_bank_init   rows 0 and 1, row_of_state = -1, counters = {2, 0, 0, 0}
+ *   glb_dfa_advance     state_out[i] = the state after tokens[i, from[i] .. to[i]) of the int32 [n, ld] matrix, starting at
+ *                       state_in[i] (null: `start` for everybody); -1 once dead; from == to copies; a range outside
+ *                       [0, ld] or a state outside [0, n_states) gives -1.  state_out may be state_in.
+ *   glb_dfa_claim_rows  every state of state_in [n] without a row gets the next one (vector atomics on row_of_state and
+ *                       counters[0]; one row per distinct state) and an entry in `work`.  Beyond `capacity`: nothing is
+ *                       written, counters[2] = 1.  Which state gets which row depends on the atomics' order; a row's bits
+ *                       do not.
+ *   glb_dfa_fill_masks  writes the mask rows of the work entries [counters[1], counters[0] - 2) - words 0 ..
+ *                       ceil(vocab / 32) - 1 of each row, nothing else - and moves counters[1] up (a second, one-thread launch).  The grid is sized by
+ *                       `max_work` (an upper bound of the entries waiting; more are served, only slower).
+ *   glb_dfa_mask_ids    out_rows[i] = the bank row of state_in[i]: 0 for a dead state or one without a row; where done[i]
+ *                       (nullable) is nonzero, 1 if the state is accepting and 0 otherwise.
+ *   glb_dfa_bank_rows   host: rows of a bank of `bank_bytes` for this vocabulary, at most n_states + 2 and 65535.
+ * Every index read from device memory (states, tokens, byte offsets, rows) is range-checked: bad input gives dead / no
+ * write, never an access out of bounds.  Argument errors return GLB_EINVAL before any GPU work; launches go on the given
+ * stream, allocate nothing, never synchronise.  Calls that share a bank must be ordered on one stream.
+ */
+#define GLB_DFA_COUNTERS 4
+typedef struct glb_dfa_args {
+  uint32_t struct_size; /* sizeof(glb_dfa_args) - ABI guard */
+  int32_t n_states, start, eos_id;
+  const int32_t *delta;     /* [n_states, 256] */
+  const uint8_t *accepting; /* [n_states] */
+  const uint8_t *live;      /* [n_states] */
+  int64_t vocab;
+  const uint8_t *tok_bytes; /* [n_bytes] */
+  int64_t n_bytes;
+  const int32_t *tok_ptr; /* [vocab + 1] */
+  const uint8_t *skip;    /* [vocab] */
+  /* advance / claim_rows / mask_ids: n particles */
+  int64_t n;
+  const int32_t *tokens; /* [n, ld] */
+  int64_t ld;
+  const int32_t *from, *to; /* [n] */
+  const int32_t *state_in;  /* [n]; advance: nullable */
+  int32_t *state_out;       /* [n] */
+  /* the bank */
+  int32_t *bank; /* [capacity, bank_ld] */
+  int64_t bank_ld, capacity;
+  int32_t *row_of_state; /* [n_states] */
+  int32_t *work;         /* [capacity, 2] */
+  int32_t *counters;     /* [GLB_DFA_COUNTERS] */
+  int64_t max_work;
+  const int32_t *done; /* [n], nullable */
+  int32_t *out_rows;   /* [n] */
+} glb_dfa_args;
+int glb_dfa_bank_init(const glb_dfa_args *args, void *hip_stream);
+int glb_dfa_advance(const glb_dfa_args *args, void *hip_stream);
+int glb_dfa_claim_rows(const glb_dfa_args *args, void *hip_stream);
+int glb_dfa_fill_masks(const glb_dfa_args *args, void *hip_stream);
+int glb_dfa_mask_ids(const glb_dfa_args *args, void *hip_stream);
+int64_t glb_dfa_bank_rows(size_t bank_bytes, int64_t vocab, int64_t n_states);
+
 /* Philox4x32-10 block function, exposed so hosts can reproduce the device draws. */
 void glb_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 
