@@ -275,6 +275,15 @@ class DfaArgs(C.Structure):
     ]
 
 
+class DfaWeightArgs(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("dfa", DfaArgs),
+        ("arc_logw", C.c_void_p), ("final_logw", C.c_void_p),
+        ("wbank", C.c_void_p), ("wbank_ld", C.c_int64),
+    ]
+
+
 # every symbol include/glb.h declares: name -> (restype, argtypes)
 _vp, _i32, _i64, _f32, _sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_size_t
 SYMBOLS = {
@@ -360,6 +369,9 @@ SYMBOLS = {
     "glb_dfa_fill_masks": (C.c_int, [C.POINTER(DfaArgs), _vp]),
     "glb_dfa_mask_ids": (C.c_int, [C.POINTER(DfaArgs), _vp]),
     "glb_dfa_bank_rows": (_i64, [_sz, _i64, _i64]),
+    "glb_dfa_weight_bank_init": (C.c_int, [C.POINTER(DfaWeightArgs), _vp]),
+    "glb_dfa_fill_weights": (C.c_int, [C.POINTER(DfaWeightArgs), _vp]),
+    "glb_dfa_weight_bank_rows": (_i64, [_sz, _i64, _i64]),
     "glb_philox4x32_10": (None, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
 }
 

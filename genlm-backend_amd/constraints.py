@@ -4,6 +4,9 @@
 `DeviceConstraint` keeps it on the GPU beside the vocabulary's byte strings and produces what the fused step consumes:
 a bank of token bit masks, one row per automaton state that some particle has reached, and every particle's row.  States
 advance on the device from the tokens drawn; nothing crosses the host per step.
+
+`ByteWFSA` is the same automaton in the log semiring (arc and final log-weights): a `DeviceConstraint` over one
+keeps a bank of float32 rows - the token log-weights from every state reached - that the step adds to the log-probabilities.
 """
 import ctypes as C
 
@@ -87,6 +90,61 @@ class ByteDFA:
         return bool(self.accepting[s])
 
 
+class ByteWFSA(ByteDFA):
+    """A deterministic automaton over bytes in the log semiring: delta as in `ByteDFA`, arc_logw float32 [S, 256], final_logw
+    float32 [S] (-inf: not accepting).  It is the `ByteDFA` with accepting = final_logw > -inf.  An arc of weight -inf is
+    removed (delta becomes -1) before `live` is computed; NaN, +inf and a finite weight on an arc that delta does not have
+    are errors."""
+
+    def __init__(self, delta, arc_logw, final_logw, start):
+        delta = np.array(delta)
+        arc = np.array(arc_logw, dtype=np.float32)
+        fin = np.ascontiguousarray(final_logw, dtype=np.float32)
+        if delta.ndim != 2 or arc.shape != delta.shape:
+            raise ValueError(f"arc_logw must have delta's shape [S, 256], got {arc.shape} beside {delta.shape}")
+        if fin.shape != delta.shape[:1]:
+            raise ValueError(f"final_logw must be [{delta.shape[0]}], got {fin.shape}")
+        for name, a in (("arc_logw", arc), ("final_logw", fin)):
+            if np.isnan(a).any() or np.isposinf(a).any():
+                raise ValueError(f"{name} holds NaN or +inf")
+        if not np.issubdtype(delta.dtype, np.integer):
+            raise ValueError("delta must hold integers")
+        if (np.isfinite(arc) & (delta == -1)).any():
+            raise ValueError("arc_logw is finite where delta has no arc")
+        delta[np.isneginf(arc)] = -1
+        arc[delta < 0] = -np.inf
+        super().__init__(delta, fin > -np.inf, start)
+        self.arc_logw, self.final_logw = np.ascontiguousarray(arc), fin
+
+    @classmethod
+    def from_dfa(cls, dfa):
+        """`dfa` with weight zero on every arc and every accepting state."""
+        return cls(dfa.delta, np.where(dfa.delta >= 0, 0.0, -np.inf), np.where(dfa.accepting, 0.0, -np.inf), dfa.start)
+
+    @classmethod
+    def from_weighted_strings(cls, weights):
+        """The trie automaton of {byte string: log-weight}: arcs weigh zero, a string's weight sits on its final state."""
+        strings = [bytes(s) for s in weights]
+        dfa = ByteDFA.from_strings(strings)
+        fin = np.full(dfa.n_states, -np.inf, np.float32)
+        for s, w in zip(strings, weights.values()):
+            cur = dfa.start
+            for b in s:
+                cur = int(dfa.delta[cur, b])
+            fin[cur] = w
+        return cls(dfa.delta, np.where(dfa.delta >= 0, 0.0, -np.inf), fin, dfa.start)
+
+    def path_logw(self, data):
+        """float32: the arcs' weights summed left to right, plus the final weight; -inf where `data` is not accepted."""
+        s, w = self.start, np.float32(0.0)
+        for b in bytes(data):
+            w = np.float32(w + self.arc_logw[s, b])
+            s = int(self.delta[s, b])
+            if s < 0:
+                return np.float32(-np.inf)
+        return np.float32(w + self.final_logw[s])
+
+
 class DeviceConstraint:
     """A `ByteDFA` over a vocabulary's byte strings, resident on the device.
 
@@ -97,6 +155,11 @@ class DeviceConstraint:
     skip_ids         tokens never allowed (special tokens)
     mask_bank_bytes  budget of the mask bank: one row of ceil(V / 32) words per distinct state reached, plus two.  A bank
                      that cannot hold a state a particle reaches is an error (`check()`), not an eviction.
+
+    With a `ByteWFSA` the bank holds float32 rows [rows, ld] instead (ld: V rounded up to 64 floats), the token log-weights
+    from each state (include/glb.h glb_dfa_weight_*): rows = min(S + 2, 65535, mask_bank_bytes / (4 ld)).  A row is 32 times
+    a bit row - about 201 KB at V = 50257, so the default 256 MiB hold 1332 states.  `step_masks` then hands the bank over
+    as `MASK_F32` in either form of the step; everything else keeps its meaning.
     """
 
     def __init__(self, llm_or_engine, dfa, byte_vocab, eos_id, skip_ids=None, mask_bank_bytes=256 << 20):
@@ -126,22 +189,32 @@ class DeviceConstraint:
         self._bytes, self._ptr, self._skip = up(flat), up(ptr.astype(np.int32)), up(skip)
         self.mask_bank_bytes = int(mask_bank_bytes)
         self._gathered, self._cus = None, None
-        rows = int(eng.lib.glb_dfa_bank_rows(self.mask_bank_bytes, V, dfa.n_states))
+        self.weighted = isinstance(dfa, ByteWFSA)
+        if self.weighted:
+            self._arc_logw, self._final_logw = up(dfa.arc_logw), up(dfa.final_logw)
+        # a row of the bank: bit words, or with weights the floats of a 256-byte aligned row
+        self._bank_dtype, self.row_elems = (torch.float32, (V + 63) // 64 * 64) if self.weighted else (torch.int32, self.words)
+        bank_rows = eng.lib.glb_dfa_weight_bank_rows if self.weighted else eng.lib.glb_dfa_bank_rows
+        rows = int(bank_rows(self.mask_bank_bytes, V, dfa.n_states))
         if rows < 3:
             raise ValueError(f"mask_bank_bytes={mask_bank_bytes} holds no state's mask: a row of this vocabulary takes "
-                             f"{self.words * 4} bytes and the bank needs at least three")
+                             f"{self.row_elems * 4} bytes{' (float32 weights: 32 times a bit row)' if self.weighted else ''} "
+                             "and the bank needs at least three")
         self._row_of_state = torch.empty(dfa.n_states, dtype=torch.int32, device=self.dev)
         self._counters = torch.zeros(_lib.DFA_COUNTERS, dtype=torch.int32, device=self.dev)
-        self._set_bank(torch.zeros((rows, self.words), dtype=torch.int32, device=self.dev))
+        self._set_bank(torch.zeros((rows, self.row_elems), dtype=self._bank_dtype, device=self.dev))
 
     # ---- the bank ------------------------------------------------------------------------------------------------------
     def _set_bank(self, bank):
-        """Use `bank` (int32 [rows, >= ceil(V / 32)], unit inner stride; rows may be padded) and start it over."""
+        """Use `bank` (int32 [rows, >= ceil(V / 32)], with weights float32 [rows, >= V]; unit inner stride; rows may be
+        padded) and start it over."""
         import torch
 
-        if bank.dtype != torch.int32 or bank.dim() != 2 or bank.stride(1) != 1 or bank.shape[0] < 3 or bank.shape[1] < self.words \
+        need = self.vocab if self.weighted else self.words
+        if bank.dtype != self._bank_dtype or bank.dim() != 2 or bank.stride(1) != 1 or bank.shape[0] < 3 or bank.shape[1] < need \
                 or bank.device != self.dev:
-            raise ValueError("bank must be an int32 [rows >= 3, >= ceil(V / 32)] device tensor with unit inner stride")
+            raise ValueError("bank must be an int32 [rows >= 3, >= ceil(V / 32)] (with weights: float32 [rows >= 3, >= V]) "
+                             "device tensor with unit inner stride")
         self.bank = bank
         self._work = torch.zeros((bank.shape[0], 2), dtype=torch.int32, device=self.dev)
         self._reset_bank()
@@ -149,7 +222,10 @@ class DeviceConstraint:
     def _reset_bank(self):
         """Forget every state's row (rows 0 and 1 are written again, the overflow word cleared)."""
         self._warm = False
-        self._call("glb_dfa_bank_init", self._args())
+        if self.weighted:
+            self._call("glb_dfa_weight_bank_init", self._weight_args(self._args()))
+        else:
+            self._call("glb_dfa_bank_init", self._args())
 
     capacity = property(lambda self: self.bank.shape[0])
 
@@ -163,6 +239,14 @@ class DeviceConstraint:
         a.bank, a.bank_ld, a.capacity = self.bank.data_ptr(), self.bank.stride(0), self.bank.shape[0]
         a.row_of_state, a.work, a.counters = self._row_of_state.data_ptr(), self._work.data_ptr(), self._counters.data_ptr()
         return a
+
+    def _weight_args(self, a):
+        """The block of glb_dfa_weight_bank_init / glb_dfa_fill_weights round `a`."""
+        w = _lib.DfaWeightArgs()
+        w.struct_size, w.dfa = C.sizeof(_lib.DfaWeightArgs), a
+        w.arc_logw, w.final_logw = self._arc_logw.data_ptr(), self._final_logw.data_ptr()
+        w.wbank, w.wbank_ld = self.bank.data_ptr(), self.bank.stride(0)
+        return w
 
     def _call(self, name, a):
         self.eng.dfa_call(name, a)
@@ -216,7 +300,10 @@ class DeviceConstraint:
         a.n, a.state_in = n, self._states(states).data_ptr()
         self._call("glb_dfa_claim_rows", a)
         a.max_work = min(n, self.dfa.n_states, self.capacity)
-        self._call("glb_dfa_fill_masks", a)
+        if self.weighted:
+            self._call("glb_dfa_fill_weights", self._weight_args(a))
+        else:
+            self._call("glb_dfa_fill_masks", a)
 
     def mask_rows(self, states, done=None):
         """int32 [n]: the bank row of every state - 0 (nothing allowed) for a dead one; where `done` (int32 [n]) is set, row
@@ -246,10 +333,13 @@ class DeviceConstraint:
         `fused`: no parity draw, more than 512 (unit, 4096-token chunk) items, at most 16 x 8 x CUs particles), and
         otherwise only the units' rows, gathered into a buffer of this object.  This is the one place the rule is
         restated; where it guesses wrong (a stream being captured, a workspace nobody registered) the step still computes
-        the same results from the whole bank, only slower."""
+        the same results from the whole bank, only slower.
+        A weight bank (`GLB_MASK_F32`) is read where it lies by both forms: always handed over, nothing gathered."""
         import torch
 
         key = "row_mask_id" if by_row else "mask_id"
+        if self.weighted:
+            return {"mask_kind": _lib.MASK_F32, "mask": self.bank, key: ids}, True
         n_units = ids.numel()
         if self._cus is None:
             self._cus = torch.cuda.get_device_properties(self.dev).multi_processor_count
@@ -261,6 +351,15 @@ class DeviceConstraint:
         buf, own = self._gathered
         self.eng.gather_rows_i32(self.bank[:, :self.words], ids, out=buf)
         return {"mask_kind": _lib.MASK_BITS, "mask": buf, key: own}, False
+
+    def forced_final_logw(self, states, forced):
+        """float32 [n]: final_logw[states[i]] where `forced` (bool [n]: the particle was served row 1 and ended) and 0.0
+        elsewhere - what a caller adds to the log-weight of a particle made to end, so that it weighs what one that chose
+        EOS from its state's own row does.  One gather, one select; no synchronisation."""
+        import torch
+
+        fw = self._final_logw[states.clamp(min=0).long()]
+        return torch.where(forced & (states >= 0), fw, torch.zeros_like(fw))
 
     def warm(self):
         """Fill the rows of ALL states when the bank holds them (later `mask_rows` calls are then one small launch).
@@ -286,6 +385,6 @@ class DeviceConstraint:
         """Raises when a state found no row in the bank (synchronises unless `word`, the overflow word's value already on
         the host, is given)."""
         if int(self._counters[2].item()) if word is None else int(word):
-            raise RuntimeError(f"the constraint's mask bank is full: {self.capacity} rows of {self.words * 4} bytes "
+            raise RuntimeError(f"the constraint's mask bank is full: {self.capacity} rows of {self.row_elems * 4} bytes "
                                f"(mask_bank_bytes={self.mask_bank_bytes}) do not hold the automaton states the particles "
                                "reached; their masks were empty.  Raise mask_bank_bytes.")

@@ -1,6 +1,8 @@
 // glb_dfa.hip — byte-level DFA constraints on the device (include/glb.h: glb_dfa_*): automaton states advance
 // token by token, every distinct state claims one row of a mask bank, and the rows are filled from the automaton - a wave
 // per (state, 64 consecutive tokens), the 64 bits by one ballot.  Everything read from device memory is range-checked.
+// Weighted automata (glb_dfa_weight_*, glb_dfa_fill_weights): the same walk summing float32 arc weights, the
+// rows 64 consecutive floats a wave.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -38,6 +40,25 @@ __device__ inline int32_t dfa_next(const Dfa &d, int32_t s, int64_t t) {
   return d.live[cur] ? cur : -1;
 }
 
+// the weight of token t from state s (include/glb.h): the float32 sum of the arcs' weights in byte order, -inf where
+// next(s, t) is dead.  Same checks, same order as dfa_next
+__device__ inline float dfa_next_weight(const Dfa &d, const float *arc_logw, int32_t s, int64_t t) {
+  const float dead = -__builtin_inff();
+  if (s < 0 || s >= d.n_states || t < 0 || t >= d.vocab) return dead;
+  if (d.skip[t]) return dead;
+  const int64_t p0 = d.ptr[t], p1 = d.ptr[t + 1];
+  if (p0 < 0 || p1 <= p0 || p1 > d.n_bytes) return dead;
+  int32_t cur = s;
+  float w = 0.0f;
+  for (int64_t p = p0; p < p1; ++p) {
+    const int64_t arc = (int64_t)cur * 256 + d.bytes[p];
+    w = w + arc_logw[arc];
+    cur = d.delta[arc];
+    if (cur < 0 || cur >= d.n_states) return dead;
+  }
+  return d.live[cur] ? w : dead;
+}
+
 __global__ void dfa_bank_init_kernel(Dfa d, int32_t *bank, int64_t bank_ld, int64_t words, int32_t *row_of_state,
                                      int32_t *counters) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -46,6 +67,22 @@ __global__ void dfa_bank_init_kernel(Dfa d, int32_t *bank, int64_t bank_ld, int6
     bank[i] = 0;
     const bool eos_here = d.eos_id >= 0 && d.eos_id < d.vocab && (d.eos_id >> 5) == i;
     bank[bank_ld + i] = eos_here ? (int32_t)(1u << (d.eos_id & 31)) : 0;
+  }
+  if (i == 0) {
+    counters[C_ROWS] = 2;
+    counters[C_FILLED] = 0;
+    counters[C_OVERFLOW] = 0;
+    counters[C_RESERVED] = 0;
+  }
+}
+
+__global__ void dfa_weight_bank_init_kernel(int32_t n_states, int32_t eos_id, int64_t vocab, float *wbank, int64_t wbank_ld,
+                                            int32_t *row_of_state, int32_t *counters) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n_states) row_of_state[i] = -1;
+  if (i < vocab) {
+    wbank[i] = -__builtin_inff();
+    wbank[wbank_ld + i] = i == eos_id ? 0.0f : -__builtin_inff();
   }
   if (i == 0) {
     counters[C_ROWS] = 2;
@@ -120,6 +157,31 @@ __global__ __launch_bounds__(FILL_THREADS) void dfa_fill_kernel(Dfa d, int32_t *
   }
 }
 
+// The float rows: the grid of dfa_fill_kernel - a wave per (work entry, 64 consecutive tokens), a workgroup looping over the
+// entries it owns - but a lane keeps its token's sum and the wave stores 64 consecutive floats (256 bytes), no ballot
+__global__ __launch_bounds__(FILL_THREADS) void dfa_fill_weights_kernel(Dfa d, const float *arc_logw, const float *final_logw,
+                                                                       float *wbank, int64_t wbank_ld, int32_t capacity,
+                                                                       const int32_t *work, const int32_t *counters) {
+  __shared__ int32_t range[2];
+  if (threadIdx.x == 0) {
+    int32_t begin = __hip_atomic_load(&counters[C_FILLED], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    int32_t end = __hip_atomic_load(&counters[C_ROWS], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    end = (end > capacity ? capacity : end) - 2;
+    if (begin < 0) begin = 0;
+    range[0] = begin;
+    range[1] = end;
+  }
+  __syncthreads();
+  const int32_t begin = range[0], end = range[1];
+  const int64_t t = (int64_t)blockIdx.x * FILL_THREADS + threadIdx.x;
+  if (t >= d.vocab) return;  // (no barrier and no cross-lane operation below)
+  for (int32_t e = begin + (int32_t)blockIdx.y; e < end; e += (int32_t)gridDim.y) {
+    const int32_t s = work[2 * (int64_t)e], r = work[2 * (int64_t)e + 1];
+    if (s < 0 || s >= d.n_states || r < 2 || r >= capacity) continue;
+    wbank[(int64_t)r * wbank_ld + t] = t == d.eos_id ? final_logw[s] : dfa_next_weight(d, arc_logw, s, t);
+  }
+}
+
 // after the fill (same stream): the filled mark moves up.  A launch of its own: a count of arrived workgroups on one word
 // costs more than this once the grid has thousands of them
 __global__ void dfa_commit_kernel(int32_t capacity, int32_t *counters) {
@@ -144,7 +206,8 @@ __global__ void dfa_mask_ids_kernel(int32_t n_states, const uint8_t *accepting, 
   out[i] = r;
 }
 
-constexpr int NEED_VOCAB = 1, NEED_BANK = 2, NEED_N = 4;
+// NEED_ROWS: the bank's bookkeeping (capacity, row_of_state, work, counters) without its bit rows - a weight bank's calls
+constexpr int NEED_VOCAB = 1, NEED_BANK = 2, NEED_N = 4, NEED_ROWS = 8;
 
 int dfa_check(const glb_dfa_args *a, const char *what, int need) {
   if (!a) return glb::api_fail(GLB_EINVAL, "%s: null argument block", what);
@@ -154,12 +217,12 @@ int dfa_check(const glb_dfa_args *a, const char *what, int need) {
   if (a->start < 0 || a->start >= a->n_states)
     return glb::api_fail(GLB_EINVAL, "%s: start %d outside [0, %d)", what, a->start, a->n_states);
   if (a->vocab <= 0 || a->vocab > 0x7fffff00ll) return glb::api_fail(GLB_EINVAL, "%s: vocab %lld", what, (long long)a->vocab);
-  if (need & NEED_BANK) {
-    if (a->bank_ld < (a->vocab + 31) / 32)
+  if (need & (NEED_BANK | NEED_ROWS)) {
+    if ((need & NEED_BANK) && a->bank_ld < (a->vocab + 31) / 32)
       return glb::api_fail(GLB_EINVAL, "%s: bank_ld %lld < %lld words", what, (long long)a->bank_ld, (long long)((a->vocab + 31) / 32));
     if (a->capacity < 2 || a->capacity > 0x7fffffffll)
       return glb::api_fail(GLB_EINVAL, "%s: capacity %lld (rows 0 and 1 are the bank's own)", what, (long long)a->capacity);
-    if (!a->bank || !a->row_of_state || !a->work || !a->counters) return glb::api_fail(GLB_EINVAL, "%s: null bank pointer", what);
+    if (((need & NEED_BANK) && !a->bank) || !a->row_of_state || !a->work || !a->counters) return glb::api_fail(GLB_EINVAL, "%s: null bank pointer", what);
   }
   if (!a->delta || !a->accepting || !a->live) return glb::api_fail(GLB_EINVAL, "%s: null automaton pointer", what);
   if (need & NEED_VOCAB) {
@@ -179,6 +242,18 @@ Dfa dfa_of(const glb_dfa_args *a) {
 int launched(const char *what) {
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? GLB_OK : glb::api_hip_fail(e, what);
+}
+
+int dfa_weight_check(const glb_dfa_weight_args *w, const char *what, int need) {
+  if (!w) return glb::api_fail(GLB_EINVAL, "%s: null argument block", what);
+  if (w->struct_size != sizeof(glb_dfa_weight_args))
+    return glb::api_fail(GLB_EINVAL, "glb_dfa_weight_args.struct_size %u != %zu (ABI mismatch)", w->struct_size,
+                         sizeof(glb_dfa_weight_args));
+  if (const int rc = dfa_check(&w->dfa, what, need | NEED_ROWS)) return rc;
+  if (w->wbank_ld < w->dfa.vocab)
+    return glb::api_fail(GLB_EINVAL, "%s: wbank_ld %lld < vocab %lld", what, (long long)w->wbank_ld, (long long)w->dfa.vocab);
+  if (!w->arc_logw || !w->final_logw || !w->wbank) return glb::api_fail(GLB_EINVAL, "%s: null weight table", what);
+  return GLB_OK;
 }
 
 }  // namespace
@@ -233,6 +308,35 @@ int glb_dfa_mask_ids(const glb_dfa_args *a, void *stream) {
   hipLaunchKernelGGL(dfa_mask_ids_kernel, dim3(blocks_for(a->n, 256)), dim3(256), 0, (hipStream_t)stream, a->n_states, a->accepting,
                      a->n, a->state_in, a->done, a->row_of_state, (int32_t)a->capacity, a->out_rows);
   return launched("dfa_mask_ids launch");
+}
+
+int64_t glb_dfa_weight_bank_rows(size_t bank_bytes, int64_t vocab, int64_t n_states) {
+  if (vocab <= 0 || n_states <= 0) return 0;
+  const size_t row = (size_t)((vocab + 63) / 64) * 64 * sizeof(float);
+  int64_t rows = (int64_t)(bank_bytes / row);
+  if (rows > n_states + 2) rows = n_states + 2;
+  return rows > 65535 ? 65535 : rows;
+}
+
+int glb_dfa_weight_bank_init(const glb_dfa_weight_args *w, void *stream) {
+  if (const int rc = dfa_weight_check(w, "glb_dfa_weight_bank_init", 0)) return rc;
+  const glb_dfa_args *a = &w->dfa;
+  const int64_t items = a->vocab > a->n_states ? a->vocab : a->n_states;
+  hipLaunchKernelGGL(dfa_weight_bank_init_kernel, dim3(blocks_for(items, 256)), dim3(256), 0, (hipStream_t)stream, a->n_states,
+                     a->eos_id, a->vocab, w->wbank, w->wbank_ld, a->row_of_state, a->counters);
+  return launched("dfa_weight_bank_init launch");
+}
+
+int glb_dfa_fill_weights(const glb_dfa_weight_args *w, void *stream) {
+  if (const int rc = dfa_weight_check(w, "glb_dfa_fill_weights", NEED_VOCAB)) return rc;
+  const glb_dfa_args *a = &w->dfa;
+  if (a->max_work <= 0) return glb::api_fail(GLB_EINVAL, "glb_dfa_fill_weights: max_work %lld <= 0", (long long)a->max_work);
+  const unsigned gy = (unsigned)(a->max_work < FILL_MAX_ENTRIES ? a->max_work : FILL_MAX_ENTRIES);
+  hipLaunchKernelGGL(dfa_fill_weights_kernel, dim3(blocks_for(a->vocab, FILL_THREADS), gy), dim3(FILL_THREADS), 0,
+                     (hipStream_t)stream, dfa_of(a), w->arc_logw, w->final_logw, w->wbank, w->wbank_ld, (int32_t)a->capacity, a->work,
+                     a->counters);
+  hipLaunchKernelGGL(dfa_commit_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (int32_t)a->capacity, a->counters);
+  return launched("dfa_fill_weights launch");
 }
 
 }  // extern "C"

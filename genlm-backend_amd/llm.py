@@ -1073,7 +1073,8 @@ class AsyncAmdLM(AsyncLM):
         No counterpart in the reference (its API takes Python lists, hf.py:346-373); this is the same evaluation.
         `constraint` (a `constraints.DeviceConstraint`, exclusive with `mask_ids`): context i's mask is that of the automaton
         state after tokens[i, prompt_lengths[i]:lengths[i]) (`prompt_lengths` int32 [n], None: zeros), recomputed here - the
-        call keeps no state; the registered masks are not used."""
+        call keeps no state; the registered masks are not used.  Over a `constraints.ByteWFSA` the state's row of token
+        log-weights is added to the log-probabilities (the bank handed over as float masks)."""
         if constraint is not None and mask_ids is not None:
             raise ValueError("give mask_ids (registered masks) or constraint (masks made on the device), not both")
         if tokens.dim() != 2 or tokens.dtype != torch.int32 or lengths.dtype != torch.int32 or lengths.numel() != tokens.shape[0]:

@@ -201,6 +201,9 @@ class DeviceSIS:
                      recomputed from the contexts after a resampling; a particle that has generated `max_tokens` may only
                      end (EOS if its state is accepting, nothing otherwise).  Exclusive with `particle_masks`; the
                      backend's registered masks are not used.
+                     Over a `constraints.ByteWFSA` the state's row holds token log-weights, added to the log-probabilities
+                     (logZ = logsumexp(log_softmax(x) + w), the token drawn from that); a particle made to end also
+                     takes its state's final weight.
     force_collectives  run the collectives of the multi-rank path (all-gather of log-weights / token matrices, the
                      set-up reductions) through `dist` even when world == 1: a one-rank "nccl" group exercises the RCCL
                      code of an 8-GPU run on a single GPU.
@@ -493,6 +496,10 @@ class DeviceSIS:
         if self.rng_mode == RNG_NOISE:  # the next step's rows set out on a side stream, under the next forward
             self.noise_src.prefetch()
         len_was = self.lengths.clone() if self.constraint is not None else None
+        if self.constraint is not None and self.constraint.weighted:
+            # a particle out of tokens was served row 1 (EOS alone, weight 0): its state's final weight is added here, so that
+            # a truncated sequence weighs what one that chose EOS itself does
+            self.log_weights += self.constraint.forced_final_logw(self.states, (mask_id > 0) & (self.active > 0) & (tok == self.eos_id))
         eng.particles_advance(self.contexts, self.lengths, self.active, self.log_weights, logZ, tok, self.eos_id,
                               self.cap, hashes=self.hashes)
         if self.constraint is not None:  # the states follow the tokens that were appended (none: the state stays)

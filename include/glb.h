@@ -987,6 +987,44 @@ int glb_dfa_fill_masks(const glb_dfa_args *args, void *hip_stream);
 int glb_dfa_mask_ids(const glb_dfa_args *args, void *hip_stream);
 int64_t glb_dfa_bank_rows(size_t bank_bytes, int64_t vocab, int64_t n_states);
 
+/*
+ * Weighted byte automata: the same deterministic automaton in the log semiring - `arc_logw` float32
+ * [n_states, 256] beside `delta`, `final_logw` float32 [n_states] (-inf: not accepting; accepting[s] = final_logw[s] >
+ * -inf, and an arc of weight -inf is no arc: the caller removes both before it computes `live`).  A state's row is a row
+ * of float log-weights the fused step adds to the log-probabilities (mask_kind GLB_MASK_F32, ids = rows).  Row of state s:
+ *   column t != eos_id   walk t's bytes exactly as next(s, t) above does, with w = 0.0f; w = w + arc_logw[cur][b] in
+ *                        float32, in byte order, cur the state the byte is read in; the column is w if next(s, t) >= 0 and
+ *                        -inf otherwise (a token is dead by the same rules: empty, skipped, a missing arc, a destination
+ *                        that is not live)
+ *   column eos_id        final_logw[s]
+ *   columns [vocab, wbank_ld)  never written
+ * The sum is one fixed chain of float32 additions (no fused multiply-add to contract, no reassociation): rows are exact
+ * against the same chain on a host.  The weight bank: float32 [dfa.capacity, wbank_ld] in place of the bit bank; row 0 all
+ * -inf, row 1 -inf except 0.0f at eos_id (a particle forced to end: its final weight is the caller's to add), rows 2 ..
+ * one state each.  States, row_of_state, work, counters and the overflow word are the machinery above and
+ * glb_dfa_advance / glb_dfa_claim_rows / glb_dfa_mask_ids serve a weight bank unchanged (they never touch `bank`; give
+ * them any non-null pointer and bank_ld >= ceil(vocab / 32)).  In the embedded block `dfa.bank` and `dfa.bank_ld` are not
+ * read by the calls below.
+ *   glb_dfa_weight_bank_init  rows 0 and 1 of wbank, row_of_state = -1, counters = {2, 0, 0, 0}
+ *   glb_dfa_fill_weights      the rows of the work entries [counters[1], counters[0] - 2), columns 0 .. vocab - 1, and moves
+ *                             counters[1] up, as glb_dfa_fill_masks does; grid sized by dfa.max_work
+ *   glb_dfa_weight_bank_rows  host: rows of a bank of `bank_bytes` whose rows are `vocab` floats padded to a multiple of 64
+ *                             (256-byte rows: a wave's store is one aligned line), at most n_states + 2 and 65535
+ * GLB_EINVAL before any launch: struct_size of either block wrong, wbank_ld < vocab, a null table; the same range checks
+ * of indices read from device memory; launches allocate nothing and may be captured.
+ */
+typedef struct glb_dfa_weight_args {
+  uint32_t struct_size; /* sizeof(glb_dfa_weight_args) - ABI guard */
+  glb_dfa_args dfa;     /* its own struct_size set too */
+  const float *arc_logw;   /* [n_states, 256] */
+  const float *final_logw; /* [n_states] */
+  float *wbank;            /* [dfa.capacity, wbank_ld] */
+  int64_t wbank_ld;
+} glb_dfa_weight_args;
+int glb_dfa_weight_bank_init(const glb_dfa_weight_args *args, void *hip_stream);
+int glb_dfa_fill_weights(const glb_dfa_weight_args *args, void *hip_stream);
+int64_t glb_dfa_weight_bank_rows(size_t bank_bytes, int64_t vocab, int64_t n_states);
+
 /* Philox4x32-10 block function, exposed so hosts can reproduce the device draws. */
 void glb_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 
