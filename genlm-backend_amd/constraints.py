@@ -192,9 +192,13 @@ class DeviceConstraint:
         self.weighted = isinstance(dfa, ByteWFSA)
         if self.weighted:
             self._arc_logw, self._final_logw = up(dfa.arc_logw), up(dfa.final_logw)
-        # a row of the bank: bit words, or with weights the floats of a 256-byte aligned row
-        self._bank_dtype, self.row_elems = (torch.float32, (V + 63) // 64 * 64) if self.weighted else (torch.int32, self.words)
-        bank_rows = eng.lib.glb_dfa_weight_bank_rows if self.weighted else eng.lib.glb_dfa_bank_rows
+        # The bank's kind, decided here once: a row's elements (bit words, or with weights the floats of a 256-byte aligned row),
+        # how many of them a caller's bank needs, the step's mask kind, the library's calls and the argument block they take
+        (self._bank_dtype, self.row_elems, self._row_need, self._mask_kind, bank_rows, self._init, self._fill, self._bank_args) = \
+            (torch.float32, (V + 63) // 64 * 64, V, _lib.MASK_F32, eng.lib.glb_dfa_weight_bank_rows, "glb_dfa_weight_bank_init",
+             "glb_dfa_fill_weights", self._weight_args) if self.weighted else \
+            (torch.int32, self.words, self.words, _lib.MASK_BITS, eng.lib.glb_dfa_bank_rows, "glb_dfa_bank_init",
+             "glb_dfa_fill_masks", lambda a: a)
         rows = int(bank_rows(self.mask_bank_bytes, V, dfa.n_states))
         if rows < 3:
             raise ValueError(f"mask_bank_bytes={mask_bank_bytes} holds no state's mask: a row of this vocabulary takes "
@@ -210,8 +214,7 @@ class DeviceConstraint:
         padded) and start it over."""
         import torch
 
-        need = self.vocab if self.weighted else self.words
-        if bank.dtype != self._bank_dtype or bank.dim() != 2 or bank.stride(1) != 1 or bank.shape[0] < 3 or bank.shape[1] < need \
+        if bank.dtype != self._bank_dtype or bank.dim() != 2 or bank.stride(1) != 1 or bank.shape[0] < 3 or bank.shape[1] < self._row_need \
                 or bank.device != self.dev:
             raise ValueError("bank must be an int32 [rows >= 3, >= ceil(V / 32)] (with weights: float32 [rows >= 3, >= V]) "
                              "device tensor with unit inner stride")
@@ -222,10 +225,7 @@ class DeviceConstraint:
     def _reset_bank(self):
         """Forget every state's row (rows 0 and 1 are written again, the overflow word cleared)."""
         self._warm = False
-        if self.weighted:
-            self._call("glb_dfa_weight_bank_init", self._weight_args(self._args()))
-        else:
-            self._call("glb_dfa_bank_init", self._args())
+        self._call(self._init, self._bank_args(self._args()))
 
     capacity = property(lambda self: self.bank.shape[0])
 
@@ -300,10 +300,7 @@ class DeviceConstraint:
         a.n, a.state_in = n, self._states(states).data_ptr()
         self._call("glb_dfa_claim_rows", a)
         a.max_work = min(n, self.dfa.n_states, self.capacity)
-        if self.weighted:
-            self._call("glb_dfa_fill_weights", self._weight_args(a))
-        else:
-            self._call("glb_dfa_fill_masks", a)
+        self._call(self._fill, self._bank_args(a))
 
     def mask_rows(self, states, done=None):
         """int32 [n]: the bank row of every state - 0 (nothing allowed) for a dead one; where `done` (int32 [n]) is set, row
@@ -325,9 +322,9 @@ class DeviceConstraint:
         self._call("glb_dfa_mask_ids", a)
         return out
 
-    def step_masks(self, ids, by_row, n_particles, parity=False):
-        """The fused step's mask arguments for bank rows `ids` (int32 [n_units]: per logits row when `by_row`, else per
-        particle), and whether the bank itself is handed over.  `GLB_MASK_BITS` rows are read as they are only by the
+    def step_masks(self, logits, ids, by_row, n_particles, parity=False):
+        """The fused step's mask arguments (masks.py; `logits` is not read) for bank rows `ids` (int32 [n_units]: per logits
+        row when `by_row`, else per particle), and whether the bank itself is handed over.  `GLB_MASK_BITS` rows are read as they are only by the
         step's one-launch form; its two-launch form first brings ALL rows of the table it is given into the kernels'
         layout.  So the bank is handed over where glb_logprob_mask_sample takes the one-launch form (csrc/glb_api.hip,
         `fused`: no parity draw, more than 512 (unit, 4096-token chunk) items, at most 16 x 8 x CUs particles), and
@@ -338,13 +335,11 @@ class DeviceConstraint:
         import torch
 
         key = "row_mask_id" if by_row else "mask_id"
-        if self.weighted:
-            return {"mask_kind": _lib.MASK_F32, "mask": self.bank, key: ids}, True
         n_units = ids.numel()
         if self._cus is None:
             self._cus = torch.cuda.get_device_properties(self.dev).multi_processor_count
-        if not parity and n_units * ((self.vocab + 4095) // 4096) > 512 and n_particles <= 16 * 8 * self._cus:
-            return {"mask_kind": _lib.MASK_BITS, "mask": self.bank, key: ids}, True
+        if self.weighted or (not parity and n_units * ((self.vocab + 4095) // 4096) > 512 and n_particles <= 16 * 8 * self._cus):
+            return {"mask_kind": self._mask_kind, "mask": self.bank, key: ids}, True
         if self._gathered is None or self._gathered[0].shape[0] != n_units:
             self._gathered = (torch.empty((n_units, self.words), dtype=torch.int32, device=self.dev),
                               torch.arange(n_units, dtype=torch.int32, device=self.dev))

@@ -6,6 +6,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/glb.h"
 #include "glb_common.hpp"
 
@@ -26,63 +28,45 @@ struct Dfa {
   int64_t vocab;
 };
 
-// next(s, t) of include/glb.h
-__device__ inline int32_t dfa_next(const Dfa &d, int32_t s, int64_t t) {
-  if (s < 0 || s >= d.n_states || t < 0 || t >= d.vocab) return -1;
-  if (d.skip[t]) return -1;
-  const int64_t p0 = d.ptr[t], p1 = d.ptr[t + 1];
-  if (p0 < 0 || p1 <= p0 || p1 > d.n_bytes) return -1;  // an empty token, or offsets that are not the vocabulary's
-  int32_t cur = s;
-  for (int64_t p = p0; p < p1; ++p) {
-    cur = d.delta[(int64_t)cur * 256 + d.bytes[p]];
-    if (cur < 0 || cur >= d.n_states) return -1;
-  }
-  return d.live[cur] ? cur : -1;
-}
-
-// the weight of token t from state s (include/glb.h): the float32 sum of the arcs' weights in byte order, -inf where
-// next(s, t) is dead.  Same checks, same order as dfa_next
-__device__ inline float dfa_next_weight(const Dfa &d, const float *arc_logw, int32_t s, int64_t t) {
-  const float dead = -__builtin_inff();
+// next(s, t) of include/glb.h; WEIGHTED: the weight of token t from state s instead - the float32 sum of the arcs' weights
+// in byte order, -inf where next(s, t) is dead.  One walk, one set of checks; without weights no float is loaded or carried
+template <bool WEIGHTED>
+__device__ inline std::conditional_t<WEIGHTED, float, int32_t> dfa_walk(const Dfa &d, const float *arc_logw, int32_t s, int64_t t) {
+  std::conditional_t<WEIGHTED, float, int32_t> dead = -1;
+  if constexpr (WEIGHTED) dead = -__builtin_inff();
   if (s < 0 || s >= d.n_states || t < 0 || t >= d.vocab) return dead;
   if (d.skip[t]) return dead;
   const int64_t p0 = d.ptr[t], p1 = d.ptr[t + 1];
-  if (p0 < 0 || p1 <= p0 || p1 > d.n_bytes) return dead;
+  if (p0 < 0 || p1 <= p0 || p1 > d.n_bytes) return dead;  // an empty token, or offsets that are not the vocabulary's
   int32_t cur = s;
-  float w = 0.0f;
+  [[maybe_unused]] float w = 0.0f;
   for (int64_t p = p0; p < p1; ++p) {
     const int64_t arc = (int64_t)cur * 256 + d.bytes[p];
-    w = w + arc_logw[arc];
+    if constexpr (WEIGHTED) w = w + arc_logw[arc];
     cur = d.delta[arc];
     if (cur < 0 || cur >= d.n_states) return dead;
   }
-  return d.live[cur] ? w : dead;
+  if (!d.live[cur]) return dead;
+  if constexpr (WEIGHTED) return w;
+  else return cur;
 }
 
-__global__ void dfa_bank_init_kernel(Dfa d, int32_t *bank, int64_t bank_ld, int64_t words, int32_t *row_of_state,
-                                     int32_t *counters) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < d.n_states) row_of_state[i] = -1;
-  if (i < words) {
-    bank[i] = 0;
-    const bool eos_here = d.eos_id >= 0 && d.eos_id < d.vocab && (d.eos_id >> 5) == i;
-    bank[bank_ld + i] = eos_here ? (int32_t)(1u << (d.eos_id & 31)) : 0;
-  }
-  if (i == 0) {
-    counters[C_ROWS] = 2;
-    counters[C_FILLED] = 0;
-    counters[C_OVERFLOW] = 0;
-    counters[C_RESERVED] = 0;
-  }
-}
-
-__global__ void dfa_weight_bank_init_kernel(int32_t n_states, int32_t eos_id, int64_t vocab, float *wbank, int64_t wbank_ld,
-                                            int32_t *row_of_state, int32_t *counters) {
+// rows 0 (nothing) and 1 (EOS alone) of a bank of bit words (T = int32_t: `elems` words) or of log-weights (float: `elems`
+// tokens), no state with a row
+template <typename T>
+__global__ void dfa_bank_init_kernel(int32_t n_states, int32_t eos_id, int64_t vocab, T *bank, int64_t bank_ld, int64_t elems,
+                                     int32_t *row_of_state, int32_t *counters) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n_states) row_of_state[i] = -1;
-  if (i < vocab) {
-    wbank[i] = -__builtin_inff();
-    wbank[wbank_ld + i] = i == eos_id ? 0.0f : -__builtin_inff();
+  if (i < elems) {
+    if constexpr (std::is_same_v<T, float>) {
+      bank[i] = -__builtin_inff();
+      bank[bank_ld + i] = i == eos_id ? 0.0f : -__builtin_inff();
+    } else {
+      bank[i] = 0;
+      const bool eos_here = eos_id >= 0 && eos_id < vocab && (eos_id >> 5) == i;
+      bank[bank_ld + i] = eos_here ? (int32_t)(1u << (eos_id & 31)) : 0;
+    }
   }
   if (i == 0) {
     counters[C_ROWS] = 2;
@@ -100,7 +84,7 @@ __global__ void dfa_advance_kernel(Dfa d, int64_t n, const int32_t *tokens, int6
   if (cur < 0 || cur >= d.n_states) cur = -1;
   const int64_t f = from[i], t = to[i];
   if (f < 0 || t > ld || f > t) cur = -1;
-  for (int64_t j = f; j < t && cur >= 0; ++j) cur = dfa_next(d, cur, tokens[i * ld + j]);
+  for (int64_t j = f; j < t && cur >= 0; ++j) cur = dfa_walk<false>(d, nullptr, cur, tokens[i * ld + j]);
   state_out[i] = cur;
 }
 
@@ -124,8 +108,14 @@ __global__ void dfa_claim_kernel(int32_t n_states, int64_t n, const int32_t *sta
   }
 }
 
-__global__ __launch_bounds__(FILL_THREADS) void dfa_fill_kernel(Dfa d, int32_t *bank, int64_t bank_ld, int32_t capacity,
-                                                               const int32_t *work, const int32_t *counters) {
+// A wave per (work entry, 64 consecutive tokens), a workgroup looping over the entries it owns.  Bit rows: lane 0 writes the
+// wave's two words from one ballot; float rows (WEIGHTED): a lane keeps its token's sum and the wave stores 64 consecutive
+// floats (256 bytes), no ballot
+template <bool WEIGHTED>
+__global__ __launch_bounds__(FILL_THREADS) void dfa_fill_kernel(Dfa d, const float *arc_logw, const float *final_logw,
+                                                               std::conditional_t<WEIGHTED, float, int32_t> *bank,
+                                                               int64_t bank_ld, int32_t capacity, const int32_t *work,
+                                                               const int32_t *counters) {
   __shared__ int32_t range[2];
   if (threadIdx.x == 0) {
     int32_t begin = __hip_atomic_load(&counters[C_FILLED], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -140,45 +130,24 @@ __global__ __launch_bounds__(FILL_THREADS) void dfa_fill_kernel(Dfa d, int32_t *
   const int64_t words = (d.vocab + 31) / 32;
   const int64_t t = (int64_t)blockIdx.x * FILL_THREADS + threadIdx.x;  // (a wave: 64 consecutive tokens, two words)
   const int64_t w0 = (t >> 6) * 2;
-  const int lane = threadIdx.x & 63;
-  if (w0 < words) {
-    for (int32_t e = begin + (int32_t)blockIdx.y; e < end; e += (int32_t)gridDim.y) {
-      const int32_t s = work[2 * (int64_t)e], r = work[2 * (int64_t)e + 1];
-      if (s < 0 || s >= d.n_states || r < 2 || r >= capacity) continue;  // (uniform over the block)
+  // who leaves: a float lane past the vocabulary (no barrier and no cross-lane operation below), but of the bit rows only a
+  // whole wave past the last word - the ballot wants every lane of the others
+  if (WEIGHTED ? t >= d.vocab : w0 >= words) return;
+  for (int32_t e = begin + (int32_t)blockIdx.y; e < end; e += (int32_t)gridDim.y) {
+    const int32_t s = work[2 * (int64_t)e], r = work[2 * (int64_t)e + 1];
+    if (s < 0 || s >= d.n_states || r < 2 || r >= capacity) continue;  // (uniform over the block)
+    if constexpr (WEIGHTED) {
+      bank[(int64_t)r * bank_ld + t] = t == d.eos_id ? final_logw[s] : dfa_walk<true>(d, arc_logw, s, t);
+    } else {
       bool bit = false;
-      if (t < d.vocab) bit = t == d.eos_id ? d.accepting[s] != 0 : dfa_next(d, s, t) >= 0;
+      if (t < d.vocab) bit = t == d.eos_id ? d.accepting[s] != 0 : dfa_walk<false>(d, nullptr, s, t) >= 0;
       const uint64_t b = __ballot(bit);
-      if (lane == 0) {
+      if ((threadIdx.x & 63) == 0) {
         int32_t *row = bank + (int64_t)r * bank_ld;
         row[w0] = (int32_t)(uint32_t)b;
         if (w0 + 1 < words) row[w0 + 1] = (int32_t)(uint32_t)(b >> 32);
       }
     }
-  }
-}
-
-// The float rows: the grid of dfa_fill_kernel - a wave per (work entry, 64 consecutive tokens), a workgroup looping over the
-// entries it owns - but a lane keeps its token's sum and the wave stores 64 consecutive floats (256 bytes), no ballot
-__global__ __launch_bounds__(FILL_THREADS) void dfa_fill_weights_kernel(Dfa d, const float *arc_logw, const float *final_logw,
-                                                                       float *wbank, int64_t wbank_ld, int32_t capacity,
-                                                                       const int32_t *work, const int32_t *counters) {
-  __shared__ int32_t range[2];
-  if (threadIdx.x == 0) {
-    int32_t begin = __hip_atomic_load(&counters[C_FILLED], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    int32_t end = __hip_atomic_load(&counters[C_ROWS], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    end = (end > capacity ? capacity : end) - 2;
-    if (begin < 0) begin = 0;
-    range[0] = begin;
-    range[1] = end;
-  }
-  __syncthreads();
-  const int32_t begin = range[0], end = range[1];
-  const int64_t t = (int64_t)blockIdx.x * FILL_THREADS + threadIdx.x;
-  if (t >= d.vocab) return;  // (no barrier and no cross-lane operation below)
-  for (int32_t e = begin + (int32_t)blockIdx.y; e < end; e += (int32_t)gridDim.y) {
-    const int32_t s = work[2 * (int64_t)e], r = work[2 * (int64_t)e + 1];
-    if (s < 0 || s >= d.n_states || r < 2 || r >= capacity) continue;
-    wbank[(int64_t)r * wbank_ld + t] = t == d.eos_id ? final_logw[s] : dfa_next_weight(d, arc_logw, s, t);
   }
 }
 
@@ -256,23 +225,39 @@ int dfa_weight_check(const glb_dfa_weight_args *w, const char *what, int need) {
   return GLB_OK;
 }
 
+// rows a bank of `bank_bytes` holds when one takes `row_bytes`: at most a row per state and the bank's own two
+int64_t bank_rows(size_t bank_bytes, size_t row_bytes, int64_t vocab, int64_t n_states) {
+  if (vocab <= 0 || n_states <= 0) return 0;
+  int64_t rows = (int64_t)(bank_bytes / row_bytes);
+  if (rows > n_states + 2) rows = n_states + 2;
+  return rows > 65535 ? 65535 : rows;
+}
+
+// the claimed rows filled (bit words, or with weights floats), then the filled mark moved up
+template <bool WEIGHTED, typename T>
+int fill_and_commit(const glb_dfa_args *a, const char *what, const char *launch, const float *arc_logw, const float *final_logw,
+                    T *bank, int64_t bank_ld, void *stream) {
+  if (a->max_work <= 0) return glb::api_fail(GLB_EINVAL, "%s: max_work %lld <= 0", what, (long long)a->max_work);
+  const unsigned gy = (unsigned)(a->max_work < FILL_MAX_ENTRIES ? a->max_work : FILL_MAX_ENTRIES);
+  hipLaunchKernelGGL(dfa_fill_kernel<WEIGHTED>, dim3(blocks_for(a->vocab, FILL_THREADS), gy), dim3(FILL_THREADS), 0,
+                     (hipStream_t)stream, dfa_of(a), arc_logw, final_logw, bank, bank_ld, (int32_t)a->capacity, a->work, a->counters);
+  hipLaunchKernelGGL(dfa_commit_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (int32_t)a->capacity, a->counters);
+  return launched(launch);
+}
+
 }  // namespace
 
 extern "C" {
 
 int64_t glb_dfa_bank_rows(size_t bank_bytes, int64_t vocab, int64_t n_states) {
-  if (vocab <= 0 || n_states <= 0) return 0;
-  const size_t row = (size_t)((vocab + 31) / 32) * sizeof(int32_t);
-  int64_t rows = (int64_t)(bank_bytes / row);
-  if (rows > n_states + 2) rows = n_states + 2;
-  return rows > 65535 ? 65535 : rows;
+  return bank_rows(bank_bytes, (size_t)((vocab + 31) / 32) * sizeof(int32_t), vocab, n_states);
 }
 
 int glb_dfa_bank_init(const glb_dfa_args *a, void *stream) {
   if (const int rc = dfa_check(a, "glb_dfa_bank_init", NEED_BANK)) return rc;
   const int64_t words = (a->vocab + 31) / 32, items = words > a->n_states ? words : a->n_states;
-  hipLaunchKernelGGL(dfa_bank_init_kernel, dim3(blocks_for(items, 256)), dim3(256), 0, (hipStream_t)stream, dfa_of(a), a->bank,
-                     a->bank_ld, words, a->row_of_state, a->counters);
+  hipLaunchKernelGGL(dfa_bank_init_kernel<int32_t>, dim3(blocks_for(items, 256)), dim3(256), 0, (hipStream_t)stream, a->n_states,
+                     a->eos_id, a->vocab, a->bank, a->bank_ld, words, a->row_of_state, a->counters);
   return launched("dfa_bank_init launch");
 }
 
@@ -294,12 +279,7 @@ int glb_dfa_claim_rows(const glb_dfa_args *a, void *stream) {
 
 int glb_dfa_fill_masks(const glb_dfa_args *a, void *stream) {
   if (const int rc = dfa_check(a, "glb_dfa_fill_masks", NEED_BANK | NEED_VOCAB)) return rc;
-  if (a->max_work <= 0) return glb::api_fail(GLB_EINVAL, "glb_dfa_fill_masks: max_work %lld <= 0", (long long)a->max_work);
-  const unsigned gy = (unsigned)(a->max_work < FILL_MAX_ENTRIES ? a->max_work : FILL_MAX_ENTRIES);
-  hipLaunchKernelGGL(dfa_fill_kernel, dim3(blocks_for(a->vocab, FILL_THREADS), gy), dim3(FILL_THREADS), 0, (hipStream_t)stream,
-                     dfa_of(a), a->bank, a->bank_ld, (int32_t)a->capacity, a->work, a->counters);
-  hipLaunchKernelGGL(dfa_commit_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (int32_t)a->capacity, a->counters);
-  return launched("dfa_fill launch");
+  return fill_and_commit<false>(a, "glb_dfa_fill_masks", "dfa_fill launch", nullptr, nullptr, a->bank, a->bank_ld, stream);
 }
 
 int glb_dfa_mask_ids(const glb_dfa_args *a, void *stream) {
@@ -311,32 +291,22 @@ int glb_dfa_mask_ids(const glb_dfa_args *a, void *stream) {
 }
 
 int64_t glb_dfa_weight_bank_rows(size_t bank_bytes, int64_t vocab, int64_t n_states) {
-  if (vocab <= 0 || n_states <= 0) return 0;
-  const size_t row = (size_t)((vocab + 63) / 64) * 64 * sizeof(float);
-  int64_t rows = (int64_t)(bank_bytes / row);
-  if (rows > n_states + 2) rows = n_states + 2;
-  return rows > 65535 ? 65535 : rows;
+  return bank_rows(bank_bytes, (size_t)((vocab + 63) / 64) * 64 * sizeof(float), vocab, n_states);
 }
 
 int glb_dfa_weight_bank_init(const glb_dfa_weight_args *w, void *stream) {
   if (const int rc = dfa_weight_check(w, "glb_dfa_weight_bank_init", 0)) return rc;
   const glb_dfa_args *a = &w->dfa;
   const int64_t items = a->vocab > a->n_states ? a->vocab : a->n_states;
-  hipLaunchKernelGGL(dfa_weight_bank_init_kernel, dim3(blocks_for(items, 256)), dim3(256), 0, (hipStream_t)stream, a->n_states,
-                     a->eos_id, a->vocab, w->wbank, w->wbank_ld, a->row_of_state, a->counters);
+  hipLaunchKernelGGL(dfa_bank_init_kernel<float>, dim3(blocks_for(items, 256)), dim3(256), 0, (hipStream_t)stream, a->n_states,
+                     a->eos_id, a->vocab, w->wbank, w->wbank_ld, a->vocab, a->row_of_state, a->counters);
   return launched("dfa_weight_bank_init launch");
 }
 
 int glb_dfa_fill_weights(const glb_dfa_weight_args *w, void *stream) {
   if (const int rc = dfa_weight_check(w, "glb_dfa_fill_weights", NEED_VOCAB)) return rc;
-  const glb_dfa_args *a = &w->dfa;
-  if (a->max_work <= 0) return glb::api_fail(GLB_EINVAL, "glb_dfa_fill_weights: max_work %lld <= 0", (long long)a->max_work);
-  const unsigned gy = (unsigned)(a->max_work < FILL_MAX_ENTRIES ? a->max_work : FILL_MAX_ENTRIES);
-  hipLaunchKernelGGL(dfa_fill_weights_kernel, dim3(blocks_for(a->vocab, FILL_THREADS), gy), dim3(FILL_THREADS), 0,
-                     (hipStream_t)stream, dfa_of(a), w->arc_logw, w->final_logw, w->wbank, w->wbank_ld, (int32_t)a->capacity, a->work,
-                     a->counters);
-  hipLaunchKernelGGL(dfa_commit_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (int32_t)a->capacity, a->counters);
-  return launched("dfa_fill_weights launch");
+  return fill_and_commit<true>(&w->dfa, "glb_dfa_fill_weights", "dfa_fill_weights launch", w->arc_logw, w->final_logw, w->wbank,
+                               w->wbank_ld, stream);
 }
 
 }  // extern "C"

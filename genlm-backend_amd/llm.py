@@ -23,9 +23,9 @@ import torch
 
 from .cache import KVPrefix, RowLRU, TokenTrie
 from .kv import PrefixLRU, PrefixTable, encode_ragged, ragged
+from .masks import MASK_BITS, MASK_F32, MASK_NONE, RegisteredMasks  # noqa: F401 (the kinds stay importable from here)
 from .tokenization import decode_vocab
 
-MASK_NONE, MASK_BITS, MASK_F32 = 0, 1, 2
 RNG_NONE, RNG_PHILOX, RNG_NOISE = 0, 1, 2
 
 
@@ -357,9 +357,7 @@ class AsyncAmdLM(AsyncLM):
 
             self._auto_kv = AutoKV(self, auto_kv_rows, auto_kv_cap, chunk=auto_kv_chunk)
         # fused-step state
-        self._mask_kind = MASK_NONE
-        self._masks = None
-        self._masks_prepared = {}
+        self.masks = RegisteredMasks(self.engine)  # what register_masks was given (masks.py)
         self._rng_mode = RNG_PHILOX
         self._rng_seed = 0
         self._noise_src = None  # "torch" draws: the CPU generator's stream on the device, made at the first evaluation
@@ -559,26 +557,33 @@ class AsyncAmdLM(AsyncLM):
         if isinstance(masks, (list, tuple)):
             masks = torch.stack([m.to(torch.float32) for m in masks])
         masks = masks.to(self.device, torch.float32).contiguous()
-        bits, flag = self.engine.mask_to_bits(masks)
-        self._masks_prepared = {}
-        if int(flag.item()) == 0:
-            self._mask_kind, self._masks = MASK_BITS, bits
-            self._mask_vocab = masks.shape[1]
-        else:
-            self._mask_kind, self._masks = MASK_F32, masks
+        self.masks.register(masks)
         return masks.shape[0]
 
     def step_masks(self, logits_dtype):
         """Mask arguments of `HipEngine.step` for logits of `logits_dtype`: bit masks are brought into the kernels'
         layout once per element width (glb_mask_prepare) and reused by every step."""
-        if self._mask_kind == MASK_NONE:
-            return {}
-        if self._mask_kind == MASK_F32:
-            return dict(mask_kind=MASK_F32, mask=self._masks)
-        wide = logits_dtype == torch.float32
-        if wide not in self._masks_prepared:
-            self._masks_prepared[wide] = self.engine.prepare_masks(self._masks, self._mask_vocab, logits_dtype)
-        return dict(mask=self._masks_prepared[wide])
+        return self.masks.tables(logits_dtype)
+
+    _mask_kind = property(lambda self: self.masks.kind)
+
+    def _fused_step(self, logits, row_of, ids, by_row, n, noise_groups, constraint=None):
+        """The fused step over logits rows for n contexts (row_of: the logits row of each): the masks of `constraint`, else
+        the registered ones, by `ids` (per logits row when `by_row`, else per context); in parity mode the Exp(1) rows in the
+        reference's resolution order - by dedup group `noise_groups`, duplicates contiguous (hf.py:285-288); None: the
+        contexts are in that order already.  Returns (logZ, token) device tensors."""
+        eng, V, parity = self.engine, logits.shape[-1], self._rng_mode == RNG_NOISE
+        kw, _ = (self.masks if constraint is None else constraint).step_masks(logits, ids, by_row, n, parity=parity)
+        if parity:
+            slot = None
+            if noise_groups is not None:
+                order = torch.argsort(noise_groups.to(torch.int64), stable=True)
+                slot = torch.empty(n, dtype=torch.int32, device=self.device)
+                slot[order] = torch.arange(n, dtype=torch.int32, device=self.device)
+            kw["noise"] = self._noise_rows(V).rows(n, row_slot=slot)
+        logZ, _, tok = eng.step(logits, vocab=V, row_of=row_of, rng_mode=self._rng_mode, seed=self._rng_seed,
+                                offset=self._batch_counter, want_lse=False, **kw)
+        return logZ, tok
 
     def set_rng(self, mode="philox", seed=0):
         """"philox": in-kernel counter RNG (fast).  "torch": parity with the reference's CPU
@@ -747,13 +752,8 @@ class AsyncAmdLM(AsyncLM):
         if step_q:
             row_of = torch.from_numpy(np.fromiter((step_row[u] for u, _ in step_q), np.int32, len(step_q))).to(dev)
             mask_id = torch.from_numpy(np.fromiter((m.mask_id for _, m in step_q), np.int32, len(step_q))).to(dev)
-            kw = self.step_masks(logits.dtype)
-            if kw:
-                kw["mask_id"] = mask_id
-            if self._rng_mode == RNG_NOISE:  # (step_q is in resolution order already: by group, duplicates contiguous)
-                kw["noise"] = self._noise_rows(V).rows(len(step_q))
-            logZ, _lse, tok = eng.step(logits, vocab=V, row_of=row_of, rng_mode=self._rng_mode, seed=self._rng_seed,
-                                       offset=self._batch_counter, want_lse=False, **kw)
+            # (step_q is in resolution order already: by group, duplicates contiguous)
+            logZ, tok = self._fused_step(logits, row_of, mask_id, False, len(step_q), None)
             step_out = (logZ.cpu().tolist(), tok.cpu().tolist())
             eng.raise_if_failed(tokens=step_out[1])
         if lp_slab is not None:  # no NaN row may reach the trie: the error word of the log-softmax launch (one small copy)
@@ -1143,26 +1143,8 @@ class AsyncAmdLM(AsyncLM):
     def _finish_batch_step(self, logits, row_of, group_of, U, n, mid_d, row_mid, by_row, constraint=None):
         """The fused step over a batch's logits rows (row_of: logits row of every context; group_of: its dedup group -
         the order parity-mode noise is dealt in).  Returns (logZ, token) device tensors."""
-        eng, dev = self.engine, self.device
-        V = logits.shape[-1]
-        kw = self.step_masks(logits.dtype) if constraint is None else {}
-        if constraint is not None:
-            # the bank rows as mask ids: the bank itself or the units' rows gathered out of it (DeviceConstraint.step_masks)
-            kw, _ = constraint.step_masks(row_mid[:U].contiguous() if by_row else mid_d, by_row, n,
-                                          parity=self._rng_mode == RNG_NOISE)
-        elif kw:
-            if by_row:
-                kw["row_mask_id"] = row_mid[:U].contiguous()
-            else:
-                kw["mask_id"] = mid_d
-        if self._rng_mode == RNG_NOISE:
-            # Exp(1) rows in the reference's resolution order: by dedup group, duplicates contiguous (hf.py:285-288)
-            order = torch.argsort(group_of.to(torch.int64), stable=True)
-            slot = torch.empty(n, dtype=torch.int32, device=dev)
-            slot[order] = torch.arange(n, dtype=torch.int32, device=dev)
-            kw["noise"] = self._noise_rows(V).rows(n, row_slot=slot)
-        logZ, _, tok = eng.step(logits, vocab=V, row_of=row_of, rng_mode=self._rng_mode, seed=self._rng_seed,
-                                offset=self._batch_counter, want_lse=False, **kw)
+        # (under a constraint the ids are bank rows: the bank itself or the units' rows gathered out of it, DeviceConstraint.step_masks)
+        logZ, tok = self._fused_step(logits, row_of, row_mid[:U].contiguous() if by_row else mid_d, by_row, n, group_of, constraint)
         self._count(n, U, U)
         return logZ, tok
 

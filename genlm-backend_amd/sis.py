@@ -19,9 +19,9 @@ import os
 import numpy as np
 import torch
 
-from ._lib import MASK_BITS
 from .cache import KVPrefix
 from .kv import PrefixTable, SlabKV, SlabRunner, encode_ragged
+from .masks import ParticleMasks
 
 RNG_PHILOX, RNG_NOISE = 1, 2
 
@@ -286,10 +286,7 @@ class DeviceSIS:
         self._kv = SlabRunner(llm, self.kv_rows, self.cap, kv_in_place, kv_graph)
         if self.particle_kv:
             assert not use_prefix_kv
-        self.particle_masks = particle_masks
-        self._pm_prepared, self._pm_dirty, self._pm_seen, self._pm_moved = None, None, None, False
-        self.pm_raw_above = None  # fraction of changed rows above which a step hands the bit rows over raw (None: by dtype)
-        self.pm_raw_steps = 0
+        self._particle = ParticleMasks(self.eng, n_particles, particle_masks)  # (raw or prepared, per step: masks.py)
         self.constraint_raw_steps = 0  # steps under a constraint that were handed the mask bank itself
         self.rows_moved = 0  # particles that changed ranks in the last resampling step (over all ranks)
         self.resample_ess = resample_ess
@@ -298,6 +295,9 @@ class DeviceSIS:
         self.reset()
 
     pkv = property(lambda self: self._kv.pkv)
+    particle_masks = property(lambda self: self._particle.masks, lambda self, masks: setattr(self._particle, "masks", masks))
+    pm_raw_above = property(lambda self: self._particle.raw_above, lambda self, frac: setattr(self._particle, "raw_above", frac))
+    pm_raw_steps = property(lambda self: self._particle.raw_steps)
     _slab_fwd = property(lambda self: self._kv._slab_fwd)
 
     @torch.no_grad()
@@ -312,7 +312,7 @@ class DeviceSIS:
     def reset(self):
         if self.noise_src is not None:  # a run starts its seeded noise stream over
             self.noise_src.reset()
-        self._pm_prepared, self._pm_dirty, self._pm_seen, self._pm_moved = None, None, None, False  # (a new run may come with new masks)
+        self._particle.reset()  # (a new run may come with new masks)
         self.contexts = self._ctx0.clone()
         self.prompt_len = self._prompt_len0.clone()
         self.lengths = self.prompt_len.clone()
@@ -432,50 +432,10 @@ class DeviceSIS:
         eng, llm, N = self.eng, self.llm, self.N
         V = logits.shape[-1]
         mask_id = ((self.lengths - self.prompt_len) >= self.max_tokens).to(torch.int32)
-        kw = llm.step_masks(logits.dtype) if self.particle_masks is None and self.constraint is None else {}
-        if self.constraint is not None:
-            kw = self._constraint_masks(logits, group_of, mask_id)
-        elif self.particle_masks is not None:  # one mask per particle: per-particle ids, no dedup of the math
-            # Two ways to hand the bit rows over.  RAW: the fused launch's stats waves read the caller's rows themselves
-            # (kMaskRaw: + 2 us a step on float32 rows, + 5 us on 16-bit ones, nothing to prepare).  PREPARED: the rows
-            # transposed into the kernels' layout (glb_mask_prepare: 11 us for 1025 rows of 50257), afterwards only the rows
-            # `update_particle_masks` named again (glb_mask_prepare_rows).  A grammar that moves every particle's mask every
-            # token is served raw; masks that stand still, or of which a few move a step, prepared.  A step goes raw
-            #  * when more than `pm_raw_above` of the rows changed since the prepared form was last brought up to date and
-            #    some did since the last step (their names are kept: a step before which nothing moved brings it up to date);
-            #  * when the tensor is in a state this object has not seen - rebound, or written in place by anyone but
-            #    `update_particle_masks` (its version counter moves); seen twice in a row, that state is prepared.
-            # The parity draw is two launches (no raw form): always prepared.
-            own = torch.arange(N, dtype=torch.int32, device=self.dev)
-            pm = self.particle_masks
-            ids = torch.where(mask_id > 0, torch.full_like(own, N), own)
-            state = (pm.data_ptr(), pm._version, logits.dtype)
-            frac = self.pm_raw_above if self.pm_raw_above is not None else (0.25 if logits.dtype == torch.float32 else 0.5)
-            raw = False
-            if self._pm_prepared is None or self._pm_prepared[1] != state:
-                if self.rng_mode != RNG_NOISE and frac < 1.0 and self._pm_seen != state:
-                    raw, self._pm_prepared, self._pm_dirty = True, None, None
-                else:
-                    self._pm_prepared, self._pm_dirty = (eng.prepare_masks(pm, V, logits.dtype), state), None
-            elif self._pm_dirty is not None:
-                if self.rng_mode != RNG_NOISE and self._pm_moved and self._pm_dirty.numel() > frac * N:
-                    raw = True  # (the prepared form stays behind by the rows named in _pm_dirty, until the masks stand still)
-                else:
-                    eng.update_prepared_masks(self._pm_prepared[0], pm, self._pm_dirty)
-                    self._pm_dirty = None
-            self._pm_seen, self._pm_moved = state, False
-            self.pm_raw_steps += int(raw)
-            kw = dict(mask_kind=MASK_BITS, mask=pm, mask_id=ids) if raw else dict(mask=self._pm_prepared[0], mask_id=ids)
-        elif kw:
-            # The mask depends on the number of generated tokens only; with prompts of one length that makes it a
-            # function of the context, so identical contexts (one logits row) share it: ids go per ROW and a shared
-            # row is reduced once (hf.py:214-220 dedup carried through the particle math).
-            if self._mask_by_row and group_of is not None:
-                kw["row_mask_id"] = mask_id[self._rep[:logits.shape[0]].long()].contiguous()
-            elif self._mask_by_row:
-                kw["row_mask_id"] = mask_id
-            else:
-                kw["mask_id"] = mask_id
+        # the step's mask source: the constraint, else the caller's row per particle, else the backend's registered masks
+        source = self.constraint if self.constraint is not None else self._particle if self.particle_masks is not None else llm.masks
+        kw, raw = source.step_masks(logits, *self._mask_units(logits, group_of, mask_id), N, parity=self.rng_mode == RNG_NOISE)
+        self.constraint_raw_steps += int(raw and self.constraint is not None)
         if self.rng_mode == RNG_NOISE:
             kw["noise"] = self._parity_noise(self._noise_groups if self._noise_groups is not None else group_of, V)
         if time_kernel:
@@ -514,21 +474,20 @@ class DeviceSIS:
             self._maybe_resample()
         return U, n_global
 
-    def _constraint_masks(self, logits, group_of, done):
-        """The step's mask arguments under a constraint: the particles' bank rows (glb_dfa_claim_rows / fill_masks / mask_ids;
-        a warmed constraint: the last alone) and the bank handed over raw - per logits row when the state is a function of
-        the context (prompts of one length), so that a shared row is reduced once.  Bank or gathered rows: `DeviceConstraint.step_masks`
-        (`constraint_raw_steps` counts the steps that were handed the bank)."""
-        c = self.constraint
-        rows = c.mask_rows(self.states, done=done)
-        by_row = self._mask_by_row
-        if by_row and group_of is not None:
-            ids = rows[self._rep[:logits.shape[0]].long()].contiguous()
-        else:
-            ids = rows
-        kw, raw = c.step_masks(ids, by_row, self.N, parity=self.rng_mode == RNG_NOISE)
-        self.constraint_raw_steps += int(raw)
-        return kw
+    def _mask_units(self, logits, group_of, done):
+        """(ids, by_row) for the step's mask source.  Particle masks: particle i's own row, row N once it is `done` - one mask
+        per particle, no dedup of the math.  Otherwise the mask - `done` itself, under a constraint the bank row of the
+        particle's state (glb_dfa_claim_rows / fill / mask_ids; a warmed constraint: the last alone) - depends on the number
+        of generated tokens only; with prompts of one length that makes it a function of the context, so identical contexts
+        (one logits row) share it: ids go per ROW and a shared row is reduced once (hf.py:214-220 dedup carried through the
+        particle math)."""
+        if self.constraint is None and self.particle_masks is not None:
+            own = torch.arange(self.N, dtype=torch.int32, device=self.dev)
+            return torch.where(done > 0, torch.full_like(own, self.N), own), False
+        ids = done if self.constraint is None else self.constraint.mask_rows(self.states, done=done)
+        if self._mask_by_row and group_of is not None:
+            ids = ids[self._rep[:logits.shape[0]].long()].contiguous()
+        return ids, self._mask_by_row
 
     def _recompute_states(self):
         """The automaton states from the contexts' generated suffixes (one launch): after the particles moved between
@@ -539,13 +498,7 @@ class DeviceSIS:
     def update_particle_masks(self, rows, bit_rows):
         """Particles `rows` (int32 device tensor) get new masks `bit_rows` (int32 [len(rows), ceil(V / 32)]): only these are
         brought into the kernels' layout again before the next step."""
-        pm = self.particle_masks
-        known = self._pm_prepared is not None and self._pm_prepared[1][:2] == (pm.data_ptr(), pm._version)
-        pm[rows.long()] = bit_rows
-        if known:  # the prepared form follows this write row by row; any other write makes the next step prepare everything
-            self._pm_prepared = (self._pm_prepared[0], (pm.data_ptr(), pm._version, self._pm_prepared[1][2]))
-            self._pm_dirty = rows if self._pm_dirty is None else torch.unique(torch.cat([self._pm_dirty, rows]))
-            self._pm_moved = True
+        self._particle.update(rows, bit_rows)
 
     def _exchange(self):
         """All-gather of the per-shard log-weights and active counts (RCCL over xGMI when the backend is nccl): every

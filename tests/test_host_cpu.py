@@ -304,7 +304,7 @@ def test_device_sis_with_one_mask_per_particle(llm, gold):
     want[7], want[9] = [10, 40, 40], [12, 12, 41]
     assert [list(map(int, c)) for c in ctx] == want
     sis.reset()  # a new run prepares its masks again
-    assert sis._pm_prepared is None
+    assert sis._particle._prepared is None
 
 
 def test_device_sis_hands_moving_masks_over_raw_and_standing_ones_prepared(llm, gold):

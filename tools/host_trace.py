@@ -190,6 +190,29 @@ def scenario():
         for _ in range(3):
             sis.step()
 
+    N = len(prompts)
+    log("== DeviceSIS with particle_masks: first seen (raw), seen again (prepared), one row updated (that row prepared again)")
+    llm = make_llm(model, masks)
+    bits = llm.engine.mask_to_bits(masks)[0]
+    sis = DeviceSIS(llm, N, prompts, max_tokens=6, eos_id=0, seed=5, particle_masks=torch.cat([bits[:1].expand(N, -1), bits[1:2]]).contiguous())
+    sis.step()
+    sis.step()
+    sis.update_particle_masks(torch.tensor([1], dtype=torch.int32), bits[1:2])
+    sis.step()
+    log("== DeviceSIS with registered float masks")
+    soft = masks.clone()
+    soft[0, 0] = -0.5  # (a finite weight: the table stays float)
+    llm = make_llm(model, soft)
+    sis = DeviceSIS(llm, N, prompts, max_tokens=6, eos_id=0, seed=5)
+    for _ in range(3):
+        sis.step()
+    log("== batch_next_token_step_sync: mask ids per logits row, per context (contexts 0 and 4 are equal, their ids are not), parity draws")
+    llm = make_llm(model, masks)
+    llm.batch_next_token_step_sync(CTXS, [0, 1, 0, 1, 0, 1])
+    llm.batch_next_token_step_sync(CTXS, [0, 1, 0, 1, 1, 1])
+    llm.set_rng("torch", 3)
+    llm.batch_next_token_step_sync(CTXS, [0, 1, 0, 1, 1, 1])
+
 
 if __name__ == "__main__":
     torch.manual_seed(0)
