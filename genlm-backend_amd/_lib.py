@@ -284,6 +284,20 @@ class DfaWeightArgs(C.Structure):
     ]
 
 
+DFA_EVICT_COUNTERS = 4  # GLB_DFA_EVICT_COUNTERS: the call's claimants and rows taken, rows filled and rows evicted (cumulative)
+
+
+class DfaEvictArgs(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("dfa", DfaArgs),
+        ("arc_logw", C.c_void_p), ("final_logw", C.c_void_p),
+        ("wbank", C.c_void_p), ("wbank_ld", C.c_int64),
+        ("row_state", C.c_void_p), ("row_stamp", C.c_void_p), ("claimants", C.c_void_p), ("victims", C.c_void_p),
+        ("ecounters", C.c_void_p), ("epoch", C.c_void_p),
+    ]
+
+
 # every symbol include/glb.h declares: name -> (restype, argtypes)
 _vp, _i32, _i64, _f32, _sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_size_t
 SYMBOLS = {
@@ -372,6 +386,8 @@ SYMBOLS = {
     "glb_dfa_weight_bank_init": (C.c_int, [C.POINTER(DfaWeightArgs), _vp]),
     "glb_dfa_fill_weights": (C.c_int, [C.POINTER(DfaWeightArgs), _vp]),
     "glb_dfa_weight_bank_rows": (_i64, [_sz, _i64, _i64]),
+    "glb_dfa_evict_bank_init": (C.c_int, [C.POINTER(DfaEvictArgs), _vp]),
+    "glb_dfa_evict_serve": (C.c_int, [C.POINTER(DfaEvictArgs), _vp]),
     "glb_philox4x32_10": (None, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
 }
 

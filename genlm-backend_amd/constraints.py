@@ -7,6 +7,9 @@ advance on the device from the tokens drawn; nothing crosses the host per step.
 
 `ByteWFSA` is the same automaton in the log semiring (arc and final log-weights): a `DeviceConstraint` over one
 keeps a bank of float32 rows - the token log-weights from every state reached - that the step adds to the log-probabilities.
+
+`DeviceConstraint(..., on_full="evict")` lets the bank be smaller than the automaton: a cache over the states,
+the least recently requested rows recycled and filled again on the device.
 """
 import ctypes as C
 
@@ -153,8 +156,20 @@ class DeviceConstraint:
     byte_vocab       the byte string of every token id (`llm.byte_vocab`); objects with a `byte_string` are accepted
     eos_id           allowed exactly in accepting states
     skip_ids         tokens never allowed (special tokens)
-    mask_bank_bytes  budget of the mask bank: one row of ceil(V / 32) words per distinct state reached, plus two.  A bank
-                     that cannot hold a state a particle reaches is an error (`check()`), not an eviction.
+    mask_bank_bytes  budget of the mask bank: one row of ceil(V / 32) words per distinct state reached, plus two.  What
+                     happens when a state a particle reaches finds the bank full is `on_full`'s to say.
+    on_full          "error" (default): the state gets no row, its particles the empty mask, and `check()` raises.
+                     "evict": the bank is a cache over the states (include/glb.h glb_dfa_evict_*) - a
+                     `mask_rows` call recycles the least recently requested rows for the states that have none and fills
+                     them again, all on the device; rows requested in the same call are never taken.  The bank then only has
+                     to hold one step's working set: as many rows as the particles occupy distinct states, plus two
+                     (`check()` raises when a single call asked for more).  A bank that holds every state (S + 2 rows)
+                     never evicts and takes the path of "error".
+
+    Lifetime of row ids: the ids a `mask_rows` call returns are valid until the next `mask_rows` / `warm` call on this
+    constraint - under "evict" that call may hand their rows to other states.  Stream order makes this safe for `DeviceSIS`
+    and `batch_next_token_step_device`: each makes one `mask_rows` call a step and enqueues the step that reads the ids
+    before the next one.
 
     With a `ByteWFSA` the bank holds float32 rows [rows, ld] instead (ld: V rounded up to 64 floats), the token log-weights
     from each state (include/glb.h glb_dfa_weight_*): rows = min(S + 2, 65535, mask_bank_bytes / (4 ld)).  A row is 32 times
@@ -162,9 +177,12 @@ class DeviceConstraint:
     as `MASK_F32` in either form of the step; everything else keeps its meaning.
     """
 
-    def __init__(self, llm_or_engine, dfa, byte_vocab, eos_id, skip_ids=None, mask_bank_bytes=256 << 20):
+    def __init__(self, llm_or_engine, dfa, byte_vocab, eos_id, skip_ids=None, mask_bank_bytes=256 << 20, on_full="error"):
+        if on_full not in ("error", "evict"):
+            raise ValueError(f'on_full must be "error" or "evict", got {on_full!r}')
         import torch
 
+        self.on_full = on_full
         eng = getattr(llm_or_engine, "engine", llm_or_engine)
         self.eng, self.dev, self.dfa = eng, eng.device, dfa
         toks = [bytes(getattr(t, "byte_string", t)) for t in byte_vocab]
@@ -220,12 +238,19 @@ class DeviceConstraint:
                              "device tensor with unit inner stride")
         self.bank = bank
         self._work = torch.zeros((bank.shape[0], 2), dtype=torch.int32, device=self.dev)
+        # a bank that cannot hold every state, allowed to evict: the tables of glb_dfa_evict_args, one allocation
+        self._evicting = self.on_full == "evict" and self.dfa.n_states + 2 > bank.shape[0]
+        self._evict_tables = torch.zeros(4 * bank.shape[0] + _lib.DFA_EVICT_COUNTERS + 1, dtype=torch.int32, device=self.dev) \
+            if self._evicting else None
         self._reset_bank()
 
     def _reset_bank(self):
         """Forget every state's row (rows 0 and 1 are written again, the overflow word cleared)."""
         self._warm = False
-        self._call(self._init, self._bank_args(self._args()))
+        if self._evicting:
+            self._call("glb_dfa_evict_bank_init", self._evict_args(self._args()))
+        else:
+            self._call(self._init, self._bank_args(self._args()))
 
     capacity = property(lambda self: self.bank.shape[0])
 
@@ -247,6 +272,19 @@ class DeviceConstraint:
         w.arc_logw, w.final_logw = self._arc_logw.data_ptr(), self._final_logw.data_ptr()
         w.wbank, w.wbank_ld = self.bank.data_ptr(), self.bank.stride(0)
         return w
+
+    def _evict_args(self, a):
+        """The block of glb_dfa_evict_bank_init / glb_dfa_evict_serve round `a`, for either kind of bank."""
+        e = _lib.DfaEvictArgs()
+        e.struct_size, e.dfa = C.sizeof(_lib.DfaEvictArgs), a
+        if self.weighted:
+            e.arc_logw, e.final_logw = self._arc_logw.data_ptr(), self._final_logw.data_ptr()
+            e.wbank, e.wbank_ld = self.bank.data_ptr(), self.bank.stride(0)
+        cap, base = self.capacity, self._evict_tables.data_ptr()
+        e.row_state, e.row_stamp, e.claimants, e.victims = (base + 4 * cap * i for i in range(4))
+        e.ecounters = base + 16 * cap
+        e.epoch = e.ecounters + 4 * _lib.DFA_EVICT_COUNTERS
+        return e
 
     def _call(self, name, a):
         self.eng.dfa_call(name, a)
@@ -304,14 +342,16 @@ class DeviceConstraint:
 
     def mask_rows(self, states, done=None):
         """int32 [n]: the bank row of every state - 0 (nothing allowed) for a dead one; where `done` (int32 [n]) is set, row
-        1 (EOS only) if the state is accepting, else 0.  Claims and fills what is missing first; no host synchronisation."""
+        1 (EOS only) if the state is accepting, else 0.  Claims and fills what is missing first - under on_full="evict" in
+        a bank smaller than the automaton, in rows taken from the states requested longest ago; no host synchronisation.
+        The ids are valid until the next `mask_rows` / `warm` call on this constraint."""
         import torch
 
         n = states.numel()
         out = torch.empty(n, dtype=torch.int32, device=self.dev)
         if n == 0:
             return out
-        if not self._warm:
+        if not self._warm and not self._evicting:
             self._claim_and_fill(states)
         a = self._args()
         a.n, a.state_in, a.out_rows = n, self._states(states).data_ptr(), out.data_ptr()
@@ -319,7 +359,11 @@ class DeviceConstraint:
             if done.dtype != torch.int32 or done.shape != (n,) or not done.is_contiguous() or done.device != self.dev:
                 raise ValueError("done must be a contiguous int32 [n] tensor on the engine's device")
             a.done = done.data_ptr()
-        self._call("glb_dfa_mask_ids", a)
+        if self._evicting:  # touch, select, fill and ids in one call: rows are recycled for the states that have none
+            a.max_work = min(n, self.dfa.n_states, self.capacity - 2)
+            self._call("glb_dfa_evict_serve", self._evict_args(a))
+        else:
+            self._call("glb_dfa_mask_ids", a)
         return out
 
     def step_masks(self, logits, ids, by_row, n_particles, parity=False):
@@ -376,10 +420,26 @@ class DeviceConstraint:
         """(synchronises)"""
         return int(self._counters[0].item())
 
+    def stats(self):
+        """{"rows_in_use", "fills", "evictions"}: the bank's rows that hold something (its own two included), the rows
+        filled so far and how many of those were taken from another state (synchronises)."""
+        rows, filled = self._counters[:2].tolist()
+        if not self._evicting:
+            return {"rows_in_use": rows, "fills": filled, "evictions": 0}
+        fills, evictions = self._evict_tables[4 * self.capacity + 2:4 * self.capacity + 4].tolist()
+        return {"rows_in_use": rows, "fills": fills, "evictions": evictions}
+
     def check(self, word=None):
         """Raises when a state found no row in the bank (synchronises unless `word`, the overflow word's value already on
-        the host, is given)."""
-        if int(self._counters[2].item()) if word is None else int(word):
-            raise RuntimeError(f"the constraint's mask bank is full: {self.capacity} rows of {self.row_elems * 4} bytes "
-                               f"(mask_bank_bytes={self.mask_bank_bytes}) do not hold the automaton states the particles "
-                               "reached; their masks were empty.  Raise mask_bank_bytes.")
+        the host, is given).  Under eviction that is: one call asked for more distinct states than the bank has rows."""
+        if not (int(self._counters[2].item()) if word is None else int(word)):
+            return
+        if self._evicting:
+            raise RuntimeError(f"the constraint's mask bank is smaller than one step's working set: a single mask_rows call "
+                               f"asked for more distinct automaton states than its {self.capacity - 2} rows for states "
+                               f"({self.capacity} rows of {self.row_elems * 4} bytes, mask_bank_bytes={self.mask_bank_bytes}); "
+                               "the states left over were served the empty mask.  The bank must hold at least as many rows "
+                               "as the particles occupy distinct states, plus two.  Raise mask_bank_bytes.")
+        raise RuntimeError(f"the constraint's mask bank is full: {self.capacity} rows of {self.row_elems * 4} bytes "
+                           f"(mask_bank_bytes={self.mask_bank_bytes}) do not hold the automaton states the particles "
+                           "reached; their masks were empty.  Raise mask_bank_bytes.")

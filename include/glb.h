@@ -1025,6 +1025,61 @@ int glb_dfa_weight_bank_init(const glb_dfa_weight_args *args, void *hip_stream);
 int glb_dfa_fill_weights(const glb_dfa_weight_args *args, void *hip_stream);
 int64_t glb_dfa_weight_bank_rows(size_t bank_bytes, int64_t vocab, int64_t n_states);
 
+/*
+ * A bank smaller than the automaton: the bank as a cache over the states, least recently used rows
+ * recycled on the device.  The block embeds glb_dfa_args, its own struct_size set too, and serves either kind of bank:
+ * `wbank` null - the bit bank dfa.bank / dfa.bank_ld; `wbank` set - the float bank, its four fields those of
+ * glb_dfa_weight_args: arc_logw, final_logw, wbank, wbank_ld; dfa.bank is then not read.  Beside row_of_state:
+ *   row_state [capacity]   the state that owns each row, -1: none (rows 0 and 1: always -1)
+ *   row_stamp [capacity]   the epoch of the serve call that last requested the row; 0: never used
+ *   claimants [capacity]   the distinct states of the running call that have no row, in the atomics' order
+ *   victims   [capacity]   the rows taken for them
+ *   ecounters [GLB_DFA_EVICT_COUNTERS]  [0] claimants of the running call  [1] rows taken by it (both zero between calls)
+ *                          [2] rows filled, cumulative  [3] of these, rows that were taken from another state, cumulative
+ *   epoch [1]              the number of the running call, from 1; advanced on the device, never read by the host
+ * dfa.counters keeps its meaning: [0] rows in use (2 + rows that own a state), [2] overflow (sticky); [1] and `work`'s
+ * order are the claim path's and are not used: `work` holds the running call's (state, row) pairs from entry 0.
+ *   glb_dfa_evict_bank_init  what glb_dfa_bank_init / glb_dfa_weight_bank_init do, and row_state = -1, row_stamp = 0,
+ *                            ecounters = 0, epoch = 1
+ *   glb_dfa_evict_serve      gives every state of dfa.state_in [n] a filled row and writes dfa.out_rows [n]; in stream order:
+ *     1 touch     every state of state_in that has a row: row_stamp[row] = epoch.  Each distinct state without one wins
+ *                 the CAS election on row_of_state (-1 -> -2) exactly once and is appended to `claimants`.
+ *     2 select    one workgroup; leaves at once when there are no claimants.  The candidates are the rows of [2, capacity)
+ *                 whose stamp is not the epoch - a row requested in this call is never taken.  take = min(claimants,
+ *                 candidates) rows are chosen in ascending order of stamp (an exact radix select over the 32-bit stamps;
+ *                 never-used rows, stamp 0, go first; ties break in any order) into `victims`.
+ *     3 reassign  (same launch) claimant j < take gets victims[j]: the row's old state loses it (row_of_state[old] = -1),
+ *                 row_state, row_of_state, row_stamp = epoch and work entry j are written.  Claimants j >= take get
+ *                 nothing: row_of_state back to -1, counters[2] = 1, nothing else written for them.
+ *     4 fill      work entries [0, take) by the fill of glb_dfa_fill_masks / glb_dfa_fill_weights (grid sized by
+ *                 dfa.max_work)
+ *     5 ids       out_rows as glb_dfa_mask_ids writes them (`done` included); a state left without a row gets 0
+ *     6 epoch     epoch += 1 (it stops at 2^31 - 1: from then on no row is a candidate and every claimant overflows),
+ *                 ecounters[0] = ecounters[1] = 0
+ * Row ids are valid until the next serve call on the bank (stream order).  Which state gets which row depends on the
+ * atomics' order; which rows may be taken, how many, and every row's contents do not.  GLB_EINVAL before any launch,
+ * buffers untouched: struct_size of either block wrong, a null table, capacity < 3, a float bank with wbank_ld < vocab or
+ * one of its tables null, and what glb_dfa_mask_ids / glb_dfa_fill_masks refuse.  Every index read from device memory
+ * (states, rows, list entries, counts) is range-checked; nothing synchronises or allocates; the launches may be captured.
+ */
+#define GLB_DFA_EVICT_COUNTERS 4
+typedef struct glb_dfa_evict_args {
+  uint32_t struct_size; /* sizeof(glb_dfa_evict_args) - ABI guard */
+  glb_dfa_args dfa;     /* its own struct_size set too */
+  const float *arc_logw;   /* [n_states, 256]; a bit bank: null */
+  const float *final_logw; /* [n_states]; a bit bank: null */
+  float *wbank;            /* [dfa.capacity, wbank_ld]; a bit bank: null */
+  int64_t wbank_ld;
+  int32_t *row_state; /* [capacity] */
+  int32_t *row_stamp; /* [capacity] */
+  int32_t *claimants; /* [capacity] */
+  int32_t *victims;   /* [capacity] */
+  int32_t *ecounters; /* [GLB_DFA_EVICT_COUNTERS] */
+  int32_t *epoch;     /* [1] */
+} glb_dfa_evict_args;
+int glb_dfa_evict_bank_init(const glb_dfa_evict_args *args, void *hip_stream);
+int glb_dfa_evict_serve(const glb_dfa_evict_args *args, void *hip_stream);
+
 /* Philox4x32-10 block function, exposed so hosts can reproduce the device draws. */
 void glb_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 
