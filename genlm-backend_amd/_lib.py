@@ -298,6 +298,21 @@ class DfaEvictArgs(C.Structure):
     ]
 
 
+DFA_PUSH_STATUS = 8  # GLB_DFA_PUSH_STATUS: sweeps performed, converged, flags, sweeps of the last call, three marks, unused
+DFA_PUSH_LOG, DFA_PUSH_MAX = 0, 1
+
+
+class DfaPushArgs(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("n_states", C.c_int32), ("start", C.c_int32), ("semiring", C.c_int32),
+        ("delta", C.c_void_p), ("arc_logw", C.c_void_p), ("final_logw", C.c_void_p),
+        ("beta", C.c_void_p), ("scratch", C.c_void_p), ("arc_out", C.c_void_p), ("final_out", C.c_void_p),
+        ("status", C.c_void_p),
+        ("sweeps", C.c_int32), ("restart", C.c_int32), ("tol", C.c_float),
+    ]
+
+
 # every symbol include/glb.h declares: name -> (restype, argtypes)
 _vp, _i32, _i64, _f32, _sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_size_t
 SYMBOLS = {
@@ -388,6 +403,8 @@ SYMBOLS = {
     "glb_dfa_weight_bank_rows": (_i64, [_sz, _i64, _i64]),
     "glb_dfa_evict_bank_init": (C.c_int, [C.POINTER(DfaEvictArgs), _vp]),
     "glb_dfa_evict_serve": (C.c_int, [C.POINTER(DfaEvictArgs), _vp]),
+    "glb_dfa_backward": (C.c_int, [C.POINTER(DfaPushArgs), _vp]),
+    "glb_dfa_push_weights": (C.c_int, [C.POINTER(DfaPushArgs), _vp]),
     "glb_philox4x32_10": (None, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
 }
 

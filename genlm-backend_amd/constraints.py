@@ -166,6 +166,19 @@ class DeviceConstraint:
                      (`check()` raises when a single call asked for more).  A bank that holds every state (S + 2 rows)
                      never evicts and takes the path of "error".
 
+    push             None (default): the automaton's weights are served as they are.  "log" / "max" (a `ByteWFSA` only): the
+                     weights are pushed toward the start state on the device before anything is served (include/glb.h
+                     glb_dfa_backward / glb_dfa_push_weights).  `backward` (float32 [S] device tensor) holds
+                     beta[s], the semiring sum ("log": logsumexp, "max": the best) over all accepted byte strings from s;
+                     every arc becomes arc + beta[next] - beta[s], every final weight final - beta[s].  An accepted
+                     string then weighs what it weighed minus `start_logw` = beta[start], but every state's row carries
+                     the look-ahead: a particle sees the weight of a branch when it enters it, not at EOS.  `DeviceSIS`
+                     starts its particles at `start_logw`; `push_stats()`, `pushed_wfsa()` are for inspection.
+    push_tol         "log": the sweeps stop when no state moved by more than push_tol * max(1, |beta|); the default 2^-20 is
+                     four float32 ulps, above the one-ulp oscillation of a converged float32 iteration.
+    push_max_sweeps  ValueError when the backward weights have not converged after this many sweeps (or, under "max",
+                     after S + 1): the weights do not sum - a cycle of total mass >= 1 under "log".
+
     Lifetime of row ids: the ids a `mask_rows` call returns are valid until the next `mask_rows` / `warm` call on this
     constraint - under "evict" that call may hand their rows to other states.  Stream order makes this safe for `DeviceSIS`
     and `batch_next_token_step_device`: each makes one `mask_rows` call a step and enqueues the step that reads the ids
@@ -177,9 +190,19 @@ class DeviceConstraint:
     as `MASK_F32` in either form of the step; everything else keeps its meaning.
     """
 
-    def __init__(self, llm_or_engine, dfa, byte_vocab, eos_id, skip_ids=None, mask_bank_bytes=256 << 20, on_full="error"):
+    def __init__(self, llm_or_engine, dfa, byte_vocab, eos_id, skip_ids=None, mask_bank_bytes=256 << 20, on_full="error",
+                 push=None, push_tol=2.0 ** -20, push_max_sweeps=4096):
         if on_full not in ("error", "evict"):
             raise ValueError(f'on_full must be "error" or "evict", got {on_full!r}')
+        if push not in (None, "log", "max"):
+            raise ValueError(f'push must be None, "log" or "max", got {push!r}')
+        if push is not None:
+            if not isinstance(dfa, ByteWFSA):
+                raise ValueError(f"push={push!r} needs a ByteWFSA: a ByteDFA has no weights to push")
+            if not float(push_tol) >= 0.0:
+                raise ValueError(f"push_tol must be >= 0, got {push_tol!r}")
+            if isinstance(push_max_sweeps, bool) or not isinstance(push_max_sweeps, (int, np.integer)) or push_max_sweeps < 1:
+                raise ValueError(f"push_max_sweeps must be an int >= 1, got {push_max_sweeps!r}")
         import torch
 
         self.on_full = on_full
@@ -210,6 +233,9 @@ class DeviceConstraint:
         self.weighted = isinstance(dfa, ByteWFSA)
         if self.weighted:
             self._arc_logw, self._final_logw = up(dfa.arc_logw), up(dfa.final_logw)
+        self.push, self.backward, self.start_logw, self._push_sweeps = push, None, 0.0, 0
+        if push is not None:
+            self._push_weights(float(push_tol), int(push_max_sweeps))
         # The bank's kind, decided here once: a row's elements (bit words, or with weights the floats of a 256-byte aligned row),
         # how many of them a caller's bank needs, the step's mask kind, the library's calls and the argument block they take
         (self._bank_dtype, self.row_elems, self._row_need, self._mask_kind, bank_rows, self._init, self._fill, self._bank_args) = \
@@ -225,6 +251,55 @@ class DeviceConstraint:
         self._row_of_state = torch.empty(dfa.n_states, dtype=torch.int32, device=self.dev)
         self._counters = torch.zeros(_lib.DFA_COUNTERS, dtype=torch.int32, device=self.dev)
         self._set_bank(torch.zeros((rows, self.row_elems), dtype=self._bank_dtype, device=self.dev))
+
+    # ---- weight pushing ------------------------------------------------------------------------------------------------
+    _PUSH_BATCH = 64  # sweeps enqueued between two reads of the status words
+
+    def _push_weights(self, tol, max_sweeps):
+        """Backward weights by Jacobi sweeps on the device (glb_dfa_backward, in batches; the stop rule is the device's, the
+        host reads three words a batch), then the automaton reweighted by them (glb_dfa_push_weights): `_arc_logw` /
+        `_final_logw` become the pushed tables, everything downstream serves them as it serves any `ByteWFSA`."""
+        import torch
+
+        S = self.dfa.n_states
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=self.dev)
+        beta, scratch, arc_out, final_out = f32(S), f32(S), f32(S, 256), f32(S)
+        status = torch.zeros(_lib.DFA_PUSH_STATUS, dtype=torch.int32, device=self.dev)
+        p = _lib.DfaPushArgs()
+        p.struct_size = C.sizeof(_lib.DfaPushArgs)
+        p.n_states, p.start = S, self.dfa.start
+        p.semiring = _lib.DFA_PUSH_LOG if self.push == "log" else _lib.DFA_PUSH_MAX
+        p.delta, p.arc_logw, p.final_logw = self._delta.data_ptr(), self._arc_logw.data_ptr(), self._final_logw.data_ptr()
+        p.beta, p.scratch, p.arc_out, p.final_out = beta.data_ptr(), scratch.data_ptr(), arc_out.data_ptr(), final_out.data_ptr()
+        p.status, p.tol, p.restart = status.data_ptr(), tol, 1
+        sweeps = converged = flags = 0
+        while not converged and not flags and sweeps < max_sweeps and not (self.push == "max" and sweeps > S + 1):
+            p.sweeps = min(self._PUSH_BATCH, max_sweeps - sweeps)
+            self._call("glb_dfa_backward", p)
+            p.restart = 0
+            sweeps, converged, flags = status[:3].tolist()
+        if flags or not converged or (self.push == "max" and sweeps > S + 1):
+            raise ValueError(f"the automaton's weights do not sum: the backward weights "
+                             f"{'overflowed' if flags else 'had not converged'} after {sweeps} sweeps under push={self.push!r} "
+                             '(under "log": a cycle of total mass >= 1; under "max": a cycle of positive weight).  '
+                             'push="max" needs only that no cycle gains weight; push=None serves the weights as they are.')
+        p.sweeps = 1
+        self._call("glb_dfa_push_weights", p)
+        self._arc_logw, self._final_logw, self.backward, self._push_sweeps = arc_out, final_out, beta, sweeps
+        self.start_logw = float(beta[self.dfa.start].item())
+
+    def push_stats(self):
+        """{"semiring", "sweeps"}: what `push` was (None: nothing pushed) and the Jacobi sweeps the backward weights took,
+        the one that found nothing moving included."""
+        return {"semiring": self.push, "sweeps": self._push_sweeps}
+
+    def pushed_wfsa(self):
+        """A host `ByteWFSA` of the weights this constraint serves (the pushed ones; under push=None the automaton's own),
+        for inspection: the arcs into states that are not live weigh -inf and are gone from its `delta` (copies the tables
+        from the device)."""
+        if not self.weighted:
+            raise ValueError("a ByteDFA has no weights")
+        return ByteWFSA(self.dfa.delta, self._arc_logw.cpu().numpy(), self._final_logw.cpu().numpy(), self.dfa.start)
 
     # ---- the bank ------------------------------------------------------------------------------------------------------
     def _set_bank(self, bank):

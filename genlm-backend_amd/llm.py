@@ -1074,7 +1074,9 @@ class AsyncAmdLM(AsyncLM):
         `constraint` (a `constraints.DeviceConstraint`, exclusive with `mask_ids`): context i's mask is that of the automaton
         state after tokens[i, prompt_lengths[i]:lengths[i]) (`prompt_lengths` int32 [n], None: zeros), recomputed here - the
         call keeps no state; the registered masks are not used.  Over a `constraints.ByteWFSA` the state's row of token
-        log-weights is added to the log-probabilities (the bank handed over as float masks)."""
+        log-weights is added to the log-probabilities (the bank handed over as float masks).  Under a constraint with
+        pushed weights (`push="log"` / `"max"`) the rows are the pushed ones and so is the logZ returned: the call is
+        stateless and adds no constant - a caller that accumulates weights starts them at `constraint.start_logw`."""
         if constraint is not None and mask_ids is not None:
             raise ValueError("give mask_ids (registered masks) or constraint (masks made on the device), not both")
         if tokens.dim() != 2 or tokens.dtype != torch.int32 or lengths.dtype != torch.int32 or lengths.numel() != tokens.shape[0]:

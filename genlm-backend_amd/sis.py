@@ -203,7 +203,9 @@ class DeviceSIS:
                      backend's registered masks are not used.
                      Over a `constraints.ByteWFSA` the state's row holds token log-weights, added to the log-probabilities
                      (logZ = logsumexp(log_softmax(x) + w), the token drawn from that); a particle made to end also
-                     takes its state's final weight.
+                     takes its state's final weight.  With pushed weights (`DeviceConstraint(..., push=...)`) every
+                     particle starts at log-weight `constraint.start_logw`, so a finished particle weighs what it weighs
+                     without pushing and the estimate of the normalising constant is unchanged.
     force_collectives  run the collectives of the multi-rank path (all-gather of log-weights / token matrices, the
                      set-up reductions) through `dist` even when world == 1: a one-rank "nccl" group exercises the RCCL
                      code of an 8-GPU run on a single GPU.
@@ -317,8 +319,9 @@ class DeviceSIS:
         self.prompt_len = self._prompt_len0.clone()
         self.lengths = self.prompt_len.clone()
         self.active = torch.ones(self.N, dtype=torch.int32, device=self.dev)
-        self.log_weights = torch.zeros(self.N, dtype=torch.float32, device=self.dev)
-        self.states = self.constraint.states0(self.N) if self.constraint is not None else None  # automaton state per particle
+        # (a constraint with pushed weights serves every path's weight minus beta[start]: the particles start with that constant)
+        self.log_weights = torch.full((self.N,), getattr(self.constraint, "start_logw", 0.0), dtype=torch.float32, device=self.dev)
+        self.states =self.constraint.states0(self.N) if self.constraint is not None else None  # automaton state per particle
         self.t = 0
         self.max_len_now = self.max_prompt
         self.last_stats = None

@@ -1080,6 +1080,60 @@ typedef struct glb_dfa_evict_args {
 int glb_dfa_evict_bank_init(const glb_dfa_evict_args *args, void *hip_stream);
 int glb_dfa_evict_serve(const glb_dfa_evict_args *args, void *hip_stream);
 
+/*
+ * Weight pushing: the backward weights of a weighted byte automaton and the automaton reweighted by them,
+ * made on the device.  beta[s] is the semiring sum of the weights of all accepted byte strings from s - the weighted form
+ * of `live` - and the pushed automaton
+ *   arc_out[s][b] = (arc_logw[s][b] + beta[delta[s][b]]) - beta[s]      final_out[s] = final_logw[s] - beta[s]
+ * (float32, in this order; everything of a state with beta[s] = -inf is -inf, and so is an arc delta does not have: -1 or
+ * a destination outside [0, n_states)) weighs every accepted string what it weighed minus beta[start], with the look-ahead
+ * in every state's row: under GLB_DFA_PUSH_LOG a live state's arcs and final weight sum to one, under GLB_DFA_PUSH_MAX
+ * their maximum is 0.  The block stands alone: no vocabulary, bank or work list.
+ *   glb_dfa_backward      `restart` != 0: beta = final_logw and status = 0 first.  Then `sweeps` launches, launch j reading
+ *                         beta_k from `beta` (j even) or `scratch` (j odd) and writing beta_{k+1} to the other - never in
+ *                         place:   beta_{k+1}[s] = final_logw[s] (+) (+)_b (arc_logw[s][b] + beta_k[delta[s][b]])
+ *                         (+) = max under MAX; under LOG m + log(sum exp(x - m)), m the maximum of the 257 terms, the sum in
+ *                         one fixed order (a lane's four bytes l, l + 64, l + 128, l + 192 pairwise, a butterfly over the
+ *                         64 lanes, the final weight's term last); m = -inf gives exactly -inf.  A result depends on the
+ *                         inputs alone.  A sweep is marked changed when some state moved: new != old under MAX; under LOG
+ *                         |new - old| > tol * max(1, |new|) (-inf to -inf: no change).  The launch after a sweep that did
+ *                         not change leaves at once, and so does every later one of the call and of later calls without
+ *                         `restart`.  The call's last launch copies `scratch` to `beta` when the last sweep performed wrote
+ *                         there, so `beta` holds the result whenever a call's work is done, and writes status:
+ *                           [0] sweeps performed since the restart   [1] converged: the last sweep performed did not change
+ *                           [2] flags, sticky: bit 0 - some sweep produced +inf or NaN (the weights do not sum)
+ *                           [3] sweeps performed by the last call    [4 .. 6] the sweeps' marks, zero between calls   [7] unused
+ *                         Marks are plain stores of 1 by the waves that saw a change, into three rotating words; nothing
+ *                         is counted with atomics.  A block never restarted has no meaning: the first call sets `restart`.
+ *   glb_dfa_push_weights  arc_out / final_out from `beta` by the formulas above (scratch and status are not touched).
+ * GLB_EINVAL before any launch, buffers untouched, for both calls: struct_size wrong, n_states < 1, start outside
+ * [0, n_states), an unknown semiring, sweeps < 1, tol negative or NaN, and a null table among those the call uses (backward:
+ * delta, arc_logw, final_logw, beta, scratch, status; push_weights: delta, arc_logw, final_logw, beta, arc_out, final_out).
+ * Every destination read from `delta` is range-checked; nothing synchronises or allocates: the host reads `status` between
+ * calls.
+ */
+#define GLB_DFA_PUSH_STATUS 8
+#define GLB_DFA_PUSH_LOG 0
+#define GLB_DFA_PUSH_MAX 1
+typedef struct glb_dfa_push_args {
+  uint32_t struct_size; /* sizeof(glb_dfa_push_args) - ABI guard */
+  int32_t n_states, start;
+  int32_t semiring;        /* GLB_DFA_PUSH_LOG / GLB_DFA_PUSH_MAX */
+  const int32_t *delta;    /* [n_states, 256] */
+  const float *arc_logw;   /* [n_states, 256] */
+  const float *final_logw; /* [n_states] */
+  float *beta;             /* [n_states], out */
+  float *scratch;          /* [n_states] */
+  float *arc_out;          /* [n_states, 256] */
+  float *final_out;        /* [n_states] */
+  int32_t *status;         /* [GLB_DFA_PUSH_STATUS] */
+  int32_t sweeps;          /* launches of this call */
+  int32_t restart;
+  float tol;
+} glb_dfa_push_args;
+int glb_dfa_backward(const glb_dfa_push_args *args, void *hip_stream);
+int glb_dfa_push_weights(const glb_dfa_push_args *args, void *hip_stream);
+
 /* Philox4x32-10 block function, exposed so hosts can reproduce the device draws. */
 void glb_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 
