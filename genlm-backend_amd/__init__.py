@@ -8,7 +8,7 @@ requires the built library and a HIP device and raises otherwise (no CPU fallbac
 from . import _lib  # noqa: F401
 from ._lib import GlbError, LIB_PATH  # noqa: F401
 
-__all__ = ["GlbError", "LIB_PATH", "load_model_by_name", "AsyncAmdLM", "HipEngine", "ByteDFA", "ByteWFSA", "DeviceConstraint"]
+__all__ = ["GlbError", "LIB_PATH", "load_model_by_name", "AsyncAmdLM", "HipEngine", "ByteDFA", "ByteWFSA", "DeviceConstraint", "minimize"]
 
 
 def __getattr__(name):
@@ -18,7 +18,7 @@ def __getattr__(name):
     if name in ("load_model_by_name", "AsyncAmdLM", "AsyncLM"):
         from . import llm
         return getattr(llm, name)
-    if name in ("ByteDFA", "ByteWFSA", "DeviceConstraint"):
+    if name in ("ByteDFA", "ByteWFSA", "DeviceConstraint", "minimize"):
         from . import constraints
         return getattr(constraints, name)
     raise AttributeError(name)

@@ -313,6 +313,24 @@ class DfaPushArgs(C.Structure):
     ]
 
 
+DFA_MIN_STATUS = 8  # GLB_DFA_MIN_STATUS: rounds performed, converged, flags, classes, three rotating counts, rounds of the last call
+
+
+class DfaMinArgs(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("n_states", C.c_int32),
+        ("delta", C.c_void_p), ("keep", C.c_void_p), ("final_bits", C.c_void_p), ("arc_bits", C.c_void_p),
+        ("cls", C.c_void_p), ("scratch", C.c_void_p),
+        ("table", C.c_void_p), ("table_slots", C.c_int64),
+        ("status", C.c_void_p),
+        ("rounds", C.c_int32), ("restart", C.c_int32),
+        ("new_id", C.c_void_p), ("rep", C.c_void_p), ("n_new", C.c_int32),
+        ("arc_logw", C.c_void_p), ("final_logw", C.c_void_p), ("accepting", C.c_void_p),
+        ("delta_out", C.c_void_p), ("arc_out", C.c_void_p), ("final_out", C.c_void_p), ("accepting_out", C.c_void_p),
+    ]
+
+
 # every symbol include/glb.h declares: name -> (restype, argtypes)
 _vp, _i32, _i64, _f32, _sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_size_t
 SYMBOLS = {
@@ -405,6 +423,8 @@ SYMBOLS = {
     "glb_dfa_evict_serve": (C.c_int, [C.POINTER(DfaEvictArgs), _vp]),
     "glb_dfa_backward": (C.c_int, [C.POINTER(DfaPushArgs), _vp]),
     "glb_dfa_push_weights": (C.c_int, [C.POINTER(DfaPushArgs), _vp]),
+    "glb_dfa_refine": (C.c_int, [C.POINTER(DfaMinArgs), _vp]),
+    "glb_dfa_quotient": (C.c_int, [C.POINTER(DfaMinArgs), _vp]),
     "glb_philox4x32_10": (None, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
 }
 

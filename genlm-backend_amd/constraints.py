@@ -84,6 +84,38 @@ class ByteDFA:
             acc[cur] = True
         return cls(np.stack(rows), np.array(acc, np.bool_), 0)
 
+    @classmethod
+    def from_regex(cls, pattern, max_states=65536):
+        """The automaton of a regular expression over bytes: accepts exactly the byte strings `d` for which
+        `re.compile(pattern).fullmatch(d)` matches, `pattern` read as Python's `re` reads a BYTES pattern without flags (a
+        `str` is encoded as UTF-8 first: a non-ASCII character is the sequence of its bytes, and a quantifier behind it
+        repeats the last byte).  Supported: literals, the escapes \\\\ \\n \\t \\r \\xHH and escaped punctuation, `.` (any byte
+        but 0x0A), classes [...] with ranges and negation, \\d \\D \\w \\W \\s \\S (ASCII) inside and outside classes, groups
+        (...) and (?:...), alternation, and the quantifiers * + ? {m} {m,} {m,n} {,n} with bounds up to 1000.  Everything
+        else - anchors, backreferences, lookaround, lazy and possessive quantifiers, inline flags, named groups, \\b \\B \\A
+        \\Z - raises ValueError naming the construct and its position, and so does a subset construction that passes
+        `max_states`.  Start state 0; the result is not minimised (`minimize`, `DeviceConstraint(minimize=True)`).  Host
+        only: a Thompson automaton and its subset construction."""
+        if isinstance(pattern, str):
+            pattern = pattern.encode("utf-8")
+        if isinstance(max_states, bool) or not isinstance(max_states, (int, np.integer)) or max_states < 1:
+            raise ValueError(f"max_states must be an int >= 1, got {max_states!r}")
+        delta, accepting = _regex_dfa(bytes(pattern), int(max_states))
+        return cls(delta, accepting, 0)
+
+    @property
+    def reachable(self):
+        """bool [S]: the states some byte string reaches from `start` (a frontier search, a NumPy step per depth)."""
+        seen = np.zeros(self.n_states, np.bool_)
+        seen[self.start] = True
+        frontier = np.array([self.start], np.int64)
+        while frontier.size:
+            nxt = np.unique(self.delta[frontier])
+            nxt = nxt[nxt >= 0]
+            frontier = nxt[~seen[nxt]]
+            seen[frontier] = True
+        return seen
+
     def accepts(self, data):
         s = self.start
         for b in bytes(data):
@@ -91,6 +123,296 @@ class ByteDFA:
             if s < 0:
                 return False
         return bool(self.accepting[s])
+
+
+# ---- the regex compiler (ByteDFA.from_regex) -----------------------------------------------------------------------------------
+_REGEX_MAX_BOUND = 1000
+
+
+def _byteset(*items):
+    s = np.zeros(256, np.bool_)
+    for it in items:
+        if isinstance(it, tuple):
+            s[it[0]:it[1] + 1] = True
+        else:
+            s[it] = True
+    return s
+
+
+_SHORTHAND = {ord("d"): _byteset((48, 57)), ord("w"): _byteset((48, 57), (65, 90), (97, 122), 95), ord("s"): _byteset((9, 13), 32)}
+_ESCAPED = {ord("n"): 10, ord("t"): 9, ord("r"): 13}
+_REFUSED_ESCAPES = {ord("b"): "the word boundary \\b", ord("B"): "the word boundary \\B", ord("A"): "the anchor \\A",
+                    ord("Z"): "the anchor \\Z"}
+
+
+class _RegexParser:
+    """Recursive descent over a bytes pattern into a tree of ("set", bool[256]) / ("cat", [nodes]) / ("alt", [nodes]) /
+    ("rep", node, m, n or None)."""
+
+    def __init__(self, pattern):
+        self.p, self.i = pattern, 0
+
+    def fail(self, what, at=None):
+        raise ValueError(f"from_regex: {what} at position {self.i if at is None else at} of {self.p!r} is not supported")
+
+    def peek(self):
+        return self.p[self.i] if self.i < len(self.p) else None
+
+    def parse(self):
+        node = self.alternation()
+        if self.i < len(self.p):
+            self.fail("an unbalanced ')'")
+        return node
+
+    def alternation(self):
+        branches = [self.sequence()]
+        while self.peek() == ord("|"):
+            self.i += 1
+            branches.append(self.sequence())
+        return branches[0] if len(branches) == 1 else ("alt", branches)
+
+    def sequence(self):
+        items = []
+        while self.peek() is not None and self.peek() not in b"|)":
+            at = self.i
+            atom = self.atom()
+            q = self.quantifier()
+            if q is not None:
+                if atom is None:
+                    self.fail("a quantifier with nothing to repeat", at)
+                nxt = self.peek()
+                if nxt == ord("?"):
+                    self.fail("a lazy quantifier")
+                if nxt == ord("+"):
+                    self.fail("a possessive quantifier")
+                if nxt == ord("*") or (nxt == ord("{") and self.quantifier(probe=True)):
+                    self.fail("a repeated quantifier")
+                atom = ("rep", atom, q[0], q[1])
+            if atom is not None:
+                items.append(atom)
+        return ("cat", items)
+
+    def quantifier(self, probe=False):
+        """(m, n or None) when a quantifier stands here (consumed unless `probe`), else None; a '{' that opens no
+        quantifier is a literal, as in `re`."""
+        c, here = self.peek(), self.i
+        if c is None or c not in b"*+?{":
+            return None
+        if c != ord("{"):
+            if not probe:
+                self.i += 1
+            return {ord("*"): (0, None), ord("+"): (1, None), ord("?"): (0, 1)}[c]
+        j = here + 1
+        lo = hi = b""
+        while j < len(self.p) and self.p[j] in b"0123456789":
+            lo, j = lo + self.p[j:j + 1], j + 1
+        if j < len(self.p) and self.p[j] == ord(","):
+            j += 1
+            while j < len(self.p) and self.p[j] in b"0123456789":
+                hi, j = hi + self.p[j:j + 1], j + 1
+            comma = True
+        else:
+            hi, comma = lo, False
+        if j >= len(self.p) or self.p[j] != ord("}") or (not comma and not lo):
+            return None  # not a quantifier: '{' is a literal
+        m, n = int(lo) if lo else 0, int(hi) if hi else None
+        if m > _REGEX_MAX_BOUND or (n is not None and n > _REGEX_MAX_BOUND):
+            self.fail(f"a repetition bound above {_REGEX_MAX_BOUND}", here)
+        if n is not None and n < m:
+            self.fail("a repetition whose maximum lies below its minimum", here)
+        if not probe:
+            self.i = j + 1
+        return (m, n)
+
+    def atom(self):
+        """A node, or None where a quantifier stands with nothing before it."""
+        c, at = self.peek(), self.i
+        if c in b"*+?" or (c == ord("{") and self.quantifier(probe=True)):
+            return None
+        self.i += 1
+        if c == ord("("):
+            if self.peek() == ord("?"):
+                nxt = self.p[self.i + 1:self.i + 3]
+                if nxt[:1] != b":":
+                    kinds = [(b"P<", "a named group"), (b"P=", "a backreference"), (b"=", "lookaround"), (b"!", "lookaround"),
+                             (b"<=", "lookaround"), (b"<!", "lookaround"), (b"#", "a comment group"), (b"(", "a conditional group"),
+                             (b">", "an atomic group")]
+                    self.fail(next((name for head, name in kinds if nxt.startswith(head)), "an inline flag or group extension"), at)
+                self.i += 2
+            node = self.alternation()
+            if self.peek() != ord(")"):
+                self.fail("an unbalanced '('", at)
+            self.i += 1
+            return node
+        if c == ord("["):
+            return ("set", self.char_class(at))
+        if c == ord("."):
+            s = np.ones(256, np.bool_)
+            s[10] = False
+            return ("set", s)
+        if c == ord("^") or c == ord("$"):
+            self.fail(f"the anchor {chr(c)}", at)
+        if c == ord("\\"):
+            return ("set", self.escape(at, in_class=False))
+        return ("set", _byteset(c))
+
+    def escape(self, at, in_class):
+        """The byte set of the escape whose backslash stands at `at` (self.i is behind the backslash)."""
+        c = self.peek()
+        if c is None:
+            self.fail("a trailing backslash", at)
+        self.i += 1
+        if (c | 32) in _SHORTHAND:
+            s = _SHORTHAND[c | 32]
+            return s.copy() if c & 32 else ~s
+        if c in _ESCAPED:
+            return _byteset(_ESCAPED[c])
+        if c == ord("x"):
+            digits = self.p[self.i:self.i + 2]
+            if len(digits) != 2 or any(d not in b"0123456789abcdefABCDEF" for d in digits):
+                self.fail("an incomplete \\x escape", at)
+            self.i += 2
+            return _byteset(int(digits, 16))
+        if c in _REFUSED_ESCAPES:
+            self.fail(_REFUSED_ESCAPES[c], at)
+        if c in b"0123456789":
+            self.fail("a backreference or octal escape", at)
+        if c < 128 and chr(c).isalpha():
+            self.fail(f"the escape \\{chr(c)}", at)
+        return _byteset(c)  # escaped punctuation (and bytes >= 0x80): the byte itself
+
+    def char_class(self, at):
+        s = np.zeros(256, np.bool_)
+        negate = self.peek() == ord("^")
+        if negate:
+            self.i += 1
+        first = True
+        while True:
+            c, here = self.peek(), self.i
+            if c is None:
+                self.fail("an unterminated character class", at)
+            self.i += 1
+            if c == ord("]") and not first:
+                break
+            first = False
+            lo = self.escape(here, in_class=True) if c == ord("\\") else _byteset(c)
+            if self.peek() == ord("-") and self.i + 1 < len(self.p) and self.p[self.i + 1] != ord("]"):
+                self.i += 1
+                c2, here2 = self.peek(), self.i
+                self.i += 1
+                hi = self.escape(here2, in_class=True) if c2 == ord("\\") else _byteset(c2)
+                if lo.sum() != 1 or hi.sum() != 1 or int(np.argmax(hi)) < int(np.argmax(lo)):
+                    self.fail("a bad character range", here)
+                s[int(np.argmax(lo)):int(np.argmax(hi)) + 1] = True
+            else:
+                s |= lo
+        return ~s if negate else s
+
+
+class _Nfa:
+    """A Thompson automaton: eps[i] the states behind state i's empty arcs, arc[i] its one (byte set, target) or None."""
+
+    def __init__(self, limit):
+        self.eps, self.arc, self.limit = [], [], limit
+
+    def state(self):
+        if len(self.eps) >= self.limit:
+            raise ValueError("from_regex: the pattern's Thompson automaton alone passes 8 * max_states + 4096 states")
+        self.eps.append([])
+        self.arc.append(None)
+        return len(self.eps) - 1
+
+    def build(self, node):
+        """(first, last) of a fragment for `node`."""
+        kind = node[0]
+        if kind == "set":
+            a, b = self.state(), self.state()
+            self.arc[a] = (node[1], b)
+            return a, b
+        if kind == "cat":
+            a = b = self.state()
+            for item in node[1]:
+                f, l = self.build(item)
+                self.eps[b].append(f)
+                b = l
+            return a, b
+        if kind == "alt":
+            a, b = self.state(), self.state()
+            for item in node[1]:
+                f, l = self.build(item)
+                self.eps[a].append(f)
+                self.eps[l].append(b)
+            return a, b
+        _, inner, m, n = node
+        a = b = self.state()
+        for _ in range(m):
+            f, l = self.build(inner)
+            self.eps[b].append(f)
+            b = l
+        end = self.state()
+        if n is None:  # a loop: zero or more further copies
+            f, l = self.build(inner)
+            self.eps[b] += [f, end]
+            self.eps[l] += [f, end]
+        else:  # n - m optional copies in a row, each one's entry also the way out
+            for _ in range(n - m):
+                f, l = self.build(inner)
+                self.eps[b] += [f, end]
+                b = l
+            self.eps[b].append(end)
+        return a, end
+
+
+def _regex_dfa(pattern, max_states):
+    """(delta int32 [S, 256], accepting bool [S]) of `pattern` by subset construction, state 0 the start."""
+    nfa = _Nfa(8 * max_states + 4096)
+    first, last = nfa.build(_RegexParser(pattern).parse())
+    n = len(nfa.eps)
+    arcs = [i for i in range(n) if nfa.arc[i] is not None]
+
+    def closure(i):
+        """The states behind empty arcs from i that matter to a subset: those with a byte arc, and `last`."""
+        seen, todo = {i}, [i]
+        while todo:
+            for v in nfa.eps[todo.pop()]:
+                if v not in seen:
+                    seen.add(v)
+                    todo.append(v)
+        return frozenset(v for v in seen if v == last or nfa.arc[v] is not None)
+
+    # bytes that no arc's set tells apart move together: one representative each
+    if arcs:
+        sets = np.stack([nfa.arc[i][0] for i in arcs])
+        _, rep, group = np.unique(sets, axis=1, return_index=True, return_inverse=True)
+        group = np.asarray(group).reshape(-1)
+    else:
+        sets, rep, group = np.zeros((0, 256), np.bool_), np.zeros(1, np.int64), np.zeros(256, np.int64)
+    by_arc = {i: (np.nonzero(sets[k][rep])[0].tolist(), closure(nfa.arc[i][1])) for k, i in enumerate(arcs)}
+    start = closure(first)
+    ids, order, rows = {start: 0}, [start], []
+    k = 0
+    while k < len(order):
+        cur = order[k]
+        k += 1
+        nxt = [set() for _ in rep]
+        for i in cur:
+            if i in by_arc:
+                groups, target = by_arc[i]
+                for g in groups:
+                    nxt[g] |= target
+        row = []
+        for t in nxt:
+            t = frozenset(t)
+            if t and t not in ids:
+                if len(order) >= max_states:
+                    raise ValueError(f"from_regex: the subset construction of {pattern!r} passes max_states={max_states}")
+                ids[t] = len(order)
+                order.append(t)
+            row.append(ids[t] if t else -1)
+        rows.append(row)
+    delta = np.asarray(rows, np.int32).reshape(len(order), len(rep))[:, group]
+    accepting = np.array([last in t for t in order], np.bool_)
+    return np.ascontiguousarray(delta), accepting
 
 
 class ByteWFSA(ByteDFA):
@@ -148,6 +470,100 @@ class ByteWFSA(ByteDFA):
         return np.float32(w + self.final_logw[s])
 
 
+# ---- minimisation (include/glb.h glb_dfa_refine / glb_dfa_quotient) -------------------------------------------------
+_MIN_BATCH = 64  # rounds enqueued between two reads of the status words
+
+
+def _minimize_on_device(eng, delta, keep, final_bits, arc_bits, arc_logw, final_logw, accepting, max_rounds):
+    """Refinement and quotient of the tables on the device (`keep` a host bool [S], the others device tensors or None).
+    Returns (new_id host int32 [S], outputs {"delta", "arc_logw", "final_logw", "accepting"} on the device, rounds).
+    Quotient states are numbered by their smallest member, in increasing order: the class of state 0 is state 0."""
+    import torch
+
+    dev, S = eng.device, delta.shape[0]
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+    slots = 1 << max(1, (2 * S - 1).bit_length())
+    cls, scratch, table = i32(S), i32(S), torch.empty(slots * 12 // 8, dtype=torch.int64, device=dev)
+    status = torch.zeros(_lib.DFA_MIN_STATUS, dtype=torch.int32, device=dev)
+    keep_d = torch.from_numpy(np.ascontiguousarray(keep, dtype=np.uint8)).to(dev)
+    p = _lib.DfaMinArgs()
+    p.struct_size, p.n_states = C.sizeof(_lib.DfaMinArgs), S
+    p.delta, p.keep, p.final_bits = delta.data_ptr(), keep_d.data_ptr(), final_bits.data_ptr()
+    p.arc_bits = None if arc_bits is None else arc_bits.data_ptr()
+    p.cls, p.scratch, p.table, p.table_slots, p.status = cls.data_ptr(), scratch.data_ptr(), table.data_ptr(), slots, status.data_ptr()
+    p.restart = 1
+    limit = S + 1 if max_rounds is None else int(max_rounds)
+    rounds = converged = flags = 0
+    while not converged and not flags and rounds < limit:
+        p.rounds = min(_MIN_BATCH, limit - rounds)
+        eng.dfa_call("glb_dfa_refine", p)
+        p.restart = 0
+        rounds, converged, flags = status[:3].tolist()
+    if flags:
+        raise RuntimeError(f"minimize: the refinement raised its flag word ({flags}: bit 0 - two different signatures shared a "
+                           f"64-bit hash; bit 1 - a key found no slot) after {rounds} rounds; nothing was merged on that ground")
+    if not converged:
+        raise RuntimeError(f"minimize: the partition was still splitting after max_rounds={limit} rounds")
+    c = cls.cpu().numpy()
+    rep = np.unique(c[c >= 0]).astype(np.int32)
+    new_id = np.where(c >= 0, np.searchsorted(rep, c), -1).astype(np.int32)
+    n_new = len(rep)
+    both = torch.from_numpy(np.concatenate([new_id, rep])).to(dev)  # (one upload)
+    out = {"delta": i32(n_new, 256), "arc_logw": None, "final_logw": None, "accepting": None}
+    p.new_id, p.rep, p.n_new, p.delta_out = both.data_ptr(), both.data_ptr() + 4 * S, n_new, out["delta"].data_ptr()
+    if arc_logw is not None:
+        out["arc_logw"] = torch.empty((n_new, 256), dtype=torch.float32, device=dev)
+        out["final_logw"] = torch.empty(n_new, dtype=torch.float32, device=dev)
+        p.arc_logw, p.final_logw = arc_logw.data_ptr(), final_logw.data_ptr()
+        p.arc_out, p.final_out = out["arc_logw"].data_ptr(), out["final_logw"].data_ptr()
+    out["accepting"] = torch.empty(n_new, dtype=torch.uint8, device=dev)
+    p.accepting, p.accepting_out = accepting.data_ptr(), out["accepting"].data_ptr()
+    eng.dfa_call("glb_dfa_quotient", p)
+    return new_id, out, rounds
+
+
+def _kept(automaton):
+    """live & reachable, and the start state whatever it is: the quotient always has one."""
+    keep = automaton.live & automaton.reachable
+    keep[automaton.start] = True
+    return keep
+
+
+def _host_quotient(automaton, new_id, out):
+    """The host automaton of the quotient tables, of `automaton`'s kind."""
+    start = int(new_id[automaton.start])
+    if isinstance(automaton, ByteWFSA):
+        return ByteWFSA(out["delta"].cpu().numpy(), out["arc_logw"].cpu().numpy(), out["final_logw"].cpu().numpy(), start)
+    return ByteDFA(out["delta"].cpu().numpy(), out["accepting"].cpu().numpy().astype(np.bool_), start)
+
+
+def minimize(llm_or_engine, automaton, max_rounds=None):
+    """(minimal, state_map): the smallest automaton that `automaton`'s labels allow, made on the device (include/glb.h
+    glb_dfa_refine / glb_dfa_quotient), and int32 [S] - every state's state in it, -1 for the states dropped
+    (those not live or not reachable from the start).  A `ByteDFA` gives the minimal `ByteDFA` of its language.  A
+    `ByteWFSA` gives the quotient by the coarsest bisimulation on (byte, weight bits): states merge where their final
+    weights and the weights of their arcs are equal bit for bit, so `path_logw` of every string is unchanged bit for bit;
+    nothing is merged within a tolerance.  Quotient states are numbered in the order of their smallest members, so a start
+    state 0 stays 0.  `max_rounds` (None: S + 1, which always suffices): RuntimeError when the partition still splits
+    after that many rounds, or when the device reports a hash collision."""
+    import torch
+
+    if not isinstance(automaton, ByteDFA):
+        raise ValueError("minimize needs a ByteDFA or a ByteWFSA")
+    if max_rounds is not None and (isinstance(max_rounds, bool) or not isinstance(max_rounds, (int, np.integer)) or max_rounds < 1):
+        raise ValueError(f"max_rounds must be None or an int >= 1, got {max_rounds!r}")
+    eng = getattr(llm_or_engine, "engine", llm_or_engine)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(eng.device)
+    delta, acc = up(automaton.delta), up(automaton.accepting.astype(np.uint8))
+    if isinstance(automaton, ByteWFSA):
+        arc, fin = up(automaton.arc_logw), up(automaton.final_logw)
+        new_id, out, _ = _minimize_on_device(eng, delta, _kept(automaton), fin, arc, arc, fin, acc, max_rounds)
+    else:
+        new_id, out, _ = _minimize_on_device(eng, delta, _kept(automaton), up(automaton.accepting.astype(np.int32)), None, None, None,
+                                             acc, max_rounds)
+    return _host_quotient(automaton, new_id, out), new_id
+
+
 class DeviceConstraint:
     """A `ByteDFA` over a vocabulary's byte strings, resident on the device.
 
@@ -179,6 +595,18 @@ class DeviceConstraint:
     push_max_sweeps  ValueError when the backward weights have not converged after this many sweeps (or, under "max",
                      after S + 1): the weights do not sum - a cycle of total mass >= 1 under "log".
 
+    minimize         False (default): the automaton is served as it is.  True: equivalent states are merged on the device
+                     before anything is served (include/glb.h glb_dfa_refine / glb_dfa_quotient) - after the
+                     push, if any, on the tables the push left.  The constraint then serves the quotient: `dfa` is the
+                     quotient's host automaton (with a push: carrying the pushed weights), and `n_states`, `start`, `live`,
+                     the bank's rows, `warm()`, eviction and `pushed_wfsa()` are the quotient's.  `source_dfa` is what
+                     the caller passed, `state_map` (int32 [S] device tensor) every source state's quotient state, -1 for
+                     the states dropped (not live, or not reachable from the start); `minimize_stats()`.  States and
+                     the ids `advance` returns are the quotient's.  `start_logw` and `backward` keep their meaning;
+                     `backward` stays indexed by the SOURCE automaton's states.  A `ByteWFSA` merges states whose weights
+                     are equal bit for bit (after a push: what weighted minimisation merges, where rounding left equal
+                     bits); every string weighs what it weighed, bit for bit.
+
     Lifetime of row ids: the ids a `mask_rows` call returns are valid until the next `mask_rows` / `warm` call on this
     constraint - under "evict" that call may hand their rows to other states.  Stream order makes this safe for `DeviceSIS`
     and `batch_next_token_step_device`: each makes one `mask_rows` call a step and enqueues the step that reads the ids
@@ -191,7 +619,7 @@ class DeviceConstraint:
     """
 
     def __init__(self, llm_or_engine, dfa, byte_vocab, eos_id, skip_ids=None, mask_bank_bytes=256 << 20, on_full="error",
-                 push=None, push_tol=2.0 ** -20, push_max_sweeps=4096):
+                 push=None, push_tol=2.0 ** -20, push_max_sweeps=4096, minimize=False):
         if on_full not in ("error", "evict"):
             raise ValueError(f'on_full must be "error" or "evict", got {on_full!r}')
         if push not in (None, "log", "max"):
@@ -203,6 +631,8 @@ class DeviceConstraint:
                 raise ValueError(f"push_tol must be >= 0, got {push_tol!r}")
             if isinstance(push_max_sweeps, bool) or not isinstance(push_max_sweeps, (int, np.integer)) or push_max_sweeps < 1:
                 raise ValueError(f"push_max_sweeps must be an int >= 1, got {push_max_sweeps!r}")
+        if not isinstance(minimize, bool):
+            raise ValueError(f"minimize must be True or False, got {minimize!r}")
         import torch
 
         self.on_full = on_full
@@ -236,6 +666,9 @@ class DeviceConstraint:
         self.push, self.backward, self.start_logw, self._push_sweeps = push, None, 0.0, 0
         if push is not None:
             self._push_weights(float(push_tol), int(push_max_sweeps))
+        self.source_dfa, self.state_map, self._min_rounds = dfa, None, 0
+        if minimize:
+            dfa = self._minimize()
         # The bank's kind, decided here once: a row's elements (bit words, or with weights the floats of a 256-byte aligned row),
         # how many of them a caller's bank needs, the step's mask kind, the library's calls and the argument block they take
         (self._bank_dtype, self.row_elems, self._row_need, self._mask_kind, bank_rows, self._init, self._fill, self._bank_args) = \
@@ -287,6 +720,31 @@ class DeviceConstraint:
         self._call("glb_dfa_push_weights", p)
         self._arc_logw, self._final_logw, self.backward, self._push_sweeps = arc_out, final_out, beta, sweeps
         self.start_logw = float(beta[self.dfa.start].item())
+
+    def _minimize(self):
+        """The tables on the device (`_delta`, and with weights `_arc_logw` / `_final_logw` as the push left them) replaced
+        by their quotient's; returns the quotient's host automaton, which becomes `dfa`."""
+        import torch
+
+        src = self.source_dfa
+        keep = _kept(src)
+        if self.weighted:
+            new_id, out, rounds = _minimize_on_device(self.eng, self._delta, keep, self._final_logw, self._arc_logw, self._arc_logw,
+                                                      self._final_logw, self._acc, None)
+            self._arc_logw, self._final_logw = out["arc_logw"], out["final_logw"]
+        else:
+            new_id, out, rounds = _minimize_on_device(self.eng, self._delta, keep, self._acc.to(torch.int32), None, None, None,
+                                                      self._acc, None)
+        self._delta, self._acc = out["delta"], out["accepting"]
+        self.dfa = _host_quotient(src, new_id, out)
+        self._live = torch.from_numpy(self.dfa.live.astype(np.uint8)).to(self.dev)
+        self.state_map, self._min_rounds = torch.from_numpy(new_id).to(self.dev), rounds
+        return self.dfa
+
+    def minimize_stats(self):
+        """{"states_in", "states_out", "rounds"}: the source automaton's states, the states served, and the refinement
+        rounds taken, the one that found nothing to split included (0: nothing was minimised)."""
+        return {"states_in": self.source_dfa.n_states, "states_out": self.dfa.n_states, "rounds": self._min_rounds}
 
     def push_stats(self):
         """{"semiring", "sweeps"}: what `push` was (None: nothing pushed) and the Jacobi sweeps the backward weights took,

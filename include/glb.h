@@ -1134,6 +1134,82 @@ typedef struct glb_dfa_push_args {
 int glb_dfa_backward(const glb_dfa_push_args *args, void *hip_stream);
 int glb_dfa_push_weights(const glb_dfa_push_args *args, void *hip_stream);
 
+/*
+ * Minimisation: the coarsest partition of an automaton's states that its labels allow, found on the device
+ * by Moore's refinement, and the quotient automaton.  The block stands alone: no vocabulary, bank or work list.  `keep` says
+ * which states take part (a host passes live & reachable).  An arc (s, b) is PRESENT when 0 <= delta[s][b] < n_states and
+ * keep[delta[s][b]]; every other arc is absent, whatever arc_bits holds there.  The result: cls[s] = -1 where !keep[s]; over
+ * the kept states `cls` is the coarsest partition in which the states of one class
+ *   - have equal final_bits,
+ *   - agree for every byte on whether the arc is present, and their present arcs lead into one class,
+ *   - and, when arc_bits is given, carry equal arc_bits on their present arcs;
+ * a class's id is its smallest member.  That partition is unique, so `cls` is one well-defined array.  Labels are compared
+ * as bit patterns: with final_bits / arc_bits the bits of a weighted automaton's float32 final_logw / arc_logw this is the
+ * coarsest bisimulation on (byte, weight bits), and the quotient by it leaves the weight of every path unchanged bit for
+ * bit - the same floats are added in the same order.  After weight pushing (above) it merges what weighted minimisation
+ * merges wherever rounding left equal bits; weights that differ in their last bit are different labels - nothing is merged
+ * within a tolerance.  An unweighted automaton: final_bits = accepting, arc_bits null.
+ *   glb_dfa_refine    `restart` != 0: first the classes by final_bits into `cls` and status = 0, status[3] their number.  Then
+ *                     `rounds` rounds, round j of the call reading the classes from `cls` (j even) or `scratch` (j odd) and
+ *                     writing the refined ones to the other - never in place.  A round is three launches: the table is
+ *                     cleared (a launch of its own); every kept state's signature - its class, the class behind each
+ *                     byte (-1: absent) and the arcs' bits - is hashed to 64 bits and the hash entered into `table` (open
+ *                     addressing; a 64-bit compare-and-swap on the key, an atomic minimum on the member); every state
+ *                     looks its hash up, compares its signature with the elected member's element by element and takes the
+ *                     member as its class.  A difference there is a hash collision: it sets flag bit 0 and the state stays
+ *                     a class of its own - never a silent merge.  Refinement only splits, so a round that leaves the
+ *                     number of classes as it was has changed nothing: it sets the converged word, and every later launch
+ *                     of the call and of later calls without `restart` leaves at once.  The call's last launch copies
+ *                     `scratch` to `cls` when the last round performed wrote there, and writes status:
+ *                       [0] rounds performed since the restart, the one that found nothing to split included
+ *                       [1] converged   [2] flags, sticky: bit 0 - a hash collision; bit 1 - a key without a slot
+ *                       [3] classes after the last round performed
+ *                       [4 .. 6] the rounds' class counts, rotating, zero between calls   [7] rounds performed by the last call
+ *                     The result does not depend on the order the atomics take: a launch ends with the same set of keys,
+ *                     each with the smallest of its states.  `table`: 12 bytes a slot (table_slots 64-bit keys, then
+ *                     table_slots int32 members), aligned to 8; its contents mean nothing between calls.
+ *   glb_dfa_quotient  row j of the outputs, j < n_new, is the row of state rep[j] relabelled: delta_out[j][b] =
+ *                     new_id[delta[rep[j]][b]] where that arc is present and the id lies in [0, n_new), else -1; arc_out
+ *                     the arc's arc_logw there, else -inf; final_out[j] = final_logw[rep[j]], accepting_out[j] =
+ *                     accepting[rep[j]].  arc_out / final_out / accepting_out may each be null (then its input may be too).
+ *                     A rep[j] outside [0, n_states) gives a row without arcs, -inf and 0.  `cls` is not read: the host
+ *                     derives new_id (every state's quotient state, -1 where dropped) and rep from it.
+ * GLB_EINVAL before any launch, buffers untouched, the field named in the message: struct_size wrong, n_states < 1, delta or
+ * keep null; refine: rounds outside [1, 65536], table_slots not a power of two or below 2 n_states, final_bits, cls, scratch,
+ * table or status null; quotient: n_new outside [1, n_states], new_id, rep or delta_out null, an output without its input.
+ * Every index read from device memory is range-checked; nothing synchronises or allocates: the host reads `status` between
+ * calls.
+ */
+#define GLB_DFA_MIN_STATUS 8
+typedef struct glb_dfa_min_args {
+  uint32_t struct_size; /* sizeof(glb_dfa_min_args) - ABI guard */
+  int32_t n_states;
+  const int32_t *delta;       /* [n_states, 256] */
+  const uint8_t *keep;        /* [n_states] */
+  const uint32_t *final_bits; /* [n_states] */
+  const uint32_t *arc_bits;   /* [n_states, 256]; unweighted: null */
+  int32_t *cls;               /* [n_states], out */
+  int32_t *scratch;           /* [n_states] */
+  void *table;                /* 12 * table_slots bytes */
+  int64_t table_slots;        /* a power of two >= 2 * n_states */
+  int32_t *status;            /* [GLB_DFA_MIN_STATUS] */
+  int32_t rounds;             /* rounds of this call */
+  int32_t restart;
+  /* glb_dfa_quotient */
+  const int32_t *new_id;      /* [n_states] */
+  const int32_t *rep;         /* [n_new] */
+  int32_t n_new;
+  const float *arc_logw;      /* [n_states, 256] or null */
+  const float *final_logw;    /* [n_states] or null */
+  const uint8_t *accepting;   /* [n_states] or null */
+  int32_t *delta_out;         /* [n_new, 256] */
+  float *arc_out;             /* [n_new, 256] or null */
+  float *final_out;           /* [n_new] or null */
+  uint8_t *accepting_out;     /* [n_new] or null */
+} glb_dfa_min_args;
+int glb_dfa_refine(const glb_dfa_min_args *args, void *hip_stream);
+int glb_dfa_quotient(const glb_dfa_min_args *args, void *hip_stream);
+
 /* Philox4x32-10 block function, exposed so hosts can reproduce the device draws. */
 void glb_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 
