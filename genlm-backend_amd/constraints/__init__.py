@@ -1,0 +1,17 @@
+"""Byte-level DFA constraints on the device (include/glb.h glb_dfa_*).
+
+`ByteDFA` is the automaton a user brings (a compiled regex, a literal set, a schema: a transition table over bytes);
+`DeviceConstraint` keeps it on the GPU beside the vocabulary's byte strings and produces what the fused step consumes:
+a bank of token bit masks, one row per automaton state that some particle has reached, and every particle's row.  States
+advance on the device from the tokens drawn; nothing crosses the host per step.
+
+`ByteWFSA` is the same automaton in the log semiring (arc and final log-weights): a `DeviceConstraint` over one
+keeps a bank of float32 rows - the token log-weights from every state reached - that the step adds to the log-probabilities.
+
+`DeviceConstraint(..., on_full="evict")` lets the bank be smaller than the automaton: a cache over the states,
+the least recently requested rows recycled and filled again on the device.
+"""
+from .automata import ByteDFA, ByteWFSA  # noqa: F401
+from .device import DeviceConstraint  # noqa: F401
+from .regex import _regex_dfa  # noqa: F401
+from .tables import DeviceTables, _kept, minimize  # noqa: F401

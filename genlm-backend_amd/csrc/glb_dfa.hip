@@ -3,9 +3,8 @@
 // per (state, 64 consecutive tokens), the 64 bits by one ballot.  Everything read from device memory is range-checked.
 // Weighted automata (glb_dfa_weight_*, glb_dfa_fill_weights): the same walk summing float32 arc weights, the
 // rows 64 consecutive floats a wave.  A bank smaller than the automaton (glb_dfa_evict_*): rows stamped with
-// the call that last asked for them, the oldest selected by one workgroup and filled again by the same fill.  Weight pushing
-// (glb_dfa_backward, glb_dfa_push_weights): Jacobi sweeps for the backward weights, a wave per state, the stop
-// rule decided on the device; then the automaton reweighted by them, elementwise.
+// the call that last asked for them, the oldest selected by one workgroup and filled again by the same fill.  (Weight
+// pushing, DESIGN.md §20: glb_dfa_push.hip; minimisation, §21: glb_dfa_min.hip.)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -144,38 +143,30 @@ __device__ inline void dfa_fill_entries(const Dfa &d, const float *arc_logw, con
   }
 }
 
-// the claim path's entries: [counters[C_FILLED], counters[C_ROWS] - 2)
-template <bool WEIGHTED>
+// The entries of the work list to fill, read by thread 0 from `counters`: the claim path's [counters[C_FILLED],
+// counters[C_ROWS] - 2); EVICT (`counters` the block's ecounters): a serve call's [0, ecounters[E_TAKEN])
+template <bool WEIGHTED, bool EVICT>
 __global__ __launch_bounds__(FILL_THREADS) void dfa_fill_kernel(Dfa d, const float *arc_logw, const float *final_logw,
                                                                std::conditional_t<WEIGHTED, float, int32_t> *bank,
                                                                int64_t bank_ld, int32_t capacity, const int32_t *work,
                                                                const int32_t *counters) {
   __shared__ int32_t range[2];
   if (threadIdx.x == 0) {
-    int32_t begin = __hip_atomic_load(&counters[C_FILLED], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    int32_t end = __hip_atomic_load(&counters[C_ROWS], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    end = (end > capacity ? capacity : end) - 2;
-    if (begin < 0) begin = 0;
-    range[0] = begin;
-    range[1] = end;
+    if constexpr (EVICT) {
+      const int32_t t = __hip_atomic_load(&counters[E_TAKEN], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      range[0] = 0;
+      range[1] = t > capacity - 2 ? capacity - 2 : t;
+    } else {
+      int32_t begin = __hip_atomic_load(&counters[C_FILLED], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      int32_t end = __hip_atomic_load(&counters[C_ROWS], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      end = (end > capacity ? capacity : end) - 2;
+      if (begin < 0) begin = 0;
+      range[0] = begin;
+      range[1] = end;
+    }
   }
   __syncthreads();
   dfa_fill_entries<WEIGHTED>(d, arc_logw, final_logw, bank, bank_ld, capacity, work, range[0], range[1]);
-}
-
-// a serve call's entries: [0, ecounters[E_TAKEN])
-template <bool WEIGHTED>
-__global__ __launch_bounds__(FILL_THREADS) void dfa_evict_fill_kernel(Dfa d, const float *arc_logw, const float *final_logw,
-                                                                     std::conditional_t<WEIGHTED, float, int32_t> *bank,
-                                                                     int64_t bank_ld, int32_t capacity, const int32_t *work,
-                                                                     const int32_t *ecounters) {
-  __shared__ int32_t taken;
-  if (threadIdx.x == 0) {
-    const int32_t t = __hip_atomic_load(&ecounters[E_TAKEN], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    taken = t > capacity - 2 ? capacity - 2 : t;
-  }
-  __syncthreads();
-  dfa_fill_entries<WEIGHTED>(d, arc_logw, final_logw, bank, bank_ld, capacity, work, 0, taken);
 }
 
 // after the fill (same stream): the filled mark moves up.  A launch of its own: a count of arrived workgroups on one word
@@ -196,9 +187,15 @@ __device__ inline int32_t dfa_mask_id(int32_t n_states, const uint8_t *accepting
   return r < 2 || r >= capacity ? 0 : r;
 }
 
-__global__ void dfa_mask_ids_kernel(int32_t n_states, const uint8_t *accepting, int64_t n, const int32_t *states,
-                                    const int32_t *done, const int32_t *row_of_state, int32_t capacity, int32_t *out) {
+// with `ecounters` and `epoch` (a serve call) the call ends here: the epoch moves on, the call's two counts go back to zero
+__global__ void dfa_mask_ids_kernel(int32_t n_states, const uint8_t *accepting, int64_t n, const int32_t *states, const int32_t *done,
+                                    const int32_t *row_of_state, int32_t capacity, int32_t *out, int32_t *ecounters, int32_t *epoch) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i == 0 && ecounters && epoch) {  // (no launch of this call reads either after the selection)
+    if (*epoch < 0x7fffffff) *epoch += 1;
+    ecounters[E_CLAIMANTS] = 0;
+    ecounters[E_TAKEN] = 0;
+  }
   if (i >= n) return;
   out[i] = dfa_mask_id(n_states, accepting, states[i], done && done[i], row_of_state, capacity);
 }
@@ -371,123 +368,11 @@ __global__ __launch_bounds__(SELECT_THREADS) void dfa_evict_select_kernel(int32_
   }
 }
 
-// the ids of glb_dfa_mask_ids; the call ends here: the epoch moves on, the call's two counts go back to zero
-__global__ void dfa_evict_ids_kernel(int32_t n_states, const uint8_t *accepting, int64_t n, const int32_t *states, const int32_t *done,
-                                     const int32_t *row_of_state, int32_t capacity, int32_t *out, int32_t *ecounters, int32_t *epoch) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i == 0) {  // (no launch of this call reads either after the selection)
-    if (*epoch < 0x7fffffff) *epoch += 1;
-    ecounters[E_CLAIMANTS] = 0;
-    ecounters[E_TAKEN] = 0;
-  }
-  if (i >= n) return;
-  out[i] = dfa_mask_id(n_states, accepting, states[i], done && done[i], row_of_state, capacity);
-}
-
-// ---- weight pushing (glb_dfa_backward / glb_dfa_push_weights) ------------------------------------------------------
-enum { P_SWEEPS = 0, P_CONVERGED = 1, P_FLAGS = 2, P_CALL = 3, P_MARK = 4 };  // glb_dfa_push_args.status; marks: P_MARK + {0, 1, 2}
-constexpr int PUSH_THREADS = 256;      // four waves, a state each; push_weights: the 256 arcs of one state
-constexpr int PUSH_MAX_SWEEPS = 65536; // launches one call may enqueue
-
-__global__ void dfa_backward_init_kernel(int32_t n_states, const float *final_logw, float *beta, int32_t *status) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n_states) beta[i] = final_logw[i];
-  if (i < GLB_DFA_PUSH_STATUS) status[i] = 0;
-}
-
-// the wave's 64 values combined by one fixed butterfly: every lane ends with the same bits
-template <bool MAX>
-__device__ inline float wave_combine(float x) {
-  for (int d = 32; d >= 1; d >>= 1) {
-    const float y = __shfl_xor(x, d);
-    x = MAX ? fmaxf(x, y) : x + y;
-  }
-  return x;
-}
-
-// Sweep j of a call: beta_{k+1} (dst) from beta_k (src), a wave per state.  Whether the iteration still runs is read from a
-// word no workgroup of this launch writes: the converged word (j = 0), else the mark of sweep j - 1; the marks rotate over
-// three words - this launch sets word j % 3 (plain stores of 1) and clears word (j + 1) % 3 for the next
-template <int SEMIRING>
-__global__ __launch_bounds__(PUSH_THREADS) void dfa_backward_kernel(int32_t n_states, const int32_t *delta, const float *arc_logw,
-                                                                   const float *final_logw, const float *src, float *dst,
-                                                                   int32_t *status, int32_t j, float tol) {
-  const bool go = j == 0 ? status[P_CONVERGED] == 0 : status[P_MARK + (j - 1) % 3] != 0;  // (uniform over the grid)
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    status[P_MARK + (j + 1) % 3] = 0;
-    if (go) {
-      status[P_SWEEPS] += 1;
-      status[P_CALL] = j + 1;
-    } else if (j == 0) {
-      status[P_CALL] = 0;
-    }
-  }
-  if (!go) return;
-  const int lane = (int)threadIdx.x & 63;
-  const int64_t s = (int64_t)blockIdx.x * (PUSH_THREADS / 64) + (threadIdx.x >> 6);
-  if (s >= n_states) return;  // (a whole wave)
-  const float ninf = -__builtin_inff();
-  const int32_t *drow = delta + s * 256;
-  const float *arow = arc_logw + s * 256;
-  float t[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int32_t d = drow[lane + 64 * k];
-    const float a = arow[lane + 64 * k];
-    t[k] = d >= 0 && d < n_states ? a + src[d] : ninf;
-  }
-  const float fin = final_logw[s], old = src[s];
-  const float m = fmaxf(wave_combine<true>(fmaxf(fmaxf(t[0], t[1]), fmaxf(t[2], t[3]))), fin);
-  float r = m;
-  bool changed;
-  if constexpr (SEMIRING == GLB_DFA_PUSH_LOG) {
-    if (m > ninf) {  // (m = -inf: no term is finite, and (-inf) - (-inf) is never formed)
-      const float sum = wave_combine<false>((expf(t[0] - m) + expf(t[1] - m)) + (expf(t[2] - m) + expf(t[3] - m)));
-      r = m + logf(sum + expf(fin - m));
-    }
-    changed = !(r == old) && fabsf(r - old) > tol * fmaxf(1.0f, fabsf(r));
-  } else {
-    changed = r != old;
-  }
-  if (lane == 0) {
-    dst[s] = r;
-    if (changed) status[P_MARK + j % 3] = 1;
-    if (!(r < __builtin_inff())) status[P_FLAGS] = 1;  // +inf or NaN
-  }
-}
-
-// the call's last launch: the result into `beta` when the last sweep performed wrote `scratch`; thread 0 settles the words
-__global__ void dfa_backward_end_kernel(int32_t n_states, float *beta, const float *scratch, int32_t *status) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int32_t p = status[P_CALL];  // (no thread of this launch writes it)
-  if ((p & 1) && i < n_states) beta[i] = scratch[i];
-  if (i == 0) {
-    if (p > 0) status[P_CONVERGED] = status[P_MARK + (p - 1) % 3] == 0;
-    status[P_MARK] = status[P_MARK + 1] = status[P_MARK + 2] = 0;
-  }
-}
-
-__global__ __launch_bounds__(PUSH_THREADS) void dfa_push_weights_kernel(int32_t n_states, const int32_t *delta, const float *arc_logw,
-                                                                       const float *final_logw, const float *beta, float *arc_out,
-                                                                       float *final_out) {
-  const int64_t s = blockIdx.x;
-  const int b = (int)threadIdx.x;
-  const float ninf = -__builtin_inff();
-  const float bs = beta[s];
-  const int32_t d = delta[s * 256 + b];
-  float w = ninf;
-  if (bs > ninf && d >= 0 && d < n_states) w = (arc_logw[s * 256 + b] + beta[d]) - bs;
-  arc_out[s * 256 + b] = w;
-  if (b == 0) final_out[s] = bs > ninf ? final_logw[s] - bs : ninf;
-}
-
 // NEED_ROWS: the bank's bookkeeping (capacity, row_of_state, work, counters) without its bit rows - a weight bank's calls
 constexpr int NEED_VOCAB = 1, NEED_BANK = 2, NEED_N = 4, NEED_ROWS = 8;
 
 int dfa_check(const glb_dfa_args *a, const char *what, int need) {
-  if (!a) return glb::api_fail(GLB_EINVAL, "%s: null argument block", what);
-  if (a->struct_size != sizeof(glb_dfa_args))
-    return glb::api_fail(GLB_EINVAL, "glb_dfa_args.struct_size %u != %zu (ABI mismatch)", a->struct_size, sizeof(glb_dfa_args));
+  if (const int rc = glb::block_ok(a, what, "glb_dfa_args")) return rc;
   if (a->n_states <= 0) return glb::api_fail(GLB_EINVAL, "%s: n_states %d <= 0", what, a->n_states);
   if (a->start < 0 || a->start >= a->n_states)
     return glb::api_fail(GLB_EINVAL, "%s: start %d outside [0, %d)", what, a->start, a->n_states);
@@ -514,76 +399,31 @@ Dfa dfa_of(const glb_dfa_args *a) {
   return Dfa{a->delta, a->accepting, a->live, a->n_states, a->start, a->eos_id, a->tok_bytes, a->n_bytes, a->tok_ptr, a->skip, a->vocab};
 }
 
-int launched(const char *what) {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? GLB_OK : glb::api_hip_fail(e, what);
+// a float bank and the weights it is filled from, of either block that carries them
+int float_bank_check(const float *arc_logw, const float *final_logw, const float *wbank, int64_t wbank_ld, int64_t vocab, const char *what) {
+  if (!wbank || !arc_logw || !final_logw) return glb::api_fail(GLB_EINVAL, "%s: null weight table", what);
+  if (wbank_ld < vocab) return glb::api_fail(GLB_EINVAL, "%s: wbank_ld %lld < vocab %lld", what, (long long)wbank_ld, (long long)vocab);
+  return GLB_OK;
 }
 
 int dfa_weight_check(const glb_dfa_weight_args *w, const char *what, int need) {
-  if (!w) return glb::api_fail(GLB_EINVAL, "%s: null argument block", what);
-  if (w->struct_size != sizeof(glb_dfa_weight_args))
-    return glb::api_fail(GLB_EINVAL, "glb_dfa_weight_args.struct_size %u != %zu (ABI mismatch)", w->struct_size,
-                         sizeof(glb_dfa_weight_args));
+  if (const int rc = glb::block_ok(w, what, "glb_dfa_weight_args")) return rc;
   if (const int rc = dfa_check(&w->dfa, what, need | NEED_ROWS)) return rc;
-  if (w->wbank_ld < w->dfa.vocab)
-    return glb::api_fail(GLB_EINVAL, "%s: wbank_ld %lld < vocab %lld", what, (long long)w->wbank_ld, (long long)w->dfa.vocab);
-  if (!w->arc_logw || !w->final_logw || !w->wbank) return glb::api_fail(GLB_EINVAL, "%s: null weight table", what);
-  return GLB_OK;
+  return float_bank_check(w->arc_logw, w->final_logw, w->wbank, w->wbank_ld, w->dfa.vocab, what);
 }
 
 // an evicting bank's block: the embedded block's checks (a bit bank's `bank` only where there is no float bank), then its own
 int dfa_evict_check(const glb_dfa_evict_args *e, const char *what, int need) {
-  if (!e) return glb::api_fail(GLB_EINVAL, "%s: null argument block", what);
-  if (e->struct_size != sizeof(glb_dfa_evict_args))
-    return glb::api_fail(GLB_EINVAL, "glb_dfa_evict_args.struct_size %u != %zu (ABI mismatch)", e->struct_size,
-                         sizeof(glb_dfa_evict_args));
+  if (const int rc = glb::block_ok(e, what, "glb_dfa_evict_args")) return rc;
   const bool weighted = e->wbank || e->arc_logw || e->final_logw;
   if (const int rc = dfa_check(&e->dfa, what, need | (weighted ? NEED_ROWS : NEED_BANK))) return rc;
   if (e->dfa.capacity < 3 || e->dfa.capacity > 65535)
     return glb::api_fail(GLB_EINVAL, "%s: capacity %lld outside [3, 65535]", what, (long long)e->dfa.capacity);
-  if (weighted) {
-    if (!e->wbank || !e->arc_logw || !e->final_logw) return glb::api_fail(GLB_EINVAL, "%s: null weight table", what);
-    if (e->wbank_ld < e->dfa.vocab)
-      return glb::api_fail(GLB_EINVAL, "%s: wbank_ld %lld < vocab %lld", what, (long long)e->wbank_ld, (long long)e->dfa.vocab);
-  }
+  if (weighted)
+    if (const int rc = float_bank_check(e->arc_logw, e->final_logw, e->wbank, e->wbank_ld, e->dfa.vocab, what)) return rc;
   if (!e->row_state || !e->row_stamp || !e->claimants || !e->victims || !e->ecounters || !e->epoch)
     return glb::api_fail(GLB_EINVAL, "%s: null eviction table", what);
   return GLB_OK;
-}
-
-// the block of glb_dfa_backward (`backward`) / glb_dfa_push_weights: the same checks, each call's own tables
-int dfa_push_check(const glb_dfa_push_args *p, const char *what, bool backward) {
-  if (!p) return glb::api_fail(GLB_EINVAL, "%s: null argument block", what);
-  if (p->struct_size != sizeof(glb_dfa_push_args))
-    return glb::api_fail(GLB_EINVAL, "glb_dfa_push_args.struct_size %u != %zu (ABI mismatch)", p->struct_size, sizeof(glb_dfa_push_args));
-  if (p->n_states < 1 || p->n_states > 0x7fffff00) return glb::api_fail(GLB_EINVAL, "%s: n_states %d outside [1, 2^31 - 256]", what, p->n_states);
-  if (p->start < 0 || p->start >= p->n_states)
-    return glb::api_fail(GLB_EINVAL, "%s: start %d outside [0, %d)", what, p->start, p->n_states);
-  if (p->semiring != GLB_DFA_PUSH_LOG && p->semiring != GLB_DFA_PUSH_MAX)
-    return glb::api_fail(GLB_EINVAL, "%s: semiring %d is neither GLB_DFA_PUSH_LOG nor GLB_DFA_PUSH_MAX", what, p->semiring);
-  if (p->sweeps < 1 || p->sweeps > PUSH_MAX_SWEEPS)
-    return glb::api_fail(GLB_EINVAL, "%s: sweeps %d outside [1, %d]", what, p->sweeps, PUSH_MAX_SWEEPS);
-  if (!(p->tol >= 0.0f)) return glb::api_fail(GLB_EINVAL, "%s: tol %g is negative or NaN", what, (double)p->tol);
-  if (!p->delta) return glb::api_fail(GLB_EINVAL, "%s: delta is null", what);
-  if (!p->arc_logw) return glb::api_fail(GLB_EINVAL, "%s: arc_logw is null", what);
-  if (!p->final_logw) return glb::api_fail(GLB_EINVAL, "%s: final_logw is null", what);
-  if (!p->beta) return glb::api_fail(GLB_EINVAL, "%s: beta is null", what);
-  if (backward) {
-    if (!p->scratch) return glb::api_fail(GLB_EINVAL, "%s: scratch is null", what);
-    if (!p->status) return glb::api_fail(GLB_EINVAL, "%s: status is null", what);
-  } else {
-    if (!p->arc_out) return glb::api_fail(GLB_EINVAL, "%s: arc_out is null", what);
-    if (!p->final_out) return glb::api_fail(GLB_EINVAL, "%s: final_out is null", what);
-  }
-  return GLB_OK;
-}
-
-template <int SEMIRING>
-void backward_sweeps(const glb_dfa_push_args *p, hipStream_t st) {
-  const unsigned grid = blocks_for(p->n_states, PUSH_THREADS / 64);
-  for (int32_t j = 0; j < p->sweeps; ++j)
-    hipLaunchKernelGGL(dfa_backward_kernel<SEMIRING>, dim3(grid), dim3(PUSH_THREADS), 0, st, p->n_states, p->delta, p->arc_logw,
-                       p->final_logw, j & 1 ? p->scratch : p->beta, j & 1 ? p->beta : p->scratch, p->status, j, p->tol);
 }
 
 // rows a bank of `bank_bytes` holds when one takes `row_bytes`: at most a row per state and the bank's own two
@@ -594,16 +434,27 @@ int64_t bank_rows(size_t bank_bytes, size_t row_bytes, int64_t vocab, int64_t n_
   return rows > 65535 ? 65535 : rows;
 }
 
+// rows 0 and 1 of a block's bank (bit words, or with T = float the floats of `elems` tokens), and no state with a row
+template <typename T>
+void bank_init(const glb_dfa_args *a, T *bank, int64_t ld, int64_t elems, hipStream_t st) {
+  hipLaunchKernelGGL(dfa_bank_init_kernel<T>, dim3(blocks_for(elems > a->n_states ? elems : a->n_states, 256)), dim3(256), 0, st,
+                     a->n_states, a->eos_id, a->vocab, bank, ld, elems, a->row_of_state, a->counters);
+}
+
+// the fill's grid: 256 tokens a block, at most FILL_MAX_ENTRIES work entries side by side
+dim3 fill_grid(const glb_dfa_args *a) {
+  return dim3(blocks_for(a->vocab, FILL_THREADS), (unsigned)(a->max_work < FILL_MAX_ENTRIES ? a->max_work : FILL_MAX_ENTRIES));
+}
+
 // the claimed rows filled (bit words, or with weights floats), then the filled mark moved up
 template <bool WEIGHTED, typename T>
 int fill_and_commit(const glb_dfa_args *a, const char *what, const char *launch, const float *arc_logw, const float *final_logw,
                     T *bank, int64_t bank_ld, void *stream) {
   if (a->max_work <= 0) return glb::api_fail(GLB_EINVAL, "%s: max_work %lld <= 0", what, (long long)a->max_work);
-  const unsigned gy = (unsigned)(a->max_work < FILL_MAX_ENTRIES ? a->max_work : FILL_MAX_ENTRIES);
-  hipLaunchKernelGGL(dfa_fill_kernel<WEIGHTED>, dim3(blocks_for(a->vocab, FILL_THREADS), gy), dim3(FILL_THREADS), 0,
-                     (hipStream_t)stream, dfa_of(a), arc_logw, final_logw, bank, bank_ld, (int32_t)a->capacity, a->work, a->counters);
+  hipLaunchKernelGGL((dfa_fill_kernel<WEIGHTED, false>), fill_grid(a), dim3(FILL_THREADS), 0, (hipStream_t)stream, dfa_of(a), arc_logw,
+                     final_logw, bank, bank_ld, (int32_t)a->capacity, a->work, a->counters);
   hipLaunchKernelGGL(dfa_commit_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (int32_t)a->capacity, a->counters);
-  return launched(launch);
+  return glb::launched(launch);
 }
 
 }  // namespace
@@ -616,10 +467,8 @@ int64_t glb_dfa_bank_rows(size_t bank_bytes, int64_t vocab, int64_t n_states) {
 
 int glb_dfa_bank_init(const glb_dfa_args *a, void *stream) {
   if (const int rc = dfa_check(a, "glb_dfa_bank_init", NEED_BANK)) return rc;
-  const int64_t words = (a->vocab + 31) / 32, items = words > a->n_states ? words : a->n_states;
-  hipLaunchKernelGGL(dfa_bank_init_kernel<int32_t>, dim3(blocks_for(items, 256)), dim3(256), 0, (hipStream_t)stream, a->n_states,
-                     a->eos_id, a->vocab, a->bank, a->bank_ld, words, a->row_of_state, a->counters);
-  return launched("dfa_bank_init launch");
+  bank_init(a, a->bank, a->bank_ld, (a->vocab + 31) / 32, (hipStream_t)stream);
+  return glb::launched("dfa_bank_init launch");
 }
 
 int glb_dfa_advance(const glb_dfa_args *a, void *stream) {
@@ -627,7 +476,7 @@ int glb_dfa_advance(const glb_dfa_args *a, void *stream) {
   if (!a->tokens || !a->from || !a->to || !a->state_out || a->ld <= 0) return glb::api_fail(GLB_EINVAL, "glb_dfa_advance: null pointer or ld <= 0");
   hipLaunchKernelGGL(dfa_advance_kernel, dim3(blocks_for(a->n, 128)), dim3(128), 0, (hipStream_t)stream, dfa_of(a), a->n, a->tokens,
                      a->ld, a->from, a->to, a->state_in, a->state_out);
-  return launched("dfa_advance launch");
+  return glb::launched("dfa_advance launch");
 }
 
 int glb_dfa_claim_rows(const glb_dfa_args *a, void *stream) {
@@ -635,7 +484,7 @@ int glb_dfa_claim_rows(const glb_dfa_args *a, void *stream) {
   if (!a->state_in) return glb::api_fail(GLB_EINVAL, "glb_dfa_claim_rows: state_in is null");
   hipLaunchKernelGGL(dfa_claim_kernel, dim3(blocks_for(a->n, 256)), dim3(256), 0, (hipStream_t)stream, a->n_states, a->n, a->state_in,
                      (int32_t)a->capacity, a->row_of_state, a->work, a->counters);
-  return launched("dfa_claim launch");
+  return glb::launched("dfa_claim launch");
 }
 
 int glb_dfa_fill_masks(const glb_dfa_args *a, void *stream) {
@@ -647,8 +496,9 @@ int glb_dfa_mask_ids(const glb_dfa_args *a, void *stream) {
   if (const int rc = dfa_check(a, "glb_dfa_mask_ids", NEED_BANK | NEED_N)) return rc;
   if (!a->state_in || !a->out_rows) return glb::api_fail(GLB_EINVAL, "glb_dfa_mask_ids: null pointer");
   hipLaunchKernelGGL(dfa_mask_ids_kernel, dim3(blocks_for(a->n, 256)), dim3(256), 0, (hipStream_t)stream, a->n_states, a->accepting,
-                     a->n, a->state_in, a->done, a->row_of_state, (int32_t)a->capacity, a->out_rows);
-  return launched("dfa_mask_ids launch");
+                     a->n, a->state_in, a->done, a->row_of_state, (int32_t)a->capacity, a->out_rows, (int32_t *)nullptr,
+                     (int32_t *)nullptr);
+  return glb::launched("dfa_mask_ids launch");
 }
 
 int64_t glb_dfa_weight_bank_rows(size_t bank_bytes, int64_t vocab, int64_t n_states) {
@@ -657,11 +507,8 @@ int64_t glb_dfa_weight_bank_rows(size_t bank_bytes, int64_t vocab, int64_t n_sta
 
 int glb_dfa_weight_bank_init(const glb_dfa_weight_args *w, void *stream) {
   if (const int rc = dfa_weight_check(w, "glb_dfa_weight_bank_init", 0)) return rc;
-  const glb_dfa_args *a = &w->dfa;
-  const int64_t items = a->vocab > a->n_states ? a->vocab : a->n_states;
-  hipLaunchKernelGGL(dfa_bank_init_kernel<float>, dim3(blocks_for(items, 256)), dim3(256), 0, (hipStream_t)stream, a->n_states,
-                     a->eos_id, a->vocab, w->wbank, w->wbank_ld, a->vocab, a->row_of_state, a->counters);
-  return launched("dfa_weight_bank_init launch");
+  bank_init(&w->dfa, w->wbank, w->wbank_ld, w->dfa.vocab, (hipStream_t)stream);
+  return glb::launched("dfa_weight_bank_init launch");
 }
 
 int glb_dfa_fill_weights(const glb_dfa_weight_args *w, void *stream) {
@@ -673,18 +520,11 @@ int glb_dfa_fill_weights(const glb_dfa_weight_args *w, void *stream) {
 int glb_dfa_evict_bank_init(const glb_dfa_evict_args *e, void *stream) {
   if (const int rc = dfa_evict_check(e, "glb_dfa_evict_bank_init", 0)) return rc;
   const glb_dfa_args *a = &e->dfa;
-  if (e->wbank) {
-    const int64_t items = a->vocab > a->n_states ? a->vocab : a->n_states;
-    hipLaunchKernelGGL(dfa_bank_init_kernel<float>, dim3(blocks_for(items, 256)), dim3(256), 0, (hipStream_t)stream, a->n_states,
-                       a->eos_id, a->vocab, e->wbank, e->wbank_ld, a->vocab, a->row_of_state, a->counters);
-  } else {
-    const int64_t words = (a->vocab + 31) / 32, items = words > a->n_states ? words : a->n_states;
-    hipLaunchKernelGGL(dfa_bank_init_kernel<int32_t>, dim3(blocks_for(items, 256)), dim3(256), 0, (hipStream_t)stream, a->n_states,
-                       a->eos_id, a->vocab, a->bank, a->bank_ld, words, a->row_of_state, a->counters);
-  }
+  if (e->wbank) bank_init(a, e->wbank, e->wbank_ld, a->vocab, (hipStream_t)stream);
+  else bank_init(a, a->bank, a->bank_ld, (a->vocab + 31) / 32, (hipStream_t)stream);
   hipLaunchKernelGGL(dfa_evict_init_kernel, dim3(blocks_for(a->capacity, 256)), dim3(256), 0, (hipStream_t)stream, (int32_t)a->capacity,
                      e->row_state, e->row_stamp, e->ecounters, e->epoch);
-  return launched("dfa_evict_bank_init launch");
+  return glb::launched("dfa_evict_bank_init launch");
 }
 
 int glb_dfa_evict_serve(const glb_dfa_evict_args *e, void *stream) {
@@ -698,37 +538,15 @@ int glb_dfa_evict_serve(const glb_dfa_evict_args *e, void *stream) {
                      a->row_of_state, e->row_stamp, e->claimants, a->counters, e->ecounters, e->epoch);
   hipLaunchKernelGGL(dfa_evict_select_kernel, dim3(1), dim3(SELECT_THREADS), 0, st, a->n_states, capacity, a->row_of_state,
                      e->row_state, e->row_stamp, e->claimants, e->victims, a->work, a->counters, e->ecounters, e->epoch);
-  const dim3 grid(blocks_for(a->vocab, FILL_THREADS), (unsigned)(a->max_work < FILL_MAX_ENTRIES ? a->max_work : FILL_MAX_ENTRIES));
   if (e->wbank)
-    hipLaunchKernelGGL(dfa_evict_fill_kernel<true>, grid, dim3(FILL_THREADS), 0, st, dfa_of(a), e->arc_logw, e->final_logw, e->wbank,
-                       e->wbank_ld, capacity, a->work, e->ecounters);
+    hipLaunchKernelGGL((dfa_fill_kernel<true, true>), fill_grid(a), dim3(FILL_THREADS), 0, st, dfa_of(a), e->arc_logw, e->final_logw,
+                       e->wbank, e->wbank_ld, capacity, a->work, e->ecounters);
   else
-    hipLaunchKernelGGL(dfa_evict_fill_kernel<false>, grid, dim3(FILL_THREADS), 0, st, dfa_of(a), nullptr, nullptr, a->bank, a->bank_ld,
-                       capacity, a->work, e->ecounters);
-  hipLaunchKernelGGL(dfa_evict_ids_kernel, dim3(blocks_for(a->n, 256)), dim3(256), 0, st, a->n_states, a->accepting, a->n, a->state_in,
+    hipLaunchKernelGGL((dfa_fill_kernel<false, true>), fill_grid(a), dim3(FILL_THREADS), 0, st, dfa_of(a), nullptr, nullptr, a->bank,
+                       a->bank_ld, capacity, a->work, e->ecounters);
+  hipLaunchKernelGGL(dfa_mask_ids_kernel, dim3(blocks_for(a->n, 256)), dim3(256), 0, st, a->n_states, a->accepting, a->n, a->state_in,
                      a->done, a->row_of_state, capacity, a->out_rows, e->ecounters, e->epoch);
-  return launched("dfa_evict_serve launch");
-}
-
-int glb_dfa_backward(const glb_dfa_push_args *p, void *stream) {
-  if (const int rc = dfa_push_check(p, "glb_dfa_backward", true)) return rc;
-  const hipStream_t st = (hipStream_t)stream;
-  const int64_t items = p->n_states > GLB_DFA_PUSH_STATUS ? p->n_states : GLB_DFA_PUSH_STATUS;
-  if (p->restart)
-    hipLaunchKernelGGL(dfa_backward_init_kernel, dim3(blocks_for(items, 256)), dim3(256), 0, st, p->n_states, p->final_logw, p->beta,
-                       p->status);
-  if (p->semiring == GLB_DFA_PUSH_MAX) backward_sweeps<GLB_DFA_PUSH_MAX>(p, st);
-  else backward_sweeps<GLB_DFA_PUSH_LOG>(p, st);
-  hipLaunchKernelGGL(dfa_backward_end_kernel, dim3(blocks_for(p->n_states, 256)), dim3(256), 0, st, p->n_states, p->beta, p->scratch,
-                     p->status);
-  return launched("dfa_backward launch");
-}
-
-int glb_dfa_push_weights(const glb_dfa_push_args *p, void *stream) {
-  if (const int rc = dfa_push_check(p, "glb_dfa_push_weights", false)) return rc;
-  hipLaunchKernelGGL(dfa_push_weights_kernel, dim3((unsigned)p->n_states), dim3(PUSH_THREADS), 0, (hipStream_t)stream, p->n_states,
-                     p->delta, p->arc_logw, p->final_logw, p->beta, p->arc_out, p->final_out);
-  return launched("dfa_push_weights launch");
+  return glb::launched("dfa_evict_serve launch");
 }
 
 }  // extern "C"

@@ -241,16 +241,9 @@ __global__ __launch_bounds__(MIN_THREADS) void min_quotient_kernel(int32_t n_sta
   }
 }
 
-int launched(const char *what) {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? GLB_OK : glb::api_hip_fail(e, what);
-}
-
 // the block of glb_dfa_refine (`refine`) / glb_dfa_quotient: the same checks, each call's own tables
 int dfa_min_check(const glb_dfa_min_args *p, const char *what, bool refine) {
-  if (!p) return glb::api_fail(GLB_EINVAL, "%s: null argument block", what);
-  if (p->struct_size != sizeof(glb_dfa_min_args))
-    return glb::api_fail(GLB_EINVAL, "glb_dfa_min_args.struct_size %u != %zu (ABI mismatch)", p->struct_size, sizeof(glb_dfa_min_args));
+  if (const int rc = glb::block_ok(p, what, "glb_dfa_min_args")) return rc;
   if (p->n_states < 1 || p->n_states > 0x7fffff00) return glb::api_fail(GLB_EINVAL, "%s: n_states %d outside [1, 2^31 - 256]", what, p->n_states);
   if (!p->delta) return glb::api_fail(GLB_EINVAL, "%s: delta is null", what);
   if (!p->keep) return glb::api_fail(GLB_EINVAL, "%s: keep is null", what);
@@ -302,7 +295,7 @@ int glb_dfa_refine(const glb_dfa_min_args *p, void *stream) {
     hipLaunchKernelGGL(min_assign_kernel<false>, waves, block, 0, st, m, src, dst, j);
   }
   hipLaunchKernelGGL(min_end_kernel, dim3(blocks_for(p->n_states, 256)), dim3(256), 0, st, p->n_states, p->cls, p->scratch, p->status);
-  return launched("dfa_refine launch");
+  return glb::launched("dfa_refine launch");
 }
 
 int glb_dfa_quotient(const glb_dfa_min_args *p, void *stream) {
@@ -310,7 +303,7 @@ int glb_dfa_quotient(const glb_dfa_min_args *p, void *stream) {
   hipLaunchKernelGGL(min_quotient_kernel, dim3((unsigned)p->n_new), dim3(MIN_THREADS), 0, (hipStream_t)stream, p->n_states, p->n_new,
                      p->delta, p->keep, p->new_id, p->rep, p->arc_logw, p->final_logw, p->accepting, p->delta_out, p->arc_out,
                      p->final_out, p->accepting_out);
-  return launched("dfa_quotient launch");
+  return glb::launched("dfa_quotient launch");
 }
 
 }  // extern "C"

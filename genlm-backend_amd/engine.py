@@ -892,14 +892,13 @@ class HipEngine:
         return y if out is not None else y.view(*x.shape[:-1], n)
 
     # ---- byte-level DFA constraints (glb_dfa_*: DESIGN.md §17; constraints.DeviceConstraint fills the argument block) ---------
+    # the glb_dfa_* entries of `_lib.SYMBOLS` that take (argument block, stream)
+    DFA_CALLS = frozenset(name for name, (_, argtypes) in _lib.SYMBOLS.items()
+                          if name.startswith("glb_dfa_") and argtypes and issubclass(argtypes[0], C._Pointer))
+
     def dfa_call(self, name, args):
-        """One of glb_dfa_bank_init / advance / claim_rows / fill_masks / mask_ids, or of glb_dfa_weight_bank_init /
-        fill_weights (their block: `_lib.DfaWeightArgs`), or of glb_dfa_evict_bank_init / evict_serve (their
-        block: `_lib.DfaEvictArgs`), or of glb_dfa_backward / push_weights (their block: `_lib.DfaPushArgs`,
-        DESIGN.md §20), or of glb_dfa_refine / quotient (their block: `_lib.DfaMinArgs`), on the current stream."""
-        if name not in ("glb_dfa_bank_init", "glb_dfa_advance", "glb_dfa_claim_rows", "glb_dfa_fill_masks", "glb_dfa_mask_ids",
-                        "glb_dfa_weight_bank_init", "glb_dfa_fill_weights", "glb_dfa_evict_bank_init", "glb_dfa_evict_serve",
-                        "glb_dfa_backward", "glb_dfa_push_weights", "glb_dfa_refine", "glb_dfa_quotient"):
+        """One of `DFA_CALLS` with its block (`_lib.SYMBOLS` names it), on the current stream."""
+        if name not in HipEngine.DFA_CALLS:
             raise ValueError(name)
         check(getattr(self.lib, name)(C.byref(args), self._stream()))
 

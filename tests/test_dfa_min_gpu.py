@@ -260,6 +260,44 @@ def test_minimised_after_the_push_equals_the_pushed_twin_through_state_map(engin
     assert plain.minimize_stats() == {"states_in": wf.n_states, "states_out": wf.n_states, "rounds": 0}
 
 
+def test_standalone_and_constructor_minimisation_are_one_pipeline(engine):
+    """Eight weighted strings that share suffixes (35 states) under a 70-token vocabulary (three bit words, two waves): what
+    `minimize` returns and what `DeviceConstraint(minimize=True)` serves are the same bits, with weights and without."""
+    from genlm_backend_amd.constraints import ByteDFA, ByteWFSA, DeviceConstraint, minimize
+
+    pieces = [b"ed", b"ing", b"walk", b"talk", b"bak", b"cak", b"ke", b"king", b"al", b"lk"]  # ids 59 .. 68: both sides of 64
+    vocab = [bytes([48 + i]) * 2 for i in range(33)] + [bytes([97 + i]) for i in range(26)] + pieces + [b"<eos>"]
+    eos, skip = 69, (69,)
+    assert len(vocab) == 70
+    words ={stem + end: w for stem in (b"walk", b"talk", b"bak", b"cak") for end, w in ((b"ed", -1.0), (b"ing", -2.5))}
+    wf = ByteWFSA.from_weighted_strings(words)
+    assert len(words) == 8 and wf.n_states == 35
+    for a in (wf, ByteDFA(wf.delta, wf.accepting, wf.start)):
+        small, state_map = minimize(engine, a)
+        c = DeviceConstraint(engine, a, vocab, eos, skip_ids=skip, minimize=True)
+        assert type(small) is type(c.dfa) is type(a) and small.n_states == c.dfa.n_states < a.n_states
+        assert state_map.dtype == np.int32 and np.array_equal(state_map, c.state_map.cpu().numpy())
+        assert small.start == c.dfa.start == c.tables.start
+        for host in (c.dfa.delta, c._delta.cpu().numpy()):
+            assert host.dtype == np.int32 and np.array_equal(small.delta, host)
+        for host in (c.dfa.accepting, c._acc.cpu().numpy().astype(np.bool_)):
+            assert np.array_equal(small.accepting, host)
+        if a is wf:
+            for arc, fin in ((c.dfa.arc_logw, c.dfa.final_logw), (c._arc_logw.cpu().numpy(), c._final_logw.cpu().numpy())):
+                assert _same(small.arc_logw, arc) and _same(small.final_logw, fin)
+            for s, w in words.items():
+                assert small.path_logw(s).tobytes() == np.float32(w).tobytes()
+        else:
+            assert c._arc_logw is None and c._final_logw is None
+        # and the rows served are those of a constraint over the standalone quotient
+        twin = DeviceConstraint(engine, small, vocab, eos, skip_ids=skip)
+        states = torch.arange(small.n_states, dtype=torch.int32, device=engine.device)
+        assert c.words == 3 and c.warm() and twin.warm()
+        rows_c, rows_t = c.mask_rows(states).cpu().numpy(), twin.mask_rows(states).cpu().numpy()
+        c.check(), twin.check()
+        assert (rows_c >= 2).all() and c.bank.cpu().numpy()[rows_c].tobytes() == twin.bank.cpu().numpy()[rows_t].tobytes()
+
+
 # ---- serving --------------------------------------------------------------------------------------------------------------------
 def _pair(engine, name, V, weighted, **kw):
     from genlm_backend_amd.constraints import ByteDFA, ByteWFSA, DeviceConstraint
