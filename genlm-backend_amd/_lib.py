@@ -331,6 +331,32 @@ class DfaMinArgs(C.Structure):
     ]
 
 
+FSA_STATUS = 16  # GLB_FSA_STATUS: the search - rounds, converged, flags, states, frontier, private, count reached; [8 ..] liveness
+FSA_LIVE_STATUS = 8  # where liveness keeps its words: sweeps, converged, flags (zero), private
+FSA_AND, FSA_OR, FSA_SUB = 0, 1, 2
+FSA_MAX_STATES = 1 << 22
+
+
+class FsaProductArgs(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("op", C.c_int32),
+        ("n_a", C.c_int32), ("n_b", C.c_int32), ("start_a", C.c_int32), ("start_b", C.c_int32),
+        ("delta_a", C.c_void_p), ("delta_b", C.c_void_p),
+        ("accepting_a", C.c_void_p), ("accepting_b", C.c_void_p),
+        ("live_a", C.c_void_p), ("live_b", C.c_void_p),
+        ("arc_a", C.c_void_p), ("final_a", C.c_void_p),
+        ("arc_b", C.c_void_p), ("final_b", C.c_void_p),
+        ("max_states", C.c_int32),
+        ("n_states", C.c_int32),
+        ("table", C.c_void_p), ("table_slots", C.c_int64),
+        ("pairs", C.c_void_p), ("delta_out", C.c_void_p), ("accepting_out", C.c_void_p),
+        ("arc_out", C.c_void_p), ("final_out", C.c_void_p),
+        ("live", C.c_void_p), ("counts", C.c_void_p), ("status", C.c_void_p),
+        ("rounds", C.c_int32), ("restart", C.c_int32),
+    ]
+
+
 # every symbol include/glb.h declares: name -> (restype, argtypes)
 _vp, _i32, _i64, _f32, _sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_size_t
 SYMBOLS = {
@@ -425,6 +451,8 @@ SYMBOLS = {
     "glb_dfa_push_weights": (C.c_int, [C.POINTER(DfaPushArgs), _vp]),
     "glb_dfa_refine": (C.c_int, [C.POINTER(DfaMinArgs), _vp]),
     "glb_dfa_quotient": (C.c_int, [C.POINTER(DfaMinArgs), _vp]),
+    "glb_fsa_product_round": (C.c_int, [C.POINTER(FsaProductArgs), _vp]),
+    "glb_fsa_live": (C.c_int, [C.POINTER(FsaProductArgs), _vp]),
     "glb_philox4x32_10": (None, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
 }
 

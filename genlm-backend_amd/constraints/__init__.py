@@ -10,8 +10,11 @@ keeps a bank of float32 rows - the token log-weights from every state reached - 
 
 `DeviceConstraint(..., on_full="evict")` lets the bank be smaller than the automaton: a cache over the states,
 the least recently requested rows recycled and filled again on the device.
+
+`product(llm, a, b, op)` makes the automaton of two automata's conjunction, union or difference on the device,
+for `DeviceConstraint(..., minimize=True)` to shrink and serve.
 """
 from .automata import ByteDFA, ByteWFSA  # noqa: F401
 from .device import DeviceConstraint  # noqa: F401
 from .regex import _regex_dfa  # noqa: F401
-from .tables import DeviceTables, _kept, minimize  # noqa: F401
+from .tables import DeviceTables, _kept, minimize, product  # noqa: F401

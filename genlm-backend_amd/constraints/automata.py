@@ -30,6 +30,20 @@ class ByteDFA:
         self.n_states = S
         self.live = self._live()
 
+    @classmethod
+    def _from_device(cls, delta, accepting, start, live, arc_logw=None, final_logw=None):
+        """The automaton of tables that the device made and checked (`product`): `live` is the device's, nothing is searched
+        again.  With weights (`cls` a `ByteWFSA`) `accepting` is final_logw > -inf, as the constructor has it."""
+        self = cls.__new__(cls)
+        self.delta = np.ascontiguousarray(delta, dtype=np.int32)
+        self.accepting = np.ascontiguousarray(accepting, dtype=np.bool_)
+        self.start, self.n_states = int(start), self.delta.shape[0]
+        self.live = np.ascontiguousarray(live, dtype=np.bool_)
+        if arc_logw is not None:
+            self.arc_logw = np.ascontiguousarray(arc_logw, dtype=np.float32)
+            self.final_logw = np.ascontiguousarray(final_logw, dtype=np.float32)
+        return self
+
     def _live(self):
         """Backwards reachability from the accepting states over the reversed transition graph."""
         S = self.n_states

@@ -1,5 +1,6 @@
 """An automaton's tables on the device, pushed and minimised (§21) there before they are served:
-`DeviceConstraint` and the standalone `minimize` prepare theirs through the same three calls, `upload`, `pushed`, `minimized`."""
+`DeviceConstraint` and the standalone `minimize` prepare theirs through the same three calls, `upload`, `pushed`, `minimized`;
+`product` (§22) makes the tables of two automata's conjunction, union or difference there, in front of that pipeline."""
 import ctypes as C
 import dataclasses
 
@@ -48,7 +49,7 @@ class DeviceTables:
         n = converged = flags = 0
         while not converged and not flags and n < budget and not stop(n):
             setattr(p, count, min(_BATCH, budget - n))
-            self.eng.dfa_call(name, p)
+            (self.eng.fsa_call if name.startswith("glb_fsa_") else self.eng.dfa_call)(name, p)
             p.restart = 0
             n, converged, flags = status[:3].tolist()
         return n, converged, flags
@@ -125,6 +126,89 @@ class DeviceTables:
         return out, new_id, rounds
 
 
+    def _product_block(self, other, op, cap):
+        """(block, buffers): the glb_fsa_product_args of these tables (A) with `other` (B) and its device buffers, the outputs
+        allocated for `cap` rows."""
+        import torch
+
+        dev = self.eng.device
+        new = lambda dtype, *shape: torch.empty(shape, dtype=dtype, device=dev)
+        slots = 1 << max(1, (2 * cap - 1).bit_length())
+        buf = dict(table=new(torch.int64, 2 * slots), pairs=new(torch.int32, cap, 2), delta=new(torch.int32, cap, 256),
+                   accepting=new(torch.uint8, cap), live=new(torch.uint8, cap), counts=new(torch.int32, cap),
+                   status=torch.zeros(_lib.FSA_STATUS, dtype=torch.int32, device=dev), arc=None, final=None)
+        p = _lib.FsaProductArgs()
+        p.struct_size, p.op = C.sizeof(_lib.FsaProductArgs), {"and": _lib.FSA_AND, "or": _lib.FSA_OR, "sub": _lib.FSA_SUB}[op]
+        p.n_a, p.n_b, p.start_a, p.start_b = self.n_states, other.n_states, self.start, other.start
+        p.delta_a, p.accepting_a, p.live_a = self.delta.data_ptr(), self.accepting.data_ptr(), self.live.data_ptr()
+        p.delta_b, p.accepting_b, p.live_b = other.delta.data_ptr(), other.accepting.data_ptr(), other.live.data_ptr()
+        if self.weighted:
+            p.arc_a, p.final_a = self.arc_logw.data_ptr(), self.final_logw.data_ptr()
+        if other.weighted:
+            p.arc_b, p.final_b = other.arc_logw.data_ptr(), other.final_logw.data_ptr()
+        if self.weighted or other.weighted:
+            buf["arc"], buf["final"] = new(torch.float32, cap, 256), new(torch.float32, cap)
+            p.arc_out, p.final_out = buf["arc"].data_ptr(), buf["final"].data_ptr()
+        p.max_states, p.table, p.table_slots = cap, buf["table"].data_ptr(), slots
+        p.pairs, p.delta_out, p.accepting_out = buf["pairs"].data_ptr(), buf["delta"].data_ptr(), buf["accepting"].data_ptr()
+        p.live, p.counts, p.status = buf["live"].data_ptr(), buf["counts"].data_ptr(), buf["status"].data_ptr()
+        return p, buf
+
+    def _product_search(self, p, status):
+        """The batch loops of `product` over a block of `_product_block`: the rounds of the search, then the liveness sweeps,
+        the status words read between batches and nothing else; {"rounds", "sweeps", "states"}.  The block's outputs then
+        hold "states" rows, nothing trimmed.  ValueError when the search passes the block's max_states."""
+        cap = p.max_states
+        rounds, converged, flags = self._iterate("glb_fsa_product_round", p, status, cap + 1, count="rounds")
+        if flags & 1:
+            raise ValueError(f"product: the search passed max_states={cap}: it had reached at least {int(status[7])} states in round "
+                             f"{rounds + 1} and was not at its end; nothing is returned")
+        if flags:
+            raise RuntimeError(f"product: the search raised flag bit 1 (flags {flags}: an id out of range) after {rounds} rounds")
+        if not converged:
+            raise RuntimeError(f"product: the search had not ended after {rounds} rounds over at most {cap} states")
+        p.n_states = n = int(status[3])
+        sweeps, converged, flags = self._iterate("glb_fsa_live", p, status[_lib.FSA_LIVE_STATUS:], n + 1, count="rounds")
+        if flags or not converged:
+            raise RuntimeError(f"product: liveness had not settled after {sweeps} sweeps over {n} states")
+        return dict(rounds=rounds, sweeps=sweeps, states=n)
+
+    def product(self, other, op, max_states):
+        """(tables, pairs, stats): the product of these tables (A) with `other` (B) under `op` ("and", "or", "sub"), searched,
+        swept for joint liveness and trimmed on the device (glb_fsa_product_round, glb_fsa_live, glb_dfa_quotient over the
+        live states with every state its own class; include/glb.h).  pairs: host int32 [S, 2], every state's
+        (A state, B state), -1 for a side that is out.  State 0 is the start pair, kept whatever it is; the others keep the
+        order of the queue search.  `live` of the result is the device's.  ValueError when the search passes `max_states`."""
+        import torch
+
+        dev = self.eng.device
+        p, buf = self._product_block(other, op, max_states)
+        stats = self._product_search(p, buf["status"])
+        n = stats["states"]
+        live = buf["live"][:n].cpu().numpy().astype(np.bool_)
+        keep = live.copy()
+        keep[0] = True
+        rep = np.nonzero(keep)[0].astype(np.int32)
+        new_id = np.where(keep, np.cumsum(keep) - 1, -1).astype(np.int32)
+        n_new = len(rep)
+        up, keep_d = _put(self.eng, np.concatenate([new_id, rep])), _put(self.eng, keep.astype(np.uint8))
+        out = DeviceTables(eng=self.eng, delta=torch.empty((n_new, 256), dtype=torch.int32, device=dev),
+                           accepting=torch.empty(n_new, dtype=torch.uint8, device=dev), live=_put(self.eng, live[rep].astype(np.uint8)),
+                           arc_logw=None, final_logw=None, start=0)
+        q = _lib.DfaMinArgs()
+        q.struct_size, q.n_states = C.sizeof(_lib.DfaMinArgs), n
+        q.delta, q.keep, q.new_id, q.rep, q.n_new = buf["delta"].data_ptr(), keep_d.data_ptr(), up.data_ptr(), up.data_ptr() + 4 * n, n_new
+        q.accepting, q.delta_out, q.accepting_out = buf["accepting"].data_ptr(), out.delta.data_ptr(), out.accepting.data_ptr()
+        if buf["arc"] is not None:
+            out.arc_logw = torch.empty((n_new, 256), dtype=torch.float32, device=dev)
+            out.final_logw = torch.empty(n_new, dtype=torch.float32, device=dev)
+            q.arc_logw, q.final_logw = buf["arc"].data_ptr(), buf["final"].data_ptr()
+            q.arc_out, q.final_out = out.arc_logw.data_ptr(), out.final_logw.data_ptr()
+        self.eng.dfa_call("glb_dfa_quotient", q)
+        pairs = buf["pairs"][:n].cpu().numpy()[rep]
+        return out, np.ascontiguousarray(pairs), dict(stats, states_out=n_new)
+
+
 def _put(eng, a):
     import torch
 
@@ -154,3 +238,44 @@ def minimize(llm_or_engine, automaton, max_rounds=None):
     tables = DeviceTables.upload(getattr(llm_or_engine, "engine", llm_or_engine), automaton)
     small, new_id, _ = tables.minimized(_kept(automaton), max_rounds)
     return small.to_host(type(automaton)), new_id
+
+
+def product(llm_or_engine, a, b, op="and", max_states=1 << 18):
+    """(automaton, pairs): the automaton of the byte strings that `a` and `b` both accept (op="and"), that either accepts
+    ("or"), or that `a` accepts and `b` does not ("sub"), made on the device (include/glb.h glb_fsa_product_round /
+    glb_fsa_live), and host int32 [S, 2]: every state's (state of a, state of b), -1 for a side that has left
+    its automaton (a side that is not live there counts as having left).  `a` and `b`: each a `ByteDFA` or a `ByteWFSA`;
+    "or" takes no weights, "sub" takes `a`'s alone.  The result is a `ByteWFSA` when an operand has weights: under "and" of
+    two weighted automata the arc and final weights are added, one float32 addition each (a + b); where one side has
+    weights its bits pass through.  State 0 is the start; the states are numbered in the order of a queue search over the
+    pairs (states in id order, bytes ascending) and then trimmed to those from which some string is still accepted, the
+    start always kept: an empty language gives one state without arcs.  `live` of the result comes from the device.
+    ValueError for an argument the above does not admit, before the device is touched, and when the search passes
+    `max_states` states before it ends (nothing partial is returned; the message names `max_states` and the count reached
+    when the search stopped - it stops in the middle of a round, so a wide search reports a count of its own, at least
+    max_states + 1).  The outputs are allocated for `max_states` rows before the search, 1 KB a row (2 KB with weights);
+    no product has more than (a.n_states + 1) * (b.n_states + 1) states, so a larger `max_states` allocates that many.  The
+    device numbers at most 2^22 states: ValueError, before the device is touched too, when the smaller of the two numbers
+    exceeds that - a `max_states` above 2^22 is accepted only where the operands are small enough to make it moot."""
+    if op not in ("and", "or", "sub"):
+        raise ValueError(f'op must be "and", "or" or "sub", got {op!r}')
+    for name, x in (("a", a), ("b", b)):
+        if not isinstance(x, ByteDFA):
+            raise ValueError(f"product needs a ByteDFA or a ByteWFSA for {name}, got {type(x).__name__}")
+    if op == "or" and (isinstance(a, ByteWFSA) or isinstance(b, ByteWFSA)):
+        raise ValueError('op="or" takes unweighted operands: the union of weighted automata needs a sum per string')
+    if op == "sub" and isinstance(b, ByteWFSA):
+        raise ValueError('op="sub" takes an unweighted `b`: the strings removed carry no weight')
+    if isinstance(max_states, bool) or not isinstance(max_states, (int, np.integer)) or max_states < 1:
+        raise ValueError(f"max_states must be an int >= 1, got {max_states!r}")
+    cap = int(min(int(max_states), (a.n_states + 1) * (b.n_states + 1)))  # (no product has more pairs)
+    if cap > _lib.FSA_MAX_STATES:
+        raise ValueError(f"max_states={max_states}: the device search numbers at most {_lib.FSA_MAX_STATES} states")
+    eng = getattr(llm_or_engine, "engine", llm_or_engine)
+    tables, pairs, _ = DeviceTables.upload(eng, a).product(DeviceTables.upload(eng, b), op, cap)  # (it can pass cap only where cap is max_states)
+    kind = ByteWFSA if tables.weighted else ByteDFA
+    host = lambda t: t.cpu().numpy()
+    if tables.weighted:
+        fin = host(tables.final_logw)
+        return kind._from_device(host(tables.delta), fin > -np.inf, 0, host(tables.live), host(tables.arc_logw), fin), pairs
+    return kind._from_device(host(tables.delta), host(tables.accepting), 0, host(tables.live)), pairs

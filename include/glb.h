@@ -1210,6 +1210,83 @@ typedef struct glb_dfa_min_args {
 int glb_dfa_refine(const glb_dfa_min_args *args, void *hip_stream);
 int glb_dfa_quotient(const glb_dfa_min_args *args, void *hip_stream);
 
+/*
+ * Products: the automaton of the strings that two byte automata A and B both accept (GLB_FSA_AND), that
+ * either accepts (GLB_FSA_OR) or that A accepts and B does not (GLB_FSA_SUB), found by a breadth-first search over the pairs
+ * of states.  A component of a pair is OUT, and stored as -1, when it is -1, outside its automaton or not live there.  Under
+ * AND a pair with a side out does not exist; under SUB a pair with the A side out; under OR a pair with both sides out.
+ * State 0 is the start pair - (-1, -1), without arcs, where that pair does not exist - and the states are numbered in the
+ * order in which a queue search meets them that takes the states in id order and the bytes 0 .. 255 in ascending order.
+ * The numbering does not depend on the order the atomics take: a new pair's slot in `table` (open addressing on the full
+ * 64-bit key (a + 1) (n_b + 1) + (b + 1): equal keys are equal pairs) keeps the smallest arc index, frontier position * 256
+ * + byte, of the round that found it, and a scan over the round's winning arcs hands out the ids.  State s accepts where
+ * both sides do (AND), either does (OR), A's does and B's does not (SUB); a side that is out never accepts.
+ * Weights: arc_a / final_a and arc_b / final_b are null for an unweighted operand; OR takes none, SUB takes A's alone.  An
+ * arc of the product weighs arc_a + arc_b where both are given (one float32 addition, in that order), else the one given;
+ * an arc that does not exist weighs -inf.  final_out likewise, -inf where the state does not accept.  arc_out / final_out
+ * are given exactly when an operand has weights.
+ *   glb_fsa_product_round  `restart` != 0: first the table emptied, status = 0 and state 0 made.  Then `rounds` rounds, six
+ *                     launches each, every grid sized to the device and striding over the frontier that the status words
+ *                     bound: every arc of the frontier expanded (delta_out, arc_out; the state's accepting_out and
+ *                     final_out), the winning arcs counted a state, the counts scanned, the new states numbered (`pairs`),
+ *                     delta_out's arcs into them resolved, the frontier moved on.  A round that numbers no state sets the
+ *                     converged word; with it or a flag set every later launch leaves at once.  status:
+ *                       [0] rounds performed since the restart   [1] converged
+ *                       [2] flags, sticky: bit 0 - more than max_states states (nothing of that round is numbered);
+ *                           bit 1 - an id out of range: a bug, never an input
+ *                       [3] states numbered   [4], [5] the frontier   [6] private
+ *                       [7] with flag bit 0: the pairs found when the search stopped, more than max_states
+ *                       [12] private: the distinct pairs entered into the table, state 0 included
+ *                     The expansion counts the new pairs as it enters them, so bit 0 goes up in the MIDDLE of the launch that
+ *                     passes max_states; its blocks leave at their next state and its probes within 32 slots.  A round of
+ *                     a wide frontier can bring 256 new pairs a state - many times the table - and neither fills it nor
+ *                     probes a full table arc by arc.  Should the table fill before the flag is seen, that is bit 0 as well
+ *                     (table_slots >= 2 max_states distinct pairs are more than max_states), [7] = table_slots.  One
+ *                     below the true count, [7] is the true count; further below it is whatever the launch had entered.
+ *                     `table`: 16 bytes a slot (table_slots 64-bit keys, then int32 arc indices, then int32 ids), aligned
+ *                     to 8.  `counts`: max_states int32 of scratch.  max_states <= 2^22.
+ *   glb_fsa_live      over the first n_states rows of delta_out: `restart` != 0: live = accepting_out and status[8 .. 11] =
+ *                     0.  Then `rounds` sweeps of live[s] |= any live[delta_out[s][b]], in place (the rule only adds: the
+ *                     fixed point is unique), two launches each.  status [8] sweeps performed, the one that changed nothing
+ *                     included   [9] converged   [10] zero   [11] private.  Reads n_states, max_states, delta_out,
+ *                     accepting_out, live, status, rounds, restart alone.
+ * GLB_EINVAL before any launch, buffers untouched, the field named in the message: struct_size wrong, max_states outside
+ * [1, 2^22], rounds outside [1, 65536], delta_out, accepting_out or status null; round: op unknown, n_a / n_b < 1, a start
+ * outside its automaton, an operand's delta, accepting or live null, arc without final, weights the op does not take,
+ * arc_out / final_out not matching them, table_slots not a power of two or below 2 max_states, table, pairs or counts null;
+ * live: n_states outside [1, max_states], live null.  Nothing synchronises or allocates: the host reads `status`.
+ */
+#define GLB_FSA_STATUS 16
+#define GLB_FSA_AND 0
+#define GLB_FSA_OR 1
+#define GLB_FSA_SUB 2
+typedef struct glb_fsa_product_args {
+  uint32_t struct_size; /* sizeof(glb_fsa_product_args) - ABI guard */
+  int32_t op;
+  int32_t n_a, n_b, start_a, start_b;
+  const int32_t *delta_a, *delta_b;       /* [n, 256] */
+  const uint8_t *accepting_a, *accepting_b; /* [n] */
+  const uint8_t *live_a, *live_b;         /* [n] */
+  const float *arc_a, *final_a;           /* [n_a, 256], [n_a] or both null */
+  const float *arc_b, *final_b;           /* [n_b, 256], [n_b] or both null */
+  int32_t max_states;
+  int32_t n_states;                       /* glb_fsa_live: the states numbered */
+  void *table;                            /* 16 * table_slots bytes */
+  int64_t table_slots;                    /* a power of two >= 2 * max_states */
+  int32_t *pairs;                         /* [max_states, 2], out */
+  int32_t *delta_out;                     /* [max_states, 256], out */
+  uint8_t *accepting_out;                 /* [max_states], out */
+  float *arc_out;                         /* [max_states, 256], out, or null */
+  float *final_out;                       /* [max_states], out, or null */
+  uint8_t *live;                          /* [max_states], out (glb_fsa_live) */
+  int32_t *counts;                        /* [max_states] */
+  int32_t *status;                        /* [GLB_FSA_STATUS] */
+  int32_t rounds;                         /* rounds / sweeps of this call */
+  int32_t restart;
+} glb_fsa_product_args;
+int glb_fsa_product_round(const glb_fsa_product_args *args, void *hip_stream);
+int glb_fsa_live(const glb_fsa_product_args *args, void *hip_stream);
+
 /* Philox4x32-10 block function, exposed so hosts can reproduce the device draws. */
 void glb_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 
