@@ -357,6 +357,31 @@ class FsaProductArgs(C.Structure):
     ]
 
 
+NFA_STATUS = 16  # GLB_NFA_STATUS: the search as FSA_STATUS has it; [8 ..] the closure - sweeps, converged, flags (zero), private
+NFA_CLOSURE_STATUS = 8
+NFA_MAX_IMPORTANT = 4096  # GLB_NFA_MAX_IMPORTANT: a set of important states is one wave, a 64-bit word a lane
+NFA_MAX_STATES = 1 << 22
+
+
+class NfaArgs(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("n_states", C.c_int32), ("start", C.c_int32),
+        ("n_important", C.c_int32), ("n_words", C.c_int32),
+        ("n_arcs", C.c_int32), ("n_eps", C.c_int32), ("n_groups", C.c_int32),
+        ("eps_off", C.c_void_p), ("eps_to", C.c_void_p), ("bit_of", C.c_void_p),
+        ("arc_off", C.c_void_p), ("arc_dst", C.c_void_p), ("arc_bytes", C.c_void_p), ("accepting_mask", C.c_void_p),
+        ("group_of", C.c_void_p), ("group_lo", C.c_void_p),
+        ("eclose", C.c_void_p),
+        ("hash_mask", C.c_uint64),
+        ("max_states", C.c_int32), ("chunk", C.c_int32),
+        ("table", C.c_void_p), ("table_slots", C.c_int64),
+        ("cand", C.c_void_p), ("sets", C.c_void_p),
+        ("delta_out", C.c_void_p), ("accepting_out", C.c_void_p), ("counts", C.c_void_p), ("status", C.c_void_p),
+        ("rounds", C.c_int32), ("restart", C.c_int32),
+    ]
+
+
 # every symbol include/glb.h declares: name -> (restype, argtypes)
 _vp, _i32, _i64, _f32, _sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_size_t
 SYMBOLS = {
@@ -453,6 +478,8 @@ SYMBOLS = {
     "glb_dfa_quotient": (C.c_int, [C.POINTER(DfaMinArgs), _vp]),
     "glb_fsa_product_round": (C.c_int, [C.POINTER(FsaProductArgs), _vp]),
     "glb_fsa_live": (C.c_int, [C.POINTER(FsaProductArgs), _vp]),
+    "glb_nfa_closure": (C.c_int, [C.POINTER(NfaArgs), _vp]),
+    "glb_nfa_subset_round": (C.c_int, [C.POINTER(NfaArgs), _vp]),
     "glb_philox4x32_10": (None, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
 }
 

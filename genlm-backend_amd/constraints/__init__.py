@@ -13,8 +13,12 @@ the least recently requested rows recycled and filled again on the device.
 
 `product(llm, a, b, op)` makes the automaton of two automata's conjunction, union or difference on the device,
 for `DeviceConstraint(..., minimize=True)` to shrink and serve.
+
+`ByteNFA` is a byte automaton with empty arcs - the union of any number of automata, their concatenation, their closure, a
+pattern's Thompson automaton - and `determinize(llm, nfa)` its `ByteDFA`, by the subset construction on the device.
 """
 from .automata import ByteDFA, ByteWFSA  # noqa: F401
 from .device import DeviceConstraint  # noqa: F401
+from .nfa import ByteNFA  # noqa: F401
 from .regex import _regex_dfa  # noqa: F401
-from .tables import DeviceTables, _kept, minimize, product  # noqa: F401
+from .tables import DeviceTables, _kept, determinize, minimize, product  # noqa: F401

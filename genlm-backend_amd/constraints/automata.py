@@ -83,7 +83,7 @@ class ByteDFA:
         return cls(np.stack(rows), np.array(acc, np.bool_), 0)
 
     @classmethod
-    def from_regex(cls, pattern, max_states=65536):
+    def from_regex(cls, pattern, max_states=65536, device=None):
         """The automaton of a regular expression over bytes: accepts exactly the byte strings `d` for which
         `re.compile(pattern).fullmatch(d)` matches, `pattern` read as Python's `re` reads a BYTES pattern without flags (a
         `str` is encoded as UTF-8 first: a non-ASCII character is the sequence of its bytes, and a quantifier behind it
@@ -93,11 +93,18 @@ class ByteDFA:
         else - anchors, backreferences, lookaround, lazy and possessive quantifiers, inline flags, named groups, \\b \\B \\A
         \\Z - raises ValueError naming the construct and its position, and so does a subset construction that passes
         `max_states`.  Start state 0; the result is not minimised (`minimize`, `DeviceConstraint(minimize=True)`).  Host
-        only: a Thompson automaton and its subset construction."""
+        only: a Thompson automaton and its subset construction - unless `device` is an `llm` or an engine: then the subset
+        construction runs there (`determinize(device, ByteNFA.from_regex(pattern), max_states)[0]`), the same
+        automaton with its states numbered in byte order instead of byte-group order."""
         if isinstance(pattern, str):
             pattern = pattern.encode("utf-8")
         if isinstance(max_states, bool) or not isinstance(max_states, (int, np.integer)) or max_states < 1:
             raise ValueError(f"max_states must be an int >= 1, got {max_states!r}")
+        if device is not None:
+            from .nfa import ByteNFA
+            from .tables import determinize
+
+            return determinize(device, ByteNFA.from_regex(pattern, int(max_states)), int(max_states))[0]
         from .regex import _regex_dfa
 
         delta, accepting = _regex_dfa(bytes(pattern), int(max_states))

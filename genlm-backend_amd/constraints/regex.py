@@ -238,10 +238,16 @@ class _Nfa:
         return a, end
 
 
-def _regex_dfa(pattern, max_states):
-    """(delta int32 [S, 256], accepting bool [S]) of `pattern` by subset construction, state 0 the start."""
+def _thompson(pattern, max_states):
+    """(automaton, first, last): the Thompson automaton of `pattern`, what `_regex_dfa` and `ByteNFA.from_regex` both start from."""
     nfa = _Nfa(8 * max_states + 4096)
     first, last = nfa.build(_RegexParser(pattern).parse())
+    return nfa, first, last
+
+
+def _regex_dfa(pattern, max_states):
+    """(delta int32 [S, 256], accepting bool [S]) of `pattern` by subset construction, state 0 the start."""
+    nfa, first, last = _thompson(pattern, max_states)
     n = len(nfa.eps)
     arcs = [i for i in range(n) if nfa.arc[i] is not None]
 

@@ -1,6 +1,7 @@
 """An automaton's tables on the device, pushed and minimised (§21) there before they are served:
 `DeviceConstraint` and the standalone `minimize` prepare theirs through the same three calls, `upload`, `pushed`, `minimized`;
-`product` (§22) makes the tables of two automata's conjunction, union or difference there, in front of that pipeline."""
+`product` (§22) makes the tables of two automata's conjunction, union or difference there, in front of that pipeline, and
+`determinize` (§23) those of a `ByteNFA`."""
 import ctypes as C
 import dataclasses
 
@@ -45,14 +46,7 @@ class DeviceTables:
         """The host side of an iteration whose stop rule is the device's: `name` called with up to `_BATCH` launches a time
         (`count`: the block's field for their number; the first call restarts) and the status words (iterations performed,
         converged, flags) read after each, until converged, flagged, `budget` iterations or `stop(iterations)`; the words."""
-        p.restart = 1
-        n = converged = flags = 0
-        while not converged and not flags and n < budget and not stop(n):
-            setattr(p, count, min(_BATCH, budget - n))
-            (self.eng.fsa_call if name.startswith("glb_fsa_") else self.eng.dfa_call)(name, p)
-            p.restart = 0
-            n, converged, flags = status[:3].tolist()
-        return n, converged, flags
+        return _iterate(self.eng, name, p, status, budget, count=count, stop=stop)
 
     def pushed(self, semiring, tol, max_sweeps):
         """(tables, beta, sweeps): backward weights by Jacobi sweeps on the device (glb_dfa_backward, in batches), then the
@@ -215,6 +209,116 @@ def _put(eng, a):
     return torch.from_numpy(np.ascontiguousarray(a)).to(eng.device)
 
 
+def _iterate(eng, name, p, status, budget, *, count, stop=lambda n: False, batch=_BATCH):
+    """`DeviceTables._iterate`, for any engine: the entry's prefix says which of the engine's calls takes it."""
+    call = eng.fsa_call if name.startswith("glb_fsa_") else eng.nfa_call if name.startswith("glb_nfa_") else eng.dfa_call
+    p.restart = 1
+    n = converged = flags = 0
+    while not converged and not flags and n < budget and not stop(n):
+        setattr(p, count, min(batch, budget - n))
+        call(name, p)
+        p.restart = 0
+        n, converged, flags = status[:3].tolist()
+    return n, converged, flags
+
+
+def _nfa_arrays(nfa):
+    """What the device reads of a `ByteNFA` (include/glb.h glb_nfa_args), as host arrays: the important states and their bit
+    indices, the empty arcs and the byte arcs as CSRs by source, the arcs' byte sets as four 64-bit words, the accepting
+    bits, and the byte groups - bytes that no arc's set tells apart - in the order of their lowest bytes.  No loop over
+    states.  Arrays the automaton leaves empty hold one unused element: the device is never handed a null pointer."""
+    n = nfa.n_states
+    imp = nfa.important
+    states = np.nonzero(imp)[0].astype(np.int32)
+    n_imp = len(states)
+    W = max(1, -(-n_imp // 64))
+    bit_of = np.where(imp, np.cumsum(imp) - 1, -1).astype(np.int32)
+    some = lambda a: a if len(a) else np.zeros((1,) + a.shape[1:], a.dtype)
+    order = np.argsort(nfa.eps_src, kind="stable")
+    eps_off = np.searchsorted(nfa.eps_src[order], np.arange(n + 1)).astype(np.int32)
+    order_a = np.argsort(bit_of[nfa.arc_src], kind="stable")
+    arc_off = np.searchsorted(bit_of[nfa.arc_src][order_a], np.arange(n_imp + 1)).astype(np.int32)
+    arc_set = nfa.arc_set[order_a]
+    bits = lambda b: np.ascontiguousarray(np.packbits(b, axis=-1, bitorder="little")).view("<u8")
+    if len(arc_set):
+        _, lo, group = np.unique(arc_set, axis=1, return_index=True, return_inverse=True)
+        rank = np.argsort(lo)  # (the groups in the order of their lowest bytes)
+        group_of = np.argsort(rank)[np.asarray(group).reshape(-1)].astype(np.int32)
+        group_lo = lo[rank].astype(np.int32)
+    else:
+        group_of, group_lo = np.zeros(256, np.int32), np.zeros(1, np.int32)
+    acc = np.zeros(W * 64, np.bool_)
+    acc[:n_imp] = nfa.accepting[states]
+    return dict(n_states=n, start=nfa.start, n_important=n_imp, n_words=W, n_arcs=len(arc_set), n_eps=len(order), n_groups=len(group_lo),
+                states=states, bit_of=bit_of, eps_off=eps_off, eps_to=some(nfa.eps_dst[order]), arc_off=arc_off,
+                arc_dst=some(nfa.arc_dst[order_a]), arc_bytes=some(bits(arc_set).reshape(-1, 4)), accepting_mask=bits(acc),
+                group_of=group_of, group_lo=group_lo)
+
+
+_NFA_CAND_BYTES = 64 << 20  # what the candidate sets of one round may take: `chunk` states of n_groups * n_words words each
+
+
+def _nfa_block(eng, arrays, cap, hash_mask=0):
+    """(block, buffers): a glb_nfa_args over `arrays` (`_nfa_arrays`) on `eng`'s device, the outputs allocated for `cap`
+    states and the candidate sets for as many states a round as `_NFA_CAND_BYTES` holds."""
+    import torch
+
+    dev = eng.device
+    new = lambda dtype, *shape: torch.empty(shape, dtype=dtype, device=dev)
+    G, W = arrays["n_groups"], arrays["n_words"]
+    chunk = int(max(1, min(cap, _NFA_CAND_BYTES // (8 * G * W))))
+    slots = 1 << max(1, (2 * cap - 1).bit_length())
+    # (uint64 arrays travel as int64: the bits are what the device reads)
+    buf = {k: _put(eng, v.view(np.int64) if v.dtype == np.uint64 else v) for k, v in arrays.items() if isinstance(v, np.ndarray)}
+    buf.update(eclose=new(torch.int64, arrays["n_states"], W), table=new(torch.int64, slots * 12 // 8), cand=new(torch.int64, chunk * G * W),
+               sets=new(torch.int64, cap, W), delta=new(torch.int32, cap, 256), accepting=new(torch.uint8, cap), counts=new(torch.int32, chunk),
+               status=torch.zeros(_lib.NFA_STATUS, dtype=torch.int32, device=dev))
+    p = _lib.NfaArgs()
+    p.struct_size = C.sizeof(_lib.NfaArgs)
+    for k in ("n_states", "start", "n_important", "n_words", "n_arcs", "n_eps", "n_groups"):
+        setattr(p, k, arrays[k])
+    for k in ("eps_off", "eps_to", "bit_of", "arc_off", "arc_dst", "arc_bytes", "accepting_mask", "group_of", "group_lo", "eclose", "table",
+              "cand", "sets", "counts", "status"):
+        setattr(p, k, buf[k].data_ptr())
+    p.delta_out, p.accepting_out = buf["delta"].data_ptr(), buf["accepting"].data_ptr()
+    p.hash_mask, p.max_states, p.chunk, p.table_slots = hash_mask, cap, chunk, slots
+    return p, buf
+
+
+def _nfa_search(eng, p, status, batch=_BATCH):
+    """The batch loops of `determinize` over a block of `_nfa_block`: the sweeps of the closure, then the rounds of the
+    search, the status words read between batches and nothing else; {"sweeps", "rounds", "states"}.  ValueError when the
+    search passes the block's max_states."""
+    cap = p.max_states
+    sweeps, converged, flags = _iterate(eng, "glb_nfa_closure", p, status[_lib.NFA_CLOSURE_STATUS:], p.n_states + 1, count="rounds", batch=batch)
+    if flags or not converged:
+        raise RuntimeError(f"determinize: the empty-arc closure had not settled after {sweeps} sweeps over {p.n_states} states")
+    rounds, converged, flags = _iterate(eng, "glb_nfa_subset_round", p, status, cap + 1, count="rounds", batch=batch)
+    if flags & 1:
+        raise ValueError(f"determinize: the search passed max_states={cap}: it had reached at least {int(status[7])} states in round "
+                         f"{rounds + 1} and was not at its end; nothing is returned")
+    if flags:
+        raise RuntimeError(f"determinize: the search raised flag bit 1 (flags {flags}: a reference out of range) after {rounds} rounds")
+    if not converged:
+        raise RuntimeError(f"determinize: the search had not ended after {rounds} rounds over at most {cap} states")
+    return dict(sweeps=sweeps, rounds=rounds, states=int(status[3]))
+
+
+def _nfa_live(eng, delta, accepting, n):
+    """uint8 [n] on the device: glb_fsa_live over the first n rows of `delta` / `accepting` (it reads nothing else of its block)."""
+    import torch
+
+    live = torch.empty(n, dtype=torch.uint8, device=eng.device)
+    status = torch.zeros(_lib.FSA_STATUS, dtype=torch.int32, device=eng.device)
+    q = _lib.FsaProductArgs()
+    q.struct_size, q.n_states, q.max_states = C.sizeof(_lib.FsaProductArgs), n, n
+    q.delta_out, q.accepting_out, q.live, q.status = delta.data_ptr(), accepting.data_ptr(), live.data_ptr(), status.data_ptr()
+    sweeps, converged, flags = _iterate(eng, "glb_fsa_live", q, status[_lib.FSA_LIVE_STATUS:], n + 1, count="rounds")
+    if flags or not converged:
+        raise RuntimeError(f"determinize: liveness had not settled after {sweeps} sweeps over {n} states")
+    return live
+
+
 def _kept(automaton):
     """live & reachable, and the start state whatever it is: the quotient always has one."""
     keep = automaton.live & automaton.reachable
@@ -279,3 +383,43 @@ def product(llm_or_engine, a, b, op="and", max_states=1 << 18):
         fin = host(tables.final_logw)
         return kind._from_device(host(tables.delta), fin > -np.inf, 0, host(tables.live), host(tables.arc_logw), fin), pairs
     return kind._from_device(host(tables.delta), host(tables.accepting), 0, host(tables.live)), pairs
+
+
+def determinize(llm_or_engine, nfa, max_states=65536, *, _hash_mask=0, _batch=_BATCH):
+    """(automaton, sets, states): the `ByteDFA` of the byte strings that the `ByteNFA` `nfa` accepts, by the subset
+    construction on the device (include/glb.h glb_nfa_closure / glb_nfa_subset_round); host uint64 [S, W], every
+    state's set of NFA states as a bitset; and int32 [n_important], the NFA state behind every bit (bit i of a set is word
+    i // 64, bit i % 64).  A state of `nfa` is important when it has a byte arc or accepts; a state of the result is the set
+    of important states inside the empty-arc closure of what was reached, W = max(1, ceil(n_important / 64)).  State 0 is the
+    closure of the start; the empty set is no state - an arc into it is -1 - and a state accepts where its set holds an
+    accepting state.  The states are numbered in the order in which a queue search first meets the sets (states in id
+    order, bytes ascending), the rule of `product`; nothing is trimmed or merged (`minimize`, `DeviceConstraint(minimize=
+    True)`), and `live` of the result comes from the device.  ValueError, before the device is touched, for something that
+    is no `ByteNFA`, a `max_states` that is no int >= 1, and more than 4096 important states (a set is one wave of 64-bit
+    words); and when the search passes `max_states` states before it ends: nothing partial is returned, the message names
+    `max_states` and the count reached when the search stopped.  The outputs are allocated for `max_states` rows before the
+    search (1 KB and W words a row); no automaton has more than 2^n_important states, so a larger `max_states` allocates
+    that many, and the device numbers at most 2^22."""
+    from .nfa import ByteNFA
+
+    if isinstance(nfa, ByteWFSA):
+        raise ValueError("determinize takes an unweighted ByteNFA: weighted determinisation need not terminate")
+    if not isinstance(nfa, ByteNFA):
+        raise ValueError(f"determinize needs a ByteNFA (ByteNFA.from_dfa wraps a ByteDFA), got {type(nfa).__name__}")
+    if isinstance(max_states, bool) or not isinstance(max_states, (int, np.integer)) or max_states < 1:
+        raise ValueError(f"max_states must be an int >= 1, got {max_states!r}")
+    n_imp = int(nfa.important.sum())
+    if n_imp > _lib.NFA_MAX_IMPORTANT:
+        raise ValueError(f"determinize: {n_imp} important states (those with a byte arc, and the accepting ones) pass the cap of "
+                         f"{_lib.NFA_MAX_IMPORTANT}: a set of them is one wave of 64-bit words")
+    cap = int(min(int(max_states), 1 << min(n_imp, 30)))  # (no automaton has more sets)
+    if cap > _lib.NFA_MAX_STATES:
+        raise ValueError(f"max_states={max_states}: the device search numbers at most {_lib.NFA_MAX_STATES} states")
+    eng = getattr(llm_or_engine, "engine", llm_or_engine)
+    arrays = _nfa_arrays(nfa)
+    p, buf = _nfa_block(eng, arrays, cap, _hash_mask)
+    n = _nfa_search(eng, p, buf["status"], _batch)["states"]  # (it can pass cap only where cap is max_states)
+    live = _nfa_live(eng, buf["delta"], buf["accepting"], n)
+    host = lambda t: t[:n].cpu().numpy()
+    dfa = ByteDFA._from_device(host(buf["delta"]), host(buf["accepting"]), 0, host(live))
+    return dfa, np.ascontiguousarray(host(buf["sets"]).view(np.uint64)), arrays["states"]

@@ -1287,6 +1287,85 @@ typedef struct glb_fsa_product_args {
 int glb_fsa_product_round(const glb_fsa_product_args *args, void *hip_stream);
 int glb_fsa_live(const glb_fsa_product_args *args, void *hip_stream);
 
+/*
+ * Determinisation: the deterministic automaton of a byte NFA with empty arcs, by the subset construction.
+ * The NFA: n_states states, `start`; empty arcs as a CSR by source (eps_off [n_states + 1], eps_to [n_eps]); byte arcs as a
+ * CSR by source over the IMPORTANT states (arc_off [n_important + 1], arc_dst [n_arcs], arc_bytes [n_arcs][4]: bit b of the
+ * 256 is set where the arc reads byte b).  A state is important when it has a byte arc or accepts; bit_of [n_states] gives an
+ * important state its bit index in [0, n_important) and every other state -1, accepting_mask [n_words] has the bits of the
+ * accepting states.  A state of the result is the set of important states inside the empty-arc closure of what was reached,
+ * a bitset of n_words = max(1, ceil(n_important / 64)) 64-bit words, n_important <= GLB_NFA_MAX_IMPORTANT: a wave holds a set,
+ * a lane a word.  State 0 is the closure of `start` (it may be empty: a state without arcs).  The empty set is no other
+ * state: an arc into it is -1.  A state accepts where its set holds an accepting state.  The states are numbered in the order
+ * in which a queue search first meets the sets, states in id order and bytes 0 .. 255 ascending, whatever order the atomics
+ * take.  Bytes that no arc's set tells apart form a GROUP (group_of [256], int32; group_lo [n_groups], the lowest byte of
+ * every group, ascending): the search expands a group once, at its lowest byte, and writes delta_out for all its bytes.
+ *   glb_nfa_closure       `restart` != 0: eclose [n_states][n_words] = every important state's own bit, status[8 .. 11] = 0.
+ *                     Then `rounds` sweeps of eclose[v] |= eclose[u] over the empty arcs v -> u, in place (the rule only
+ *                     adds: the fixed point is unique), two launches each.  status [8] sweeps performed, the one that
+ *                     changed nothing included   [9] converged   [10] zero   [11] private.  Reads n_states, start,
+ *                     n_important, n_words, n_eps, eps_off, eps_to, bit_of, eclose, status, rounds, restart alone.
+ *   glb_nfa_subset_round  over a converged eclose.  `restart` != 0: the table emptied, status[0 .. 7] and [12 ..] = 0, state 0
+ *                     made.  Then `rounds` rounds, seven launches each, every grid sized to the device and striding over
+ *                     the states the status words bound; a round takes the next `chunk` states of the queue: the target
+ *                     set of every (state, group) written to `cand` [chunk][n_groups][n_words]; every target entered into
+ *                     `table`; the arcs that are first to a new set counted a state, the counts scanned, the new states
+ *                     numbered (`sets` [max_states][n_words], accepting_out), delta_out's arcs into them resolved, the
+ *                     queue moved on.  A round that finds the queue empty behind it sets the converged word; with it or a
+ *                     flag set every later launch leaves at once.  status:
+ *                       [0] rounds performed since the restart   [1] converged
+ *                       [2] flags, sticky: bit 0 - more than max_states states (nothing of that round is numbered);
+ *                           bit 1 - a reference or an id out of range: a bug, never an input
+ *                       [3] states numbered   [4], [5] the states of the round   [6] private
+ *                       [7] with flag bit 0: the sets found when the search stopped, more than max_states
+ *                       [12] private: the distinct sets entered into the table, state 0 included
+ *                     Bit 0 goes up in the middle of the launch that enters the set past max_states, and that launch
+ *                     drains: its waves leave at their next target and their probes within 32 slots.
+ *                     `table`: 12 bytes a slot (table_slots 64-bit words, then int32 arc indices), aligned to 8.  A slot's
+ *                     word holds no set: 31 bits of the set's hash and a reference, the arc index (queue position in the
+ *                     round * 256 + the group's lowest byte) that claimed it in this round - the set is that arc's row of
+ *                     `cand` - or the id of a numbered state - the set is its row of `sets`.  An equal hash is followed by
+ *                     a compare of the sets, unequal sets probe on.  hash_mask != 0 is ANDed onto the 64-bit hash before
+ *                     it is used (a test's way of making nearly all sets collide: the arrays must not change).
+ *                     `counts`: `chunk` int32 of scratch.  max_states <= 2^22, chunk in [1, max_states].
+ * GLB_EINVAL before any launch, buffers untouched, the field named in the message: struct_size wrong, n_states outside
+ * [1, 2^24], n_important outside [0, min(n_states, GLB_NFA_MAX_IMPORTANT)], n_words not what n_important gives, start outside
+ * the automaton, rounds outside [1, 65536], eclose or status null; closure: n_eps negative, eps_off, eps_to or bit_of null;
+ * round: n_arcs negative, n_groups outside [1, 256], max_states or chunk out of range, an arc, mask or group table null,
+ * table_slots not a power of two or below 2 max_states, table, cand, sets, delta_out, accepting_out or counts null.  Nothing
+ * synchronises or allocates: the host reads `status`.  Liveness of the result: glb_fsa_live over delta_out / accepting_out.
+ */
+#define GLB_NFA_STATUS 16
+#define GLB_NFA_MAX_IMPORTANT 4096
+typedef struct glb_nfa_args {
+  uint32_t struct_size; /* sizeof(glb_nfa_args) - ABI guard */
+  int32_t n_states, start;
+  int32_t n_important, n_words;
+  int32_t n_arcs, n_eps, n_groups;
+  const int32_t *eps_off, *eps_to;        /* [n_states + 1], [n_eps] */
+  const int32_t *bit_of;                  /* [n_states] */
+  const int32_t *arc_off, *arc_dst;       /* [n_important + 1], [n_arcs] */
+  const uint64_t *arc_bytes;              /* [n_arcs][4] */
+  const uint64_t *accepting_mask;         /* [n_words] */
+  const int32_t *group_of, *group_lo;     /* [256], [n_groups] */
+  uint64_t *eclose;                       /* [n_states][n_words] */
+  uint64_t hash_mask;                     /* 0: every bit of the hash */
+  int32_t max_states;
+  int32_t chunk;                          /* states of the queue a round takes */
+  void *table;                            /* 12 * table_slots bytes */
+  int64_t table_slots;                    /* a power of two >= 2 * max_states */
+  uint64_t *cand;                         /* [chunk][n_groups][n_words] */
+  uint64_t *sets;                         /* [max_states][n_words], out */
+  int32_t *delta_out;                     /* [max_states, 256], out */
+  uint8_t *accepting_out;                 /* [max_states], out */
+  int32_t *counts;                        /* [chunk] */
+  int32_t *status;                        /* [GLB_NFA_STATUS] */
+  int32_t rounds;                         /* sweeps / rounds of this call */
+  int32_t restart;
+} glb_nfa_args;
+int glb_nfa_closure(const glb_nfa_args *args, void *hip_stream);
+int glb_nfa_subset_round(const glb_nfa_args *args, void *hip_stream);
+
 /* Philox4x32-10 block function, exposed so hosts can reproduce the device draws. */
 void glb_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 
