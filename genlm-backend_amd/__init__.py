@@ -18,7 +18,7 @@ def __getattr__(name):
     if name in ("load_model_by_name", "AsyncAmdLM", "AsyncLM"):
         from . import llm
         return getattr(llm, name)
-    if name in ("ByteDFA", "ByteWFSA", "DeviceConstraint", "minimize", "product", "ByteNFA", "determinize"):
+    if name in ("ByteDFA", "ByteWFSA", "DeviceConstraint", "minimize", "product", "ByteNFA", "determinize", "LazyConstraint"):
         from . import constraints
         return getattr(constraints, name)
     raise AttributeError(name)

@@ -382,6 +382,30 @@ class NfaArgs(C.Structure):
     ]
 
 
+LAZY_STATUS = 8  # GLB_LAZY_STATUS: states numbered, flags (sticky), the states numbered when the running call began, private
+LAZY_OVERFLOW, LAZY_BUG = 1, 2
+
+
+class LazyArgs(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("dfa", DfaArgs),
+        ("n_nfa_states", C.c_int32), ("nfa_start", C.c_int32),
+        ("n_important", C.c_int32), ("n_words", C.c_int32),
+        ("n_arcs", C.c_int32),
+        ("max_states", C.c_int32),
+        ("arc_off", C.c_void_p), ("arc_dst", C.c_void_p), ("arc_bytes", C.c_void_p), ("accepting_mask", C.c_void_p),
+        ("eclose", C.c_void_p),
+        ("hash_mask", C.c_uint64),
+        ("table", C.c_void_p), ("table_slots", C.c_int64),
+        ("cand", C.c_void_p), ("counts", C.c_void_p), ("cand_rows", C.c_int64),
+        ("sets", C.c_void_p), ("accepting_out", C.c_void_p), ("status", C.c_void_p),
+        ("row_state", C.c_void_p), ("row_stamp", C.c_void_p), ("claimants", C.c_void_p), ("victims", C.c_void_p),
+        ("ecounters", C.c_void_p), ("epoch", C.c_void_p),
+        ("force_wave", C.c_int32),
+    ]
+
+
 # every symbol include/glb.h declares: name -> (restype, argtypes)
 _vp, _i32, _i64, _f32, _sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_size_t
 SYMBOLS = {
@@ -480,6 +504,9 @@ SYMBOLS = {
     "glb_fsa_live": (C.c_int, [C.POINTER(FsaProductArgs), _vp]),
     "glb_nfa_closure": (C.c_int, [C.POINTER(NfaArgs), _vp]),
     "glb_nfa_subset_round": (C.c_int, [C.POINTER(NfaArgs), _vp]),
+    "glb_lazy_init": (C.c_int, [C.POINTER(LazyArgs), _vp]),
+    "glb_lazy_advance": (C.c_int, [C.POINTER(LazyArgs), _vp]),
+    "glb_lazy_serve": (C.c_int, [C.POINTER(LazyArgs), _vp]),
     "glb_philox4x32_10": (None, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
 }
 

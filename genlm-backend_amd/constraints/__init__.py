@@ -16,9 +16,13 @@ for `DeviceConstraint(..., minimize=True)` to shrink and serve.
 
 `ByteNFA` is a byte automaton with empty arcs - the union of any number of automata, their concatenation, their closure, a
 pattern's Thompson automaton - and `determinize(llm, nfa)` its `ByteDFA`, by the subset construction on the device.
+
+`LazyConstraint` serves a `ByteNFA` as it is: the subset states are made on the device when a particle reaches
+them, so a pattern whose deterministic automaton is too large to build still constrains a population that visits little of it.
 """
 from .automata import ByteDFA, ByteWFSA  # noqa: F401
 from .device import DeviceConstraint  # noqa: F401
+from .lazy import LazyConstraint  # noqa: F401
 from .nfa import ByteNFA  # noqa: F401
 from .regex import _regex_dfa  # noqa: F401
 from .tables import DeviceTables, _kept, determinize, minimize, product  # noqa: F401

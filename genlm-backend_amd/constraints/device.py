@@ -17,7 +17,118 @@ _FLOAT_BANK = _BankKind("float32", lambda V: (V + 63) // 64 * 64, lambda V: V, _
                         "glb_dfa_weight_bank_init", "glb_dfa_fill_weights", lambda c, a: c._weight_args(a))
 
 
-class DeviceConstraint:
+class _Bank:
+    """What every constraint that serves rows of a bank shares (`DeviceConstraint`, `lazy.LazyConstraint`): the vocabulary on
+    the device, the bank's row ids as the fused step takes them, its counters and what `check()` says of a full bank.  A
+    subclass sets `eng`, `dev`, `bank`, `_kind`, `weighted`, `_counters`, `_evicting`, `_evict_tables`, `mask_bank_bytes` and
+    `row_elems`."""
+
+    def _upload_vocab(self, llm_or_engine, byte_vocab, eos_id, skip_ids):
+        """The byte strings of the vocabulary back to back, their offsets and the skipped ids on `self.eng`'s device;
+        `vocab`, `eos_id`, `words`, `n_bytes`."""
+        toks = [bytes(getattr(t, "byte_string", t)) for t in byte_vocab]
+        V = len(toks)
+        if V == 0:
+            raise ValueError("empty vocabulary")
+        if skip_ids is None:
+            skip_ids = getattr(getattr(llm_or_engine, "tokenizer", None), "all_special_ids", None) or ()
+        skip = np.zeros(V, np.uint8)
+        for t in skip_ids:
+            if 0 <= int(t) < V:
+                skip[int(t)] = 1
+        ptr = np.zeros(V + 1, np.int64)
+        np.cumsum([len(t) for t in toks], out=ptr[1:])
+        if ptr[-1] > 0x7fffffff:
+            raise ValueError("the vocabulary's byte strings exceed 2^31 bytes")
+        flat = np.frombuffer(b"".join(toks) or b"\0", np.uint8).copy()
+        self.vocab, self.eos_id, self.words = V, int(eos_id), (V + 31) // 32
+        self.n_bytes = int(ptr[-1])
+        eng = self.eng
+        self._bytes, self._ptr, self._skip = _put(eng, flat), _put(eng, ptr.astype(np.int32)), _put(eng, skip)
+        self._gathered, self._cus = None, None
+
+    capacity = property(lambda self: self.bank.shape[0])
+
+    def _states(self, states):
+        import torch
+
+        if states.dtype != torch.int32 or states.dim() != 1 or states.device != self.dev or not states.is_contiguous():
+            raise ValueError("states must be a contiguous int32 [n] tensor on the engine's device")
+        return states
+
+    def step_masks(self, logits, ids, by_row, n_particles, parity=False):
+        """The fused step's mask arguments (masks.py; `logits` is not read) for bank rows `ids` (int32 [n_units]: per logits
+        row when `by_row`, else per particle), and whether the bank itself is handed over.  `GLB_MASK_BITS` rows are read as they are only by the
+        step's one-launch form; its two-launch form first brings ALL rows of the table it is given into the kernels'
+        layout.  So the bank is handed over where glb_logprob_mask_sample takes the one-launch form (csrc/glb_api.hip,
+        `fused`: no parity draw, more than 512 (unit, 4096-token chunk) items, at most 16 x 8 x CUs particles), and
+        otherwise only the units' rows, gathered into a buffer of this object.  This is the one place the rule is
+        restated; where it guesses wrong (a stream being captured, a workspace nobody registered) the step still computes
+        the same results from the whole bank, only slower.
+        A weight bank (`GLB_MASK_F32`) is read where it lies by both forms: always handed over, nothing gathered."""
+        import torch
+
+        key = "row_mask_id" if by_row else "mask_id"
+        n_units = ids.numel()
+        if self._cus is None:
+            self._cus = torch.cuda.get_device_properties(self.dev).multi_processor_count
+        if self.weighted or (not parity and n_units * ((self.vocab + 4095) // 4096) > 512 and n_particles <= 16 * 8 * self._cus):
+            return {"mask_kind": self._kind.mask_kind, "mask": self.bank, key: ids}, True
+        if self._gathered is None or self._gathered[0].shape[0] != n_units:
+            self._gathered = (torch.empty((n_units, self.words), dtype=torch.int32, device=self.dev),
+                              torch.arange(n_units, dtype=torch.int32, device=self.dev))
+        buf, own = self._gathered
+        self.eng.gather_rows_i32(self.bank[:, :self.words], ids, out=buf)
+        return {"mask_kind": _lib.MASK_BITS, "mask": buf, key: own}, False
+
+    def _new_evict_tables(self):
+        """The tables of an evicting bank, one allocation: four int32 [capacity], the eviction counters, the epoch."""
+        import torch
+
+        return torch.zeros(4 * self.capacity + _lib.DFA_EVICT_COUNTERS + 1, dtype=torch.int32, device=self.dev)
+
+    def _evict_fields(self, e):
+        """(the six fields of the eviction tables, of either block that carries them)"""
+        cap, base = self.capacity, self._evict_tables.data_ptr()
+        e.row_state, e.row_stamp, e.claimants, e.victims = (base + 4 * cap * i for i in range(4))
+        e.ecounters = base + 16 * cap
+        e.epoch = e.ecounters + 4 * _lib.DFA_EVICT_COUNTERS
+        return e
+
+    def _overflow_word(self):
+        """int32 [1] device view of the sticky overflow word, for hosts that let it ride on a copy they make anyway."""
+        return self._counters[2:3]
+
+    def _rows_in_use(self):
+        """(synchronises)"""
+        return int(self._counters[0].item())
+
+    def stats(self):
+        """{"rows_in_use", "fills", "evictions"}: the bank's rows that hold something (its own two included), the rows
+        filled so far and how many of those were taken from another state (synchronises)."""
+        rows, filled = self._counters[:2].tolist()
+        if not self._evicting:
+            return {"rows_in_use": rows, "fills": filled, "evictions": 0}
+        fills, evictions = self._evict_tables[4 * self.capacity + 2:4 * self.capacity + 4].tolist()
+        return {"rows_in_use": rows, "fills": fills, "evictions": evictions}
+
+    def check(self, word=None):
+        """Raises when a state found no row in the bank (synchronises unless `word`, the overflow word's value already on
+        the host, is given).  Under eviction that is: one call asked for more distinct states than the bank has rows."""
+        if not (int(self._counters[2].item()) if word is None else int(word)):
+            return
+        if self._evicting:
+            raise RuntimeError(f"the constraint's mask bank is smaller than one step's working set: a single mask_rows call "
+                               f"asked for more distinct automaton states than its {self.capacity - 2} rows for states "
+                               f"({self.capacity} rows of {self.row_elems * 4} bytes, mask_bank_bytes={self.mask_bank_bytes}); "
+                               "the states left over were served the empty mask.  The bank must hold at least as many rows "
+                               "as the particles occupy distinct states, plus two.  Raise mask_bank_bytes.")
+        raise RuntimeError(f"the constraint's mask bank is full: {self.capacity} rows of {self.row_elems * 4} bytes "
+                           f"(mask_bank_bytes={self.mask_bank_bytes}) do not hold the automaton states the particles "
+                           "reached; their masks were empty.  Raise mask_bank_bytes.")
+
+
+class DeviceConstraint(_Bank):
     """A `ByteDFA` over a vocabulary's byte strings, resident on the device.
 
     llm_or_engine    an `AsyncAmdLM` (its engine and, for the default `skip_ids`, its tokenizer's `all_special_ids`) or a
@@ -91,26 +202,9 @@ class DeviceConstraint:
         self.on_full = on_full
         eng = getattr(llm_or_engine, "engine", llm_or_engine)
         self.eng, self.dev, self.dfa = eng, eng.device, dfa
-        toks = [bytes(getattr(t, "byte_string", t)) for t in byte_vocab]
-        V = len(toks)
-        if V == 0:
-            raise ValueError("empty vocabulary")
-        if skip_ids is None:
-            skip_ids = getattr(getattr(llm_or_engine, "tokenizer", None), "all_special_ids", None) or ()
-        skip = np.zeros(V, np.uint8)
-        for t in skip_ids:
-            if 0 <= int(t) < V:
-                skip[int(t)] = 1
-        ptr = np.zeros(V + 1, np.int64)
-        np.cumsum([len(t) for t in toks], out=ptr[1:])
-        if ptr[-1] > 0x7fffffff:
-            raise ValueError("the vocabulary's byte strings exceed 2^31 bytes")
-        flat = np.frombuffer(b"".join(toks) or b"\0", np.uint8).copy()
-        self.vocab, self.eos_id, self.words = V, int(eos_id), (V + 31) // 32
-        self.n_bytes = int(ptr[-1])
-        self._bytes, self._ptr, self._skip = _put(eng, flat), _put(eng, ptr.astype(np.int32)), _put(eng, skip)
+        self._upload_vocab(llm_or_engine, byte_vocab, eos_id, skip_ids)
+        V = self.vocab
         self.mask_bank_bytes = int(mask_bank_bytes)
-        self._gathered, self._cus = None, None
         self.tables = DeviceTables.upload(eng, dfa)
         self.weighted = self.tables.weighted
         self.push, self.backward, self.start_logw, self._push_sweeps = push, None, 0.0, 0
@@ -176,8 +270,7 @@ class DeviceConstraint:
         self._work = torch.zeros((bank.shape[0], 2), dtype=torch.int32, device=self.dev)
         # a bank that cannot hold every state, allowed to evict: the tables of glb_dfa_evict_args, one allocation
         self._evicting = self.on_full == "evict" and self.dfa.n_states + 2 > bank.shape[0]
-        self._evict_tables = torch.zeros(4 * bank.shape[0] + _lib.DFA_EVICT_COUNTERS + 1, dtype=torch.int32, device=self.dev) \
-            if self._evicting else None
+        self._evict_tables = self._new_evict_tables() if self._evicting else None
         self._reset_bank()
 
     def _reset_bank(self):
@@ -187,8 +280,6 @@ class DeviceConstraint:
             self._call("glb_dfa_evict_bank_init", self._evict_args(self._args()))
         else:
             self._call(self._kind.init, self._kind.args(self, self._args()))
-
-    capacity = property(lambda self: self.bank.shape[0])
 
     def _args(self):
         a = _lib.DfaArgs()
@@ -219,21 +310,10 @@ class DeviceConstraint:
         e.struct_size, e.dfa = C.sizeof(_lib.DfaEvictArgs), a
         if self.weighted:
             self._float_bank(e)
-        cap, base = self.capacity, self._evict_tables.data_ptr()
-        e.row_state, e.row_stamp, e.claimants, e.victims = (base + 4 * cap * i for i in range(4))
-        e.ecounters = base + 16 * cap
-        e.epoch = e.ecounters + 4 * _lib.DFA_EVICT_COUNTERS
-        return e
+        return self._evict_fields(e)
 
     def _call(self, name, a):
         self.eng.dfa_call(name, a)
-
-    def _states(self, states):
-        import torch
-
-        if states.dtype != torch.int32 or states.dim() != 1 or states.device != self.dev or not states.is_contiguous():
-            raise ValueError("states must be a contiguous int32 [n] tensor on the engine's device")
-        return states
 
     # ---- states --------------------------------------------------------------------------------------------------------
     def states0(self, n):
@@ -305,31 +385,6 @@ class DeviceConstraint:
             self._call("glb_dfa_mask_ids", a)
         return out
 
-    def step_masks(self, logits, ids, by_row, n_particles, parity=False):
-        """The fused step's mask arguments (masks.py; `logits` is not read) for bank rows `ids` (int32 [n_units]: per logits
-        row when `by_row`, else per particle), and whether the bank itself is handed over.  `GLB_MASK_BITS` rows are read as they are only by the
-        step's one-launch form; its two-launch form first brings ALL rows of the table it is given into the kernels'
-        layout.  So the bank is handed over where glb_logprob_mask_sample takes the one-launch form (csrc/glb_api.hip,
-        `fused`: no parity draw, more than 512 (unit, 4096-token chunk) items, at most 16 x 8 x CUs particles), and
-        otherwise only the units' rows, gathered into a buffer of this object.  This is the one place the rule is
-        restated; where it guesses wrong (a stream being captured, a workspace nobody registered) the step still computes
-        the same results from the whole bank, only slower.
-        A weight bank (`GLB_MASK_F32`) is read where it lies by both forms: always handed over, nothing gathered."""
-        import torch
-
-        key = "row_mask_id" if by_row else "mask_id"
-        n_units = ids.numel()
-        if self._cus is None:
-            self._cus = torch.cuda.get_device_properties(self.dev).multi_processor_count
-        if self.weighted or (not parity and n_units * ((self.vocab + 4095) // 4096) > 512 and n_particles <= 16 * 8 * self._cus):
-            return {"mask_kind": self._kind.mask_kind, "mask": self.bank, key: ids}, True
-        if self._gathered is None or self._gathered[0].shape[0] != n_units:
-            self._gathered = (torch.empty((n_units, self.words), dtype=torch.int32, device=self.dev),
-                              torch.arange(n_units, dtype=torch.int32, device=self.dev))
-        buf, own = self._gathered
-        self.eng.gather_rows_i32(self.bank[:, :self.words], ids, out=buf)
-        return {"mask_kind": _lib.MASK_BITS, "mask": buf, key: own}, False
-
     def forced_final_logw(self, states, forced):
         """float32 [n]: final_logw[states[i]] where `forced` (bool [n]: the particle was served row 1 and ended) and 0.0
         elsewhere - what a caller adds to the log-weight of a particle made to end, so that it weighs what one that chose
@@ -350,35 +405,3 @@ class DeviceConstraint:
             self._claim_and_fill(torch.arange(self.dfa.n_states, dtype=torch.int32, device=self.dev))
             self._warm = True
         return True
-
-    def _overflow_word(self):
-        """int32 [1] device view of the sticky overflow word, for hosts that let it ride on a copy they make anyway."""
-        return self._counters[2:3]
-
-    def _rows_in_use(self):
-        """(synchronises)"""
-        return int(self._counters[0].item())
-
-    def stats(self):
-        """{"rows_in_use", "fills", "evictions"}: the bank's rows that hold something (its own two included), the rows
-        filled so far and how many of those were taken from another state (synchronises)."""
-        rows, filled = self._counters[:2].tolist()
-        if not self._evicting:
-            return {"rows_in_use": rows, "fills": filled, "evictions": 0}
-        fills, evictions = self._evict_tables[4 * self.capacity + 2:4 * self.capacity + 4].tolist()
-        return {"rows_in_use": rows, "fills": fills, "evictions": evictions}
-
-    def check(self, word=None):
-        """Raises when a state found no row in the bank (synchronises unless `word`, the overflow word's value already on
-        the host, is given).  Under eviction that is: one call asked for more distinct states than the bank has rows."""
-        if not (int(self._counters[2].item()) if word is None else int(word)):
-            return
-        if self._evicting:
-            raise RuntimeError(f"the constraint's mask bank is smaller than one step's working set: a single mask_rows call "
-                               f"asked for more distinct automaton states than its {self.capacity - 2} rows for states "
-                               f"({self.capacity} rows of {self.row_elems * 4} bytes, mask_bank_bytes={self.mask_bank_bytes}); "
-                               "the states left over were served the empty mask.  The bank must hold at least as many rows "
-                               "as the particles occupy distinct states, plus two.  Raise mask_bank_bytes.")
-        raise RuntimeError(f"the constraint's mask bank is full: {self.capacity} rows of {self.row_elems * 4} bytes "
-                           f"(mask_bank_bytes={self.mask_bank_bytes}) do not hold the automaton states the particles "
-                           "reached; their masks were empty.  Raise mask_bank_bytes.")

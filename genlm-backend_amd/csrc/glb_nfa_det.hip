@@ -14,6 +14,7 @@
 
 #include "../../include/glb.h"
 #include "glb_common.hpp"
+#include "glb_set.hpp"
 
 namespace {
 
@@ -23,12 +24,10 @@ enum { P_ROUNDS = 0, P_CONVERGED = 1, P_FLAGS = 2, P_COUNT = 3, P_LO = 4, P_HI =
 enum { F_OVERFLOW = 1, F_TABLE = 2 };
 constexpr int NFA_THREADS = 256;  // four waves, an item each; count / number / resolve: the 256 bytes of one state
 constexpr int NFA_WAVES = NFA_THREADS / 64;
-constexpr int SCAN_THREADS = 1024;
 constexpr int NFA_MAX_ROUNDS = 65536;        // rounds / sweeps one call may enqueue
 constexpr int32_t NFA_MAX_STATES = 1 << 22;  // (an arc index queue position * 256 + byte stays below 2^31)
 constexpr int32_t NFA_MAX_NFA_STATES = 1 << 24;
 constexpr int32_t NO_ARC = 0x7fffffff;
-constexpr uint32_t TAG_USED = 0x80000000u;  // the high half of a slot that is not empty: this bit and 31 bits of hash
 constexpr uint32_t REF_ARC = 0x80000000u;   // the low half: this bit and an arc index of the round, else the id of a numbered state
 
 struct Det {
@@ -47,34 +46,6 @@ struct Det {
   uint8_t *accepting_out;
   int32_t *status;
 };
-
-__device__ inline uint64_t mix64(uint64_t x) {  // (the finaliser of splitmix64)
-  x ^= x >> 30;
-  x *= 0xbf58476d1ce4e5b9ull;
-  x ^= x >> 27;
-  x *= 0x94d049bb133111ebull;
-  return x ^ (x >> 31);
-}
-
-// lane `src`'s value in every lane
-__device__ inline uint64_t bcast64(uint64_t v, int src) {
-  const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, src), hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), src);
-  return ((uint64_t)hi << 32) | lo;
-}
-
-// the hash of the set a wave holds (lanes >= W hold zero and add nothing), the same in every lane
-__device__ inline uint64_t set_hash(uint64_t word, int lane) {
-  uint64_t h = word ? mix64(word ^ ((uint64_t)(lane + 1) * 0x9e3779b97f4a7c15ull)) : 0ull;
-  for (int d = 32; d >= 1; d >>= 1) {
-    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)h, d), hi = (uint32_t)__shfl_xor((int)(uint32_t)(h >> 32), d);
-    h ^= ((uint64_t)hi << 32) | lo;
-  }
-  return mix64(h);
-}
-
-__device__ inline unsigned long long word_now(const unsigned long long *w) {
-  return __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 
 __device__ inline int32_t flags_now(const int32_t *status) {
   return __hip_atomic_load(&status[P_FLAGS], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -152,10 +123,7 @@ __device__ inline bool set_accepts(const Det &p, uint64_t word, int lane) { retu
 
 // where the probing of a set starts, and the high half of its slot
 __device__ inline void set_key(const Det &p, uint64_t word, int lane, uint64_t &slot, uint32_t &high) {
-  uint64_t h = set_hash(word, lane);
-  if (p.hash_mask) h &= p.hash_mask;
-  high = TAG_USED | (uint32_t)((h ^ (h >> 31)) & 0x7fffffffu);
-  slot = mix64(h) & p.mask;
+  set_key(p.hash_mask, p.mask, word, lane, slot, high);
 }
 
 // state 0: the closure of the start, one wave; an empty set is a state here and nowhere else, and stays out of the table
@@ -313,28 +281,9 @@ __global__ __launch_bounds__(SCAN_THREADS) void nfa_scan_kernel(Det p) {
   if (stopped(p.status)) return;  // (uniform: the block's one writer of the words comes behind the last barrier)
   int32_t lo;
   const int32_t nk = round_states(p, lo);
-  const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
-  if (threadIdx.x == 0) carry = 0;
-  __syncthreads();
-  for (int32_t base = 0; base < nk; base += SCAN_THREADS) {
-    const int32_t k = base + (int32_t)threadIdx.x;
-    const int32_t v = k < nk ? p.cnt[k] : 0;
-    int32_t incl = v;
-    for (int d = 1; d < 64; d <<= 1) {
-      const int32_t up = __shfl_up(incl, d);
-      if (lane >= d) incl += up;
-    }
-    if (lane == 63) wave_sum[wave] = incl;
-    __syncthreads();
-    int32_t before = carry;
-    for (int w = 0; w < wave; ++w) before += wave_sum[w];
-    if (k < nk) p.cnt[k] = before + incl - v;
-    __syncthreads();
-    if (threadIdx.x == SCAN_THREADS - 1) carry = before + incl;
-    __syncthreads();
-  }
+  const int32_t total = scan_exclusive(p.cnt, nk, wave_sum, &carry);
   if (threadIdx.x == 0) {
-    const int64_t next = (int64_t)p.status[P_COUNT] + carry;  // (carry <= 256 * chunk <= 2^30)
+    const int64_t next = (int64_t)p.status[P_COUNT] + total;  // (total <= 256 * chunk <= 2^30)
     if (next > p.max_states) {
       atomicMax(&p.status[P_REACHED], (int32_t)next);
       atomicOr(&p.status[P_FLAGS], F_OVERFLOW);

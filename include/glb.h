@@ -1366,6 +1366,95 @@ typedef struct glb_nfa_args {
 int glb_nfa_closure(const glb_nfa_args *args, void *hip_stream);
 int glb_nfa_subset_round(const glb_nfa_args *args, void *hip_stream);
 
+/*
+ * Lazy determinisation: a byte NFA served as a constraint, its subset states made on the device when a
+ * particle reaches them.  The NFA arrays are those of glb_nfa_args - arc_off, arc_dst, arc_bytes, accepting_mask, n_important,
+ * n_words = W - and `eclose` a converged closure of glb_nfa_closure, every row of which the caller has ANDed with `useful`: the
+ * important states from which an accepting state can be reached.
+ *   States and sets.  A state is a set of important NFA states closed under empty arcs, inside `useful`, a bitset of W words.
+ *     So a set is live exactly when it is not empty, and there is no `live` table.  Id 0 is the closure of nfa_start (it may
+ *     be empty: the language is).  The empty set is no state: it is -1, the dead state of glb_dfa_*.  A state accepts where
+ *     its set meets accepting_mask.  The ids are [0, max_states); status[0] of them are numbered.
+ *   step(set, b) = the union of eclose[dst] over the byte arcs (m, dst) of the set's members m whose byte set holds b.
+ *   next(set, t) = step over the bytes of token t in turn, or empty when the token is skipped, empty, outside [0, vocab) or
+ *     its offsets are not the vocabulary's: the rules of glb_dfa_advance.
+ *   glb_lazy_advance: state_out[i] of dfa.tokens[i, from[i] .. to[i]) from dfa.state_in[i] (null: id 0).  A range outside
+ *     [0, ld] or from > to, or a state outside [0, n) - n the states numbered when the call began - gives -1.  from == to
+ *     gives the state back.  Else the tokens are walked from the state's set; an empty set at any point gives -1.  Sets in
+ *     the middle of a range are never numbered: the set the particle ends in is looked up and, when new, numbered.
+ *   Numbering.  The new sets of a call get consecutive ids, from status[0] up, in the order of the smallest particle index
+ *     that ended in them - whatever order the atomics take; sets[id], accepting_out[id] are written.
+ *   Overflow.  A new set beyond max_states gets no id: its particles get -1 and status[1] bit 0 (sticky) goes up.  What
+ *     fits is decided by the same order.  The table never fills first: a call's particles are walked `cand_rows` at a time
+ *     (the order of the chunks is the order of the particles), cand_rows <= table_slots - max_states, and a chunk that
+ *     begins with every id taken claims no slot; the slots of the sets that found no id in the one chunk that crossed the
+ *     bound stay behind as tombstones.
+ *   Rows.  The row of state s in the bank (of glb_dfa_args: bank, row_of_state, work, counters, rows 0 and 1, `done`, the
+ *     lifetime of ids) has bit t = next(sets[s], t) not empty, bit eos_id = accepting_out[s].  An id in [status[0],
+ *     max_states) that a caller names before a set has it (glb_lazy_advance never returns one) is served row 0: the fill
+ *     takes its claim back, so that the set that takes the id later gets a row of its own; the row claimed for it is lost
+ *     to a bank that does not evict and free in one that does.
+ * The embedded glb_dfa_args, its own struct_size set, carries the vocabulary, the particles, the bank and its counters; its
+ * n_states, start, delta, accepting and live are not read: max_states, 0 and accepting_out stand in their places.
+ *   status [GLB_LAZY_STATUS]: [0] states numbered  [1] flags, sticky: GLB_LAZY_OVERFLOW, GLB_LAZY_BUG (a reference out of
+ *     range: never an input)  [2] the states numbered when the running call began  [3] private
+ *   table: 12 bytes a slot as in glb_nfa_args - table_slots 64-bit words (31 bits of the set's hash; a particle index of the
+ *     running chunk, its row of `cand`, or a numbered id, its row of `sets`), then int32 [table_slots], the smallest particle
+ *     index that brought the slot's set.  hash_mask as in glb_nfa_args.
+ *   glb_lazy_init     the table emptied, status = {1, 0, 1, ..}, accepting_out zeroed, sets[0] = eclose[nfa_start] and entered;
+ *                     the bank started over (rows 0 and 1, row_of_state = -1 over max_states, counters) and, where the
+ *                     eviction tables are given, those too (glb_dfa_evict_bank_init).
+ *   glb_lazy_advance  six launches a chunk of cand_rows particles, no wave waiting on another's stores: walk (a wave per
+ *                     particle, the set a word a lane; the end set to `cand`), enter (the table probed; a new set's slot
+ *                     claimed by one compare-and-swap; the smallest particle index kept by atomicMin), count, scan, number
+ *                     (cand copied to sets[id], accepting_out[id], the slot's reference turned into the id), resolve.
+ *                     state_out may be state_in.  dfa.n == 0 is GLB_EINVAL, as for glb_dfa_advance.
+ *   glb_lazy_serve    out_rows of state_in [n], `done` as glb_dfa_mask_ids: without eviction tables the launches of
+ *                     glb_dfa_claim_rows, the fill, the commit, glb_dfa_mask_ids; with them those of glb_dfa_evict_serve.
+ *                     The fill walks every token from sets[s]: n_words == 1 and force_wave == 0 - a lane a token, the set a
+ *                     register, 64 tokens one ballot; else a wave a token, the set across the lanes, a workgroup of four
+ *                     waves the 32 tokens of one word, eight each, the word written once.  force_wave != 0 gives a one-word
+ *                     automaton the second form (a test compares the two).
+ * GLB_EINVAL before any launch, the field named: struct_size of either block wrong; max_states outside [1, 2^22]; n_important
+ * outside [0, min(n_nfa_states, GLB_NFA_MAX_IMPORTANT)]; n_words not max(1, ceil(n_important / 64)); n_nfa_states outside
+ * [1, 2^24]; nfa_start outside the automaton; n_arcs negative; a null arc, mask, closure, table, sets, accepting_out, cand,
+ * counts or status pointer; table_slots no power of two in [2 max_states, 2^30]; table not aligned to 8; cand_rows outside
+ * [1, table_slots - max_states]; the eviction tables given in part; and for the bank and the vocabulary what glb_dfa_* refuse.
+ * Everything read from device memory is range-checked; a bad work entry is skipped.  Nothing synchronises or allocates.
+ */
+#define GLB_LAZY_STATUS 8
+#define GLB_LAZY_OVERFLOW 1
+#define GLB_LAZY_BUG 2
+typedef struct glb_lazy_args {
+  uint32_t struct_size; /* sizeof(glb_lazy_args) - ABI guard */
+  glb_dfa_args dfa;     /* its own struct_size set too: vocabulary, particles, bank, counters */
+  int32_t n_nfa_states, nfa_start;
+  int32_t n_important, n_words;
+  int32_t n_arcs;
+  int32_t max_states;
+  const int32_t *arc_off, *arc_dst; /* [n_important + 1], [n_arcs] */
+  const uint64_t *arc_bytes;        /* [n_arcs][4] */
+  const uint64_t *accepting_mask;   /* [n_words] */
+  const uint64_t *eclose;           /* [n_nfa_states][n_words], converged, inside `useful` */
+  uint64_t hash_mask;               /* 0: every bit of the hash */
+  void *table;                      /* 12 * table_slots bytes */
+  int64_t table_slots;              /* a power of two >= 2 * max_states */
+  uint64_t *cand;                   /* [cand_rows][n_words] */
+  int32_t *counts;                  /* [ceil(cand_rows / 256)] */
+  int64_t cand_rows;                /* particles a chunk of glb_lazy_advance takes */
+  uint64_t *sets;                   /* [max_states][n_words] */
+  uint8_t *accepting_out;           /* [max_states] */
+  int32_t *status;                  /* [GLB_LAZY_STATUS] */
+  /* the tables of glb_dfa_evict_args, all null: a bank that never evicts */
+  int32_t *row_state, *row_stamp, *claimants, *victims; /* [dfa.capacity] each */
+  int32_t *ecounters;                                   /* [GLB_DFA_EVICT_COUNTERS] */
+  int32_t *epoch;                                       /* [1] */
+  int32_t force_wave; /* debug: the wave form of the fill where n_words == 1 */
+} glb_lazy_args;
+int glb_lazy_init(const glb_lazy_args *args, void *hip_stream);
+int glb_lazy_advance(const glb_lazy_args *args, void *hip_stream);
+int glb_lazy_serve(const glb_lazy_args *args, void *hip_stream);
+
 /* Philox4x32-10 block function, exposed so hosts can reproduce the device draws. */
 void glb_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 
