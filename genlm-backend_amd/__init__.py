@@ -18,7 +18,8 @@ def __getattr__(name):
     if name in ("load_model_by_name", "AsyncAmdLM", "AsyncLM"):
         from . import llm
         return getattr(llm, name)
-    if name in ("ByteDFA", "ByteWFSA", "DeviceConstraint", "minimize", "product", "ByteNFA", "determinize", "LazyConstraint"):
+    if name in ("ByteDFA", "ByteWFSA", "DeviceConstraint", "minimize", "product", "ByteNFA", "determinize", "LazyConstraint", "BytePDA",
+                "PDAConstraint"):
         from . import constraints
         return getattr(constraints, name)
     raise AttributeError(name)

@@ -406,6 +406,29 @@ class LazyArgs(C.Structure):
     ]
 
 
+PDA_MAX_DEPTH = 504  # GLB_PDA_MAX_DEPTH: a configuration is one wave, a 64-bit word a lane: the head and 63 words of 8 symbols
+PDA_STATUS = 8  # GLB_PDA_STATUS: configurations numbered, flags (sticky), those numbered when the running call began, private
+PDA_OVERFLOW, PDA_BUG = 1, 2
+PDA_MAX_SYMBOLS, PDA_POP = 126, 127  # an entry of delta: next | op << 24, op 0 (keep), 1 .. G (push), 127 (pop)
+
+
+class PdaArgs(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("dfa", DfaArgs),
+        ("n_pda_states", C.c_int32), ("n_symbols", C.c_int32), ("start", C.c_int32),
+        ("max_depth", C.c_int32), ("n_words", C.c_int32), ("max_states", C.c_int32),
+        ("delta", C.c_void_p), ("accepting", C.c_void_p),
+        ("hash_mask", C.c_uint64),
+        ("table", C.c_void_p), ("table_slots", C.c_int64),
+        ("cand", C.c_void_p), ("counts", C.c_void_p), ("cand_rows", C.c_int64),
+        ("configs", C.c_void_p), ("accepting_out", C.c_void_p), ("status", C.c_void_p),
+        ("row_state", C.c_void_p), ("row_stamp", C.c_void_p), ("claimants", C.c_void_p), ("victims", C.c_void_p),
+        ("ecounters", C.c_void_p), ("epoch", C.c_void_p),
+        ("max_token_bytes", C.c_int32),
+    ]
+
+
 # every symbol include/glb.h declares: name -> (restype, argtypes)
 _vp, _i32, _i64, _f32, _sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_size_t
 SYMBOLS = {
@@ -507,6 +530,9 @@ SYMBOLS = {
     "glb_lazy_init": (C.c_int, [C.POINTER(LazyArgs), _vp]),
     "glb_lazy_advance": (C.c_int, [C.POINTER(LazyArgs), _vp]),
     "glb_lazy_serve": (C.c_int, [C.POINTER(LazyArgs), _vp]),
+    "glb_pda_init": (C.c_int, [C.POINTER(PdaArgs), _vp]),
+    "glb_pda_advance": (C.c_int, [C.POINTER(PdaArgs), _vp]),
+    "glb_pda_serve": (C.c_int, [C.POINTER(PdaArgs), _vp]),
     "glb_philox4x32_10": (None, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
 }
 

@@ -19,10 +19,15 @@ pattern's Thompson automaton - and `determinize(llm, nfa)` its `ByteDFA`, by the
 
 `LazyConstraint` serves a `ByteNFA` as it is: the subset states are made on the device when a particle reaches
 them, so a pattern whose deterministic automaton is too large to build still constrains a population that visits little of it.
+
+`BytePDA` is a real-time deterministic pushdown automaton over bytes - nested brackets, `BytePDA.json()` - and `PDAConstraint`
+serves one: a state is a configuration, the automaton's state and a bounded stack, numbered on the device when
+a particle reaches it.
 """
 from .automata import ByteDFA, ByteWFSA  # noqa: F401
 from .device import DeviceConstraint  # noqa: F401
 from .lazy import LazyConstraint  # noqa: F401
 from .nfa import ByteNFA  # noqa: F401
+from .pda import BytePDA, PDAConstraint  # noqa: F401
 from .regex import _regex_dfa  # noqa: F401
 from .tables import DeviceTables, _kept, determinize, minimize, product  # noqa: F401

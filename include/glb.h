@@ -1455,6 +1455,98 @@ int glb_lazy_init(const glb_lazy_args *args, void *hip_stream);
 int glb_lazy_advance(const glb_lazy_args *args, void *hip_stream);
 int glb_lazy_serve(const glb_lazy_args *args, void *hip_stream);
 
+/*
+ * Nested languages: a real-time deterministic pushdown automaton over bytes served as a constraint, its
+ * configurations numbered on the device when a particle ends a call in them - the machinery of glb_lazy_* with a
+ * configuration in place of a set.
+ *   The automaton.  delta int32 [n_pda_states][n_symbols + 1][256], the middle index the top of the stack: plane 0 the empty
+ *     stack, planes 1 .. G = n_symbols the stack symbols.  An entry is -1 (dead) or next | op << 24: next in [0, n_pda_states),
+ *     op 0 (keep), g in 1 .. G (push g) or 127 (pop).  accepting uint8 [n_pda_states].  A byte string is accepted when its walk
+ *     from (start, the empty stack) never dies and ends in an accepting state with the empty stack.
+ *   Configurations.  A configuration is W = n_words = 1 + ceil(max_depth / 8) 64-bit words, 1 <= max_depth <=
+ *     GLB_PDA_MAX_DEPTH, so W <= 64: word 0 is state | depth << 32, words 1 .. hold the stack, one byte a symbol, bottom
+ *     first (symbol i: word 1 + i / 8, byte i % 8), every byte above depth zero - two configurations are equal exactly when
+ *     their words are.  Id 0 is (start, empty).  The dead configuration is no state: it is -1, the dead state of glb_dfa_*.
+ *     The ids are [0, max_states); status[0] of them are numbered.
+ *   step(c, b): the entry delta[state, top(c), b], top the symbol at depth - 1 or 0 on the empty stack.  Dead on -1, on a
+ *     push at depth == max_depth, on a pop from the empty stack and on an entry or a top whose fields are out of range
+ *     (next >= n_pda_states, op in (G, 127), top > G).  Else the state becomes next and the stack is kept, pushed or popped.
+ *   next(c, t) = step over the bytes of token t in turn, dead as soon as a step is; dead when the token is skipped, empty,
+ *     outside [0, vocab) or its offsets are not the vocabulary's: the rules of glb_dfa_advance.
+ *   glb_pda_advance: state_out[i] of dfa.tokens[i, from[i] .. to[i]) from dfa.state_in[i] (null: id 0).  A range outside
+ *     [0, ld] or from > to, or a state outside [0, n) - n the configurations numbered when the call began - gives -1.
+ *     from == to gives the state back.  Else the tokens are walked from the state's configuration; dead at any point gives
+ *     -1.  Configurations in the middle of a range are never numbered: the one the particle ends in is looked up and, when
+ *     new, numbered.
+ *   Numbering.  The new configurations of a call get consecutive ids, from status[0] up, in the order of the smallest
+ *     particle index that ended in them - whatever order the atomics take; configs[id] and accepting_out[id] =
+ *     accepting[state] && depth == 0 are written.
+ *   Overflow.  A new configuration beyond max_states gets no id: its particles get -1 and status[1] bit 0 (sticky) goes up.
+ *     What fits is decided by the same order.  The table never fills first: a call's particles are walked `cand_rows` at a
+ *     time (the order of the chunks is the order of the particles), cand_rows <= table_slots - max_states, and a chunk that
+ *     begins with every id taken claims no slot; the slots of the configurations that found no id in the one chunk that
+ *     crossed the bound stay behind as tombstones.
+ *   Rows.  The row of state s in the bank (of glb_dfa_args: bank, row_of_state, work, counters, rows 0 and 1, `done`, the
+ *     lifetime of ids) has bit t = next(configs[s], t) not dead, bit eos_id = accepting_out[s].  An id in [status[0],
+ *     max_states) that a caller names before a configuration has it (glb_pda_advance never returns one) is served row 0: the
+ *     fill takes its claim back, so that the configuration that takes the id later gets a row of its own; the row claimed for
+ *     it is lost to a bank that does not evict and free in one that does.
+ * The embedded glb_dfa_args, its own struct_size set, carries the vocabulary, the particles, the bank and its counters; its
+ * n_states, start, delta, accepting and live are not read: max_states, 0 and accepting_out stand in their places.
+ *   status [GLB_PDA_STATUS]: [0] configurations numbered  [1] flags, sticky: GLB_PDA_OVERFLOW, GLB_PDA_BUG (a reference
+ *     out of range: never an input)  [2] the configurations numbered when the running call began  [3] private
+ *   table: 12 bytes a slot as in glb_lazy_args.  hash_mask as in glb_nfa_args.
+ *   max_token_bytes: at least the length of the vocabulary's longest token.  A lane of the fill keeps what a token pushed in
+ *     min(max_token_bytes, max_depth) bytes; a token that pushes more than that is served dead.
+ *   glb_pda_init     the table emptied, status = {1, 0, 1, ..}, accepting_out zeroed, configs[0] = (start, empty) and
+ *                    entered; the bank started over and, where the eviction tables are given, those too.
+ *   glb_pda_advance  six launches a chunk of cand_rows particles, no wave waiting on another's stores: walk (a wave per
+ *                    particle, the configuration a word a lane: the top one lane's word in every lane and a shift, a push
+ *                    or a pop a masked update in that lane; the end configuration to `cand`), then enter, count, scan,
+ *                    number, resolve as glb_lazy_advance has them, keyed on the W raw words.  state_out may be state_in.
+ *                    dfa.n == 0 is GLB_EINVAL, as for glb_dfa_advance.
+ *   glb_pda_serve    out_rows of state_in [n], `done` as glb_dfa_mask_ids: without eviction tables the launches of
+ *                    glb_dfa_claim_rows, the fill, the commit, glb_dfa_mask_ids; with them those of glb_dfa_evict_serve.
+ *                    The fill: a lane a token, a workgroup one wave, 64 tokens one ballot and two words of the row; the
+ *                    served configuration's stack read-only in LDS, a lane's own pushes in dynamic LDS [position][lane].
+ * GLB_EINVAL before any launch, the field named: struct_size of either block wrong; max_states outside [1, 2^22];
+ * n_pda_states outside [1, 2^24]; n_symbols outside [1, 126]; start outside the automaton; max_depth outside [1,
+ * GLB_PDA_MAX_DEPTH]; n_words not 1 + ceil(max_depth / 8); a null delta, accepting, table, configs, accepting_out, cand,
+ * counts or status pointer; table_slots no power of two in [2 max_states, 2^30]; table, configs or cand not aligned to 8;
+ * cand_rows outside [1, table_slots - max_states]; max_token_bytes < 1 (glb_pda_serve); the eviction tables given in part;
+ * and for the bank and the vocabulary what glb_dfa_* refuse.
+ * Everything read from device memory is range-checked; a bad work entry is skipped.  Nothing synchronises or allocates.
+ */
+#define GLB_PDA_MAX_DEPTH 504
+#define GLB_PDA_STATUS 8
+#define GLB_PDA_OVERFLOW 1
+#define GLB_PDA_BUG 2
+typedef struct glb_pda_args {
+  uint32_t struct_size; /* sizeof(glb_pda_args) - ABI guard */
+  glb_dfa_args dfa;     /* its own struct_size set too: vocabulary, particles, bank, counters */
+  int32_t n_pda_states, n_symbols, start;
+  int32_t max_depth, n_words, max_states;
+  const int32_t *delta;     /* [n_pda_states][n_symbols + 1][256] */
+  const uint8_t *accepting; /* [n_pda_states] */
+  uint64_t hash_mask;       /* 0: every bit of the hash */
+  void *table;              /* 12 * table_slots bytes */
+  int64_t table_slots;      /* a power of two >= 2 * max_states */
+  uint64_t *cand;           /* [cand_rows][n_words] */
+  int32_t *counts;          /* [ceil(cand_rows / 256)] */
+  int64_t cand_rows;        /* particles a chunk of glb_pda_advance takes */
+  uint64_t *configs;        /* [max_states][n_words] */
+  uint8_t *accepting_out;   /* [max_states] */
+  int32_t *status;          /* [GLB_PDA_STATUS] */
+  /* the tables of glb_dfa_evict_args, all null: a bank that never evicts */
+  int32_t *row_state, *row_stamp, *claimants, *victims; /* [dfa.capacity] each */
+  int32_t *ecounters;                                   /* [GLB_DFA_EVICT_COUNTERS] */
+  int32_t *epoch;                                       /* [1] */
+  int32_t max_token_bytes; /* >= the longest token of the vocabulary */
+} glb_pda_args;
+int glb_pda_init(const glb_pda_args *args, void *hip_stream);
+int glb_pda_advance(const glb_pda_args *args, void *hip_stream);
+int glb_pda_serve(const glb_pda_args *args, void *hip_stream);
+
 /* Philox4x32-10 block function, exposed so hosts can reproduce the device draws. */
 void glb_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 
