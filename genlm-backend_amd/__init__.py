@@ -19,7 +19,7 @@ def __getattr__(name):
         from . import llm
         return getattr(llm, name)
     if name in ("ByteDFA", "ByteWFSA", "DeviceConstraint", "minimize", "product", "ByteNFA", "determinize", "LazyConstraint", "BytePDA",
-                "PDAConstraint"):
+                "PDAConstraint", "ConstraintProduct"):
         from . import constraints
         return getattr(constraints, name)
     raise AttributeError(name)

@@ -429,6 +429,32 @@ class PdaArgs(C.Structure):
     ]
 
 
+CONJ_MAX_PARTS = 8  # GLB_CONJ_MAX_PARTS: a tuple of part states is at most four 64-bit words, two states a word
+CONJ_STATUS = 8  # GLB_CONJ_STATUS: tuples numbered, flags (sticky), those numbered when the running call began, private
+CONJ_OVERFLOW, CONJ_BUG = 1, 2
+
+
+class ConjArgs(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("dfa", DfaArgs),
+        ("n_parts", C.c_int32), ("n_words", C.c_int32), ("max_states", C.c_int32),
+        ("part_start", C.c_int32 * CONJ_MAX_PARTS),
+        ("hash_mask", C.c_uint64),
+        ("table", C.c_void_p), ("table_slots", C.c_int64),
+        ("tuples", C.c_void_p), ("status", C.c_void_p),
+        ("counts", C.c_void_p), ("cand_rows", C.c_int64),
+        ("part_states", C.c_void_p), ("part_ld", C.c_int64),
+        ("claim_states", C.c_void_p), ("rep", C.c_void_p),
+        ("part_rows", C.c_void_p * CONJ_MAX_PARTS), ("part_bank", C.c_void_p * CONJ_MAX_PARTS),
+        ("part_bank_ld", C.c_int64 * CONJ_MAX_PARTS), ("part_capacity", C.c_int64 * CONJ_MAX_PARTS),
+        ("part_weighted", C.c_int32 * CONJ_MAX_PARTS),
+        ("wbank", C.c_void_p), ("wbank_ld", C.c_int64),
+        ("row_state", C.c_void_p), ("row_stamp", C.c_void_p), ("claimants", C.c_void_p), ("victims", C.c_void_p),
+        ("ecounters", C.c_void_p), ("epoch", C.c_void_p),
+    ]
+
+
 # every symbol include/glb.h declares: name -> (restype, argtypes)
 _vp, _i32, _i64, _f32, _sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_size_t
 SYMBOLS = {
@@ -533,6 +559,10 @@ SYMBOLS = {
     "glb_pda_init": (C.c_int, [C.POINTER(PdaArgs), _vp]),
     "glb_pda_advance": (C.c_int, [C.POINTER(PdaArgs), _vp]),
     "glb_pda_serve": (C.c_int, [C.POINTER(PdaArgs), _vp]),
+    "glb_conj_init": (C.c_int, [C.POINTER(ConjArgs), _vp]),
+    "glb_conj_unpack": (C.c_int, [C.POINTER(ConjArgs), _vp]),
+    "glb_conj_number": (C.c_int, [C.POINTER(ConjArgs), _vp]),
+    "glb_conj_serve": (C.c_int, [C.POINTER(ConjArgs), _vp]),
     "glb_philox4x32_10": (None, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
 }
 

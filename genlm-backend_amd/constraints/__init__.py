@@ -23,8 +23,14 @@ them, so a pattern whose deterministic automaton is too large to build still con
 `BytePDA` is a real-time deterministic pushdown automaton over bytes - nested brackets, `BytePDA.json()` - and `PDAConstraint`
 serves one: a state is a configuration, the automaton's state and a bounded stack, numbered on the device when
 a particle reaches it.
+
+`ConstraintProduct(llm, parts)` serves the conjunction of 2 to 8 constraints of any of these kinds, products included (DESIGN.md
+§26), without building a product automaton: a state is the tuple of the parts' states, numbered on the device when a particle
+reaches it, and its row is combined from the parts' rows - the AND of bit rows, the sum of weighted rows with -inf where an
+unweighted part forbids the token.  A grammar with a pattern, a length bound and the soft preferences of a `ByteWFSA`.
 """
 from .automata import ByteDFA, ByteWFSA  # noqa: F401
+from .conj import ConstraintProduct  # noqa: F401
 from .device import DeviceConstraint  # noqa: F401
 from .lazy import LazyConstraint  # noqa: F401
 from .nfa import ByteNFA  # noqa: F401

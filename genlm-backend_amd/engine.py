@@ -942,6 +942,17 @@ class HipEngine:
             raise ValueError(name)
         check(getattr(self.lib, name)(C.byref(args), self._stream()))
 
+    # the glb_conj_* entries (conjunctions of constraints, tuples of part states numbered while decoding) that
+    # take (argument block, stream)
+    CONJ_CALLS = frozenset(name for name, (_, argtypes) in _lib.SYMBOLS.items()
+                           if name.startswith("glb_conj_") and argtypes and issubclass(argtypes[0], C._Pointer))
+
+    def conj_call(self, name, args):
+        """One of `CONJ_CALLS` with its block, on the current stream."""
+        if name not in HipEngine.CONJ_CALLS:
+            raise ValueError(name)
+        check(getattr(self.lib, name)(C.byref(args), self._stream()))
+
     # ---- device-resident particle state ------------------------------------------------------------------
     def kv_append(self, slab, new_rows, pos, rows=None):
         """slab[rows[i] (or i), h, pos[i], :] = new_rows[i, h, 0, :] (glb_kv_append).  slab [R, H, cap, Dh] contiguous;

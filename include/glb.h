@@ -1547,6 +1547,95 @@ int glb_pda_init(const glb_pda_args *args, void *hip_stream);
 int glb_pda_advance(const glb_pda_args *args, void *hip_stream);
 int glb_pda_serve(const glb_pda_args *args, void *hip_stream);
 
+/*
+ * Conjunctions of constraints: K = n_parts constraints of any kind - each with a bank of rows and state ids
+ * of its own - served as one.  A state of the conjunction is the tuple of the K part states, numbered on the device when a
+ * particle ends a call in it: the machinery of glb_lazy_* and glb_pda_* with a tuple in place of a set or a configuration.
+ * No product automaton is made: a token survives from a tuple exactly when it survives from every part, so the tuple's row
+ * is combined from the parts' rows.
+ *   Tuples.  A tuple is W = n_words = ceil(K / 2) 64-bit words, 2 <= K <= GLB_CONJ_MAX_PARTS: part 2 j in the low half of
+ *     word j, part 2 j + 1 in the high half; for odd K the high half of the last word is zero.  Every part state of a tuple is
+ *     >= 0: a tuple with a dead part is no state but -1.  Id 0 is part_start[0 .. K).  The ids are [0, max_states);
+ *     status[0] of them are numbered.
+ *   glb_conj_unpack: part_states[k * part_ld + i] = part k of tuples[state_in[i]] (state_in null: id 0) for i in [0, n);
+ *     every part -1 where state_in[i] is outside [0, status[0]).  With claim_states (glb_conj_serve's input, [n]):
+ *     claim_states[i] = state_in[i] where it is numbered and done (nullable) is not set for i, else -1, and rep[state_in[i]]
+ *     = i for those - some particle that holds the state, whichever store comes last.  One launch, a lane a particle.
+ *   glb_conj_number: state_out[i] = the id of the tuple part_states[0 .. K)[i], -1 where a part is < 0.  Numbering and
+ *     overflow are glb_pda_advance's, word for word: the new tuples of a call get consecutive ids, from status[0] up, in the
+ *     order of the smallest particle index that ended in them; a new tuple beyond max_states gets no id, its particles -1,
+ *     and status[1] bit 0 (sticky) goes up; the particles are taken cand_rows at a time, cand_rows <= table_slots -
+ *     max_states, and a chunk that begins with every id taken claims no slot.  Five launches a chunk - enter, count, scan,
+ *     number, resolve - a LANE a particle: a tuple is at most four words, which a lane packs from part_states, hashes and
+ *     compares by itself (a reference to a particle of the chunk is compared against that particle's part states, so the
+ *     packed tuples are not stored anywhere before they are numbered).
+ *   glb_conj_serve: out_rows[i] of state_in[i] given claim_states, rep and part_rows[k] (int32 [n]: particle i's row in
+ *     part k's bank, as that part's own serve call returned it under the same `done`).  Where done[i] is set: row 1 when
+ *     part_rows[k][i] == 1 for every k, else row 0.  A state outside [0, max_states) or without a row: row 0.  Without
+ *     eviction tables the launches are glb_dfa_claim_rows's (over claim_states), the combine, the commit and the ids; with
+ *     them touch, select, the combine and the ids, as glb_dfa_evict_serve has them.
+ *   The combine fills the row of every work entry (s, r) from the part rows of particle rep[s]: an entry whose s, r, rep[s]
+ *     (it must hold s in claim_states) or part row (outside [0, part_capacity[k])) is out of range is skipped and its claim
+ *     taken back.  A bit bank (wbank null): word w of the row is the AND over the parts of word w of their rows, words
+ *     [0, ceil(vocab / 32)).  A float bank (wbank given): float t = 0.0f + the floats t of the weighted parts' rows (part
+ *     order, float32, no fma), then -inf where the bit t of any unweighted part's row is clear; floats [0, vocab).  A part
+ *     with part_weighted[k] != 0 has float rows [part_capacity[k]][part_bank_ld[k]], else int32 bit rows.  A lane takes
+ *     four words (four floats) as one 16-byte access a part; what is left of a row is taken word by word.  A word or a
+ *     float is written once: no atomic, no zeroing launch.
+ * The embedded glb_dfa_args, its own struct_size set, carries vocab, eos_id, the particles (n, state_in, state_out, done,
+ * out_rows) and the bank's bookkeeping (bank - or wbank here -, capacity, row_of_state [max_states], work, counters,
+ * max_work); nothing else of it is read.
+ *   status [GLB_CONJ_STATUS]: [0] tuples numbered  [1] flags, sticky: GLB_CONJ_OVERFLOW, GLB_CONJ_BUG (a reference out of
+ *     range: never an input)  [2] the tuples numbered when the running call began  [3] private
+ *   table: 12 bytes a slot as in glb_lazy_args.  hash_mask as in glb_nfa_args.
+ *   glb_conj_init  the table emptied, status = {1, 0, 1, ..}, tuples[0] = part_start packed and entered, rep = -1; the bank
+ *                  started over (rows 0 and 1 as glb_dfa_bank_init / glb_dfa_weight_bank_init write them) and, where the
+ *                  eviction tables are given, those too.
+ * GLB_EINVAL before any launch, the field named: struct_size of either block wrong; n_parts outside [2,
+ * GLB_CONJ_MAX_PARTS]; n_words not ceil(n_parts / 2); max_states outside [1, 2^22]; a null table, tuples, status or rep
+ * pointer; table_slots no power of two in [2 max_states, 2^30]; table or tuples not aligned to 8; the eviction tables given
+ * in part; vocab outside [1, 2^31 - 256]; n <= 0; part_start[k] < 0 (init); a null part_states, part_ld < n (unpack,
+ * number); a null state_out, counts, cand_rows outside [1, table_slots - max_states] (number); a null state_in,
+ * claim_states, out_rows, part_rows[k] or part_bank[k], part_bank_ld[k] or bank_ld (wbank_ld) below a row's elements,
+ * part_capacity[k] < 2, max_work <= 0 (serve); for the bank what glb_dfa_* refuse.
+ * Everything read from device memory is range-checked.  Nothing synchronises or allocates.
+ */
+#define GLB_CONJ_MAX_PARTS 8
+#define GLB_CONJ_STATUS 8
+#define GLB_CONJ_OVERFLOW 1
+#define GLB_CONJ_BUG 2
+typedef struct glb_conj_args {
+  uint32_t struct_size; /* sizeof(glb_conj_args) - ABI guard */
+  glb_dfa_args dfa;     /* its own struct_size set too: vocab, eos_id, particles, the bank's bookkeeping */
+  int32_t n_parts, n_words, max_states;
+  int32_t part_start[GLB_CONJ_MAX_PARTS]; /* init: the parts of id 0 */
+  uint64_t hash_mask;                     /* 0: every bit of the hash */
+  void *table;                            /* 12 * table_slots bytes */
+  int64_t table_slots;                    /* a power of two >= 2 * max_states */
+  uint64_t *tuples;                       /* [max_states][n_words] */
+  int32_t *status;                        /* [GLB_CONJ_STATUS] */
+  int32_t *counts;                        /* [ceil(cand_rows / 256)] */
+  int64_t cand_rows;                      /* particles a chunk of glb_conj_number takes */
+  int32_t *part_states;                   /* [n_parts][part_ld] */
+  int64_t part_ld;                        /* >= dfa.n */
+  int32_t *claim_states;                  /* [n]: unpack (nullable there), serve */
+  int32_t *rep;                           /* [max_states] */
+  const int32_t *part_rows[GLB_CONJ_MAX_PARTS]; /* [n] each */
+  const void *part_bank[GLB_CONJ_MAX_PARTS];    /* int32 or float [part_capacity][part_bank_ld] */
+  int64_t part_bank_ld[GLB_CONJ_MAX_PARTS], part_capacity[GLB_CONJ_MAX_PARTS];
+  int32_t part_weighted[GLB_CONJ_MAX_PARTS];
+  float *wbank; /* [dfa.capacity][wbank_ld]; null: the bit bank dfa.bank */
+  int64_t wbank_ld;
+  /* the tables of glb_dfa_evict_args, all null: a bank that never evicts */
+  int32_t *row_state, *row_stamp, *claimants, *victims; /* [dfa.capacity] each */
+  int32_t *ecounters;                                   /* [GLB_DFA_EVICT_COUNTERS] */
+  int32_t *epoch;                                       /* [1] */
+} glb_conj_args;
+int glb_conj_init(const glb_conj_args *args, void *hip_stream);
+int glb_conj_unpack(const glb_conj_args *args, void *hip_stream);
+int glb_conj_number(const glb_conj_args *args, void *hip_stream);
+int glb_conj_serve(const glb_conj_args *args, void *hip_stream);
+
 /* Philox4x32-10 block function, exposed so hosts can reproduce the device draws. */
 void glb_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 
