@@ -581,7 +581,11 @@ class TokenByteTrie:
         that needs one part of nine is better off gathered: 58 against 99 us); layout "slots": node-major [n_slots, pitch] over the folded trie (`compact()`: the value of node
         n for row r is at [slot_of[n], r] - nothing is transposed back); layout "nodes": the same over all nodes,
         [n_nodes, pitch] (see HipEngine.trie_masses); layout "slot_rows": row-major [B, n_slots] over the plan's slots
-        (`slot_plan()["slot_of"]`: node -> slot) - the cheapest form: the logits are read once and nothing else is written."""
+        (`slot_plan()["slot_of"]`: node -> slot) - the cheapest form: the logits are read once and nothing else is written.
+        Edges (pinned by tests/test_trie_exact_gpu.py): a -inf logit under a finite lse is exactly +0.0; a row whose lse is
+        -inf (nothing allowed) has NaN leaves (exp(-inf + inf)), NaN sums above them and, for op=1, +0.0 at every node with
+        two children and more (a NaN is never taken) while the folded one-child nodes show their leaf's NaN
+        (`batch_weight_max`); leaves below 2^-126 may flush to +0.0 (the hardware's 2^x)."""
         if logits.shape[1] < len(self.decode):
             raise ValueError(f"logits rows have {logits.shape[1]} columns, vocabulary has {len(self.decode)}")
         if lse is None:  # (one more reading of the rows: hand the fused step's lse over when there is one)
@@ -633,7 +637,13 @@ class TokenByteTrie:
         return self.batch_weight_sum_device(ws).cpu().numpy()
 
     def batch_weight_max(self, ws):
-        """base.py:207-216 / parallel.py:120-145"""
+        """base.py:207-216 / parallel.py:120-145.  Weights outside [+0, inf] (pinned by tests/test_trie_exact_gpu.py): a node
+        with two children and more takes the maximum from +0.0 - negatives clamp to +0.0 (the reference's max(0, ...)), a NaN
+        child is never taken, +inf is; the same nodes sum from +0.0, so children of -0.0 sum to +0.0 and a NaN or inf - inf
+        child makes the sum and every sum above it NaN.  A node with exactly ONE child is folded away (`compact()`) and shows
+        its child's value as it is - a negative, -0.0 or NaN leaf shows on the chain of one-child nodes right above it, for
+        max and for sum, where the level kernels on the unfolded trie (fewer than 32 rows with `resident` off,
+        `HipEngine.trie_reduce`) give +0.0 there.  For weights that are +0.0 or greater the two agree bit for bit."""
         return self.batch_weight_max_device(ws).cpu().numpy()
 
     def weight_sum(self, ws):
