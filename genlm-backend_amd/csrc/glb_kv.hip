@@ -919,6 +919,159 @@ hipError_t launch_short_attention(const ShortArgs &a, int head_dim, hipStream_t 
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// glb_short_attention_packed: short_attention_rows_kernel over a ROW-PACKED batch whose contexts share their prompt's rows.
+// q / k / v are [M, heads, DH] views of one projection output (row and head strides, unit inner stride); segment s of the plan
+// is (pre_start, pre_len, tail_start, tail_len): its tail_len queries are rows tail_start .., its keys 0 .. pre_len - 1 are
+// rows pre_start .. (the shared prompt, computed once for every context behind it), its keys pre_len .. rows tail_start ..;
+// query t sees keys 0 .. pre_len + t.  A prompt itself is a segment without a prefix.  One wave per (segment, KV head); the
+// arithmetic is short_attention_rows_kernel's with Lk = pre_len + tail_len and Lq = tail_len - same key order, same
+// KREG / LDS choice by the call's most keys, same slot_sum, same max-then-exp - so a query's output has the bits
+// glb_short_attention gives it on the right-padded batch (there the keys behind a context's end weigh exactly 0).
+// Every index comes from the plan, so every segment is range-checked before an address is formed: one that holds more than
+// `max_keys` keys, no query, or rows outside [0, M) writes nothing and counts in the error word.
+// ---------------------------------------------------------------------------------------------------------------------
+struct PackedArgs {
+  const char *q, *k, *v;
+  char *out;
+  const int32_t *plan;  // [S][4]
+  uint32_t *err;
+  int64_t q_sr, q_sh, k_sr, k_sh, v_sr, v_sh;  // element strides: packed row, head
+  int32_t S, M, H, Hkv, max_keys;
+  float scale;
+};
+
+template <int DT, int DH, int KMAX>
+__global__ __launch_bounds__(64) void short_attention_packed_kernel(const PackedArgs a) {
+  constexpr int ES = DT == GLB_F32 ? 4 : 2, EPV = 16 / ES, LP = DH / EPV, PP = 64 / LP;
+  static_assert(LP >= 1 && LP <= 64 && PP * LP == 64, "head_dim / vector width must divide the wave");
+  constexpr bool KREG = KMAX * EPV <= 128;
+  extern __shared__ float kv_lds[];  // as short_attention_rows_kernel: (K,) V [Lk][DH] float32, then a word per query
+  const int lane = threadIdx.x, j = lane / LP, i = lane - j * LP;
+  const int G = a.H / a.Hkv;
+  const int hk = blockIdx.x % a.Hkv, s = blockIdx.x / a.Hkv;
+  if (s >= a.S) return;
+  const int32_t *seg = a.plan + (int64_t)s * 4;
+  const int64_t pre_start = seg[0], pre_len = seg[1], tail_start = seg[2], tail_len = seg[3];
+  const int64_t n_keys = pre_len + tail_len;
+  // (wave-uniform: the whole workgroup leaves before any address is formed and before the barrier)
+  if (pre_len < 0 || tail_len < 1 || n_keys > a.max_keys || n_keys > KMAX || pre_start < 0 || pre_start + pre_len > a.M ||
+      tail_start < 0 || tail_start + tail_len > a.M) {
+    if (lane == 0 && hk == 0) atomicAdd(a.err, 1u);
+    return;
+  }
+  const int Lk = (int)n_keys, Lq = (int)tail_len, pre = (int)pre_len;
+  auto key_row = [&](int p) -> int64_t { return p < pre ? pre_start + p : tail_start + (p - pre); };
+  float *Ks = kv_lds, *Vs = KREG ? kv_lds : kv_lds + Lk * DH;
+  const char *kb = a.k + (int64_t)hk * a.k_sh * ES;
+  const char *vb = a.v + (int64_t)hk * a.v_sh * ES;
+  const int nq = G * Lq;
+  auto q_addr = [&](int qi) {
+    const int qc = qi < nq ? qi : nq - 1;
+    const int g = qc / Lq, t = qc - g * Lq;
+    return a.q + ((tail_start + t) * a.q_sr + (int64_t)(hk * G + g) * a.q_sh + i * EPV) * ES;
+  };
+  u32x4 q_raw = *reinterpret_cast<const u32x4 *>(q_addr(j));
+  float kr[KREG ? KMAX : 1][EPV];
+  if constexpr (KREG) {
+    u32x4 raw[KMAX];
+#pragma unroll
+    for (int p = 0; p < KMAX; ++p)
+      raw[p] = *reinterpret_cast<const u32x4 *>(kb + (key_row(p < Lk ? p : 0) * a.k_sr + i * EPV) * ES);
+#pragma unroll
+    for (int p = 0; p < KMAX; ++p) unpack16<DT>(raw[p], kr[p]);
+  }
+  for (int x = lane; x < Lk * LP; x += 64) {
+    const int p = x / LP, c = x - p * LP;
+    const int64_t row = key_row(p);
+    float vf[EPV];
+    unpack16<DT>(*reinterpret_cast<const u32x4 *>(vb + (row * a.v_sr + c * EPV) * ES), vf);
+#pragma unroll
+    for (int k = 0; k < EPV; ++k) Vs[p * DH + c * EPV + k] = vf[k];
+    if constexpr (!KREG) {
+      float kf[EPV];
+      unpack16<DT>(*reinterpret_cast<const u32x4 *>(kb + (row * a.k_sr + c * EPV) * ES), kf);
+#pragma unroll
+      for (int k = 0; k < EPV; ++k) Ks[p * DH + c * EPV + k] = kf[k];
+    }
+  }
+  const uint32_t all_keys = Lk >= 32 ? 0xffffffffu : ((1u << Lk) - 1u);
+  uint32_t *vis_t = reinterpret_cast<uint32_t *>(kv_lds + (KREG ? 1 : 2) * Lk * DH);
+  for (int t = lane; t < Lq; t += 64) {
+    const int last = t + pre;  // causal behind the prompt: keys 0 .. pre_len + t
+    const uint32_t vis = last >= 31 ? 0xffffffffu : ((2u << last) - 1u);
+    vis_t[t] = vis & all_keys;
+  }
+  __syncthreads();
+  for (int q0 = 0; q0 < nq; q0 += PP) {
+    const int qi = q0 + j;
+    const bool live = qi < nq;
+    const int qc = live ? qi : nq - 1;
+    const int g = qc / Lq, t = qc - g * Lq, h = hk * G + g;
+    float qf[EPV];
+    unpack16<DT>(q_raw, qf);
+    if (q0 + PP < nq) q_raw = *reinterpret_cast<const u32x4 *>(q_addr(qi + PP));
+    const uint32_t vis = vis_t[t];
+    float sc[KMAX];
+    float m = -__builtin_huge_valf();
+#pragma unroll
+    for (int p = 0; p < KMAX; ++p) {
+      sc[p] = -__builtin_huge_valf();
+      if (p < Lk) {  // (wave-uniform)
+        float sv = 0.0f;
+        if constexpr (KREG) {
+#pragma unroll
+          for (int k = 0; k < EPV; ++k) sv = __builtin_fmaf(qf[k], kr[p][k], sv);
+        } else {
+          const float *kp = Ks + p * DH + i * EPV;
+#pragma unroll
+          for (int k = 0; k < EPV; ++k) sv = __builtin_fmaf(qf[k], kp[k], sv);
+        }
+        sv = slot_sum<LP>(sv) * a.scale;
+        sc[p] = ((vis >> p) & 1u) ? sv : -__builtin_huge_valf();
+        m = fmaxf(m, sc[p]);
+      }
+    }
+    float l = 0.0f, acc[EPV];
+#pragma unroll
+    for (int k = 0; k < EPV; ++k) acc[k] = 0.0f;
+#pragma unroll
+    for (int p = 0; p < KMAX; ++p) {
+      if (p < Lk) {
+        const float w = ((vis >> p) & 1u) ? __expf(sc[p] - m) : 0.0f;
+        const float *vp = Vs + p * DH + i * EPV;
+        l += w;
+#pragma unroll
+        for (int k = 0; k < EPV; ++k) acc[k] = __builtin_fmaf(w, vp[k], acc[k]);
+      }
+    }
+    if (live) {
+      const float inv = l > 0.0f ? 1.0f / l : 0.0f;
+#pragma unroll
+      for (int k = 0; k < EPV; ++k) acc[k] *= inv;
+      *reinterpret_cast<u32x4 *>(a.out + (((tail_start + t) * a.H + h) * DH + i * EPV) * ES) = pack16v<DT>(acc);
+    }
+  }
+}
+
+template <int DT, int DH>
+hipError_t launch_short_packed_dh(const PackedArgs &a, hipStream_t s) {
+  const dim3 grid((unsigned)((int64_t)a.S * a.Hkv)), block(64);
+  const size_t lds = (size_t)2 * a.max_keys * DH * sizeof(float) + (size_t)a.max_keys * sizeof(uint32_t);
+  if (a.max_keys <= 16) hipLaunchKernelGGL((short_attention_packed_kernel<DT, DH, 16>), grid, block, lds, s, a);
+  else hipLaunchKernelGGL((short_attention_packed_kernel<DT, DH, 32>), grid, block, lds, s, a);
+  return hipGetLastError();
+}
+
+template <int DT>
+hipError_t launch_short_packed(const PackedArgs &a, int head_dim, hipStream_t s) {
+  if (head_dim == 64) return launch_short_packed_dh<DT, 64>(a, s);
+  if (head_dim == 128) return launch_short_packed_dh<DT, 128>(a, s);
+  if (head_dim == 32) return launch_short_packed_dh<DT, 32>(a, s);
+  if (head_dim == 16) return launch_short_packed_dh<DT, 16>(a, s);
+  return hipErrorInvalidValue;
+}
+
 // ---- KV slab rows: append, gather (moved here from glb_api.hip in round 5) ---------------------------------------------------
 
 // slab[row_of[i] (or i), h, pos[i], :] = rows[i, h, :]  (one new token per forward row; rows may be a strided view)
@@ -1285,6 +1438,51 @@ int glb_short_attention(const void *q, const int64_t q_strides[3], const void *k
     default: e = launch_short_attention<GLB_F16>(a, (int)head_dim, (hipStream_t)stream); break;
   }
   if (e != hipSuccess) return glb::api_hip_fail(e, "short_attention launch");
+  return GLB_OK;
+}
+
+int glb_short_attention_packed(const void *q, int64_t q_stride_row, int64_t q_stride_head, const void *k, int64_t k_stride_row,
+                               int64_t k_stride_head, const void *v, int64_t v_stride_row, int64_t v_stride_head,
+                               const int32_t *plan, int64_t n_segments, int64_t n_rows, int64_t heads, int64_t kv_heads,
+                               int64_t max_keys, int64_t head_dim, float scale, int32_t dtype, void *out, uint32_t *err_word,
+                               void *stream) {
+  if (!q || !k || !v || !out || !plan || !err_word) return glb::api_fail(GLB_EINVAL, "glb_short_attention_packed: null pointer");
+  if (dtype < GLB_F32 || dtype > GLB_F16) return glb::api_fail(GLB_EINVAL, "bad dtype %d", dtype);
+  if (n_segments <= 0 || n_rows <= 0 || heads <= 0 || kv_heads <= 0 || heads % kv_heads || heads > 0x7fffffffll ||
+      n_rows > 0x7fffffffll || n_segments > 0x7fffffffll || n_segments * kv_heads > 0x7fffffffll)
+    return glb::api_fail(GLB_EINVAL, "glb_short_attention_packed: bad sizes");
+  if (max_keys < 1 || max_keys > 32)
+    return glb::api_fail(GLB_EINVAL, "glb_short_attention_packed: %lld keys per context (1 .. 32 are served)", (long long)max_keys);
+  if (head_dim != 16 && head_dim != 32 && head_dim != 64 && head_dim != 128)
+    return glb::api_fail(GLB_EUNSUPPORTED, "glb_short_attention_packed: head_dim %lld (16, 32, 64 and 128 are built)", (long long)head_dim);
+  const int es = dtype == GLB_F32 ? 4 : 2;
+  bool aligned = (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out | (uintptr_t)plan) % 16) == 0 && ((uintptr_t)err_word % 4) == 0;
+  for (int64_t st : {q_stride_row, q_stride_head, k_stride_row, k_stride_head, v_stride_row, v_stride_head})
+    aligned = aligned && st >= 0 && (st * es) % 16 == 0;
+  if (!aligned) return glb::api_fail(GLB_EINVAL, "glb_short_attention_packed: pointers and strides must be 16-byte aligned");
+  PackedArgs a{};
+  a.q = (const char *)q;
+  a.k = (const char *)k;
+  a.v = (const char *)v;
+  a.out = (char *)out;
+  a.plan = plan;
+  a.err = err_word;
+  a.q_sr = q_stride_row, a.q_sh = q_stride_head;
+  a.k_sr = k_stride_row, a.k_sh = k_stride_head;
+  a.v_sr = v_stride_row, a.v_sh = v_stride_head;
+  a.S = (int32_t)n_segments;
+  a.M = (int32_t)n_rows;
+  a.H = (int32_t)heads;
+  a.Hkv = (int32_t)kv_heads;
+  a.max_keys = (int32_t)max_keys;
+  a.scale = scale;
+  hipError_t e;
+  switch (dtype) {
+    case GLB_F32: e = launch_short_packed<GLB_F32>(a, (int)head_dim, (hipStream_t)stream); break;
+    case GLB_BF16: e = launch_short_packed<GLB_BF16>(a, (int)head_dim, (hipStream_t)stream); break;
+    default: e = launch_short_packed<GLB_F16>(a, (int)head_dim, (hipStream_t)stream); break;
+  }
+  if (e != hipSuccess) return glb::api_hip_fail(e, "short_attention_packed launch");
   return GLB_OK;
 }
 

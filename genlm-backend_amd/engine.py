@@ -1002,6 +1002,29 @@ class HipEngine:
                                            _DT[query.dtype], _ptr(out), self._stream()))
         return out
 
+    def short_attention_packed(self, query, key, value, plan, max_keys, scale, err=None, out=None):
+        """Attention of a row-packed batch whose contexts share their prompt's rows (glb_short_attention_packed).  query
+        [M, H, Dh], key / value [M, H_kv, Dh] (unit inner stride: views of the projection output), plan int32 [S, 4] on the
+        device: (pre_start, pre_len, tail_start, tail_len) per segment, max_keys: the most keys of a segment (<= 32).
+        Returns [M, H, Dh] (`out`, contiguous, when given); rows no segment names are left as they were.  A segment the kernel
+        refuses (out of range) adds to `err` (int32 [1] device; default: `error_word()`, which `raise_if_failed` reports)."""
+        M, H, Dh = query.shape
+        Hkv = key.shape[1]
+        assert key.shape == value.shape == (M, Hkv, Dh) and key.dtype == value.dtype == query.dtype
+        assert query.stride(2) == 1 and key.stride(2) == 1 and value.stride(2) == 1
+        assert plan.dtype == torch.int32 and plan.dim() == 2 and plan.shape[1] == 4 and plan.is_contiguous()
+        self._check_dev(plan)
+        err = self.error_word() if err is None else err
+        assert err.dtype == torch.int32 and err.device == self.device
+        if out is None:
+            out = torch.empty((M, H, Dh), dtype=query.dtype, device=self.device)
+        assert out.shape == (M, H, Dh) and out.dtype == query.dtype and out.device == self.device and out.is_contiguous()
+        check(self.lib.glb_short_attention_packed(_ptr(query), query.stride(0), query.stride(1), _ptr(key), key.stride(0),
+                                                  key.stride(1), _ptr(value), value.stride(0), value.stride(1), _ptr(plan),
+                                                  plan.shape[0], M, H, Hkv, int(max_keys), Dh, float(scale),
+                                                  _DT[query.dtype], _ptr(out), _ptr(err), self._stream()))
+        return out
+
     def kv_gather_rows(self, srcs, dsts, src_row_of, len_of, srcs_stable=True):
         """dsts[t][i, h, p] = srcs[t][src_row_of[i], h, p] for p < len_of[i], for every tensor pair of the two lists
         (all [rows, heads, cap, head_dim], contiguous) in ONE launch through device pointer tables

@@ -153,6 +153,25 @@ SPLIT_GEMM_MIN_ROWS = {
 }
 
 
+class split_gemm_all_rows:
+    """For the duration of one forward, every `SplitConv1D` over `engine` runs the split kernel whatever its row count (the
+    table above is not touched).  The row-packed encoding (kv.encode_packed) feeds a fraction of the padded batch's rows; the
+    kernel's bits of a row do not depend on the batch around it, the library GEMM's may: with this, a row
+    has the bits it has in the padded batch that ran the kernel.  Nests; not for use from two threads over one engine."""
+
+    def __init__(self, engine):
+        self.engine = engine
+
+    def __enter__(self):
+        self.was = getattr(self.engine, "_split_all_rows", False)
+        self.engine._split_all_rows = True
+        return self
+
+    def __exit__(self, *exc):
+        self.engine._split_all_rows = self.was
+        return False
+
+
 def _is_tanh_gelu(act):
     return isinstance(act, torch.nn.GELU) and act.approximate == "tanh"
 
@@ -191,7 +210,8 @@ class SplitConv1D(torch.nn.Module):
     def _native(self, x):
         w = self.weight
         return (x.dtype == torch.float32 and w.dtype == torch.float32 and x.is_cuda and x.device == w.device
-                and x.device == self._glb_engine.device and x.shape[:-1].numel() >= self.min_rows
+                and x.device == self._glb_engine.device
+                and (x.shape[:-1].numel() >= self.min_rows or getattr(self._glb_engine, "_split_all_rows", False))
                 and not (torch.is_grad_enabled() and (x.requires_grad or w.requires_grad
                                                       or (self.bias is not None and self.bias.requires_grad))))
 

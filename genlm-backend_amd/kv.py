@@ -11,6 +11,8 @@
 * `PrefixTable` — the device table of cached prompt prefixes and the `DynamicCache` a batch that uses them is run with.
 * `encode_ragged` — the one forward that ENCODES a selection of a ragged batch (padded gather, body, last rows, K / V):
   every re-encoding path of `AsyncAmdLM`, `DeviceSIS` and `SlabRunner.run`'s rows of kind B goes through it.
+* `encode_packed` — the same encoding ROW-PACKED for contexts that are a shared prompt plus a short tail: every prompt's
+  rows once per forward (`PromptGroups`, `PackedKV`, glb_short_attention_packed).
 * `PrefixLRU` — byte-budgeted least-recently-used store for the prompt prefixes `cache_kv` pins (hf.py:155-164);
   the eviction policy of cache.py:103-191 (`DynamicTokenTrie`), applied to whole prefix slabs.
 """
@@ -58,6 +60,17 @@ def _glb_attention_forward(module, query, key, value, attention_mask, dropout=0.
         o = layer.owner
         scale = scaling if scaling is not None else query.shape[-1] ** -0.5
         return o.engine.slab_attention(query, k_new, v_new, layer.keys, layer.values, o.pos, scale), None
+    packed = getattr(key, "_glb_packed", None)
+    if packed is not None:
+        # a row-packed forward (encode_packed): batch 1, the M rows of every prompt and every tail; q / k / v are read where
+        # c_attn left them and the output is [M, H * Dh] already - no transpose, no copy
+        if query.shape[0] != 1 or key.shape[2] != query.shape[2] or query.shape[2] != packed.n_rows or value.shape != key.shape:
+            raise RuntimeError("glb_short_attention_packed: the attention module changed the shape of the packed batch")
+        scale = scaling if scaling is not None else query.shape[-1] ** -0.5
+        out = packed.engine.short_attention_packed(query[0].transpose(0, 1), key[0].transpose(0, 1), value[0].transpose(0, 1),
+                                                   packed.segments, packed.max_keys, scale)
+        packed.served += 1
+        return out.unsqueeze(0), None
     eng = getattr(getattr(module, "config", None), "_glb_engine", None)
     Lq, Lk = query.shape[2], key.shape[2]
     # the kernels write into fresh tensors outside autograd: a forward that may be differentiated keeps the SDPA path
@@ -646,6 +659,152 @@ def encode_ragged(llm, batch, sel, n_sel, l_max, pad_id=0, base=None, prefixes=N
     cache = None if table is None else table.cache_for(eng, pref)
     return RaggedEncoding(llm._body(input_ids=ids, attention_mask=am, position_ids=pos, past_key_values=cache,
                                     use_cache=keep_kv or cache is not None), last)
+
+
+# ---- the row-packed encoding: every shared prompt once per forward ----------------------------------------
+PACKED_MAX_KEYS = 32  # glb_short_attention_packed: prompt + tail tokens of a context
+
+
+class PromptGroups:
+    """The G prompts a population was built from, as the packed encoding wants them: `lens` (host ints, each >= 1), their
+    tokens and positions as the first rows of every packed batch (int64 [sum P_g], made once), the rows' offsets."""
+
+    def __init__(self, prompts, device):
+        if not prompts or any(len(p) < 1 for p in prompts):
+            raise ValueError("a prompt group needs at least one token")
+        self.lens = [len(p) for p in prompts]
+        self.n_rows, self.p_max = sum(self.lens), max(self.lens)
+        starts = np.concatenate([[0], np.cumsum(self.lens[:-1])]).astype(np.int32)
+        lens = np.asarray(self.lens, np.int32)
+        self.ids = torch.tensor([t for p in prompts for t in p], dtype=torch.int64, device=device)
+        self.pos = torch.tensor([j for p in prompts for j in range(len(p))], dtype=torch.int64, device=device)
+        self.starts_d, self.lens_d = torch.from_numpy(starts).to(device), torch.from_numpy(lens).to(device)
+        zero = np.zeros_like(lens)
+        self.segments = torch.from_numpy(np.stack([zero, zero, starts, lens], 1)).to(device)  # a prompt: no prefix, causal in itself
+
+
+def packed_plan(group_lens, grp, lens):
+    """The packing plan of contexts u = 0 .. U - 1 (group grp[u], lens[u] tokens = its prompt + a tail of t_u >= 1), in NumPy:
+    what `encode_packed` computes on the device, restated for tests and for readers.  Rows: the G prompts, then the tails in
+    context order.  Returns (segments int32 [G + U, 4]: (pre_start, pre_len, tail_start, tail_len), the prompts' segments
+    first; positions int64 [M]; (context, offset) int64 [M] of every row, context -1 - g for prompt g; last int64 [U]: the
+    row of every context's last token)."""
+    group_lens, grp, lens = np.asarray(group_lens, np.int64), np.asarray(grp, np.int64), np.asarray(lens, np.int64)
+    g_start = np.concatenate([[0], np.cumsum(group_lens[:-1])])
+    n_pre = int(group_lens.sum())
+    tail = lens - group_lens[grp]
+    if (tail < 1).any():
+        raise ValueError("every context needs a tail of at least one token behind its prompt")
+    t_start = n_pre + np.concatenate([[0], np.cumsum(tail[:-1])])
+    zero = np.zeros_like(group_lens)
+    seg = np.concatenate([np.stack([zero, zero, g_start, group_lens], 1),
+                          np.stack([g_start[grp], group_lens[grp], t_start, tail], 1)]).astype(np.int32)
+    ctx = np.concatenate([np.repeat(-1 - np.arange(len(group_lens)), group_lens), np.repeat(np.arange(len(lens)), tail)])
+    off = np.concatenate([np.arange(p) for p in group_lens] + [group_lens[grp[u]] + np.arange(tail[u]) for u in range(len(lens))])
+    return seg, off.astype(np.int64), np.stack([ctx, off], 1).astype(np.int64), (t_start + tail - 1).astype(np.int64)
+
+
+class _PackedLayer(CacheLayerMixin):
+    """Every layer of `PackedKV`: keeps nothing; hands the keys back tagged with the plan (how the attention entry finds it)."""
+
+    is_compileable = False
+    is_sliding = False
+
+    def __init__(self, owner):
+        super().__init__()
+        self.owner = owner
+
+    def lazy_initialization(self, key_states, value_states):
+        self.is_initialized = True
+
+    def update(self, key_states, value_states, *args, **kwargs):
+        key_states._glb_packed = self.owner
+        return key_states, value_states
+
+    def get_mask_sizes(self, query_length):
+        return query_length, 0
+
+    def get_seq_length(self):
+        return 0
+
+    def get_max_length(self):
+        return -1
+
+
+class PackedKV(Cache):
+    """The side channel of one row-packed forward: a `Cache` that stores nothing (so transformers builds no mask and looks
+    for no packed sequences in the position ids) and carries the plan to the "glb" attention entry on the key tensor.
+    `segments`: int32 [G + U, 4] device, `n_rows` = M, `max_keys` <= 32; `served` counts the layers that reached the kernel."""
+
+    def __init__(self, engine, segments, n_rows, max_keys, n_layers):
+        self.engine, self.segments, self.n_rows, self.max_keys = engine, segments, int(n_rows), int(max_keys)
+        self.served = 0
+        layer = _PackedLayer(self)
+        super().__init__(layers=[layer] * n_layers)
+
+
+class PackedEncoding:
+    """What `encode_packed` ran: `hidden` [M, d] and the row `last` [n_sel] of every context's last token."""
+
+    def __init__(self, out, last, n_rows):
+        self.out, self.hidden, self.last, self.n_rows = out, out.last_hidden_state[0], last, n_rows
+
+    def last_rows(self):
+        """[n_sel, d]: the hidden state at every context's last token."""
+        return self.hidden[self.last]
+
+
+def packed_supported(llm):
+    """Whether `llm._body`'s attention is served by this library's short-context kernels (the shadow points at the "glb"
+    entry with the backend's engine, a head width the kernels are built for)."""
+    body, eng = llm._body, llm.engine
+    cfg = getattr(body, "config", None)
+    if cfg is None or getattr(cfg, "_attn_implementation", None) != _ATTN_NAME or getattr(cfg, "_glb_engine", None) is not eng:
+        return False
+    heads = getattr(cfg, "num_attention_heads", None)
+    head_dim = getattr(cfg, "head_dim", None) or (cfg.hidden_size // heads if heads else None)
+    return bool(head_dim in (16, 32, 64, 128) and getattr(cfg, "num_hidden_layers", 0) > 0)
+
+
+def encode_packed(llm, batch, sel, n_sel, grp, groups, n_tail_rows, max_keys=PACKED_MAX_KEYS):
+    """Encode contexts `sel` (int32 device, its first n_sel entries) of the ragged `batch` = (tokens, starts, lengths) in one
+    ROW-PACKED forward of `llm._body`: context u is prompt `grp[u]` (int32 [n_sel] device) of `groups` (PromptGroups) plus a
+    tail of t_u >= 1 tokens, and the batch is [1, M]: the G prompts once, then the tails in context order - M = sum P_g +
+    n_tail_rows, where n_tail_rows = sum t_u is the CALLER's (host) number: nothing is read back here.  The prompts' hidden
+    states, K and V are the same for every context behind them (same tokens, same positions, causal), so computing them once
+    changes no result; attention is glb_short_attention_packed through `PackedKV`.  max_keys: the most P + t of a context
+    (<= 32).  Lengths that do not match n_tail_rows, a tail < 1 or a context longer than max_keys are refused row by row in
+    the kernel (engine.error_word / raise_if_failed); every index used here is clamped into range first."""
+    eng, dev = llm.engine, llm.device
+    tokens, starts, lengths = batch
+    if not 1 <= max_keys <= PACKED_MAX_KEYS:
+        raise ValueError(f"encode_packed serves contexts of up to {PACKED_MAX_KEYS} tokens")
+    if n_sel < 1 or n_tail_rows < n_sel:
+        raise ValueError("encode_packed: every context feeds at least one tail row")
+    if not packed_supported(llm):
+        raise RuntimeError("encode_packed: this model's attention is not served by glb_short_attention")
+    G, n_pre = len(groups.lens), groups.n_rows
+    M = n_pre + int(n_tail_rows)
+    sel_l, grp_l = sel[:n_sel].long(), grp[:n_sel].long().clamp(0, G - 1)
+    pre_len, pre_start = groups.lens_d[grp_l], groups.starts_d[grp_l]
+    tail = lengths[sel_l] - pre_len  # int32 [U]
+    ends = torch.cumsum(tail, 0, dtype=torch.int32)
+    tail_start = n_pre + ends - tail
+    segments = torch.cat([groups.segments, torch.stack([pre_start, pre_len, tail_start, tail], 1)]).contiguous()
+    # row -> (context, offset in its tail): the context whose [tail_start, tail_start + t) holds the row
+    r = torch.arange(int(n_tail_rows), dtype=torch.int32, device=dev)
+    u = torch.searchsorted(ends, r, right=True).clamp_(max=n_sel - 1)
+    pos_t = (pre_len[u] + (r - (ends - tail)[u])).long()
+    at = (starts[sel_l[u]] + pos_t).clamp_(0, tokens.numel() - 1)
+    ids = torch.cat([groups.ids, tokens[at].long()]).view(1, M)
+    max_pos = getattr(llm._body.config, "max_position_embeddings", None) or (1 << 30)
+    pos = torch.cat([groups.pos, pos_t.clamp_(0, min(PACKED_MAX_KEYS, max_pos) - 1)]).view(1, M)
+    pkv = PackedKV(eng, segments, M, max_keys, llm._body.config.num_hidden_layers)
+    out = llm._body(input_ids=ids, position_ids=pos, attention_mask=None, past_key_values=pkv, use_cache=True)
+    if pkv.served != len(pkv.layers):
+        raise RuntimeError(f"glb_short_attention_packed served {pkv.served} of {len(pkv.layers)} layers: an attention module "
+                           "bypassed the attention interface and attended across the packed contexts")
+    return PackedEncoding(out, (tail_start + tail - 1).long().clamp_(0, M - 1), M)
 
 
 class PrefixLRU:

@@ -20,7 +20,8 @@ import numpy as np
 import torch
 
 from .cache import KVPrefix
-from .kv import PrefixTable, SlabKV, SlabRunner, encode_ragged
+from .fuse import SplitConv1D, split_gemm_all_rows
+from .kv import PACKED_MAX_KEYS, PrefixTable, PromptGroups, SlabKV, SlabRunner, encode_packed, encode_ragged, packed_supported
 from .masks import ParticleMasks
 
 RNG_PHILOX, RNG_NOISE = 1, 2
@@ -214,7 +215,7 @@ class DeviceSIS:
     def __init__(self, llm, n_particles, prompt_ids, max_tokens, eos_id, seed=0, rng="philox", rank=0, world=1,
                  dist=None, use_prefix_kv=False, use_particle_kv=False, resample_ess=None, force_collectives=False,
                  share_kv=True, kv_rows=None, kv_in_place=0.75, kv_graph=True, particle_masks=None, migrate_kv=True,
-                 constraint=None):
+                 constraint=None, share_prompt_rows=True):
         if constraint is not None and particle_masks is not None:
             raise ValueError("give particle_masks (the caller's bit rows) or constraint (masks made on the device), not both")
         self.constraint = constraint
@@ -281,6 +282,16 @@ class DeviceSIS:
             self._build_prefixes(sorted(distinct))
         self.particle_kv = bool(use_particle_kv)
         self.share_kv = bool(share_kv) and self.particle_kv
+        # the row-packed re-encoding (kv.encode_packed): every distinct prompt's rows once per step instead of once per
+        # distinct context; `_packed_ready` says per step whether it applies
+        self.share_prompt_rows = bool(share_prompt_rows)
+        self.packed_steps = 0
+        self._groups = self._grp0 = None
+        if self.share_prompt_rows and not use_prefix_kv and not use_particle_kv and not (self.collective and world > 1):
+            index = {}
+            grp = [index.setdefault(tuple(p), len(index)) for p in prompts]
+            self._groups = PromptGroups(list(index), self.dev)
+            self._grp0 = torch.tensor(grp, dtype=torch.int32, device=self.dev)
         self.kv_rows = int(kv_rows) if kv_rows is not None else n_particles
         self.kv_stats = dict(forward_rows=0, encoded_rows=0, copied_rows=0, unkept_rows=0, steps=0, in_place_steps=0)
         # the KV slabs and the forwards over them: one runs on the slab rows where they lie when at least the fraction
@@ -317,6 +328,7 @@ class DeviceSIS:
         self._particle.reset()  # (a new run may come with new masks)
         self.contexts = self._ctx0.clone()
         self.prompt_len = self._prompt_len0.clone()
+        self._grp = self._grp0  # prompt group of every particle (follows its ancestor when the population is resampled)
         self.lengths = self.prompt_len.clone()
         self.active = torch.ones(self.N, dtype=torch.int32, device=self.dev)
         # (a constraint with pushed weights serves every path's weight minus beta[start]: the particles start with that constant)
@@ -565,10 +577,35 @@ class DeviceSIS:
             pref, base = eng.match_prefixes(ctx_flat, self.starts, lengths_eff, P.tokens, P.starts, P.lengths)
             prefixes = (P, pref[rep[:U].long()].contiguous())
             l_max = max(self.t, 1)  # every prompt is cached: only the generated tokens (<= t) are fed
-        enc = encode_ragged(llm, (ctx_flat, self.starts, lengths_eff), rep, U, l_max, base=base, prefixes=prefixes)
+        if self._packed_ready(U, n_active, l_max):
+            # every context is its prompt + t tokens: the G prompts' rows once, then U tails of t rows (host numbers: no
+            # read-back), every projection on the split kernel so that a row keeps the bits it has in the padded batch
+            with split_gemm_all_rows(eng):
+                enc = encode_packed(llm, (ctx_flat, self.starts, lengths_eff), rep, U, self._grp[rep[:U].long()],
+                                    self._groups, U * self.t, max_keys=l_max)
+            self._fwd_tokens = enc.n_rows
+            self.packed_steps += 1
+        else:
+            enc = encode_ragged(llm, (ctx_flat, self.starts, lengths_eff), rep, U, l_max, base=base, prefixes=prefixes)
         logits = llm._lm_head(enc.last_rows())  # [U, V]
         self._noise_groups = None
         return self._finish_step(logits, group_of, U, n_active, n_global, time_kernel, l_max)
+
+    def _packed_ready(self, U, n_active, l_max):
+        """Whether this step's re-encoding runs row-packed (kv.encode_packed): the option is on and the population was built
+        from prompts this rank knows (no KV option, no cached prefixes, one rank), every particle is still generating - so
+        every context is its prompt plus exactly t >= 1 tokens, none a finished particle's stub -, a context fits the
+        kernel's 32 keys, the body's attention is this library's, and the padded batch would have run every projection on
+        the split kernel (U * l_max rows reach the largest threshold of the body's SplitConv1D modules; a body without
+        them keeps the padded path: its library GEMMs give a row no batch-independent bits)."""
+        if self._groups is None or self.t < 1 or n_active != self.N or l_max > PACKED_MAX_KEYS or self.prefixes is not None:
+            return False
+        body = self.llm._body
+        ent = self.__dict__.get("_packed_body")
+        if ent is None or ent[0] is not body:  # (set_lora makes the backend's shadow anew)
+            rows = [m.min_rows for m in body.modules() if isinstance(m, SplitConv1D)]
+            ent = self._packed_body = (body, max(rows) if rows and packed_supported(self.llm) else None)
+        return ent[1] is not None and U * l_max >= ent[1]
 
     def _parity_noise(self, group_of, V):
         """Exp(1) rows in the order the reference's particles reach torch.multinomial: by dedup group (first appearance),
@@ -692,6 +729,8 @@ class DeviceSIS:
         self.lengths, self.prompt_len, self.active = (new_state[:, self.cap + k].contiguous() for k in range(3))
         # equal weights: log of the population's mean weight
         self.log_weights = (lse - float(np.log(n_total))).expand(N).contiguous()
+        if self._grp is not None:  # (one rank: every ancestor is local)
+            self._grp = self._grp[local.clamp(0, N - 1).long()]
         if self.share_kv:  # re-point: a particle takes its ancestor's row; ancestors of another rank leave it without one
             local = mine - self.rank * N
             ok = (local >= 0) & (local < N)
@@ -827,7 +866,7 @@ class SisBenchWorkload:
 
     def __init__(self, eng, dev, rank, world, dist, n_particles=1024, max_tokens=10, prefix_kv=False, particle_kv=False,
                  model="gpt2", n_prompts=1, resample=False, force_collectives=False, kv_in_place=0.75,
-                 per_particle_masks=False, rng="philox", gemms="library"):
+                 per_particle_masks=False, rng="philox", gemms="library", share_prompt_rows=True):
         from .llm import AsyncAmdLM
 
         if model == "gpt2":
@@ -882,7 +921,8 @@ class SisBenchWorkload:
         self.sis = DeviceSIS(self.llm, n_particles, prompts, max_tokens, cfg.eos_token_id,
                              seed=1234, rng=rng, rank=rank, world=world, dist=dist, use_prefix_kv=prefix_kv,
                              use_particle_kv=particle_kv, resample_ess=1.0 if resample else None,
-                             force_collectives=force_collectives, kv_in_place=kv_in_place, particle_masks=pm)
+                             force_collectives=force_collectives, kv_in_place=kv_in_place, particle_masks=pm,
+                             share_prompt_rows=share_prompt_rows)
         self.prefix_kv = prefix_kv
         self.particle_kv = particle_kv
         self.resample = resample

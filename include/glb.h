@@ -485,6 +485,26 @@ int glb_short_attention(const void *q, const int64_t q_strides[3], const void *k
                         float scale, int32_t dtype, void *out, void *hip_stream);
 
 /*
+ * The same attention over a ROW-PACKED batch whose contexts share the rows of their prompt: q / k / v are
+ * [n_rows, heads, head_dim] views by element strides {row, head} with unit inner stride (one projection output, read where
+ * it lies), plan [n_segments][4] int32 on the device: (pre_start, pre_len, tail_start, tail_len) per segment.  The tail_len
+ * queries of a segment are rows tail_start ..; its keys are rows pre_start .. pre_start + pre_len - 1 (the prompt, shared by
+ * every context behind it), then rows tail_start ..; query t sees keys 0 .. pre_len + t.  A prompt is a segment with
+ * pre_len = 0.  out [n_rows, heads, head_dim] contiguous; rows no segment names are not written.  max_keys: the most keys
+ * (pre_len + tail_len) of a segment, 1 .. 32 - GLB_EINVAL beyond, nothing launched.  A query's output has the bits
+ * glb_short_attention gives it on the right-padded batch of the same contexts.
+ * The plan is device data: a segment with more than max_keys keys, no query, or rows outside [0, n_rows) is never
+ * followed - it writes nothing and adds 1 to *err_word (a device word, e.g. glb_workspace_error_word's).  head_dim
+ * 16 / 32 / 64 / 128 (GLB_EUNSUPPORTED otherwise); pointers and strides multiples of 16 bytes; n_segments * kv_heads and
+ * n_rows below 2^31.
+ */
+int glb_short_attention_packed(const void *q, int64_t q_stride_row, int64_t q_stride_head, const void *k, int64_t k_stride_row,
+                               int64_t k_stride_head, const void *v, int64_t v_stride_row, int64_t v_stride_head,
+                               const int32_t *plan, int64_t n_segments, int64_t n_rows, int64_t heads, int64_t kv_heads,
+                               int64_t max_keys, int64_t head_dim, float scale, int32_t dtype, void *out, uint32_t *err_word,
+                               void *hip_stream);
+
+/*
  * Systematic resampling of the whole population from the all-gathered log-weights (the step the all-gather of
  * README.md:108-110's weights exists for; the reference itself stops at the normalised weights).  Exact integer
  * comb over the fixed-point weights of glb_normalize_weights with one Philox draw keyed by (seed, offset):
