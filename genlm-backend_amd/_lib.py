@@ -455,6 +455,27 @@ class ConjArgs(C.Structure):
     ]
 
 
+class ImportanceArgs(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("target", C.c_void_p), ("target_dtype", C.c_int32), ("ld_p", C.c_int64),
+        ("proposal", C.c_void_p), ("proposal_dtype", C.c_int32), ("ld_q", C.c_int64),
+        ("n_rows", C.c_int64), ("vocab", C.c_int64),
+        ("proposal_scale", C.c_float),
+        ("n_particles", C.c_int64), ("row_of", C.c_void_p),
+        ("mask_kind", C.c_int32), ("mask", C.c_void_p), ("mask_ld", C.c_int64), ("n_masks", C.c_int64),
+        ("mask_id", C.c_void_p), ("row_mask_id", C.c_void_p),
+        ("seed", C.c_uint64), ("offset", C.c_uint64), ("particle_base", C.c_int64),
+        ("out_token", C.c_void_p), ("out_dlogw", C.c_void_p), ("out_lse_target", C.c_void_p),
+        ("out_logZ_proposal", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+    ]
+
+
+IMPORTANCE_CHUNK = 4096  # vocabulary indices per chunk of glb_importance_step's two-stage draw
+IMPORTANCE_RECORD_BYTES = 64  # workspace bytes per (unit, chunk)
+
+
 # every symbol include/glb.h declares: name -> (restype, argtypes)
 _vp, _i32, _i64, _f32, _sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_size_t
 SYMBOLS = {
@@ -565,6 +586,8 @@ SYMBOLS = {
     "glb_conj_unpack": (C.c_int, [C.POINTER(ConjArgs), _vp]),
     "glb_conj_number": (C.c_int, [C.POINTER(ConjArgs), _vp]),
     "glb_conj_serve": (C.c_int, [C.POINTER(ConjArgs), _vp]),
+    "glb_importance_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "glb_importance_step": (C.c_int, [C.POINTER(ImportanceArgs), _vp]),
     "glb_philox4x32_10": (None, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
 }
 

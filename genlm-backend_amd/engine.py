@@ -261,6 +261,7 @@ class HipEngine:
         self.lib = _OnDevice(lib, self.device.index)
         self._ws = None
         self._step_ws = None
+        self._imp_ws = None
         self._trie_ws = None
         self._lora_rows_ws = None
         self._mt_polys = {}
@@ -388,6 +389,75 @@ class HipEngine:
         else:
             check(self.lib.glb_logprob_mask_sample(C.byref(a), self._stream()))
         return logZ, lse, tok
+
+    def importance_step(self, target, proposal=None, *, proposal_scale=1.0, vocab=None, row_of=None, mask_kind=MASK_NONE,
+                        mask=None, mask_id=None, row_mask_id=None, seed=0, offset=0, particle_base=0, want_lse=False,
+                        want_logZ_proposal=False, out=None):
+        """Importance-weighted particle step (glb_importance_step): the token drawn from
+        softmax(proposal * proposal_scale + mask), dlogw = log[softmax(target)_tok e^{mask_tok}] - log of the probability
+        it was drawn with.  Returns (dlogw, token, lse_target or None) - with `want_logZ_proposal` a fourth tensor,
+        lse(y + m) - lse(y).
+
+        target, proposal: [n_rows, ld] logits of the same contexts under two models (last dim contiguous, any of float32 /
+        bfloat16 / float16 each); proposal None: the target's own rows.  mask: int32 bit rows (MASK_BITS) or float rows
+        (MASK_F32) as they lie - not a `PreparedMasks`; `mask_id` per particle or `row_mask_id` per logits row.
+        out: (dlogw, token, lse or None) to write into.  The records live in a scratch buffer of their own: the fused
+        step's is registered with the library and carries its tags."""
+        if isinstance(mask, PreparedMasks):
+            raise TypeError("importance_step reads bit rows or float rows as they lie, not prepared masks")
+        mats = [("target", target)] + ([("proposal", proposal)] if proposal is not None else [])
+        for name, t in mats:
+            if t.dim() != 2 or t.stride(1) != 1:
+                raise ValueError(f"{name} must be 2-D with unit inner stride")
+            if t.dtype not in _DT:
+                raise TypeError(f"unsupported {name} dtype {t.dtype}")
+            if t.device != self.device:
+                raise ValueError(f"{name} on {t.device}, engine on {self.device}")
+        n_rows, width = target.shape
+        if proposal is not None and tuple(proposal.shape) != (n_rows, width):
+            raise ValueError(f"proposal is {tuple(proposal.shape)}, target {tuple(target.shape)}: row r of one pairs with row r "
+                             "of the other")
+        V = width if vocab is None else vocab
+        n = n_rows if row_of is None else row_of.numel()
+        self._check_dev(row_of, mask_id, row_mask_id)
+        if out is None:
+            dlogw, tok, lse = self._f32(n), self._i32(n), (self._f32(n) if want_lse else None)
+        else:
+            dlogw, tok, lse = out
+        logZq = self._f32(n) if want_logZ_proposal else None
+        a = _lib.ImportanceArgs()
+        a.struct_size = C.sizeof(_lib.ImportanceArgs)
+        a.target, a.target_dtype = target.data_ptr(), _DT[target.dtype]
+        a.ld_p = target.stride(0) if n_rows > 1 else max(width, target.stride(0))
+        if proposal is not None:
+            a.proposal, a.proposal_dtype = proposal.data_ptr(), _DT[proposal.dtype]
+            a.ld_q = proposal.stride(0) if n_rows > 1 else max(width, proposal.stride(0))
+        a.n_rows, a.vocab, a.proposal_scale, a.n_particles = n_rows, V, proposal_scale, n
+        a.row_of = None if row_of is None else row_of.data_ptr()
+        a.mask_kind = mask_kind
+        if mask_kind != MASK_NONE:
+            if mask.device != self.device:
+                raise ValueError(f"mask on {mask.device}, engine on {self.device}")
+            if mask.dim() != 2 or mask.stride(1) != 1:
+                raise ValueError("mask must be 2-D with unit inner stride (rows may be strided)")
+            want = torch.float32 if mask_kind == MASK_F32 else torch.int32
+            if mask.dtype != want:
+                raise TypeError(f"mask dtype {mask.dtype}, expected {want}")
+            a.mask, a.n_masks = mask.data_ptr(), mask.shape[0]
+            a.mask_ld = mask.stride(0) if mask.shape[0] > 1 else mask.shape[1]
+            a.mask_id = None if mask_id is None else mask_id.data_ptr()
+            a.row_mask_id = None if row_mask_id is None else row_mask_id.data_ptr()
+        a.seed, a.offset, a.particle_base = seed, offset, particle_base
+        a.out_token = None if tok is None else tok.data_ptr()
+        a.out_dlogw = None if dlogw is None else dlogw.data_ptr()
+        a.out_lse_target = None if lse is None else lse.data_ptr()
+        a.out_logZ_proposal = None if logZq is None else logZq.data_ptr()
+        need = self.lib.glb_importance_workspace_bytes(n, n_rows, V)
+        if self._imp_ws is None or self._imp_ws.numel() < need:
+            self._imp_ws = torch.empty(max(need, 1 << 20), dtype=torch.uint8, device=self.device)
+        a.workspace, a.workspace_bytes = self._imp_ws.data_ptr(), self._imp_ws.numel()
+        check(self.lib.glb_importance_step(C.byref(a), self._stream()))
+        return (dlogw, tok, lse, logZq) if want_logZ_proposal else (dlogw, tok, lse)
 
     # ---- failed one-launch calls (include/glb.h: glb_workspace_check) ---------------------------------------------
     def error_word(self):

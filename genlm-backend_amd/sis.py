@@ -22,6 +22,7 @@ import torch
 from .cache import KVPrefix
 from .fuse import SplitConv1D, split_gemm_all_rows
 from .kv import PACKED_MAX_KEYS, PrefixTable, PromptGroups, SlabKV, SlabRunner, encode_packed, encode_ragged, packed_supported
+from ._lib import MASK_BITS, MASK_NONE
 from .masks import ParticleMasks
 
 RNG_PHILOX, RNG_NOISE = 1, 2
@@ -207,6 +208,14 @@ class DeviceSIS:
                      takes its state's final weight.  With pushed weights (`DeviceConstraint(..., push=...)`) every
                      particle starts at log-weight `constraint.start_logw`, so a finished particle weighs what it weighs
                      without pushing and the estimate of the normalising constant is unchanged.
+    proposal_temperature  T > 0: every token is PROPOSED from the target's own logits at 1/T under the step's mask and the
+                     particle's weight takes log[softmax(p)_tok e^{m_tok}] - log qt(tok) where it takes logZ otherwise
+                     (glb_importance_step): properly weighted for the same target, flatter draws under a tight
+                     constraint.  No second forward; every KV mode.
+    proposal         a second `AsyncAmdLM` on the same device with the same vocabulary size: each step encodes the same
+                     distinct contexts through it as well and proposes from ITS logits (times 1 / proposal_temperature when
+                     that is given too).  The re-encoding path only (no use_prefix_kv / use_particle_kv).
+                     With both None the step is the fused one, untouched.  Either needs rng="philox".
     force_collectives  run the collectives of the multi-rank path (all-gather of log-weights / token matrices, the
                      set-up reductions) through `dist` even when world == 1: a one-rank "nccl" group exercises the RCCL
                      code of an 8-GPU run on a single GPU.
@@ -215,9 +224,29 @@ class DeviceSIS:
     def __init__(self, llm, n_particles, prompt_ids, max_tokens, eos_id, seed=0, rng="philox", rank=0, world=1,
                  dist=None, use_prefix_kv=False, use_particle_kv=False, resample_ess=None, force_collectives=False,
                  share_kv=True, kv_rows=None, kv_in_place=0.75, kv_graph=True, particle_masks=None, migrate_kv=True,
-                 constraint=None, share_prompt_rows=True):
+                 constraint=None, share_prompt_rows=True, proposal_temperature=None, proposal=None):
         if constraint is not None and particle_masks is not None:
             raise ValueError("give particle_masks (the caller's bit rows) or constraint (masks made on the device), not both")
+        self._propose = proposal_temperature is not None or proposal is not None
+        if self._propose:
+            if rng != "philox":
+                raise ValueError(f"proposal_temperature / proposal need rng='philox', got rng={rng!r}: the reference has no draw "
+                                 "from a proposal for the parity mode to be on par with")
+            if proposal_temperature is not None and not float(proposal_temperature) > 0.0:
+                raise ValueError(f"proposal_temperature must be > 0, got {proposal_temperature!r}")
+            if proposal is not None:
+                for flag, name in ((use_prefix_kv, "use_prefix_kv"), (use_particle_kv, "use_particle_kv")):
+                    if flag:
+                        raise ValueError(f"proposal= conflicts with {name}: a proposal model is served on the re-encoding path "
+                                         "only (it keeps no KV rows)")
+                vp, vq = int(llm.model.config.vocab_size), int(proposal.model.config.vocab_size)
+                if vp != vq:
+                    raise ValueError(f"proposal= has another vocabulary: {vq} tokens, the target {vp}")
+                if proposal.device != llm.device:
+                    raise ValueError(f"proposal= is on {proposal.device}, the target on {llm.device}")
+        self.proposal = proposal
+        self._q_scale = 1.0 if proposal_temperature is None else 1.0 / float(proposal_temperature)
+        self._q_logits = None  # the running step's proposal logits, row for row the target's
         self.constraint = constraint
         self.llm, self.eng, self.dev = llm, llm.engine, llm.device
         # the LoRA adapter this population's KV is made with: a step after set_lora / clear_lora raises (llm._lora_sync)
@@ -447,6 +476,8 @@ class DeviceSIS:
         eng, llm, N = self.eng, self.llm, self.N
         V = logits.shape[-1]
         mask_id = ((self.lengths - self.prompt_len) >= self.max_tokens).to(torch.int32)
+        if self._propose:
+            return self._finish_proposed(logits, group_of, U, n_active, n_global, time_kernel, l_max, mask_id)
         # the step's mask source: the constraint, else the caller's row per particle, else the backend's registered masks
         source = self.constraint if self.constraint is not None else self._particle if self.particle_masks is not None else llm.masks
         kw, raw = source.step_masks(logits, *self._mask_units(logits, group_of, mask_id), N, parity=self.rng_mode == RNG_NOISE)
@@ -470,6 +501,43 @@ class DeviceSIS:
             self.outer_events.append((e0, e1))
         if self.rng_mode == RNG_NOISE:  # the next step's rows set out on a side stream, under the next forward
             self.noise_src.prefetch()
+        return self._advance(logits, mask_id, logZ, tok, U, n_active, n_global, l_max)
+
+    def _proposal_masks(self, logits, ids, by_row):
+        """The step's mask rows in a form glb_importance_step reads: a constraint's bank or gathered bit rows, a weight
+        bank, the caller's particle rows raw, the backend's registered masks as bit or float rows - never prepared."""
+        key = "row_mask_id" if by_row else "mask_id"
+        if self.constraint is not None:
+            kw, raw = self.constraint.step_masks(logits, ids, by_row, self.N, parity=False)
+            self.constraint_raw_steps += int(raw)
+            return kw
+        if self.particle_masks is not None:
+            return {"mask_kind": MASK_BITS, "mask": self.particle_masks, key: ids}
+        m = self.llm.masks
+        return {} if m.kind == MASK_NONE else {"mask_kind": m.kind, "mask": m.table, key: ids}
+
+    def _finish_proposed(self, logits, group_of, U, n_active, n_global, time_kernel, l_max, mask_id):
+        """`_finish_step` with a proposal: the token from the proposal's rows (the target's own at 1 / T without a proposal
+        model), log[softmax(p)_tok e^{m_tok}] - log qt(tok) to the weight where the fused step's logZ goes."""
+        eng, N = self.eng, self.N
+        kw = self._proposal_masks(logits, *self._mask_units(logits, group_of, mask_id))
+        q, self._q_logits = self._q_logits, None
+        if time_kernel:
+            if len(self._event_pool) < 2:
+                self._event_pool = eng.timing_events(64)
+            e0, e1 = self._event_pool.pop()
+            e0.record()
+        dlogw, tok, _ = eng.importance_step(logits, q, proposal_scale=self._q_scale, vocab=logits.shape[-1], row_of=group_of,
+                                            seed=self.seed, offset=self.t, particle_base=self.rank * N, **kw)
+        if time_kernel:
+            e1.record()
+            self.kernel_events.append((e0, e1))
+            self.outer_events.append((e0, e1))
+        return self._advance(logits, mask_id, dlogw, tok, U, n_active, n_global, l_max)
+
+    def _advance(self, logits, mask_id, logZ, tok, U, n_active, n_global, l_max):
+        """What follows the draw: the weights take `logZ`, the contexts the tokens, the constraint's states follow."""
+        eng = self.eng
         len_was = self.lengths.clone() if self.constraint is not None else None
         if self.constraint is not None and self.constraint.weighted:
             # a particle out of tokens was served row 1 (EOS alone, weight 0): its state's final weight is added here, so that
@@ -588,6 +656,9 @@ class DeviceSIS:
         else:
             enc = encode_ragged(llm, (ctx_flat, self.starts, lengths_eff), rep, U, l_max, base=base, prefixes=prefixes)
         logits = llm._lm_head(enc.last_rows())  # [U, V]
+        if self.proposal is not None:  # the same distinct contexts through the proposal model: row r pairs with row r
+            other = self.proposal
+            self._q_logits = other._lm_head(encode_ragged(other, (ctx_flat, self.starts, lengths_eff), rep, U, l_max).last_rows())
         self._noise_groups = None
         return self._finish_step(logits, group_of, U, n_active, n_global, time_kernel, l_max)
 

@@ -1656,6 +1656,72 @@ int glb_conj_unpack(const glb_conj_args *args, void *hip_stream);
 int glb_conj_number(const glb_conj_args *args, void *hip_stream);
 int glb_conj_serve(const glb_conj_args *args, void *hip_stream);
 
+/*
+ * Importance-weighted particle step: propose from q, weight toward p.  Per particle i, with target
+ * row p = target[row_of[i]], proposal row q = proposal[row_of[i]] (the same context under two models; proposal null: the
+ * target's own row, read from memory once), y_j = fl32(q_j * proposal_scale) when the scale is not 1 (else q_j), and mask row
+ * m (GLB_MASK_BITS: 0 / -inf; GLB_MASK_F32: any float, -inf ok):
+ *     qt(j)  ∝ exp(y_j + m_j)                              the proposal actually drawn from
+ *     token  ~ qt
+ *     dlogw  = (p_tok - lse(p)) - (y_tok - lse(y + m))     = log[softmax(p)_tok e^{m_tok}] - log qt(tok)
+ * so that E_qt[exp(dlogw)] = sum_j softmax(p)_j e^{m_j}: adding dlogw to a particle's log-weight where the fused step adds
+ * logZ keeps the population properly weighted for the same target.  With proposal null and scale 1, dlogw IS the fused
+ * step's logZ, whatever token is drawn.
+ *   out_token          -1 when nothing has proposal mass (the mask allows nothing, or y + m is -inf everywhere)
+ *   out_dlogw          -inf for token -1 and where p_tok is -inf
+ *   out_lse_target     lse(p)
+ *   out_logZ_proposal  lse(y + m) - lse(y); -inf for token -1
+ * Each output is nullable.  Masks: the table, mask_ld, n_masks, mask_id / row_mask_id and their null rules are those of
+ * the fused step's argument block; kinds GLB_MASK_NONE, GLB_MASK_BITS (raw rows) and GLB_MASK_F32 - GLB_MASK_PREPARED is
+ * the fused step's own layout and GLB_EINVAL here.  A row or mask id read from device memory that is out of range makes its
+ * particle one whose mask allows nothing.  +inf and NaN logits, and logits beyond 2^21 in magnitude, are not supported
+ * (no fault; the results are unspecified).
+ * The draw: the fused step's Philox block - counter = (particle_base + i, offset), key = seed -, R1 = its words 0 and 1,
+ * R2 = its words 2 and 3 (low word first).  Chunks are 4096 consecutive vocabulary indices; R1 / 2^64 picks the chunk by
+ * inverse CDF over the chunks' masses under qt in chunk order, R2 / 2^64 the element by inverse CDF over that chunk's
+ * elements of nonzero mass in index order.  Results are a function of the inputs alone: the same for a row alone or among
+ * others, shared by many particles or copied for each, and however the particles are cut into calls (particle_base).
+ * Arithmetic: a term is the hardware's 2^(x log2 e - N - 1) against the chunk's binary scale N; log-sum-exps within 1e-4
+ * of the exact values of the inputs (observed: DESIGN.md section 28), CDF boundaries within 1e-5 of the stage's mass.
+ * Two plain launches on `hip_stream` (one wave per unit and chunk - a unit is a logits row when row_mask_id or no mask is
+ * given, else a particle -, then one wave per particle); nothing waits inside a launch, nothing synchronises or allocates;
+ * safe under stream capture.  workspace: device scratch of at least the bytes glb_importance_workspace_bytes names (64 per
+ * unit and chunk), 16-byte aligned, not shared with a workspace that glb_workspace_init registered; too small: GLB_ENOSPC.
+ * GLB_EINVAL before any launch: struct_size wrong; target null; a dtype outside GLB_F32 .. GLB_F16 (the proposal's only
+ * when a proposal is given - proposal_dtype and ld_q are not read otherwise); sizes not positive or beyond 31 bits; ld_p
+ * or ld_q below vocab; a NaN scale; row_of null with n_particles != n_rows; a bad mask_kind; with a mask: the table null,
+ * mask_ld below a row's elements, both id arrays given, no ids with n_masks neither 1 nor the number of units; workspace
+ * null or misaligned.  With GLB_MASK_NONE no mask field is read.
+ */
+typedef struct glb_importance_args {
+  uint32_t struct_size; /* sizeof this block - ABI guard */
+  const void *target;   /* [n_rows, ld_p] device */
+  int32_t target_dtype; /* GLB_F32 / GLB_BF16 / GLB_F16 */
+  int64_t ld_p;         /* row pitch in elements, >= vocab */
+  const void *proposal; /* [n_rows, ld_q] device, nullable: the target's own rows */
+  int32_t proposal_dtype;
+  int64_t ld_q;
+  int64_t n_rows, vocab;
+  float proposal_scale;
+  int64_t n_particles;
+  const int32_t *row_of; /* [n_particles] device, nullable: identity (needs n_particles == n_rows) */
+  int32_t mask_kind;
+  const void *mask; /* [n_masks, mask_ld] device: uint32 words or floats */
+  int64_t mask_ld, n_masks;
+  const int32_t *mask_id;     /* [n_particles] device, nullable */
+  const int32_t *row_mask_id; /* [n_rows] device, nullable; exclusive with mask_id */
+  uint64_t seed, offset;
+  int64_t particle_base;
+  int32_t *out_token;       /* [n_particles] */
+  float *out_dlogw;         /* [n_particles] */
+  float *out_lse_target;    /* [n_particles] */
+  float *out_logZ_proposal; /* [n_particles] */
+  void *workspace;
+  size_t workspace_bytes;
+} glb_importance_args;
+size_t glb_importance_workspace_bytes(int64_t n_particles, int64_t n_rows, int64_t vocab);
+int glb_importance_step(const glb_importance_args *args, void *hip_stream);
+
 /* Philox4x32-10 block function, exposed so hosts can reproduce the device draws. */
 void glb_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 
