@@ -15,7 +15,7 @@ def __getattr__(name):
     if name == "HipEngine":
         from .engine import HipEngine
         return HipEngine
-    if name in ("load_model_by_name", "AsyncAmdLM", "AsyncLM"):
+    if name in ("load_model_by_name", "AsyncAmdLM", "AsyncLM", "SequenceScores"):
         from . import llm
         return getattr(llm, name)
     if name in ("ByteDFA", "ByteWFSA", "DeviceConstraint", "minimize", "product", "ByteNFA", "determinize", "LazyConstraint", "BytePDA",

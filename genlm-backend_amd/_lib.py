@@ -476,6 +476,21 @@ IMPORTANCE_CHUNK = 4096  # vocabulary indices per chunk of glb_importance_step's
 IMPORTANCE_RECORD_BYTES = 64  # workspace bytes per (unit, chunk)
 
 
+class ScoreArgs(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("logits", C.c_void_p), ("dtype", C.c_int32),
+        ("n_rows", C.c_int64), ("vocab", C.c_int64), ("ld", C.c_int64),
+        ("logit_scale", C.c_float),
+        ("token", C.c_void_p),
+        ("mask_kind", C.c_int32), ("mask", C.c_void_p), ("mask_ld", C.c_int64), ("n_masks", C.c_int64),
+        ("row_mask_id", C.c_void_p),
+        ("out_logp", C.c_void_p), ("out_lse", C.c_void_p), ("out_logZ", C.c_void_p), ("out_logp_masked", C.c_void_p),
+        ("seq_start", C.c_void_p), ("n_seq", C.c_int64),
+        ("out_seq_logp", C.c_void_p), ("out_seq_logZ", C.c_void_p), ("out_seq_logp_masked", C.c_void_p),
+    ]
+
+
 # every symbol include/glb.h declares: name -> (restype, argtypes)
 _vp, _i32, _i64, _f32, _sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_size_t
 SYMBOLS = {
@@ -588,6 +603,8 @@ SYMBOLS = {
     "glb_conj_serve": (C.c_int, [C.POINTER(ConjArgs), _vp]),
     "glb_importance_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "glb_importance_step": (C.c_int, [C.POINTER(ImportanceArgs), _vp]),
+    "glb_score_rows": (C.c_int, [C.POINTER(ScoreArgs), _vp]),
+    "glb_score_seq_sums": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp]),
     "glb_philox4x32_10": (None, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
 }
 

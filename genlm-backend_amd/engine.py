@@ -459,6 +459,101 @@ class HipEngine:
         check(self.lib.glb_importance_step(C.byref(a), self._stream()))
         return (dlogw, tok, lse, logZq) if want_logZ_proposal else (dlogw, tok, lse)
 
+    SCORE_OUTPUTS = ("logp", "lse", "logZ", "logp_masked")
+
+    def score_rows(self, logits, tokens, *, vocab=None, logit_scale=1.0, mask_kind=MASK_NONE, mask=None, row_mask_id=None,
+                   seq_start=None, want=("logp",)):
+        """Scores of given tokens (glb_score_rows): per logits row r, with y = logits[r] * logit_scale and
+        t = tokens[r], any of "logp" = y_t - lse(y), "lse" = lse(y), "logZ" = lse(y + m) - lse(y), "logp_masked" =
+        y_t + m_t - lse(y + m) - the names in `want` -, as a dict of float32 [n_rows] device tensors.  No log-softmax is
+        written.  logits: [n_rows, ld] (last dim contiguous; float32 / bfloat16 / float16); tokens int32 [n_rows]; mask:
+        int32 bit rows (MASK_BITS) or float rows (MASK_F32) as they lie with `row_mask_id` int32 [n_rows] (None: one mask
+        for all, or one per row) - the keywords a constraint's `step_masks(..., by_row=True, ...)` returns.  seq_start:
+        int64 [n_seq + 1] ascending row offsets; the dict then also holds "seq_" + name, float32 [n_seq], for "logp",
+        "logZ" and "logp_masked" where wanted: the sums over each sequence's rows."""
+        if isinstance(mask, PreparedMasks) or mask_kind == MASK_PREPARED:
+            raise TypeError("score_rows reads bit rows or float rows as they lie, not prepared masks")
+        want = tuple(want)
+        for w in want:
+            if w not in self.SCORE_OUTPUTS:
+                raise ValueError(f"want names {w!r}; the outputs are {self.SCORE_OUTPUTS}")
+        if logits.dim() != 2 or logits.stride(1) != 1:
+            raise ValueError("logits must be 2-D with unit inner stride")
+        if logits.dtype not in _DT:
+            raise TypeError(f"unsupported logits dtype {logits.dtype}")
+        if logits.device != self.device:
+            raise ValueError(f"logits on {logits.device}, engine on {self.device}")
+        n_rows, width = logits.shape
+        V = width if vocab is None else vocab
+        if not 0 < V <= width:
+            raise ValueError(f"vocab {V} outside (0, {width}]")
+        if n_rows == 0:
+            raise ValueError("no rows to score")
+        if not 0 < logit_scale < float("inf"):  # (NaN too; 0 or a negative scale would turn -inf logits into NaN / +inf)
+            raise ValueError(f"logit_scale must be positive and finite, got {logit_scale!r}")
+        self._check_dev(tokens, row_mask_id, seq_start)
+        if tokens.dtype != torch.int32 or tokens.shape != (n_rows,) or not tokens.is_contiguous():
+            raise ValueError("tokens must be a contiguous int32 [n_rows] tensor")
+        if mask_kind not in (MASK_NONE, MASK_BITS, MASK_F32):
+            raise ValueError(f"bad mask_kind {mask_kind}")
+        a = _lib.ScoreArgs()
+        a.struct_size = C.sizeof(_lib.ScoreArgs)
+        a.logits, a.dtype = logits.data_ptr(), _DT[logits.dtype]
+        a.n_rows, a.vocab, a.logit_scale = n_rows, V, logit_scale
+        a.ld = logits.stride(0) if n_rows > 1 else max(width, logits.stride(0))
+        a.token = tokens.data_ptr()
+        a.mask_kind = mask_kind
+        if mask_kind != MASK_NONE:
+            if mask is None:
+                raise ValueError("mask_kind given without a mask table")
+            if mask.device != self.device:
+                raise ValueError(f"mask on {mask.device}, engine on {self.device}")
+            if mask.dim() != 2 or mask.stride(1) != 1:
+                raise ValueError("mask must be 2-D with unit inner stride (rows may be strided)")
+            want_dt = torch.float32 if mask_kind == MASK_F32 else torch.int32
+            if mask.dtype != want_dt:
+                raise TypeError(f"mask dtype {mask.dtype}, expected {want_dt}")
+            if mask.shape[1] < (V if mask_kind == MASK_F32 else (V + 31) // 32):
+                raise ValueError(f"mask rows of {mask.shape[1]} elements are too short for {V} tokens")
+            if row_mask_id is not None and (row_mask_id.dtype != torch.int32 or row_mask_id.shape != (n_rows,)
+                                            or not row_mask_id.is_contiguous()):
+                raise ValueError("row_mask_id must be a contiguous int32 [n_rows] tensor")
+            if row_mask_id is None and mask.shape[0] not in (1, n_rows):
+                raise ValueError(f"no row_mask_id given but the table has {mask.shape[0]} rows: neither 1 nor {n_rows}")
+            a.mask, a.n_masks = mask.data_ptr(), mask.shape[0]
+            a.mask_ld = mask.stride(0) if mask.shape[0] > 1 else mask.shape[1]
+            a.row_mask_id = None if row_mask_id is None else row_mask_id.data_ptr()
+        elif mask is not None or row_mask_id is not None:
+            raise ValueError("a mask table or row_mask_id given with MASK_NONE")
+        out = {w: self._f32(n_rows) for w in want}
+        for w in want:
+            setattr(a, "out_" + w, out[w].data_ptr())
+        if seq_start is not None:
+            if seq_start.dtype != torch.int64 or seq_start.dim() != 1 or seq_start.numel() < 1 or not seq_start.is_contiguous():
+                raise ValueError("seq_start must be a contiguous int64 [n_seq + 1] tensor")
+            a.seq_start, a.n_seq = seq_start.data_ptr(), seq_start.numel() - 1
+            for w in want:
+                if w != "lse":
+                    out["seq_" + w] = self._f32(a.n_seq)
+                    setattr(a, "out_seq_" + w, out["seq_" + w].data_ptr())
+        check(self.lib.glb_score_rows(C.byref(a), self._stream()))
+        return out
+
+    def score_seq_sums(self, values, seq_start):
+        """float32 [n_seq]: the sums of `values` (float32 [n_rows]) over rows seq_start[s] .. seq_start[s + 1] - 1, in row
+        order, in double, rounded once (glb_score_seq_sums: the sums of `score_rows` for rows that were scored in chunks)."""
+        self._check_dev(values, seq_start)
+        if values.dtype != torch.float32 or values.dim() != 1:
+            raise ValueError("values must be a float32 [n_rows] tensor")
+        if seq_start.dtype != torch.int64 or seq_start.dim() != 1 or seq_start.numel() < 1:
+            raise ValueError("seq_start must be an int64 [n_seq + 1] tensor")
+        out = self._f32(seq_start.numel() - 1)
+        if out.numel():
+            # (an empty `values` has no storage to point at: any valid pointer serves, no row is read)
+            src = values if values.numel() else out
+            check(self.lib.glb_score_seq_sums(_ptr(src), values.numel(), _ptr(seq_start), out.numel(), _ptr(out), self._stream()))
+        return out
+
     # ---- failed one-launch calls (include/glb.h: glb_workspace_check) ---------------------------------------------
     def error_word(self):
         """int32 [1] device view of the scratch buffer's error word: nonzero after a one-launch call whose waves gave

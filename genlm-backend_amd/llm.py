@@ -135,6 +135,34 @@ class _Slot:
         self.exc = e
 
 
+class SequenceScores:
+    """What `batch_sequence_logprobs*` return, all float32 device tensors: `token_logprobs` [total] = log p(token | what
+    precedes it) of every scored token, sequence after sequence (sequence i's are token_logprobs[starts[i]:starts[i + 1]],
+    `starts` int64 [N + 1]); `logprobs` [N], their sums per sequence (0 for an empty continuation).  Under a constraint
+    also `token_logZ` / `logZ` (log of the probability mass the constraint allowed at each position: what the fused step
+    adds to a particle's log-weight - a pushed constraint's `start_logw` is not added) and `token_logprobs_masked` /
+    `logprobs_masked` (log-probabilities under the constrained, renormalised distribution: -inf from a sequence's first
+    forbidden token on); None without one."""
+
+    FIELDS = ("token_logprobs", "token_logZ", "token_logprobs_masked")
+
+    def __init__(self, starts, token_logprobs, logprobs, token_logZ=None, logZ=None, token_logprobs_masked=None,
+                 logprobs_masked=None):
+        self.starts, self.token_logprobs, self.logprobs = starts, token_logprobs, logprobs
+        self.token_logZ, self.logZ = token_logZ, logZ
+        self.token_logprobs_masked, self.logprobs_masked = token_logprobs_masked, logprobs_masked
+
+    def __len__(self):
+        return self.starts.numel() - 1
+
+    def tolist(self, field="token_logprobs"):
+        """Per-sequence Python lists of one per-token field (one D2H copy of it and of `starts`)."""
+        if field not in self.FIELDS or getattr(self, field) is None:
+            raise ValueError(f"no per-token field {field!r} in these scores")
+        st, v = self.starts.tolist(), getattr(self, field).tolist()
+        return [v[st[i]:st[i + 1]] for i in range(len(st) - 1)]
+
+
 class AsyncAmdLM(AsyncLM):
     """Autobatching wrapper around a HuggingFace causal LM on one MI355X (hf.py:73-422)."""
 
@@ -244,7 +272,7 @@ class AsyncAmdLM(AsyncLM):
     def __init__(self, hf_model, hf_tokenizer, batch_size=20, timeout=0.02, engine=None, fuse_activations=True,
                  kv_budget_bytes=8 << 30, logprob_budget_bytes=16 << 30, auto_kv_rows=0, auto_kv_cap=64,
                  auto_kv_chunk=1, logprob_dtype="float32", glb_attention=True, merge_mlp=True, contract=None, gemms="library",
-                 split_gemms=True, w4_gemm="auto"):
+                 split_gemms=True, w4_gemm="auto", score_chunk_bytes=1 << 30):
         """The caller's `hf_model` is never modified (hf.py:114-140 leaves it alone too): with `fuse_activations` or
         `glb_attention` the forwards of this backend run on a private SHADOW of its module tree that shares every weight
         (fuse.shadow_model); `self.model` stays the caller's object.
@@ -279,7 +307,12 @@ class AsyncAmdLM(AsyncLM):
         `gemms` still decides every GEMM this path does not take.  False: not swapped.
         w4_gemm: how the 4-bit layers of a quantised model (quant.W4Linear) multiply - "auto": glb_w4_gemm on the 4-bit image
         for the row counts where it was measured faster (quant.MIN_ROWS_FUSED), dequantise + library GEMM otherwise;
-        "fused" / "dequant": one path wherever it is able to serve the call (tests, A/Bs)."""
+        "fused" / "dequant": one path wherever it is able to serve the call (tests, A/Bs).
+        score_chunk_bytes: the most logits bytes `batch_sequence_logprobs*` hold at a time (never above logprob_budget_bytes;
+        always at least one row)."""
+        if score_chunk_bytes <= 0:
+            raise ValueError(f"score_chunk_bytes must be positive, got {score_chunk_bytes!r}")
+        self.score_chunk_bytes = min(int(score_chunk_bytes), int(logprob_budget_bytes))
         self.model = hf_model
         self.tokenizer = hf_tokenizer
         self.device = hf_model.device
@@ -1281,6 +1314,137 @@ class AsyncAmdLM(AsyncLM):
         if lora_names is not None:
             return self._batch_lora_logprobs(token_ids_list, lora_names)
         return self._batch_logprobs(token_ids_list)
+
+    # ---- scoring given sequences (glb_score_rows: DESIGN.md §29) -----------------------------------------------------------
+    def batch_sequence_logprobs_sync(self, prompts, continuations, *, temperature=1.0, constraint=None):
+        """log p(continuation token | prompt, earlier continuation tokens) for every token of every pair, in ONE forward over
+        prompt + continuation[:-1] and without a log-softmax of any row: `SequenceScores`.  prompts, continuations: lists of
+        token-id lists of equal count; a prompt needs at least one token, a continuation may be empty.  temperature: the
+        scores are those of softmax(logits / temperature).  constraint (any constraint of `constraints`): the continuation
+        is also walked through it from its start state - `SequenceScores`' logZ and masked fields."""
+        prompts, continuations = [list(p) for p in prompts], [list(c) for c in continuations]
+        if len(prompts) != len(continuations):
+            raise ValueError(f"{len(prompts)} prompts for {len(continuations)} continuations")
+        if any(len(p) == 0 for p in prompts):
+            raise ValueError("a prompt needs at least one token: the first scored token needs a position before it")
+        n = len(prompts)
+        cap = max((len(p) + len(c) for p, c in zip(prompts, continuations)), default=1)
+        tok = np.zeros((n, cap), np.int32)
+        for i, (p, c) in enumerate(zip(prompts, continuations)):
+            tok[i, :len(p) + len(c)] = p + c
+        plen = np.fromiter(map(len, prompts), np.int32, n)
+        lens = plen + np.fromiter(map(len, continuations), np.int32, n)
+        dev = self.device
+        return self.batch_sequence_logprobs_device(torch.from_numpy(tok).to(dev), torch.from_numpy(lens).to(dev),
+                                                   torch.from_numpy(plen).to(dev), temperature=temperature, constraint=constraint)
+
+    async def batch_sequence_logprobs(self, prompts, continuations, *, temperature=1.0, constraint=None):
+        """Awaitable form of `batch_sequence_logprobs_sync` (the evaluation itself blocks the loop)."""
+        return self.batch_sequence_logprobs_sync(prompts, continuations, temperature=temperature, constraint=constraint)
+
+    async def sequence_logprobs(self, prompt, continuation, *, temperature=1.0, constraint=None):
+        """`batch_sequence_logprobs` of one pair."""
+        return self.batch_sequence_logprobs_sync([prompt], [continuation], temperature=temperature, constraint=constraint)
+
+    @torch.no_grad()
+    def batch_sequence_logprobs_device(self, tokens, lengths, prompt_lengths, *, temperature=1.0, constraint=None, forced_at=None):
+        """`batch_sequence_logprobs_sync` for sequences that live on the device, as `batch_next_token_step_device` takes
+        them: `tokens` int32 [N, cap] (row i's first lengths[i] entries: prompt, then continuation), `lengths` and
+        `prompt_lengths` int32 [N].  No token and no score crosses the host, but the call is not asynchronous: it copies back
+        six counts to size the forward and the score buffers (and, under a constraint, how many sequences have a token at each
+        position), and each copy waits for the stream - a caller that queues work behind a population stalls here.
+        forced_at (needs a constraint): int32 [N] device, the place in its continuation at which sequence i was MADE to end
+        (negative: nowhere) - that token is scored against the row a finished sequence is served (EOS alone if its state
+        accepts, else nothing), as a `DeviceSIS` particle out of tokens is."""
+        if tokens.dim() != 2 or tokens.dtype != torch.int32 or lengths.dtype != torch.int32 or lengths.shape != (tokens.shape[0],):
+            raise ValueError("tokens must be int32 [n, cap] and lengths int32 [n]")
+        if prompt_lengths.dtype != torch.int32 or prompt_lengths.shape != lengths.shape:
+            raise ValueError("prompt_lengths must be int32 [n]")
+        if not 0 < temperature < float("inf"):
+            raise ValueError(f"temperature must be positive and finite, got {temperature!r}")
+        if forced_at is not None and (constraint is None or forced_at.dtype != torch.int32 or forced_at.shape != lengths.shape):
+            raise ValueError("forced_at must be int32 [n] and needs a constraint")
+        eng, dev = self.engine, self.device
+        tokens = tokens.contiguous()
+        N, cap = tokens.shape
+        f32 = lambda k: torch.zeros(k, dtype=torch.float32, device=dev)
+        if N == 0:
+            return SequenceScores(torch.zeros(1, dtype=torch.int64, device=dev), f32(0), f32(0),
+                                  *([f32(0)] * 4 if constraint is not None else []))
+        self._lora_sync()
+        P, T = prompt_lengths.long(), (lengths - prompt_lengths).long()
+        starts = torch.zeros(N + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(T.clamp(min=0), 0, out=starts[1:])
+        enc_len = (lengths - 1).clamp(min=1)  # prompt + continuation[:-1]; a lone prompt token stands for itself
+        R, l_max, t_max, p_min, t_min, len_max = torch.stack([starts[-1], enc_len.max().long(), T.max(), P.min(), T.min(),
+                                                              lengths.max().long()]).tolist()  # the call's D2H copy
+        if p_min < 1:
+            raise ValueError("a prompt needs at least one token: the first scored token needs a position before it")
+        if t_min < 0 or len_max > cap:
+            raise ValueError("prompt_lengths must not exceed lengths, nor lengths the width of tokens")
+        names = ("logp",) if constraint is None else ("logp", "logZ", "logp_masked")
+        tok_out = {w: torch.empty(R, dtype=torch.float32, device=dev) for w in names}
+        if R:
+            row_start = torch.arange(N, dtype=torch.int64, device=dev) * cap
+            enc = encode_ragged(self, (tokens.view(-1), row_start, enc_len), torch.arange(N, dtype=torch.int32, device=dev), N,
+                                l_max, pad_id=self._pad_id)
+            hidden = enc.hidden.reshape(N * l_max, -1)  # (right-padded: position j of sequence i is row i * l_max + j)
+            rows_per = self._score_rows_per_chunk(hidden)
+            scale = 1.0 / temperature
+            if constraint is None:
+                seq = torch.repeat_interleave(torch.arange(N, device=dev), T, output_size=R)
+                k = torch.arange(R, device=dev) - starts[seq]  # the token's place in its continuation
+                h_idx, tgt = seq * l_max + P[seq] - 1 + k, tokens.view(-1)[seq * cap + P[seq] + k]
+                for a in range(0, R, rows_per):  # (a chunk boundary may fall inside a sequence)
+                    logits = self._lm_head(hidden[h_idx[a:a + rows_per]])
+                    got = eng.score_rows(logits, tgt[a:a + rows_per].contiguous(), vocab=logits.shape[-1], logit_scale=scale,
+                                         want=names)
+                    tok_out["logp"][a:a + rows_per] = got["logp"]
+            else:
+                self._score_constrained(constraint, tokens, lengths, P, T, starts, hidden, l_max, t_max, rows_per, scale, tok_out,
+                                        forced_at)
+        sums = {w: eng.score_seq_sums(v, starts) for w, v in tok_out.items()}
+        if constraint is None:
+            return SequenceScores(starts, tok_out["logp"], sums["logp"])
+        constraint.check()
+        return SequenceScores(starts, tok_out["logp"], sums["logp"], tok_out["logZ"], sums["logZ"], tok_out["logp_masked"],
+                              sums["logp_masked"])
+
+    def _score_rows_per_chunk(self, hidden):
+        """Logits rows a scoring chunk may hold: `score_chunk_bytes` over the bytes of a row as `_lm_head` returns it (the
+        head's own width and dtype, found by running it on one row), a third of that where the head soft-caps its logits
+        (x / cap and tanh(.) are temporaries of the logits' size)."""
+        one = self._lm_head(hidden[:1])
+        per_row = one.shape[-1] * one.element_size() * (3 if self._head_cap is not None else 1)
+        return max(1, self.score_chunk_bytes // per_row)
+
+    def _score_constrained(self, constraint, tokens, lengths, P, T, starts, hidden, l_max, t_max, rows_per, scale, tok_out,
+                           forced_at=None):
+        """Position by position: the sequences that have a token at position t are scored against the mask rows of their
+        current states, then every state moves over its token.  Row ids are asked for afresh at each position (an evicting
+        bank may recycle rows between two `mask_rows` calls)."""
+        eng, dev = self.engine, self.device
+        N, cap = tokens.shape
+        order = torch.argsort(T, descending=True, stable=True)  # the sequences with a token at position t: a prefix of it
+        counts = (T[:, None] > torch.arange(t_max, device=dev)[None]).sum(0).tolist()  # (D2H: t_max counts)
+        states = constraint.states0(N)
+        P32 = P.to(torch.int32)
+        flat = tokens.view(-1)
+        for t in range(t_max):
+            done = T <= t
+            if forced_at is not None:  # (a sequence made to end here: the row of a finished one)
+                done = done | (forced_at == t)
+            ids = constraint.mask_rows(states, done.to(torch.int32))
+            for a in range(0, counts[t], rows_per):
+                act = order[a:min(a + rows_per, counts[t])]
+                logits = self._lm_head(hidden[act * l_max + P[act] - 1 + t])
+                kw, _ = constraint.step_masks(logits, ids[act].contiguous(), True, act.numel())
+                got = eng.score_rows(logits, flat[act * cap + P[act] + t].contiguous(), vocab=logits.shape[-1], logit_scale=scale,
+                                     want=tuple(tok_out), **kw)
+                for w, v in tok_out.items():
+                    v[starts[act] + t] = got[w]
+            frm = torch.minimum(P32 + t, lengths)
+            states = constraint.advance(states, tokens, frm.contiguous(), torch.minimum(P32 + t + 1, lengths).contiguous())
 
     # ---- sampling (base.py:110-179): a device-resident multi-token loop -----------------------------------------------
     @torch.no_grad()

@@ -860,6 +860,42 @@ class DeviceSIS:
                 break
         return steps
 
+    @torch.no_grad()
+    def rescore(self, llm=None, prompt_ids=None, constraint=None):
+        """`SequenceScores` (llm.py) of the particles' generated tokens as they stand: under `llm` (None: the run's own
+        model), behind `prompt_ids` (a list of token ids shared by all particles; None: every particle's own prompt) and
+        walked through `constraint` from its start state (None: unconstrained - hand a fresh constraint of the run's
+        automaton to get the per-step logZ the run accumulated).
+        A particle that ended drew EOS, which the run does not store: it is scored as its last token, so that `logZ` has one
+        term per step the particle took, as its log-weight has; one made to end at max_tokens is scored there against the
+        EOS-only row it was served.  A particle the constraint killed (log-weight -inf: it drew nothing) keeps its tokens
+        and gets no EOS: its scores are those of the tokens it has, its `logZ` is not its log-weight.  A weighted constraint's
+        final weight of a particle made to end (`forced_final_logw`) and a pushed one's `start_logw` are not in `logZ`.
+        One forward on the device; like `batch_sequence_logprobs_device` it waits for the stream to read back the counts that
+        size it.  Touches no state of the run."""
+        llm = self.llm if llm is None else llm
+        gen = self.lengths - self.prompt_len
+        drew_eos = (self.active == 0) & torch.isfinite(self.log_weights) & (self.lengths < self.cap)
+        at_end = self.lengths.clamp(max=self.cap - 1).long()[:, None]  # where the EOS goes
+        last = torch.where(drew_eos[:, None], torch.full_like(at_end, self.eos_id), self.contexts.gather(1, at_end))
+        tokens = self.contexts.scatter(1, at_end, last.to(torch.int32))
+        lengths, plen = self.lengths + drew_eos.to(torch.int32), self.prompt_len
+        forced_at = None
+        if constraint is not None:
+            forced_at = torch.where(drew_eos & (gen >= self.max_tokens), gen, torch.full_like(gen, -1))
+        if prompt_ids is not None:
+            prompt = torch.tensor(list(prompt_ids), dtype=torch.int32, device=self.dev)
+            if prompt.numel() == 0:
+                raise ValueError("a prompt needs at least one token")
+            n_p = prompt.numel()
+            j = torch.arange(n_p + self.cap, device=self.dev)[None] - n_p  # column j of the new matrix: generated token j
+            own = torch.gather(tokens, 1, (plen[:, None].long() + j).clamp(0, self.cap - 1))
+            shared = prompt[(j + n_p).clamp(min=0, max=n_p - 1)].expand(self.N, -1)
+            tokens = torch.where(j < 0, shared, own).contiguous()
+            plen = torch.full_like(plen, n_p)
+            lengths = plen + gen + drew_eos.to(torch.int32)
+        return llm.batch_sequence_logprobs_device(tokens, lengths, plen, constraint=constraint, forced_at=forced_at)
+
     def results(self):
         self.eng.check()  # the last steps' fused calls completed (glb_workspace_check; synchronises like the copies below)
         if self.constraint is not None:

@@ -1722,6 +1722,65 @@ typedef struct glb_importance_args {
 size_t glb_importance_workspace_bytes(int64_t n_particles, int64_t n_rows, int64_t vocab);
 int glb_importance_step(const glb_importance_args *args, void *hip_stream);
 
+/*
+ * Score given tokens: per logits row r, with y_j = fl32(x_j * logit_scale) when the scale is not 1
+ * (else x_j), t = token[r] and mask row m (GLB_MASK_BITS: 0 / -inf; GLB_MASK_F32: any float, -inf ok):
+ *     out_lse          = lse(y)
+ *     out_logp         = y_t - lse(y)
+ *     out_logZ         = lse(y + m) - lse(y)               -inf when nothing has mass
+ *     out_logp_masked  = fl32(y_t + m_t) - lse(y + m)      -inf when m_t = -inf or nothing has mass
+ * Each output is nullable, float32 [n_rows].  A token outside [0, vocab) gives -inf in out_logp and out_logp_masked (nothing
+ * is loaded for it); a mask id outside [0, n_masks) makes the row one whose mask allows nothing; a row of all -inf gives -inf
+ * in every output.  +inf and NaN logits, and logits beyond 2^21 in magnitude, are not supported (no fault; the results are
+ * unspecified).  Masks: the table, mask_ld, n_masks, row_mask_id and the null rules are those of the fused step's argument
+ * block with the logits row as the unit; kinds GLB_MASK_NONE, GLB_MASK_BITS (raw rows) and GLB_MASK_F32 -
+ * GLB_MASK_PREPARED is GLB_EINVAL.  With GLB_MASK_NONE no mask field is read, out_logZ is 0 (-inf for a row of all -inf) and
+ * out_logp_masked equals out_logp.
+ * Sequence sums (seq_start non-null): out_seq_*[s] = the sum of the per-row output over rows seq_start[s] ..
+ * seq_start[s + 1] - 1 in row order, accumulated in double and rounded once; an empty sequence sums to 0, any -inf term makes
+ * the sum -inf.  seq_start is read on the device (ascending, last value n_rows; bounds outside [0, n_rows] are clipped).  A
+ * sequence output needs its per-row output (out_seq_logp needs out_logp, and so on).
+ * One launch, one workgroup of four waves per row: every logit and every mask word of the row is read once in 16-byte
+ * loads (element aligned: any base and pitch), nothing of size [n_rows, vocab] is written, y_t and m_t are taken by the lane
+ * that streams index t.  One more small launch per sequence sum asked for.  Nothing waits inside a launch, nothing
+ * synchronises or allocates; safe under stream capture; no workspace.  A row's outputs are a function of that row's inputs
+ * alone: the reduction tree (chunks of 4096 indices, chunk c on wave c mod 4, the four waves folded in order) does not
+ * depend on n_rows, so the bits are the same for a row alone or among others and however the rows are cut into calls.
+ * Arithmetic: glb_importance_step's - log-sum-exps within 1e-4 of the exact values of the inputs.
+ * GLB_EINVAL before any launch: struct_size wrong; logits or token null; a dtype outside GLB_F32 .. GLB_F16; n_rows or vocab
+ * not positive or beyond 31 bits; ld below vocab; logits not element aligned; a scale that is NaN, not positive or infinite; a bad or prepared mask_kind; with
+ * a mask: the table null or misaligned, mask_ld below a row's elements, n_masks not positive or beyond 31 bits, no ids with
+ * n_masks neither 1 nor n_rows; seq_start given with n_seq < 0; a sequence output given without seq_start or without its
+ * per-row output.
+ */
+typedef struct glb_score_args {
+  uint32_t struct_size; /* sizeof this block - ABI guard */
+  const void *logits;   /* [n_rows, ld] device */
+  int32_t dtype;        /* GLB_F32 / GLB_BF16 / GLB_F16 */
+  int64_t n_rows, vocab;
+  int64_t ld; /* row pitch in elements, >= vocab */
+  float logit_scale;
+  const int32_t *token; /* [n_rows] device */
+  int32_t mask_kind;
+  const void *mask; /* [n_masks, mask_ld] device: uint32 words or floats */
+  int64_t mask_ld, n_masks;
+  const int32_t *row_mask_id; /* [n_rows] device, nullable: n_masks == 1 ? 0 : identity */
+  float *out_logp;            /* [n_rows] each, nullable */
+  float *out_lse;
+  float *out_logZ;
+  float *out_logp_masked;
+  const int64_t *seq_start; /* [n_seq + 1] device, nullable */
+  int64_t n_seq;
+  float *out_seq_logp; /* [n_seq] each, nullable */
+  float *out_seq_logZ;
+  float *out_seq_logp_masked;
+} glb_score_args;
+int glb_score_rows(const glb_score_args *args, void *hip_stream);
+/* The sequence sums alone, for per-row values that several glb_score_rows calls wrote (rows scored in chunks): out[s] = the
+ * sum of values[seq_start[s] .. seq_start[s + 1]) under the same rules.  One launch; GLB_EINVAL for a null pointer or a size
+ * that is negative or beyond 31 bits; n_seq == 0 launches nothing. */
+int glb_score_seq_sums(const float *values, int64_t n_rows, const int64_t *seq_start, int64_t n_seq, float *out, void *hip_stream);
+
 /* Philox4x32-10 block function, exposed so hosts can reproduce the device draws. */
 void glb_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 
