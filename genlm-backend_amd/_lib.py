@@ -16,6 +16,7 @@ MASK_NONE, MASK_BITS, MASK_F32, MASK_PREPARED = 0, 1, 2, 3
 RNG_NONE, RNG_PHILOX, RNG_NOISE = 0, 1, 2
 STEP_HW_EXP = 1  # glb_step_args.flags: the hardware-exponential contract of 16-bit rows
 GEMM_BIAS, GEMM_BIAS_GELU_TANH = 0, 1  # glb_gemm_args.epilogue
+GEMM_FORM_LARGE, GEMM_FORM_SMALL = 1, 2  # glb_gemm_f32_split_form's tile form (0: picked from the shape)
 
 
 class GlbError(RuntimeError):
@@ -559,7 +560,10 @@ SYMBOLS = {
     "glb_gemm_split_bytes": (_sz, [_i64, _i64]),
     "glb_gemm_split_weights": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _sz, _vp]),
     "glb_gemm_f32_split": (C.c_int, [C.POINTER(GemmArgs), _vp]),
+    "glb_gemm_split_pick": (C.c_int, [_i64, _i64, _i64, C.c_int, C.POINTER(C.c_int)]),
+    "glb_gemm_f32_split_form": (C.c_int, [C.POINTER(GemmArgs), C.c_int, _vp]),
     "glb_gemm_split_blocks_per_cu": (C.c_int, [C.c_int, C.POINTER(C.c_int)]),
+    "glb_gemm_split_form_blocks_per_cu": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "glb_lora_merge_workspace_bytes": (_sz, [_i32]),
     "glb_lora_merge": (C.c_int, [C.POINTER(LoraJob), _i32, _vp, _sz, _vp]),
     "glb_lora_rows_table_bytes": (_sz, [_i32, _i32]),

@@ -23,8 +23,13 @@
 // registers, one K step ahead of its use, and splits it there.  (The four lanes that share l & 15 read 128 contiguous bytes
 // of one row.)
 //
-// Tiling: 128 x 128 output tile per 256-thread block, K step 32, two LDS stages of the B pieces (48 KiB: three blocks per CU,
-// within 168 VGPRs); wave w owns rows 32w .. 32w+31 and all 128 columns (2 x 8 fragments of 16 x 16).
+// Tiling: one output tile per 256-thread block, K step 32, two LDS stages of the B pieces; wave w owns MF row fragments
+// (16 rows each) and all NF column fragments of the tile.  Two forms of the one kernel (Geom below):
+//   large: 128 x 128, MF = 2, NF = 8, 48 KiB of LDS, three blocks per CU within 168 VGPRs - wave w owns rows 32w .. 32w+31;
+//   small:  64 x  64, MF = 1, NF = 4, 24 KiB of LDS, six blocks per CU - wave w owns rows 16w .. 16w+15.  For launches whose
+//          128 x 128 tiles would leave CUs empty (glb_gemm_split_pick).
+// An output element is the same chain in either form - six MFMAs on a fresh accumulator per K step, partial sums added in K
+// order, bias, GELU - so a call's bits do not depend on the form (tests/test_split_gemm_forms_gpu.py).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -40,12 +45,24 @@ typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 
-constexpr int BM = 128, BN = 128, BK = 32, THREADS = 256;
-constexpr int PIECE = 1024;                          // bytes of one staged piece (64 lanes x 16 B)
-constexpr int B_PIECES = (BN / 16) * 3;              // 24
-constexpr int STAGE_BYTES = B_PIECES * PIECE;        // 24 KiB
-constexpr int LDS_BYTES = 2 * STAGE_BYTES;           // 48 KiB
-constexpr int BLOCKS_PER_CU = 3;                     // 144 of the CU's 160 KiB of LDS
+constexpr int BK = 32, THREADS = 256, WAVES = THREADS / 64;
+constexpr int PIECE = 1024;  // bytes of one staged piece (64 lanes x 16 B)
+
+// tile geometry: MF row fragments per wave, NF column fragments per block, BLOCKS blocks per CU
+template <int MF_, int NF_, int BLOCKS_>
+struct Geom {
+  static constexpr int MF = MF_, NF = NF_, BLOCKS_PER_CU = BLOCKS_;
+  static constexpr int BM = WAVES * MF * 16, BN = NF * 16;
+  static constexpr int B_PIECES = NF * 3;                 // large 24, small 12
+  static constexpr int WAVE_PIECES = B_PIECES / WAVES;    // pieces one wave stages per K step: 6, 3
+  static constexpr int STAGE_BYTES = B_PIECES * PIECE;    // 24 KiB, 12 KiB
+  static constexpr int LDS_BYTES = 2 * STAGE_BYTES;       // 48 KiB, 24 KiB
+  static_assert(B_PIECES % WAVES == 0, "every wave stages the same number of pieces");
+  static_assert(BLOCKS_PER_CU * LDS_BYTES <= 160 * 1024, "the CU has 160 KiB of LDS");
+};
+using Large = Geom<2, 8, 3>;  // 128 x 128: 144 of the CU's 160 KiB of LDS
+using Small = Geom<1, 4, 6>;  //  64 x  64: 144 KiB as well
+constexpr int BN_MAX = Large::BN;  // what shape_supported asks of n (a multiple of every form's BN)
 
 // round-to-nearest-even split of two fp32 values into packed bf16 pairs hi / mid / lo (hi + mid + lo == x)
 __device__ __forceinline__ void split2(f32x2 x, uint32_t &h, uint32_t &m, uint32_t &l) {
@@ -105,10 +122,11 @@ __device__ __forceinline__ void glds16(const void *src, char *lds) {
   __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void *)lds, 16, 0, 0);
 }
 
-template <bool GELU>
-__global__ __launch_bounds__(THREADS, BLOCKS_PER_CU) void gemm_split_kernel(const float *__restrict__ a, int64_t lda,
+template <class G, bool GELU>
+__global__ __launch_bounds__(THREADS, G::BLOCKS_PER_CU) void gemm_split_kernel(const float *__restrict__ a, int64_t lda,
                                                                 const char *__restrict__ wsplit, const float *__restrict__ bias,
                                                                 float *__restrict__ c, int64_t ldc, int m, int n, int k) {
+  constexpr int MF = G::MF, NF = G::NF, BM = G::BM, BN = G::BN, WAVE_PIECES = G::WAVE_PIECES, STAGE_BYTES = G::STAGE_BYTES;
   extern __shared__ __attribute__((aligned(16))) char lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int ntn = n / BN, ntm = (m + BM - 1) / BM;
@@ -120,30 +138,30 @@ __global__ __launch_bounds__(THREADS, BLOCKS_PER_CU) void gemm_split_kernel(cons
   const int kt_count = k / BK;
 
   // sources (per lane, advanced by one K step each iteration)
-  // A operand of this lane for the wave's two row fragments mf = 2 * wave + i: eight floats of one row
-  const float *a_src[2];
+  // A operand of this lane for the wave's row fragments mf = MF * wave + i: eight floats of one row
+  const float *a_src[MF];
 #pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    int row = m0 + (2 * wave + i) * 16 + (lane & 15);
+  for (int i = 0; i < MF; ++i) {
+    int row = m0 + (MF * wave + i) * 16 + (lane & 15);
     row = row < m ? row : m - 1;  // rows past M read the last row; their results are never stored
     a_src[i] = a + (int64_t)row * lda + 8 * (lane >> 4);
   }
-  // B pieces of this wave: p = 6 * wave + i -> (nf = p / 3, plane = p % 3); LDS image: plane-major (plane * 8 + nf)
-  const char *b_src[6];
-  int b_dst[6];
+  // B pieces of this wave: p = WAVE_PIECES * wave + i -> (nf = p / 3, plane = p % 3); LDS image: plane-major (plane * NF + nf)
+  const char *b_src[WAVE_PIECES];
+  int b_dst[WAVE_PIECES];
 #pragma unroll
-  for (int i = 0; i < 6; ++i) {
-    const int p = 6 * wave + i, nf = p / 3, pl = p % 3;
+  for (int i = 0; i < WAVE_PIECES; ++i) {
+    const int p = WAVE_PIECES * wave + i, nf = p / 3, pl = p % 3;
     const int64_t nb = n0 / 16 + nf;
     b_src[i] = wsplit + ((nb * kt_count) * 3 + pl) * PIECE + lane * 16;
-    b_dst[i] = (pl * 8 + nf) * PIECE;
+    b_dst[i] = (pl * NF + nf) * PIECE;
   }
   const int64_t b_step = 3 * PIECE;  // one K step further in the packed image
 
-  f32x4 ax[2][2];  // this lane's A operand of the next K step (prefetched: the loop's closing wait retires it)
+  f32x4 ax[MF][2];  // this lane's A operand of the next K step (prefetched: the loop's closing wait retires it)
   auto load_a = [&](int kt) {
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
+    for (int i = 0; i < MF; ++i) {
       ax[i][0] = *(const f32x4 *)(a_src[i] + kt * BK);
       ax[i][1] = *(const f32x4 *)(a_src[i] + kt * BK + 4);
     }
@@ -151,18 +169,18 @@ __global__ __launch_bounds__(THREADS, BLOCKS_PER_CU) void gemm_split_kernel(cons
   auto stage_b = [&](int buf, int kt) {
     char *base = lds + buf * STAGE_BYTES;
 #pragma unroll
-    for (int i = 0; i < 6; ++i) glds16(b_src[i] + kt * b_step, base + b_dst[i]);
+    for (int i = 0; i < WAVE_PIECES; ++i) glds16(b_src[i] + kt * b_step, base + b_dst[i]);
   };
 
-  f32x4 acc[2][8];
+  f32x4 acc[MF][NF];
 #pragma unroll
-  for (int i = 0; i < 2; ++i)
+  for (int i = 0; i < MF; ++i)
 #pragma unroll
-    for (int j = 0; j < 8; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < NF; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  float bcol[8];  // (loaded ahead: the loop's waits retire it)
+  float bcol[NF];  // (loaded ahead: the loop's waits retire it)
 #pragma unroll
-  for (int nf = 0; nf < 8; ++nf) bcol[nf] = bias ? bias[n0 + nf * 16 + (lane & 15)] : 0.0f;
+  for (int nf = 0; nf < NF; ++nf) bcol[nf] = bias ? bias[n0 + nf * 16 + (lane & 15)] : 0.0f;
 
   load_a(0);
   stage_b(0, 0);
@@ -172,21 +190,21 @@ __global__ __launch_bounds__(THREADS, BLOCKS_PER_CU) void gemm_split_kernel(cons
   for (int kt = 0; kt < kt_count; ++kt) {
     const int cur = kt & 1;
     const char *base = lds + cur * STAGE_BYTES;
-    bf16x8 ah[2], am[2], al[2];
+    bf16x8 ah[MF], am[MF], al[MF];
 #pragma unroll
-    for (int i = 0; i < 2; ++i) split8(ax[i][0], ax[i][1], ah[i], am[i], al[i]);
+    for (int i = 0; i < MF; ++i) split8(ax[i][0], ax[i][1], ah[i], am[i], al[i]);
     // (after the split: the prefetch registers are free, and nothing beyond column K of a row is ever addressed)
     if (kt + 1 < kt_count) {
       load_a(kt + 1);
       stage_b(cur ^ 1, kt + 1);
     }
 #pragma unroll
-    for (int nf = 0; nf < 8; ++nf) {
-      const bf16x8 bh = *(const bf16x8 *)(base + (0 * 8 + nf) * PIECE + lane * 16);
-      const bf16x8 bm = *(const bf16x8 *)(base + (1 * 8 + nf) * PIECE + lane * 16);
-      const bf16x8 bl = *(const bf16x8 *)(base + (2 * 8 + nf) * PIECE + lane * 16);
+    for (int nf = 0; nf < NF; ++nf) {
+      const bf16x8 bh = *(const bf16x8 *)(base + (0 * NF + nf) * PIECE + lane * 16);
+      const bf16x8 bm = *(const bf16x8 *)(base + (1 * NF + nf) * PIECE + lane * 16);
+      const bf16x8 bl = *(const bf16x8 *)(base + (2 * NF + nf) * PIECE + lane * 16);
 #pragma unroll
-      for (int i = 0; i < 2; ++i) {
+      for (int i = 0; i < MF; ++i) {
         f32x4 t = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am[i], bm, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
         t = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[i], bh, t, 0, 0, 0);
         t = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[i], bl, t, 0, 0, 0);
@@ -204,12 +222,12 @@ __global__ __launch_bounds__(THREADS, BLOCKS_PER_CU) void gemm_split_kernel(cons
 
   // epilogue: C/D map of 16x16 MFMA - col = lane & 15, row = 4 * (lane >> 4) + reg
 #pragma unroll
-  for (int nf = 0; nf < 8; ++nf) {
+  for (int nf = 0; nf < NF; ++nf) {
     const int col = n0 + nf * 16 + (lane & 15);
     const float b = bcol[nf];
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int row0 = m0 + wave * 32 + i * 16 + 4 * (lane >> 4);
+    for (int i = 0; i < MF; ++i) {
+      const int row0 = m0 + wave * (MF * 16) + i * 16 + 4 * (lane >> 4);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int row = row0 + j;
@@ -223,9 +241,54 @@ __global__ __launch_bounds__(THREADS, BLOCKS_PER_CU) void gemm_split_kernel(cons
   }
 }
 
-bool shape_supported(int64_t k, int64_t n) { return k > 0 && n > 0 && n % BN == 0 && k % 64 == 0 && k <= (1 << 20) && n <= (1 << 20); }
+bool shape_supported(int64_t k, int64_t n) { return k > 0 && n > 0 && n % BN_MAX == 0 && k % 64 == 0 && k <= (1 << 20) && n <= (1 << 20); }
 
-std::atomic<uint64_t> g_lds_plain{0}, g_lds_gelu{0};
+// one instantiation's host side: its LDS attribute (one bit per device), its launch and its residency
+template <class G, bool GELU>
+struct Form {
+  static inline std::atomic<uint64_t> lds_done{0};
+  static const void *kernel() { return (const void *)gemm_split_kernel<G, GELU>; }
+  static int launch(const glb_gemm_args &g, hipStream_t stream) {
+    const int64_t tiles = ((g.m + G::BM - 1) / G::BM) * (g.n / G::BN);
+    if (tiles > INT32_MAX / 2 || g.m > INT32_MAX / 2) return glb::api_fail(GLB_EUNSUPPORTED, "too many rows");
+    hipError_t e = glb::allow_dynamic_lds(kernel(), G::LDS_BYTES, lds_done);
+    if (e != hipSuccess) return glb::api_hip_fail(e, "split GEMM LDS attribute");
+    hipLaunchKernelGGL((gemm_split_kernel<G, GELU>), dim3((unsigned)tiles), dim3(THREADS), G::LDS_BYTES, stream, g.a, g.lda,
+                       (const char *)g.w_split, g.bias, g.c, g.ldc, (int)g.m, (int)g.n, (int)g.k);
+    e = hipGetLastError();
+    if (e != hipSuccess) return glb::api_hip_fail(e, "split GEMM launch");
+    return GLB_OK;
+  }
+  static int blocks_per_cu(int *blocks) {
+    hipError_t e = glb::allow_dynamic_lds(kernel(), G::LDS_BYTES, lds_done);
+    if (e != hipSuccess) return glb::api_hip_fail(e, "split GEMM LDS attribute");
+    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, gemm_split_kernel<G, GELU>, THREADS, G::LDS_BYTES);
+    if (e != hipSuccess) return glb::api_hip_fail(e, "split GEMM occupancy query");
+    return GLB_OK;
+  }
+};
+
+bool form_ok(int form) { return form == GLB_GEMM_FORM_LARGE || form == GLB_GEMM_FORM_SMALL; }
+
+// the CU count of the current device (asked once per device)
+hipError_t device_cus(int *n_cus) {
+  static std::atomic<int> cached[64];
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return e;
+  const bool slot = dev >= 0 && dev < 64;
+  if (slot && (*n_cus = cached[dev].load(std::memory_order_relaxed)) > 0) return hipSuccess;
+  e = hipDeviceGetAttribute(n_cus, hipDeviceAttributeMultiprocessorCount, dev);
+  if (e == hipSuccess && slot) cached[dev].store(*n_cus, std::memory_order_relaxed);
+  return e;
+}
+
+// The small form is picked while the launch's 128 x 128 tiles number fewer than 3/2 per CU.  One threshold serves the four
+// projections (profiles/r28/split_gemm_forms_ab.txt, 256 CUs): below it the small form wins at every measured point, its
+// slowest round faster than the large form's fastest (0.41-0.93 of its time); from it on the large form wins or the two lie
+// within each other's spread.  For every (n, k) it is below the first row count from which the large form wins at every
+// larger one.
+constexpr int PICK_TILES_NUM = 3, PICK_TILES_DEN = 2;
 
 }  // namespace
 
@@ -250,11 +313,25 @@ int glb_gemm_split_weights(const float *w, int64_t k, int64_t n, int64_t ldw, vo
   return GLB_OK;
 }
 
-int glb_gemm_f32_split(const glb_gemm_args *args, void *stream) {
+
+int glb_gemm_split_pick(int64_t m, int64_t n, int64_t k, int n_cus, int *form) {
+  if (!form) return glb::api_fail(GLB_EINVAL, "null pointer");
+  if (m <= 0 || n <= 0 || k <= 0 || n_cus <= 0)
+    return glb::api_fail(GLB_EINVAL, "bad shape (m %lld, n %lld, k %lld, %d CUs)", (long long)m, (long long)n, (long long)k,
+                         n_cus);
+  // (monotone in m: the tile count never falls as m grows; k does not enter today's rule)
+  if (m > INT32_MAX || n > INT32_MAX) return *form = GLB_GEMM_FORM_LARGE, GLB_OK;  // (the product below stays in 64 bits)
+  const int64_t tiles = ((m + Large::BM - 1) / Large::BM) * ((n + Large::BN - 1) / Large::BN);
+  *form = tiles * PICK_TILES_DEN < (int64_t)PICK_TILES_NUM * n_cus ? GLB_GEMM_FORM_SMALL : GLB_GEMM_FORM_LARGE;
+  return GLB_OK;
+}
+
+int glb_gemm_f32_split_form(const glb_gemm_args *args, int form, void *stream) {
   if (!args) return glb::api_fail(GLB_EINVAL, "null argument block");
   if (args->struct_size != sizeof(glb_gemm_args))
     return glb::api_fail(GLB_EINVAL, "glb_gemm_args.struct_size %u != %zu (ABI mismatch)", args->struct_size,
                          sizeof(glb_gemm_args));
+  if (form != 0 && !form_ok(form)) return glb::api_fail(GLB_EINVAL, "bad form %d", form);
   const glb_gemm_args &g = *args;
   if (!g.a || !g.w_split || !g.c) return glb::api_fail(GLB_EINVAL, "null pointer");
   if (g.m <= 0 || g.n <= 0 || g.k <= 0 || g.lda < g.k || g.ldc < g.n)
@@ -265,32 +342,30 @@ int glb_gemm_f32_split(const glb_gemm_args *args, void *stream) {
   if (!shape_supported(g.k, g.n)) return glb::api_fail(GLB_EUNSUPPORTED, "split GEMM needs n %% 128 == 0 and k %% 64 == 0");
   if (((uintptr_t)g.a) % 16 || g.lda % 4 || ((uintptr_t)g.w_split) % 16)
     return glb::api_fail(GLB_EUNSUPPORTED, "split GEMM needs A and its row pitch 16-byte aligned");
-  const int64_t tiles = ((g.m + BM - 1) / BM) * (g.n / BN);
-  if (tiles > INT32_MAX / 2 || g.m > INT32_MAX / 2) return glb::api_fail(GLB_EUNSUPPORTED, "too many rows");
+  if (form == 0) {
+    int n_cus = 0;
+    const hipError_t e = device_cus(&n_cus);
+    if (e != hipSuccess) return glb::api_hip_fail(e, "split GEMM CU count");
+    const int rc = glb_gemm_split_pick(g.m, g.n, g.k, n_cus, &form);
+    if (rc != GLB_OK) return rc;
+  }
   const bool gelu = g.epilogue == GLB_GEMM_BIAS_GELU_TANH;
-  const void *kern = gelu ? (const void *)gemm_split_kernel<true> : (const void *)gemm_split_kernel<false>;
-  hipError_t e = glb::allow_dynamic_lds(kern, LDS_BYTES, gelu ? g_lds_gelu : g_lds_plain);
-  if (e != hipSuccess) return glb::api_hip_fail(e, "split GEMM LDS attribute");
-  if (gelu)
-    hipLaunchKernelGGL(gemm_split_kernel<true>, dim3((unsigned)tiles), dim3(THREADS), LDS_BYTES, (hipStream_t)stream, g.a,
-                       g.lda, (const char *)g.w_split, g.bias, g.c, g.ldc, (int)g.m, (int)g.n, (int)g.k);
-  else
-    hipLaunchKernelGGL(gemm_split_kernel<false>, dim3((unsigned)tiles), dim3(THREADS), LDS_BYTES, (hipStream_t)stream, g.a,
-                       g.lda, (const char *)g.w_split, g.bias, g.c, g.ldc, (int)g.m, (int)g.n, (int)g.k);
-  e = hipGetLastError();
-  if (e != hipSuccess) return glb::api_hip_fail(e, "split GEMM launch");
-  return GLB_OK;
+  hipStream_t s = (hipStream_t)stream;
+  if (form == GLB_GEMM_FORM_SMALL) return gelu ? Form<Small, true>::launch(g, s) : Form<Small, false>::launch(g, s);
+  return gelu ? Form<Large, true>::launch(g, s) : Form<Large, false>::launch(g, s);
+}
+
+int glb_gemm_f32_split(const glb_gemm_args *args, void *stream) { return glb_gemm_f32_split_form(args, 0, stream); }
+
+int glb_gemm_split_form_blocks_per_cu(int form, int gelu, int *blocks) {
+  if (!blocks) return glb::api_fail(GLB_EINVAL, "null pointer");
+  if (!form_ok(form)) return glb::api_fail(GLB_EINVAL, "bad form %d", form);
+  if (form == GLB_GEMM_FORM_SMALL) return gelu ? Form<Small, true>::blocks_per_cu(blocks) : Form<Small, false>::blocks_per_cu(blocks);
+  return gelu ? Form<Large, true>::blocks_per_cu(blocks) : Form<Large, false>::blocks_per_cu(blocks);
 }
 
 int glb_gemm_split_blocks_per_cu(int gelu, int *blocks) {
-  if (!blocks) return glb::api_fail(GLB_EINVAL, "null pointer");
-  const void *kern = gelu ? (const void *)gemm_split_kernel<true> : (const void *)gemm_split_kernel<false>;
-  hipError_t e = glb::allow_dynamic_lds(kern, LDS_BYTES, gelu ? g_lds_gelu : g_lds_plain);
-  if (e != hipSuccess) return glb::api_hip_fail(e, "split GEMM LDS attribute");
-  e = gelu ? hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, gemm_split_kernel<true>, THREADS, LDS_BYTES)
-           : hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, gemm_split_kernel<false>, THREADS, LDS_BYTES);
-  if (e != hipSuccess) return glb::api_hip_fail(e, "split GEMM occupancy query");
-  return GLB_OK;
+  return glb_gemm_split_form_blocks_per_cu(GLB_GEMM_FORM_LARGE, gelu, blocks);
 }
 
 }  // extern "C"

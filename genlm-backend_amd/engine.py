@@ -775,12 +775,25 @@ class HipEngine:
     def gemm_split_supports(self, k, n):
         return self.lib.glb_gemm_split_bytes(k, n) > 0
 
-    def gemm_split_blocks_per_cu(self, gelu=False):
-        """Blocks of the split GEMM's kernel (with the GELU epilogue when `gelu`) resident on one CU of this device."""
+    def gemm_split_blocks_per_cu(self, gelu=False, form=None):
+        """Blocks of the split GEMM's kernel (with the GELU epilogue when `gelu`) resident on one CU of this device; `form`:
+        _lib.GEMM_FORM_LARGE (the default) or _lib.GEMM_FORM_SMALL."""
         blocks = C.c_int(0)
         with torch.cuda.device(self.device):
-            check(self.lib.glb_gemm_split_blocks_per_cu(int(bool(gelu)), C.byref(blocks)))
+            if form is None:
+                check(self.lib.glb_gemm_split_blocks_per_cu(int(bool(gelu)), C.byref(blocks)))
+            else:
+                check(self.lib.glb_gemm_split_form_blocks_per_cu(int(form), int(bool(gelu)), C.byref(blocks)))
         return blocks.value
+
+    def gemm_split_pick(self, m, n, k, n_cus=None):
+        """The tile form glb_gemm_f32_split runs for an [m, k] x [k, n] call on a device of `n_cus` CUs (this one's by
+        default): _lib.GEMM_FORM_LARGE or _lib.GEMM_FORM_SMALL (glb_gemm_split_pick: host arithmetic only)."""
+        if n_cus is None:
+            n_cus = torch.cuda.get_device_properties(self.device).multi_processor_count
+        form = C.c_int(0)
+        check(self.lib.glb_gemm_split_pick(m, n, k, n_cus, C.byref(form)))
+        return form.value
 
     def gemm_split_weights(self, w):
         """The packed hi / mid / lo bf16 image of a float32 weight w [K, N] (glb_gemm_split_weights: 6 bytes per element),
@@ -795,12 +808,14 @@ class HipEngine:
         check(self.lib.glb_gemm_split_weights(_ptr(w), k, n, w.stride(0), _ptr(out), nbytes, self._stream()))
         return out
 
-    def gemm_split(self, x, w_split, n, bias=None, gelu=False, out=None):
+    def gemm_split(self, x, w_split, n, bias=None, gelu=False, out=None, form=None):
         """x [..., K] float32 (rows of unit inner stride) times the weight whose image is `w_split`, plus bias [N], then the
         tanh GELU when `gelu` (glb_gemm_f32_split).  Returns [..., N] float32, or None when the kernel does not serve the
         call (alignment, shape, a bias that is not contiguous float32): the caller then runs its library GEMM.  `out`: a
         float32 [M, N] tensor on the engine's device with unit inner stride (rows may be padded); ValueError otherwise, and
-        for a bias of the wrong length or device.  Non-finite and out-of-range operands: include/glb.h."""
+        for a bias of the wrong length or device.  `form`: None lets the library pick the tile form from the shape;
+        _lib.GEMM_FORM_LARGE / _lib.GEMM_FORM_SMALL force one (glb_gemm_f32_split_form) - the result's bits are the same.
+        Non-finite and out-of-range operands: include/glb.h."""
         k = x.shape[-1]
         x2 = x.reshape(-1, k)
         m = x2.shape[0]
@@ -830,7 +845,10 @@ class HipEngine:
         a.bias = bias.data_ptr() if bias is not None else None
         a.c, a.ldc = out.data_ptr(), max(out.stride(0), n)  # (a one-row tensor's stride is arbitrary)
         a.epilogue = _lib.GEMM_BIAS_GELU_TANH if gelu else _lib.GEMM_BIAS
-        rc = self.lib.glb_gemm_f32_split(C.byref(a), self._stream())
+        if form is None:
+            rc = self.lib.glb_gemm_f32_split(C.byref(a), self._stream())
+        else:
+            rc = self.lib.glb_gemm_f32_split_form(C.byref(a), int(form), self._stream())
         if rc == _lib.GLB_EUNSUPPORTED:
             return None
         check(rc)

@@ -779,10 +779,24 @@ typedef struct glb_gemm_args {
 size_t glb_gemm_split_bytes(int64_t k, int64_t n);
 int glb_gemm_split_weights(const float *w, int64_t k, int64_t n, int64_t ldw, void *out, size_t out_bytes, void *hip_stream);
 int glb_gemm_f32_split(const glb_gemm_args *args, void *hip_stream);
+/* The kernel has two tile forms: 128 x 128 output tiles (large) and 64 x 64 (small: more blocks for launches whose large
+ * tiles would leave CUs empty).  An element of C is the same chain of operations in both, so the bits of a call DO NOT
+ * depend on the form (tests/test_split_gemm_forms_gpu.py); the choice is one of speed alone.
+ * glb_gemm_split_pick: the form glb_gemm_f32_split runs for an (m, n, k) call on a device of n_cus CUs, into *form.  A
+ * function of its arguments only - host code, no GPU work, callable on a machine without one - and monotone: once a row
+ * count picks the large form, every larger one does (tests/test_split_gemm_pick_cpu.py).  GLB_EINVAL for a null pointer or
+ * a non-positive argument.
+ * glb_gemm_f32_split_form: glb_gemm_f32_split with the form forced; form 0 picks (exactly glb_gemm_f32_split), any value
+ * other than 0 and the two constants returns GLB_EINVAL without a launch. */
+enum { GLB_GEMM_FORM_LARGE = 1, GLB_GEMM_FORM_SMALL = 2 };
+int glb_gemm_split_pick(int64_t m, int64_t n, int64_t k, int n_cus, int *form);
+int glb_gemm_f32_split_form(const glb_gemm_args *args, int form, void *hip_stream);
 /* How many blocks of the split GEMM's kernel (gelu != 0: the instantiation with the GELU epilogue) the runtime keeps resident
  * on one CU of the current device, given the kernel's registers and its dynamic LDS (hipOccupancyMaxActiveBlocksPerMultiprocessor).
- * The kernel is built for three; no GPU work. */
+ * The kernel is built for three; no GPU work.  This is the large form; glb_gemm_split_form_blocks_per_cu
+ * reports either form's (the small one is built for six; a bad form: GLB_EINVAL). */
 int glb_gemm_split_blocks_per_cu(int gelu, int *blocks);
+int glb_gemm_split_form_blocks_per_cu(int form, int gelu, int *blocks);
 
 /*
  * LoRA merge: out = W + scale * B . A for every matrix of an adapter in one call - what peft's merged
