@@ -18,6 +18,9 @@ def __getattr__(name):
     if name in ("load_model_by_name", "AsyncAmdLM", "AsyncLM", "SequenceScores"):
         from . import llm
         return getattr(llm, name)
+    if name == "DeviceBeam":
+        from .beam import DeviceBeam
+        return DeviceBeam
     if name in ("ByteDFA", "ByteWFSA", "DeviceConstraint", "minimize", "product", "ByteNFA", "determinize", "LazyConstraint", "BytePDA",
                 "PDAConstraint", "ConstraintProduct"):
         from . import constraints

@@ -554,6 +554,105 @@ class HipEngine:
             check(self.lib.glb_score_seq_sums(_ptr(src), values.numel(), _ptr(seq_start), out.numel(), _ptr(out), self._stream()))
         return out
 
+    TOPK_OUTPUTS = ("logp", "logp_masked", "lse", "logZ")
+    TOPK_MAX = 64
+
+    def topk_rows(self, logits, k, *, vocab=None, logit_scale=1.0, mask_kind=MASK_NONE, mask=None, row_mask_id=None, want=("logp",)):
+        """The k most probable tokens of every logits row (glb_topk_rows): with y = logits[r] * logit_scale,
+        m the row's mask and key = y + m, a dict holding "token" int32 [n_rows, k] - the indices of the k largest keys, largest
+        first, equal keys by lower index, -1 beyond the finite keys - and the names in `want`: "logp" = key - lse(y) and
+        "logp_masked" = key - lse(y + m), float32 [n_rows, k] (-inf where the token is -1); "lse" = lse(y) and "logZ" =
+        lse(y + m) - lse(y), float32 [n_rows].  No log-softmax is written.  logits, mask and row_mask_id as `score_rows`
+        takes them - the keywords a constraint's `step_masks(..., by_row=True, ...)` returns."""
+        if isinstance(mask, PreparedMasks) or mask_kind == MASK_PREPARED:
+            raise TypeError("topk_rows reads bit rows or float rows as they lie, not prepared masks")
+        want = tuple(want)
+        for w in want:
+            if w not in self.TOPK_OUTPUTS:
+                raise ValueError(f"want names {w!r}; the outputs are {self.TOPK_OUTPUTS}")
+        if not isinstance(k, int) or not 1 <= k <= self.TOPK_MAX:
+            raise ValueError(f"k must be an integer in 1..{self.TOPK_MAX}, got {k!r}")
+        if logits.dim() != 2 or logits.stride(1) != 1:
+            raise ValueError("logits must be 2-D with unit inner stride")
+        if logits.dtype not in _DT:
+            raise TypeError(f"unsupported logits dtype {logits.dtype}")
+        if logits.device != self.device:
+            raise ValueError(f"logits on {logits.device}, engine on {self.device}")
+        n_rows, width = logits.shape
+        V = width if vocab is None else vocab
+        if not 0 < V <= width:
+            raise ValueError(f"vocab {V} outside (0, {width}]")
+        if n_rows == 0:
+            raise ValueError("no rows to select from")
+        if not 0 < logit_scale < float("inf"):  # (NaN too; 0 or a negative scale would turn -inf logits into NaN / +inf)
+            raise ValueError(f"logit_scale must be positive and finite, got {logit_scale!r}")
+        self._check_dev(row_mask_id)
+        if mask_kind not in (MASK_NONE, MASK_BITS, MASK_F32):
+            raise ValueError(f"bad mask_kind {mask_kind}")
+        a = _lib.TopkArgs()
+        a.struct_size = C.sizeof(_lib.TopkArgs)
+        a.logits, a.dtype = logits.data_ptr(), _DT[logits.dtype]
+        a.n_rows, a.vocab, a.logit_scale, a.k = n_rows, V, logit_scale, k
+        a.ld = logits.stride(0) if n_rows > 1 else max(width, logits.stride(0))
+        a.mask_kind = mask_kind
+        if mask_kind != MASK_NONE:
+            if mask is None:
+                raise ValueError("mask_kind given without a mask table")
+            if mask.device != self.device:
+                raise ValueError(f"mask on {mask.device}, engine on {self.device}")
+            if mask.dim() != 2 or mask.stride(1) != 1:
+                raise ValueError("mask must be 2-D with unit inner stride (rows may be strided)")
+            want_dt = torch.float32 if mask_kind == MASK_F32 else torch.int32
+            if mask.dtype != want_dt:
+                raise TypeError(f"mask dtype {mask.dtype}, expected {want_dt}")
+            if mask.shape[1] < (V if mask_kind == MASK_F32 else (V + 31) // 32):
+                raise ValueError(f"mask rows of {mask.shape[1]} elements are too short for {V} tokens")
+            if row_mask_id is not None and (row_mask_id.dtype != torch.int32 or row_mask_id.shape != (n_rows,)
+                                            or not row_mask_id.is_contiguous()):
+                raise ValueError("row_mask_id must be a contiguous int32 [n_rows] tensor")
+            if row_mask_id is None and mask.shape[0] not in (1, n_rows):
+                raise ValueError(f"no row_mask_id given but the table has {mask.shape[0]} rows: neither 1 nor {n_rows}")
+            a.mask, a.n_masks = mask.data_ptr(), mask.shape[0]
+            a.mask_ld = mask.stride(0) if mask.shape[0] > 1 else mask.shape[1]
+            a.row_mask_id = None if row_mask_id is None else row_mask_id.data_ptr()
+        elif mask is not None or row_mask_id is not None:
+            raise ValueError("a mask table or row_mask_id given with MASK_NONE")
+        out = {"token": torch.empty((n_rows, k), dtype=torch.int32, device=self.device)}
+        a.out_token = out["token"].data_ptr()
+        for w in want:
+            out[w] = torch.empty((n_rows, k) if w.startswith("logp") else (n_rows,), dtype=torch.float32, device=self.device)
+            setattr(a, "out_" + w, out[w].data_ptr())
+        check(self.lib.glb_topk_rows(C.byref(a), self._stream()))
+        return out
+
+    def beam_select(self, score, alive, cand_token, cand_logp, width):
+        """A beam step's selection (glb_beam_select): groups of `width` beams - score float32 and alive int32
+        [G * width], cand_token int32 and cand_logp float32 [G * width, k] as `topk_rows` writes them.  Returns (parent int32,
+        token int32, score float32), each [G * width]: per group the `width` largest of score[b] + cand_logp[b, j] over the
+        live beams' candidates and of score[b] over the finished beams (token -1), largest first, ties by lower (b, j);
+        parent is the beam's index within its group; missing positions are (-1, -1, -inf)."""
+        self._check_dev(score, alive, cand_token, cand_logp)
+        if not isinstance(width, int) or not 1 <= width <= self.TOPK_MAX:
+            raise ValueError(f"width must be an integer in 1..{self.TOPK_MAX}, got {width!r}")
+        n = score.numel()
+        if score.dtype != torch.float32 or score.dim() != 1 or n == 0 or n % width or not score.is_contiguous():
+            raise ValueError("score must be a contiguous float32 [G * width] tensor, G >= 1")
+        if alive.dtype != torch.int32 or alive.shape != (n,) or not alive.is_contiguous():
+            raise ValueError("alive must be a contiguous int32 [G * width] tensor")
+        if cand_token.dtype != torch.int32 or cand_token.dim() != 2 or cand_token.shape[0] != n or not cand_token.is_contiguous():
+            raise ValueError("cand_token must be a contiguous int32 [G * width, k] tensor")
+        k = cand_token.shape[1]
+        if not 1 <= k <= self.TOPK_MAX:
+            raise ValueError(f"k must be in 1..{self.TOPK_MAX}, got {k}")
+        if cand_logp.dtype != torch.float32 or cand_logp.shape != (n, k) or not cand_logp.is_contiguous():
+            raise ValueError("cand_logp must be a contiguous float32 tensor of cand_token's shape")
+        parent = torch.empty(n, dtype=torch.int32, device=self.device)
+        token = torch.empty(n, dtype=torch.int32, device=self.device)
+        out = torch.empty(n, dtype=torch.float32, device=self.device)
+        check(self.lib.glb_beam_select(_ptr(score), _ptr(alive), _ptr(cand_token), _ptr(cand_logp), n // width, width, k,
+                                       _ptr(parent), _ptr(token), _ptr(out), self._stream()))
+        return parent, token, out
+
     # ---- failed one-launch calls (include/glb.h: glb_workspace_check) ---------------------------------------------
     def error_word(self):
         """int32 [1] device view of the scratch buffer's error word: nonzero after a one-launch call whose waves gave

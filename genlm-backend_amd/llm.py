@@ -1130,10 +1130,12 @@ class AsyncAmdLM(AsyncLM):
             mid_d = torch.zeros(n, dtype=torch.int32, device=self.device) if mask_ids is None else mask_ids
         return self._batch_step(tokens.view(-1), self._row_starts[1], lengths, n, mid_d, l_max=None, constraint=constraint)
 
-    def _batch_step(self, tok_d, st_d, ln_d, n, mid_d, l_max, constraint=None):
+    def _batch_step(self, tok_d, st_d, ln_d, n, mid_d, l_max, constraint=None, finish=None):
         """The batched step on a ragged batch that is on the device already.  l_max: the longest context if the host
-        knows it (else it rides on the call's D2H copy).  Returns device tensors."""
+        knows it (else it rides on the call's D2H copy).  Returns device tensors.  finish: what is made of the logits rows in
+        place of the fused step (`_finish_batch_step`'s arguments: `_topk_finisher`)."""
         eng, dev = self.engine, self.device
+        finish = finish or self._finish_batch_step
         self._lora_sync()
         group_of, rep, ng = eng.group_contexts(tok_d, st_d, ln_d)
         P = self._prefix_table()
@@ -1158,7 +1160,7 @@ class AsyncAmdLM(AsyncLM):
             by_row = bool(extra[-2]) if mid_d is not None else False
             if mid_d is not None:
                 row_mid = row_mid[group_of_row]
-            return self._finish_batch_step(logits, row_of_group[group_of.long()], group_of, U, n, mid_d, row_mid, by_row, constraint)
+            return finish(logits, row_of_group[group_of.long()], group_of, U, n, mid_d, row_mid, by_row, constraint)
         n_head = len(head)
         head = torch.stack(head) if used_d is None else torch.cat([torch.stack(head), used_d])
         head = head.cpu().tolist()  # the call's one D2H copy before the forward
@@ -1173,7 +1175,7 @@ class AsyncAmdLM(AsyncLM):
         prefixes = (T, pref[rep[:U].long()].contiguous()) if P["n"] else None
         enc = encode_ragged(self, (tok_d, st_d, ln_d), rep, U, l_max, pad_id=self._pad_id, base=base, prefixes=prefixes)
         logits = self._lm_head(enc.last_rows())  # [U, V]
-        return self._finish_batch_step(logits, group_of, group_of, U, n, mid_d, row_mid, by_row, constraint)
+        return finish(logits, group_of, group_of, U, n, mid_d, row_mid, by_row, constraint)
 
     def _finish_batch_step(self, logits, row_of, group_of, U, n, mid_d, row_mid, by_row, constraint=None):
         """The fused step over a batch's logits rows (row_of: logits row of every context; group_of: its dedup group -
@@ -1187,6 +1189,81 @@ class AsyncAmdLM(AsyncLM):
         """Awaitable form of `batch_next_token_step_sync` (the evaluation itself blocks the loop, like
         `batch_evaluate_queries` does in the reference, hf.py:307-308)."""
         return self.batch_next_token_step_sync(contexts, mask_ids, lora_names=lora_names)
+
+    # ---- the k most probable next tokens (glb_topk_rows: DESIGN.md §30) ------------------------------------------------------
+    def _topk_finisher(self, k, scale):
+        """`_batch_step`'s `finish` for the top-k calls: `topk_rows` on the distinct logits rows, under the constraint's mask
+        rows, and a gather of the [U, k] results to the contexts.  Returns (token int32 [n, k], logp float32 [n, k])."""
+        def finish(logits, row_of, group_of, U, n, mid_d, row_mid, by_row, constraint=None):
+            rows, kw = logits[:U], {}
+            if constraint is not None:
+                if not by_row:  # contexts that share a logits row under different masks: a row per context
+                    rows, row_mid, row_of = logits[row_of.long()], mid_d, None
+                kw, _ = constraint.step_masks(rows, row_mid[:rows.shape[0]].contiguous(), True, n, parity=False)
+            got = self.engine.topk_rows(rows, k, vocab=logits.shape[-1], logit_scale=scale, want=("logp",), **kw)
+            self._count(n, U, U)
+            if row_of is None:
+                return got["token"], got["logp"]
+            idx = row_of.long()
+            return got["token"][idx], got["logp"][idx]
+
+        return finish
+
+    @staticmethod
+    def _topk_scale(k, temperature):
+        if not isinstance(k, int) or not 1 <= k <= 64:
+            raise ValueError(f"k must be an integer in 1..64, got {k!r}")
+        if not float(temperature) > 0.0:
+            raise ValueError(f"temperature must be > 0, got {temperature!r}")
+        return 1.0 / float(temperature)
+
+    @torch.no_grad()
+    def batch_next_token_topk_sync(self, token_ids_list, k, temperature=1.0):
+        """The k most probable next tokens of every context and their log-probabilities under softmax(logits /
+        temperature): (tokens int32 [n, k], logprobs float32 [n, k]) as device tensors, most probable first, equal
+        log-probabilities by lower token id.  The pipeline of `batch_next_token_step_sync` - dedup, cached-prefix match,
+        one forward - with `HipEngine.topk_rows` on the distinct rows: no [n, V] log-softmax is written."""
+        scale = self._topk_scale(k, temperature)
+        n = len(token_ids_list)
+        if n == 0:
+            return (torch.zeros((0, k), dtype=torch.int32, device=self.device), torch.zeros((0, k), dtype=torch.float32, device=self.device))
+        flat, starts, lens = ragged(token_ids_list)
+        if int(lens.min()) == 0:
+            raise ValueError("Token ids must not be empty")
+        dev = self.device
+        return self._batch_step(torch.from_numpy(flat).to(dev), torch.from_numpy(starts).to(dev), torch.from_numpy(lens).to(dev), n,
+                                None, l_max=int(lens.max()), finish=self._topk_finisher(k, scale))
+
+    async def batch_next_token_topk(self, token_ids_list, k, temperature=1.0):
+        """Awaitable form of `batch_next_token_topk_sync` (the evaluation itself blocks the loop)."""
+        return self.batch_next_token_topk_sync(token_ids_list, k, temperature)
+
+    @torch.no_grad()
+    def batch_next_token_topk_device(self, tokens, lengths, k, constraint=None, prompt_lengths=None, *, temperature=1.0, mask_rows=None):
+        """`batch_next_token_topk_sync` for contexts that live on the device: `tokens` int32 [n, cap], `lengths` int32 [n] as
+        `batch_next_token_step_device` takes them.  `constraint`: context i's candidates are those its automaton state after
+        tokens[i, prompt_lengths[i]:lengths[i]) allows, and `logprobs` is the model's log-probability of the token (over a
+        `constraints.ByteWFSA`: plus the token's weight) - not renormalised: what a search adds up.  mask_rows: the
+        constraint's bank rows of the contexts when the caller keeps the states itself (`DeviceBeam`); else recomputed here."""
+        scale = self._topk_scale(k, temperature)
+        if tokens.dim() != 2 or tokens.dtype != torch.int32 or lengths.dtype != torch.int32 or lengths.numel() != tokens.shape[0]:
+            raise ValueError("tokens must be int32 [n, cap] and lengths int32 [n]")
+        if mask_rows is not None and constraint is None:
+            raise ValueError("mask_rows given without the constraint whose bank they index")
+        if not tokens.is_contiguous():
+            tokens = tokens.contiguous()
+        n, cap = tokens.shape
+        if n == 0:
+            return (torch.zeros((0, k), dtype=torch.int32, device=self.device), torch.zeros((0, k), dtype=torch.float32, device=self.device))
+        key = (n, cap)
+        if getattr(self, "_row_starts", (None,))[0] != key:
+            self._row_starts = (key, torch.arange(n, device=self.device, dtype=torch.int64) * cap)
+        mid_d = mask_rows
+        if constraint is not None and mid_d is None:
+            frm = torch.zeros_like(lengths) if prompt_lengths is None else prompt_lengths
+            mid_d = constraint.mask_rows(constraint.advance(None, tokens, frm, lengths))
+        return self._batch_step(tokens.view(-1), self._row_starts[1], lengths, n, mid_d, l_max=None, constraint=constraint,
+                                finish=self._topk_finisher(k, scale))
 
     # ---- one adapter per context in one forward (lora.RowLora, glb_lora_rows: DESIGN.md §15) --------------------------------
     def _lora_slots(self, lora_names, n):

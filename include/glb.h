@@ -1795,6 +1795,70 @@ int glb_score_rows(const glb_score_args *args, void *hip_stream);
  * that is negative or beyond 31 bits; n_seq == 0 launches nothing. */
 int glb_score_seq_sums(const float *values, int64_t n_rows, const int64_t *seq_start, int64_t n_seq, float *out, void *hip_stream);
 
+/*
+ * The k most probable tokens of every logits row: per logits row r, with y_j = fl32(x_j * logit_scale)
+ * when the scale is not 1 (else x_j), mask row m (GLB_MASK_BITS: 0 / -inf; GLB_MASK_F32: any float, -inf ok) and
+ * key_j = fl32(y_j + m_j), for k in 1 .. 64, dense outputs [n_rows, k] (out_lse, out_logZ: [n_rows]), each nullable except
+ * out_token:
+ *     out_token        the indices of the k largest keys, largest first.  Keys compare as floats, -0 equals +0, equal keys
+ *                      order by lower index.  A key of -inf is never selected: positions beyond the number of finite keys
+ *                      hold token -1, and -inf in both float outputs.
+ *     out_logp         = key - lse(y)        bit masks: the token's log-probability under the model; float masks: that plus
+ *                                            the token's weight - what a search adds up
+ *     out_logp_masked  = key - lse(y + m)
+ *     out_lse          = lse(y)
+ *     out_logZ         = lse(y + m) - lse(y)               -inf when nothing has mass
+ * A mask id outside [0, n_masks) makes the row one whose mask allows nothing; a row of all -inf gives every token -1 and
+ * every float -inf, no NaN.  +inf and NaN logits or mask floats, and magnitudes beyond 2^21, are not supported (no fault; the
+ * results are unspecified).  Masks: the table, mask_ld, n_masks, row_mask_id and the null rules are glb_score_args's; kinds
+ * GLB_MASK_NONE, GLB_MASK_BITS (raw rows) and GLB_MASK_F32 - GLB_MASK_PREPARED is GLB_EINVAL.  With GLB_MASK_NONE no mask
+ * field is read, out_logZ is 0 (-inf for a row of all -inf) and out_logp_masked equals out_logp.
+ * One launch, one workgroup of four waves per row: every logit and every mask word of the row is read once in 16-byte loads
+ * (element aligned: any base and pitch), nothing of size [n_rows, vocab] is written.  Nothing waits inside the launch,
+ * nothing synchronises or allocates; safe under stream capture; no workspace.
+ * The token ids are exact: a key is one rounded multiply and one rounded add, the selection compares keys and indices only, so
+ * the ids are a function of the inputs that float32 arithmetic on the host reproduces bit for bit.  The log-sum-exps are
+ * glb_score_rows's: within 1e-4 of the exact values of the inputs.  A row's outputs are a function of that row's inputs alone
+ * (chunks of 4096 indices, chunk c on wave c mod 4, the four waves folded in order): the same bytes for a row alone or among
+ * others and however the rows are cut into calls.
+ * GLB_EINVAL before any launch: struct_size wrong; logits or out_token null; k outside 1 .. 64; a dtype outside GLB_F32 ..
+ * GLB_F16; n_rows or vocab not positive or beyond 31 bits; ld below vocab; logits not element aligned; a scale that is NaN, not
+ * positive or infinite; a bad or prepared mask_kind; with a mask: the table null or misaligned, mask_ld below a row's
+ * elements, n_masks not positive or beyond 31 bits, no ids with n_masks neither 1 nor n_rows.
+ */
+typedef struct glb_topk_args {
+  uint32_t struct_size; /* sizeof this block - ABI guard */
+  const void *logits;   /* [n_rows, ld] device */
+  int32_t dtype;        /* GLB_F32 / GLB_BF16 / GLB_F16 */
+  int64_t n_rows, vocab;
+  int64_t ld; /* row pitch in elements, >= vocab */
+  float logit_scale;
+  int32_t k; /* 1 .. 64 */
+  int32_t mask_kind;
+  const void *mask; /* [n_masks, mask_ld] device: uint32 words or floats */
+  int64_t mask_ld, n_masks;
+  const int32_t *row_mask_id; /* [n_rows] device, nullable: n_masks == 1 ? 0 : identity */
+  int32_t *out_token;         /* [n_rows, k] */
+  float *out_logp;            /* [n_rows, k] each, nullable */
+  float *out_logp_masked;
+  float *out_lse; /* [n_rows] each, nullable */
+  float *out_logZ;
+} glb_topk_args;
+int glb_topk_rows(const glb_topk_args *args, void *hip_stream);
+/*
+ * A beam step's selection: n_groups groups of `width` beams (1 .. 64).  score float32 [n_groups * width], alive int32
+ * [n_groups * width], cand_token int32 and cand_logp float32 [n_groups * width, k] as glb_topk_rows writes them (k in 1 .. 64).
+ * Group g's candidates, per beam b: an alive beam with a finite score gives (b, j) with value fl32(score[b] + cand_logp[b, j])
+ * for every j with cand_token[b, j] >= 0 and a finite value; a beam that is not alive but has a finite score is a finished
+ * hypothesis and gives one candidate (b, token -1) with value score[b]; a beam whose score is not finite gives nothing.
+ * out_parent (the beam's index within its group), out_token and out_score, each [n_groups * width]: the `width` largest
+ * values, largest first (-0 equals +0), ties by lower (b, j); missing positions get parent -1, token -1, score -inf.
+ * One launch, one wave per group, no workspace, nothing waits; safe under stream capture.  GLB_EINVAL before the launch: a
+ * null pointer; width or k outside 1 .. 64; n_groups not positive or 2^19 and above.
+ */
+int glb_beam_select(const float *score, const int32_t *alive, const int32_t *cand_token, const float *cand_logp, int64_t n_groups,
+                    int32_t width, int32_t k, int32_t *out_parent, int32_t *out_token, float *out_score, void *hip_stream);
+
 /* Philox4x32-10 block function, exposed so hosts can reproduce the device draws. */
 void glb_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 
