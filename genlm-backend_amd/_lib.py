@@ -193,6 +193,18 @@ class GemmArgs(C.Structure):
     ]
 
 
+class PackedPlanArgs(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("n_tokens", C.c_int64), ("n_contexts", C.c_int64), ("n_sel", C.c_int64), ("n_groups", C.c_int64),
+        ("n_pre", C.c_int64), ("n_tail_rows", C.c_int64), ("pos_cap", C.c_int64),
+        ("tokens", C.c_void_p), ("starts", C.c_void_p), ("lengths", C.c_void_p), ("sel", C.c_void_p), ("grp", C.c_void_p),
+        ("group_starts", C.c_void_p), ("group_lens", C.c_void_p), ("group_segments", C.c_void_p),
+        ("group_ids", C.c_void_p), ("group_pos", C.c_void_p),
+        ("segments", C.c_void_p), ("ids", C.c_void_p), ("pos", C.c_void_p), ("last", C.c_void_p), ("ends", C.c_void_p),
+    ]
+
+
 class LoraJob(C.Structure):
     _fields_ = [
         ("struct_size", C.c_uint32),
@@ -575,6 +587,8 @@ SYMBOLS = {
     "glb_gemm_f32_split": (C.c_int, [C.POINTER(GemmArgs), _vp]),
     "glb_gemm_split_pick": (C.c_int, [_i64, _i64, _i64, C.c_int, C.POINTER(C.c_int)]),
     "glb_gemm_f32_split_form": (C.c_int, [C.POINTER(GemmArgs), C.c_int, _vp]),
+    "glb_gemm_f32_split_residual": (C.c_int, [C.POINTER(GemmArgs), _vp, _i64, C.c_int, _vp]),
+    "glb_packed_plan": (C.c_int, [C.POINTER(PackedPlanArgs), _vp]),
     "glb_gemm_split_blocks_per_cu": (C.c_int, [C.c_int, C.POINTER(C.c_int)]),
     "glb_gemm_split_form_blocks_per_cu": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "glb_lora_merge_workspace_bytes": (_sz, [_i32]),

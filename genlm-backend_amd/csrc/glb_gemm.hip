@@ -1,6 +1,7 @@
 // glb_gemm.hip - fp32 projection GEMM on bf16 MFMA (include/glb.h: glb_gemm_split_bytes, glb_gemm_split_weights,
 // glb_gemm_f32_split): C[M, N] = A[M, K] . W[K, N] + bias, optionally followed by the tanh GELU, for GPT-2's Conv1D
-// projections (hf modeling_gpt2.py: `addmm(bias, x, weight)`).
+// projections (hf modeling_gpt2.py: `addmm(bias, x, weight)`); or followed by the block's residual, C = (A . W + bias) + R
+// (glb_gemm_f32_split_residual: the add behind `c_proj` in the GEMM's epilogue).
 //
 // Numerics ("split bf16"): every fp32 operand element is written as x = hi + mid + lo, three bf16 values made by
 // round-to-nearest-even (v_cvt_pk_bf16_f32), each residual an exact fp32 subtraction; the sum is exact for every finite x
@@ -33,6 +34,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #include "../../include/glb.h"
 #include "glb_common.hpp"
@@ -122,10 +124,26 @@ __device__ __forceinline__ void glds16(const void *src, char *lds) {
   __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void *)lds, 16, 0, 0);
 }
 
-template <class G, bool GELU>
-__global__ __launch_bounds__(THREADS, G::BLOCKS_PER_CU) void gemm_split_kernel(const float *__restrict__ a, int64_t lda,
-                                                                const char *__restrict__ wsplit, const float *__restrict__ bias,
-                                                                float *__restrict__ c, int64_t ldc, int m, int n, int k) {
+// what follows acc + bias in the epilogue
+enum Epi { EPI_NONE, EPI_GELU, EPI_RESIDUAL };
+
+// The residual operand of the EPI_RESIDUAL instantiations: R fp32 [m, n] of row pitch ld.  The other instantiations take an
+// empty last argument, so their argument block and their code are what they were without it.
+template <bool ON>
+struct Residual {
+  const float *p;
+  int64_t ld;
+};
+template <>
+struct Residual<false> {};
+
+// EPI_RESIDUAL: C[row, col] = (acc + bias[col]) + R[row, col], two separately rounded adds.  R may be C itself (same pointer,
+// same pitch: every element is read and written by one thread, the read first), so that instantiation's C is not __restrict__.
+template <class G, Epi EPI>
+__global__ __launch_bounds__(THREADS, G::BLOCKS_PER_CU) void gemm_split_kernel(
+    const float *__restrict__ a, int64_t lda, const char *__restrict__ wsplit, const float *__restrict__ bias,
+    typename std::conditional<EPI == EPI_RESIDUAL, float *, float *__restrict__>::type c, int64_t ldc, int m, int n, int k,
+    Residual<EPI == EPI_RESIDUAL> res) {
   constexpr int MF = G::MF, NF = G::NF, BM = G::BM, BN = G::BN, WAVE_PIECES = G::WAVE_PIECES, STAGE_BYTES = G::STAGE_BYTES;
   extern __shared__ __attribute__((aligned(16))) char lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -220,6 +238,21 @@ __global__ __launch_bounds__(THREADS, G::BLOCKS_PER_CU) void gemm_split_kernel(c
     __syncthreads();
   }
 
+  // the residual's elements of this lane, all loaded before the first store (C may be R: loads issued one by one between
+  // the stores would each wait out a trip to memory), under the store's own guard
+  float rv[EPI == EPI_RESIDUAL ? MF : 1][EPI == EPI_RESIDUAL ? NF : 1][4];
+  if constexpr (EPI == EPI_RESIDUAL) {
+#pragma unroll
+    for (int nf = 0; nf < NF; ++nf)
+#pragma unroll
+      for (int i = 0; i < MF; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int row = m0 + wave * (MF * 16) + i * 16 + 4 * (lane >> 4) + j;
+          rv[i][nf][j] = row < m ? res.p[(int64_t)row * res.ld + n0 + nf * 16 + (lane & 15)] : 0.0f;
+        }
+  }
+
   // epilogue: C/D map of 16x16 MFMA - col = lane & 15, row = 4 * (lane >> 4) + reg
 #pragma unroll
   for (int nf = 0; nf < NF; ++nf) {
@@ -233,7 +266,8 @@ __global__ __launch_bounds__(THREADS, G::BLOCKS_PER_CU) void gemm_split_kernel(c
         const int row = row0 + j;
         if (row < m) {
           float v = acc[i][nf][j] + b;
-          if (GELU) v = gelu_tanh(v);
+          if (EPI == EPI_GELU) v = gelu_tanh(v);
+          if (EPI == EPI_RESIDUAL) v += rv[i][nf][j];
           c[(int64_t)row * ldc + col] = v;
         }
       }
@@ -244,17 +278,17 @@ __global__ __launch_bounds__(THREADS, G::BLOCKS_PER_CU) void gemm_split_kernel(c
 bool shape_supported(int64_t k, int64_t n) { return k > 0 && n > 0 && n % BN_MAX == 0 && k % 64 == 0 && k <= (1 << 20) && n <= (1 << 20); }
 
 // one instantiation's host side: its LDS attribute (one bit per device), its launch and its residency
-template <class G, bool GELU>
+template <class G, Epi EPI>
 struct Form {
   static inline std::atomic<uint64_t> lds_done{0};
-  static const void *kernel() { return (const void *)gemm_split_kernel<G, GELU>; }
-  static int launch(const glb_gemm_args &g, hipStream_t stream) {
+  static const void *kernel() { return (const void *)gemm_split_kernel<G, EPI>; }
+  static int launch(const glb_gemm_args &g, hipStream_t stream, Residual<EPI == EPI_RESIDUAL> res = {}) {
     const int64_t tiles = ((g.m + G::BM - 1) / G::BM) * (g.n / G::BN);
     if (tiles > INT32_MAX / 2 || g.m > INT32_MAX / 2) return glb::api_fail(GLB_EUNSUPPORTED, "too many rows");
     hipError_t e = glb::allow_dynamic_lds(kernel(), G::LDS_BYTES, lds_done);
     if (e != hipSuccess) return glb::api_hip_fail(e, "split GEMM LDS attribute");
-    hipLaunchKernelGGL((gemm_split_kernel<G, GELU>), dim3((unsigned)tiles), dim3(THREADS), G::LDS_BYTES, stream, g.a, g.lda,
-                       (const char *)g.w_split, g.bias, g.c, g.ldc, (int)g.m, (int)g.n, (int)g.k);
+    hipLaunchKernelGGL((gemm_split_kernel<G, EPI>), dim3((unsigned)tiles), dim3(THREADS), G::LDS_BYTES, stream, g.a, g.lda,
+                       (const char *)g.w_split, g.bias, g.c, g.ldc, (int)g.m, (int)g.n, (int)g.k, res);
     e = hipGetLastError();
     if (e != hipSuccess) return glb::api_hip_fail(e, "split GEMM launch");
     return GLB_OK;
@@ -262,7 +296,7 @@ struct Form {
   static int blocks_per_cu(int *blocks) {
     hipError_t e = glb::allow_dynamic_lds(kernel(), G::LDS_BYTES, lds_done);
     if (e != hipSuccess) return glb::api_hip_fail(e, "split GEMM LDS attribute");
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, gemm_split_kernel<G, GELU>, THREADS, G::LDS_BYTES);
+    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, gemm_split_kernel<G, EPI>, THREADS, G::LDS_BYTES);
     if (e != hipSuccess) return glb::api_hip_fail(e, "split GEMM occupancy query");
     return GLB_OK;
   }
@@ -326,7 +360,8 @@ int glb_gemm_split_pick(int64_t m, int64_t n, int64_t k, int n_cus, int *form) {
   return GLB_OK;
 }
 
-int glb_gemm_f32_split_form(const glb_gemm_args *args, int form, void *stream) {
+// the argument checks every split GEMM entry point shares; picks the form where `form` is 0
+static int split_check(const glb_gemm_args *args, int &form) {
   if (!args) return glb::api_fail(GLB_EINVAL, "null argument block");
   if (args->struct_size != sizeof(glb_gemm_args))
     return glb::api_fail(GLB_EINVAL, "glb_gemm_args.struct_size %u != %zu (ABI mismatch)", args->struct_size,
@@ -349,10 +384,46 @@ int glb_gemm_f32_split_form(const glb_gemm_args *args, int form, void *stream) {
     const int rc = glb_gemm_split_pick(g.m, g.n, g.k, n_cus, &form);
     if (rc != GLB_OK) return rc;
   }
+  return GLB_OK;
+}
+
+int glb_gemm_f32_split_form(const glb_gemm_args *args, int form, void *stream) {
+  const int rc = split_check(args, form);
+  if (rc != GLB_OK) return rc;
+  const glb_gemm_args &g = *args;
   const bool gelu = g.epilogue == GLB_GEMM_BIAS_GELU_TANH;
   hipStream_t s = (hipStream_t)stream;
-  if (form == GLB_GEMM_FORM_SMALL) return gelu ? Form<Small, true>::launch(g, s) : Form<Small, false>::launch(g, s);
-  return gelu ? Form<Large, true>::launch(g, s) : Form<Large, false>::launch(g, s);
+  if (form == GLB_GEMM_FORM_SMALL) return gelu ? Form<Small, EPI_GELU>::launch(g, s) : Form<Small, EPI_NONE>::launch(g, s);
+  return gelu ? Form<Large, EPI_GELU>::launch(g, s) : Form<Large, EPI_NONE>::launch(g, s);
+}
+
+int glb_gemm_f32_split_residual(const glb_gemm_args *args, const float *residual, int64_t ldr, int form, void *stream) {
+  const int rc = split_check(args, form);
+  if (rc != GLB_OK) return rc;
+  const glb_gemm_args &g = *args;
+  if (g.epilogue != GLB_GEMM_BIAS) return glb::api_fail(GLB_EINVAL, "the residual epilogue takes GLB_GEMM_BIAS only (epilogue %d)", g.epilogue);
+  if (!residual) return glb::api_fail(GLB_EINVAL, "null residual");
+  if (ldr < g.n || ((uintptr_t)residual) % sizeof(float))
+    return glb::api_fail(GLB_EINVAL, "residual misaligned or its pitch %lld below n %lld", (long long)ldr, (long long)g.n);
+  // C may be the residual itself (same pointer, same pitch: an element is read and written by one thread); no other overlap
+  if (!(residual == g.c && ldr == g.ldc)) {
+    const uintptr_t c0 = (uintptr_t)g.c, c1 = c0 + ((uint64_t)(g.m - 1) * (uint64_t)g.ldc + (uint64_t)g.n) * sizeof(float);
+    const uintptr_t r0 = (uintptr_t)residual, r1 = r0 + ((uint64_t)(g.m - 1) * (uint64_t)ldr + (uint64_t)g.n) * sizeof(float);
+    if (r0 < c1 && c0 < r1) return glb::api_fail(GLB_EINVAL, "the residual overlaps C without being C");
+  }
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return glb::api_hip_fail(e, "split GEMM device");
+  hipPointerAttribute_t at;
+  e = hipPointerGetAttributes(&at, residual);
+  if (e != hipSuccess || at.type != hipMemoryTypeDevice || at.device != dev) {
+    (void)hipGetLastError();  // (a pointer the runtime does not know leaves its error behind)
+    return glb::api_fail(GLB_EINVAL, "the residual is not memory of the current device");
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const Residual<true> res{residual, ldr};
+  if (form == GLB_GEMM_FORM_SMALL) return Form<Small, EPI_RESIDUAL>::launch(g, s, res);
+  return Form<Large, EPI_RESIDUAL>::launch(g, s, res);
 }
 
 int glb_gemm_f32_split(const glb_gemm_args *args, void *stream) { return glb_gemm_f32_split_form(args, 0, stream); }
@@ -360,8 +431,8 @@ int glb_gemm_f32_split(const glb_gemm_args *args, void *stream) { return glb_gem
 int glb_gemm_split_form_blocks_per_cu(int form, int gelu, int *blocks) {
   if (!blocks) return glb::api_fail(GLB_EINVAL, "null pointer");
   if (!form_ok(form)) return glb::api_fail(GLB_EINVAL, "bad form %d", form);
-  if (form == GLB_GEMM_FORM_SMALL) return gelu ? Form<Small, true>::blocks_per_cu(blocks) : Form<Small, false>::blocks_per_cu(blocks);
-  return gelu ? Form<Large, true>::blocks_per_cu(blocks) : Form<Large, false>::blocks_per_cu(blocks);
+  if (form == GLB_GEMM_FORM_SMALL) return gelu ? Form<Small, EPI_GELU>::blocks_per_cu(blocks) : Form<Small, EPI_NONE>::blocks_per_cu(blocks);
+  return gelu ? Form<Large, EPI_GELU>::blocks_per_cu(blocks) : Form<Large, EPI_NONE>::blocks_per_cu(blocks);
 }
 
 int glb_gemm_split_blocks_per_cu(int gelu, int *blocks) {

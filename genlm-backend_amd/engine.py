@@ -907,13 +907,16 @@ class HipEngine:
         check(self.lib.glb_gemm_split_weights(_ptr(w), k, n, w.stride(0), _ptr(out), nbytes, self._stream()))
         return out
 
-    def gemm_split(self, x, w_split, n, bias=None, gelu=False, out=None, form=None):
+    def gemm_split(self, x, w_split, n, bias=None, gelu=False, out=None, form=None, residual=None):
         """x [..., K] float32 (rows of unit inner stride) times the weight whose image is `w_split`, plus bias [N], then the
         tanh GELU when `gelu` (glb_gemm_f32_split).  Returns [..., N] float32, or None when the kernel does not serve the
         call (alignment, shape, a bias that is not contiguous float32): the caller then runs its library GEMM.  `out`: a
         float32 [M, N] tensor on the engine's device with unit inner stride (rows may be padded); ValueError otherwise, and
         for a bias of the wrong length or device.  `form`: None lets the library pick the tile form from the shape;
         _lib.GEMM_FORM_LARGE / _lib.GEMM_FORM_SMALL force one (glb_gemm_f32_split_form) - the result's bits are the same.
+        `residual`: float32 [..., N] (M rows of unit inner stride) added to the result in the kernel's epilogue, after the bias
+        (glb_gemm_f32_split_residual): the bits of `gemm_split(x, ...) + residual`.  `out` may be `residual` itself; with
+        `gelu`, on another device or of another shape it is a ValueError, overlapping `out` in part a GlbError: no launch.
         Non-finite and out-of-range operands: include/glb.h."""
         k = x.shape[-1]
         x2 = x.reshape(-1, k)
@@ -944,7 +947,18 @@ class HipEngine:
         a.bias = bias.data_ptr() if bias is not None else None
         a.c, a.ldc = out.data_ptr(), max(out.stride(0), n)  # (a one-row tensor's stride is arbitrary)
         a.epilogue = _lib.GEMM_BIAS_GELU_TANH if gelu else _lib.GEMM_BIAS
-        if form is None:
+        if residual is not None:
+            if gelu:
+                raise ValueError("gemm_split: the residual epilogue does not follow the GELU")
+            if residual.device != self.device:
+                raise ValueError(f"residual on {residual.device}, engine on {self.device}")
+            r2 = residual.view(-1, n) if residual.dim() != 2 else residual
+            if residual.dtype != torch.float32 or tuple(r2.shape) != (m, n) or r2.stride(1) != 1 or (m > 1 and r2.stride(0) < n):
+                raise ValueError(f"residual is {residual.dtype} {tuple(residual.shape)} with strides {residual.stride()}: "
+                                 f"torch.float32 {(m, n)} rows of unit inner stride are needed")
+            rc = self.lib.glb_gemm_f32_split_residual(C.byref(a), r2.data_ptr(), max(r2.stride(0), n), int(form or 0),
+                                                      self._stream())  # (a partial overlap with out: GlbError below)
+        elif form is None:
             rc = self.lib.glb_gemm_f32_split(C.byref(a), self._stream())
         else:
             rc = self.lib.glb_gemm_f32_split_form(C.byref(a), int(form), self._stream())
@@ -952,6 +966,38 @@ class HipEngine:
             return None
         check(rc)
         return out.view(*x.shape[:-1], n)
+
+    # ---- the plan of a row-packed encoding (glb_packed_plan: DESIGN.md §27) -----------------------------------------
+    def packed_plan(self, batch, sel, n_sel, grp, groups, n_tail_rows, pos_cap):
+        """The four arrays of kv.encode_packed's plan in two launches: (segments int32 [G + n_sel, 4], ids int64 [M], pos
+        int64 [M], last int64 [n_sel]) for the ragged `batch` = (tokens int32, starts int64, lengths int32), `sel` / `grp`
+        int32 (their first n_sel entries) and `groups` (kv.PromptGroups); M = groups.n_rows + n_tail_rows.  Nothing is read
+        back; hostile lengths are clamped as the torch-op plan clamps them (include/glb.h)."""
+        tokens, starts, lengths = batch
+        G, n_pre = len(groups.lens), groups.n_rows
+        ins = (tokens, starts, lengths, sel, grp, groups.starts_d, groups.lens_d, groups.segments, groups.ids, groups.pos)
+        self._check_dev(*ins)
+        want = (torch.int32, torch.int64, torch.int32, torch.int32, torch.int32, torch.int32, torch.int32, torch.int32,
+                torch.int64, torch.int64)
+        if any(t.dtype != d for t, d in zip(ins, want)):
+            raise ValueError(f"packed_plan: dtypes {[t.dtype for t in ins]}, expected {list(want)}")
+        if sel.numel() < n_sel or grp.numel() < n_sel or starts.numel() != lengths.numel() or groups.ids.numel() != n_pre:
+            raise ValueError("packed_plan: sel / grp shorter than n_sel, or starts / lengths / the prompts' rows disagree")
+        M = n_pre + int(n_tail_rows)
+        seg = torch.empty((G + n_sel, 4), dtype=torch.int32, device=self.device)
+        ids = torch.empty(M, dtype=torch.int64, device=self.device)
+        pos = torch.empty(M, dtype=torch.int64, device=self.device)
+        last = torch.empty(n_sel, dtype=torch.int64, device=self.device)
+        ends = self._i32(n_sel)
+        a = _lib.PackedPlanArgs()
+        a.struct_size = C.sizeof(_lib.PackedPlanArgs)
+        a.n_tokens, a.n_contexts, a.n_sel, a.n_groups = tokens.numel(), lengths.numel(), n_sel, G
+        a.n_pre, a.n_tail_rows, a.pos_cap = n_pre, int(n_tail_rows), int(pos_cap)
+        (a.tokens, a.starts, a.lengths, a.sel, a.grp, a.group_starts, a.group_lens, a.group_segments, a.group_ids,
+         a.group_pos) = (t.data_ptr() for t in ins)
+        a.segments, a.ids, a.pos, a.last, a.ends = (t.data_ptr() for t in (seg, ids, pos, last, ends))
+        check(self.lib.glb_packed_plan(C.byref(a), self._stream()))
+        return seg, ids, pos, last
 
     # ---- LoRA merge (glb_lora_merge: DESIGN.md §13) ------------------------------------------------------------------
     def lora_merge(self, jobs):

@@ -21,7 +21,8 @@ What the shadow swaps (PyTorch ops only - no kernels of this library inside the 
   * GPT-2's Conv1D projections (float32)                     -> `SplitConv1D`: this library's split-bf16 MFMA GEMM
                                                                 (glb_gemm_f32_split, on a derived bf16 image of the weight)
                                                                 for the batches where it was measured faster; the MLP's
-                                                                tanh GELU then runs in that GEMM's epilogue
+                                                                tanh GELU then runs in that GEMM's epilogue, and a block's
+                                                                two residual adds in the epilogues of its `c_proj`s
   * the attention interface                                  -> kv.py's "glb" entry (glb_short_attention /
                                                                 glb_slab_attention where they apply, SDPA otherwise)
 Same functions, different rounding (float32 inside the fused ops, one rounding at the end; the split GEMM is fp32-accurate
@@ -194,6 +195,7 @@ class SplitConv1D(torch.nn.Module):
         self._parameters = src._parameters
         self.nf, self.nx = src.nf, src.nx
         self.min_rows = min_rows
+        self.fused_residuals = 0  # calls whose epilogue added a block's residual
         self.__dict__["_glb_engine"] = engine  # (not a submodule)
 
     def _split(self):
@@ -215,11 +217,29 @@ class SplitConv1D(torch.nn.Module):
                 and not (torch.is_grad_enabled() and (x.requires_grad or w.requires_grad
                                                       or (self.bias is not None and self.bias.requires_grad))))
 
+    def offer_residual(self, residual):
+        """A GPT-2 block hands its residual over for the ONE call that follows (`_gpt2_block_forward`): if that call runs the
+        kernel, the add happens in its epilogue.  `residual_taken` tells the block afterwards, and clears the offer."""
+        self.__dict__["_glb_residual"] = residual
+
+    def residual_taken(self):
+        self.__dict__.pop("_glb_residual", None)  # (an offer no call consumed)
+        return self.__dict__.pop("_glb_residual_taken", False)
+
     def forward(self, x, act=None):
+        residual = self.__dict__.pop("_glb_residual", None)
         if self._native(x):
             img = self._split()
             if img is not None:
                 gelu = _is_tanh_gelu(act)
+                if (residual is not None and act is None and residual.dtype == torch.float32 and residual.device == x.device
+                        and residual.shape == x.shape[:-1] + (self.nf,) and residual.is_contiguous()
+                        and not (torch.is_grad_enabled() and residual.requires_grad)):
+                    y = self._glb_engine.gemm_split(x, img, self.nf, self.bias, residual=residual)
+                    if y is not None:
+                        self.__dict__["_glb_residual_taken"] = True
+                        self.fused_residuals += 1
+                        return y
                 y = self._glb_engine.gemm_split(x, img, self.nf, self.bias, gelu=gelu)
                 if y is not None:
                     return y if gelu or act is None else act(y)
@@ -235,6 +255,43 @@ def _gpt2_mlp_forward(self, hidden_states):
     """modeling_gpt2.py GPT2MLP.forward with the activation handed to c_fc (SplitConv1D: the tanh GELU in its epilogue)."""
     h = self.c_fc(hidden_states, act=self.act)
     return self.dropout(self.c_proj(h))
+
+
+RESIDUAL_EPILOGUE = True  # False: every block runs its own adds (the A/B switch of tests/test_packed_fused_forward_gpu.py)
+
+
+def _gpt2_block_forward(self, hidden_states, past_key_values=None, attention_mask=None, encoder_hidden_states=None,
+                        encoder_attention_mask=None, use_cache=False, **kwargs):
+    """modeling_gpt2.py GPT2Block.forward with each residual offered to the `c_proj` that precedes its add: a SplitConv1D
+    about to run the kernel adds it in the epilogue (the bits of `attn_output + residual` and of `residual +
+    feed_forward_hidden_states`: fp32 addition commutes), and the block skips its own add.  Offered only while the dropout
+    behind that `c_proj` is the identity (not training); a projection that runs its library GEMM, is wrapped (per-row LoRA)
+    or is no SplitConv1D leaves the add to the block, as does a block with cross-attention (the module's own code)."""
+    if encoder_hidden_states is not None or not RESIDUAL_EPILOGUE:
+        return type(self).forward(self, hidden_states, past_key_values=past_key_values, attention_mask=attention_mask,
+                                  encoder_hidden_states=encoder_hidden_states, encoder_attention_mask=encoder_attention_mask,
+                                  use_cache=use_cache, **kwargs)
+    residual = hidden_states
+    proj = self.attn._modules.get("c_proj")
+    offered = isinstance(proj, SplitConv1D) and not self.attn.training
+    if offered:
+        proj.offer_residual(residual)
+    try:
+        attn_output, _ = self.attn(self.ln_1(hidden_states), past_key_values=past_key_values, attention_mask=attention_mask,
+                                   use_cache=use_cache, **kwargs)
+    finally:
+        taken = offered and proj.residual_taken()
+    hidden_states = attn_output if taken else attn_output + residual
+    residual = hidden_states
+    proj = self.mlp._modules.get("c_proj")
+    offered = isinstance(proj, SplitConv1D) and not self.mlp.training
+    if offered:
+        proj.offer_residual(residual)
+    try:
+        feed_forward_hidden_states = self.mlp(self.ln_2(hidden_states))
+    finally:
+        taken = offered and proj.residual_taken()
+    return feed_forward_hidden_states if taken else residual + feed_forward_hidden_states
 
 
 def weights_version(net):
@@ -349,4 +406,8 @@ def _split_conv1d(shadow, engine):
             done.append("split_gemm")
         if type(mod).__name__ == "GPT2MLP" and isinstance(mod._modules.get("c_fc"), SplitConv1D):
             mod.forward = types.MethodType(_gpt2_mlp_forward, mod)
+    for mod in shadow.modules():  # (after the swaps: a block is listed before its children)
+        if type(mod).__name__ == "GPT2Block" and any(
+                isinstance(getattr(mod, part)._modules.get("c_proj"), SplitConv1D) for part in ("attn", "mlp") if hasattr(mod, part)):
+            mod.forward = types.MethodType(_gpt2_block_forward, mod)
     return done

@@ -766,25 +766,19 @@ def packed_supported(llm):
     return bool(head_dim in (16, 32, 64, 128) and getattr(cfg, "num_hidden_layers", 0) > 0)
 
 
-def encode_packed(llm, batch, sel, n_sel, grp, groups, n_tail_rows, max_keys=PACKED_MAX_KEYS):
-    """Encode contexts `sel` (int32 device, its first n_sel entries) of the ragged `batch` = (tokens, starts, lengths) in one
-    ROW-PACKED forward of `llm._body`: context u is prompt `grp[u]` (int32 [n_sel] device) of `groups` (PromptGroups) plus a
-    tail of t_u >= 1 tokens, and the batch is [1, M]: the G prompts once, then the tails in context order - M = sum P_g +
-    n_tail_rows, where n_tail_rows = sum t_u is the CALLER's (host) number: nothing is read back here.  The prompts' hidden
-    states, K and V are the same for every context behind them (same tokens, same positions, causal), so computing them once
-    changes no result; attention is glb_short_attention_packed through `PackedKV`.  max_keys: the most P + t of a context
-    (<= 32).  Lengths that do not match n_tail_rows, a tail < 1 or a context longer than max_keys are refused row by row in
-    the kernel (engine.error_word / raise_if_failed); every index used here is clamped into range first."""
+def _packed_plan_arrays(llm, batch, sel, n_sel, grp, groups, n_tail_rows, native_plan=True):
+    """The plan of `encode_packed` on the device: (segments int32 [G + U, 4], ids int64 [M], pos int64 [M], last int64 [U], M).
+    native_plan: glb_packed_plan, two launches; False, or an engine without `packed_plan`: the torch ops below, the
+    restatement the kernel is tested against (tests/test_packed_plan_native_gpu.py) - the same arrays for every input."""
     eng, dev = llm.engine, llm.device
     tokens, starts, lengths = batch
-    if not 1 <= max_keys <= PACKED_MAX_KEYS:
-        raise ValueError(f"encode_packed serves contexts of up to {PACKED_MAX_KEYS} tokens")
-    if n_sel < 1 or n_tail_rows < n_sel:
-        raise ValueError("encode_packed: every context feeds at least one tail row")
-    if not packed_supported(llm):
-        raise RuntimeError("encode_packed: this model's attention is not served by glb_short_attention")
     G, n_pre = len(groups.lens), groups.n_rows
     M = n_pre + int(n_tail_rows)
+    max_pos = getattr(llm._body.config, "max_position_embeddings", None) or (1 << 30)
+    pos_cap = min(PACKED_MAX_KEYS, max_pos)
+    native = getattr(eng, "packed_plan", None) if native_plan else None  # (None: an engine without the kernel)
+    if native is not None:
+        return native(batch, sel, n_sel, grp, groups, n_tail_rows, pos_cap) + (M,)
     sel_l, grp_l = sel[:n_sel].long(), grp[:n_sel].long().clamp(0, G - 1)
     pre_len, pre_start = groups.lens_d[grp_l], groups.starts_d[grp_l]
     tail = lengths[sel_l] - pre_len  # int32 [U]
@@ -796,15 +790,36 @@ def encode_packed(llm, batch, sel, n_sel, grp, groups, n_tail_rows, max_keys=PAC
     u = torch.searchsorted(ends, r, right=True).clamp_(max=n_sel - 1)
     pos_t = (pre_len[u] + (r - (ends - tail)[u])).long()
     at = (starts[sel_l[u]] + pos_t).clamp_(0, tokens.numel() - 1)
-    ids = torch.cat([groups.ids, tokens[at].long()]).view(1, M)
-    max_pos = getattr(llm._body.config, "max_position_embeddings", None) or (1 << 30)
-    pos = torch.cat([groups.pos, pos_t.clamp_(0, min(PACKED_MAX_KEYS, max_pos) - 1)]).view(1, M)
+    ids = torch.cat([groups.ids, tokens[at].long()])
+    pos = torch.cat([groups.pos, pos_t.clamp_(0, pos_cap - 1)])
+    return segments, ids, pos, (tail_start + tail - 1).long().clamp_(0, M - 1), M
+
+
+def encode_packed(llm, batch, sel, n_sel, grp, groups, n_tail_rows, max_keys=PACKED_MAX_KEYS, native_plan=True):
+    """Encode contexts `sel` (int32 device, its first n_sel entries) of the ragged `batch` = (tokens, starts, lengths) in one
+    ROW-PACKED forward of `llm._body`: context u is prompt `grp[u]` (int32 [n_sel] device) of `groups` (PromptGroups) plus a
+    tail of t_u >= 1 tokens, and the batch is [1, M]: the G prompts once, then the tails in context order - M = sum P_g +
+    n_tail_rows, where n_tail_rows = sum t_u is the CALLER's (host) number: nothing is read back here.  The prompts' hidden
+    states, K and V are the same for every context behind them (same tokens, same positions, causal), so computing them once
+    changes no result; attention is glb_short_attention_packed through `PackedKV`.  max_keys: the most P + t of a context
+    (<= 32).  Lengths that do not match n_tail_rows, a tail < 1 or a context longer than max_keys are refused row by row in
+    the kernel (engine.error_word / raise_if_failed); every index used here is clamped into range first.  native_plan: the
+    plan's four arrays come from glb_packed_plan (`_packed_plan_arrays`); False keeps the torch ops."""
+    eng = llm.engine
+    if not 1 <= max_keys <= PACKED_MAX_KEYS:
+        raise ValueError(f"encode_packed serves contexts of up to {PACKED_MAX_KEYS} tokens")
+    if n_sel < 1 or n_tail_rows < n_sel:
+        raise ValueError("encode_packed: every context feeds at least one tail row")
+    if not packed_supported(llm):
+        raise RuntimeError("encode_packed: this model's attention is not served by glb_short_attention")
+    segments, ids, pos, last, M = _packed_plan_arrays(llm, batch, sel, n_sel, grp, groups, n_tail_rows, native_plan)
+    ids, pos = ids.view(1, M), pos.view(1, M)
     pkv = PackedKV(eng, segments, M, max_keys, llm._body.config.num_hidden_layers)
     out = llm._body(input_ids=ids, position_ids=pos, attention_mask=None, past_key_values=pkv, use_cache=True)
     if pkv.served != len(pkv.layers):
         raise RuntimeError(f"glb_short_attention_packed served {pkv.served} of {len(pkv.layers)} layers: an attention module "
                            "bypassed the attention interface and attended across the packed contexts")
-    return PackedEncoding(out, (tail_start + tail - 1).long().clamp_(0, M - 1), M)
+    return PackedEncoding(out, last, M)
 
 
 class PrefixLRU:

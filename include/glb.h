@@ -791,12 +791,59 @@ int glb_gemm_f32_split(const glb_gemm_args *args, void *hip_stream);
 enum { GLB_GEMM_FORM_LARGE = 1, GLB_GEMM_FORM_SMALL = 2 };
 int glb_gemm_split_pick(int64_t m, int64_t n, int64_t k, int n_cus, int *form);
 int glb_gemm_f32_split_form(const glb_gemm_args *args, int form, void *hip_stream);
+/* The residual epilogue: C[row, col] = (acc + bias[col]) + R[row, col] - two separately rounded fp32 adds, the bias first -
+ * with R = `residual`, fp32 [m, n] of row pitch ldr >= n, 4-byte aligned, memory of the current device.  The bits are those
+ * of glb_gemm_f32_split followed by a float add of R in either operand order; a transformer block's `x + proj(h)` in one
+ * launch and without the pass over [m, n] the add takes.  R is read under the store's guard: nothing outside its m x n
+ * elements is read, and a non-finite element of R reaches its own element of C only.  C may be R itself (same pointer and
+ * ldc == ldr: every element is read and written by one thread, in that order); any other overlap of the two, a null or
+ * misaligned R, ldr < n, an R the current device does not own and an epilogue other than GLB_GEMM_BIAS return GLB_EINVAL
+ * without a launch.  Every other check, `form` and the return codes are glb_gemm_f32_split_form's. */
+int glb_gemm_f32_split_residual(const glb_gemm_args *args, const float *residual, int64_t ldr, int form, void *hip_stream);
 /* How many blocks of the split GEMM's kernel (gelu != 0: the instantiation with the GELU epilogue) the runtime keeps resident
  * on one CU of the current device, given the kernel's registers and its dynamic LDS (hipOccupancyMaxActiveBlocksPerMultiprocessor).
  * The kernel is built for three; no GPU work.  This is the large form; glb_gemm_split_form_blocks_per_cu
  * reports either form's (the small one is built for six; a bad form: GLB_EINVAL). */
 int glb_gemm_split_blocks_per_cu(int gelu, int *blocks);
 int glb_gemm_split_form_blocks_per_cu(int form, int gelu, int *blocks);
+
+/*
+ * The plan of a row-packed encoding (kv.encode_packed): context u of the n_sel selected ones is prompt
+ * grp[u] of n_groups prompts plus a tail of t_u = lengths[sel[u]] - group_lens[grp[u]] tokens; the packed batch holds the
+ * prompts' n_pre rows once, then the tails in context order, M = n_pre + n_tail_rows rows (n_tail_rows: the CALLER's number,
+ * nothing is read back).  Inputs, all device memory: the ragged batch tokens [n_tokens] / starts [n_contexts] / lengths
+ * [n_contexts], sel and grp (their first n_sel entries), the prompts' group_starts / group_lens [n_groups],
+ * group_segments [n_groups, 4], group_ids / group_pos [n_pre].  Outputs: segments int32 [n_groups + n_sel, 4] =
+ * (pre_start, pre_len, tail_start, tail_len) with the prompts' rows first, ids and pos int64 [M] (pos clamped to
+ * [0, pos_cap - 1]), last int64 [n_sel] (the row of every context's last token, clamped into [0, M - 1]); ends int32
+ * [n_sel] is scratch (the tails' inclusive sums).  Two plain launches on the stream - one workgroup scans the tails, then a
+ * thread per row finds its context by binary search - no workspace beyond these, no allocation, safe under stream capture.
+ * Lengths that do not match n_tail_rows, tails < 1 and grp out of range are NOT errors here: every index is clamped into
+ * range (grp into [0, n_groups - 1], a tail row's context into [0, n_sel - 1], its token's index into [0, n_tokens - 1],
+ * sel read as an index from the end when negative and kept inside [0, n_contexts - 1]), int32 sums wrap, and
+ * glb_short_attention_packed refuses the bad segments row by row.  GLB_EINVAL: null pointers, a size below 1,
+ * n_tail_rows < n_sel, M or n_sel beyond INT32_MAX.
+ */
+typedef struct glb_packed_plan_args {
+  uint32_t struct_size; /* sizeof(glb_packed_plan_args) - ABI guard */
+  int64_t n_tokens, n_contexts, n_sel, n_groups, n_pre, n_tail_rows, pos_cap;
+  const int32_t *tokens;
+  const int64_t *starts;
+  const int32_t *lengths;
+  const int32_t *sel;
+  const int32_t *grp;
+  const int32_t *group_starts;
+  const int32_t *group_lens;
+  const int32_t *group_segments;
+  const int64_t *group_ids;
+  const int64_t *group_pos;
+  int32_t *segments;
+  int64_t *ids;
+  int64_t *pos;
+  int64_t *last;
+  int32_t *ends;
+} glb_packed_plan_args;
+int glb_packed_plan(const glb_packed_plan_args *args, void *hip_stream);
 
 /*
  * LoRA merge: out = W + scale * B . A for every matrix of an adapter in one call - what peft's merged
