@@ -517,6 +517,20 @@ class TopkArgs(C.Structure):
     ]
 
 
+class TruncateArgs(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("logits", C.c_void_p), ("dtype", C.c_int32),
+        ("n_rows", C.c_int64), ("vocab", C.c_int64), ("ld", C.c_int64),
+        ("logit_scale", C.c_float),
+        ("mask_kind", C.c_int32), ("mask", C.c_void_p), ("mask_ld", C.c_int64), ("n_masks", C.c_int64),
+        ("row_mask_id", C.c_void_p),
+        ("top_k", C.c_int64), ("top_p", C.c_float), ("log_min_p", C.c_float),
+        ("out_bits", C.c_void_p), ("out_ld", C.c_int64),
+        ("out_threshold", C.c_void_p), ("out_kept", C.c_void_p), ("out_logmass", C.c_void_p),
+    ]
+
+
 # every symbol include/glb.h declares: name -> (restype, argtypes)
 _vp, _i32, _i64, _f32, _sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_size_t
 SYMBOLS = {
@@ -637,6 +651,7 @@ SYMBOLS = {
     "glb_score_rows": (C.c_int, [C.POINTER(ScoreArgs), _vp]),
     "glb_score_seq_sums": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp]),
     "glb_topk_rows": (C.c_int, [C.POINTER(TopkArgs), _vp]),
+    "glb_truncate_rows": (C.c_int, [C.POINTER(TruncateArgs), _vp]),
     "glb_beam_select": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "glb_philox4x32_10": (None, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
 }

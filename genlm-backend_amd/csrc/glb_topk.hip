@@ -59,7 +59,7 @@ __device__ __forceinline__ void fold_chunk(float N, uint64_t S, float &M, double
 
 template <int DT, int MASK>
 __global__ __launch_bounds__(64 * kWaves) void topk_rows_kernel(const TopkParams a) {
-  constexpr int EPV = ElemTraits<DT>::EPV, NVC = ElemTraits<DT>::NVC;
+  constexpr int EPV = ElemTraits<DT>::EPV;
   __shared__ WaveAcc acc[kWaves];
   __shared__ uint64_t lists[kWaves * 64];
   __shared__ double row_lse[2];
@@ -79,14 +79,7 @@ __global__ __launch_bounds__(64 * kWaves) void topk_rows_kernel(const TopkParams
     for (int c = wave; c < a.nch; c += kWaves) {
       const int e_base = c * kChunk;
       float y[64];
-      {
-        u32x4_t raw[NVC];
-        load_chunk_raw<DT>(xrow, e_base, V, lane, raw);
-#pragma unroll
-        for (int i = 0; i < NVC; ++i) unpack_vec<DT>(raw[i], &y[i * EPV]);
-      }
-#pragma unroll
-      for (int j = 0; j < 64; ++j) y[j] *= a.scale;  // (times 1.0f: the same bits)
+      chunk_scaled<DT>(xrow, e_base, V, lane, a.scale, y);
       const float Ny = exp_n(wave_max(lane_max64(y)));
       float Nz = kNegInf;
       uint64_t Sy = 0, Sz = 0;
@@ -95,37 +88,8 @@ __global__ __launch_bounds__(64 * kWaves) void topk_rows_kernel(const TopkParams
         Nz = Ny;
         Sz = Sy;
       } else {
-        // y becomes the keys y + m in place
-        if (!mask_ok) {
-#pragma unroll
-          for (int j = 0; j < 64; ++j) y[j] = kNegInf;
-        } else if constexpr (MASK == GLB_MASK_BITS) {
-          // the words that hold this lane's bits: vector i covers EPV bits from bit (lane * EPV) % 32 of word
-          // e_base / 32 + i * (64 * EPV / 32) + lane * EPV / 32
-          const uint32_t *mrow = reinterpret_cast<const uint32_t *>(a.mask) + (int64_t)mid * a.mask_ld;
-          const int nw = (V + 31) >> 5, w0 = (e_base >> 5) + ((lane * EPV) >> 5), sh = (lane * EPV) & 31;
-          uint32_t mw[NVC];
-#pragma unroll
-          for (int i = 0; i < NVC; ++i) {
-            const int wi = w0 + i * (64 * EPV / 32);
-            mw[i] = wi < nw ? mrow[wi] >> sh : 0u;
-          }
-#pragma unroll
-          for (int j = 0; j < 64; ++j) y[j] = ((mw[j / EPV] >> (j % EPV)) & 1u) ? y[j] : kNegInf;
-        } else {  // GLB_MASK_F32: the floats in y's lane layout
-          const char *mrow = reinterpret_cast<const char *>(reinterpret_cast<const float *>(a.mask) + (int64_t)mid * a.mask_ld);
-#pragma unroll
-          for (int i = 0; i < NVC; ++i) {
-#pragma unroll
-            for (int h = 0; h < EPV / 4; ++h) {
-              float m[4];
-              unpack_vec<kDtF32>(load_vec_guarded<kDtF32>(mrow, e_base + (i * 64 + lane) * EPV + 4 * h, V), m);
-#pragma unroll
-              for (int q = 0; q < 4; ++q) y[i * EPV + 4 * h + q] += m[q];
-            }
-          }
-        }
-        Nz = exp_n(wave_max(lane_max64(y)));
+        chunk_add_mask<DT, MASK>(y, mask_ok, a.mask, mid, a.mask_ld, e_base, V, lane);  // y becomes the keys y + m in place
+        Nz =exp_n(wave_max(lane_max64(y)));
         if (Nz != kNegInf) Sz = wave_fix_sum(lane_sum64<EPV>(y, Nz));
       }
       fold_chunk(Ny, Sy, My, Wy);

@@ -233,6 +233,21 @@ class _OnDevice:
         return call
 
 
+def check_truncation(top_k, top_p, min_p):
+    """(top_k, top_p, log_min_p) as glb_truncate_rows takes them, from the sampling options top_k (0: off), top_p (1: off) and
+    min_p (0: off); a ValueError names the offending value.  log_min_p is the float32 log(min_p), so key_max + log_min_p is one
+    rounded add on the host and on the device."""
+    if isinstance(top_k, bool) or not isinstance(top_k, int) or top_k < 0:
+        raise ValueError(f"top_k must be a non-negative integer (0: off), got {top_k!r}")
+    if isinstance(top_p, bool) or not isinstance(top_p, (int, float)) or not 0.0 < top_p <= 1.0:  # (NaN fails both)
+        raise ValueError(f"top_p must lie in (0, 1] (1: off), got {top_p!r}")
+    if isinstance(min_p, bool) or not isinstance(min_p, (int, float)) or not 0.0 <= min_p <= 1.0:
+        raise ValueError(f"min_p must lie in [0, 1] (0: off), got {min_p!r}")
+    with np.errstate(divide="ignore"):
+        log_min_p = float(np.log(np.float32(min_p)))
+    return top_k, float(top_p), log_min_p
+
+
 class HipEngine:
     """All device work of the hot path for one GPU."""
 
@@ -554,24 +569,9 @@ class HipEngine:
             check(self.lib.glb_score_seq_sums(_ptr(src), values.numel(), _ptr(seq_start), out.numel(), _ptr(out), self._stream()))
         return out
 
-    TOPK_OUTPUTS = ("logp", "logp_masked", "lse", "logZ")
-    TOPK_MAX = 64
-
-    def topk_rows(self, logits, k, *, vocab=None, logit_scale=1.0, mask_kind=MASK_NONE, mask=None, row_mask_id=None, want=("logp",)):
-        """The k most probable tokens of every logits row (glb_topk_rows; DESIGN.md §30): with y = logits[r] * logit_scale,
-        m the row's mask and key = y + m, a dict holding "token" int32 [n_rows, k] - the indices of the k largest keys, largest
-        first, equal keys by lower index, -1 beyond the finite keys - and the names in `want`: "logp" = key - lse(y) and
-        "logp_masked" = key - lse(y + m), float32 [n_rows, k] (-inf where the token is -1); "lse" = lse(y) and "logZ" =
-        lse(y + m) - lse(y), float32 [n_rows].  No log-softmax is written.  logits, mask and row_mask_id as `score_rows`
-        takes them - the keywords a constraint's `step_masks(..., by_row=True, ...)` returns."""
-        if isinstance(mask, PreparedMasks) or mask_kind == MASK_PREPARED:
-            raise TypeError("topk_rows reads bit rows or float rows as they lie, not prepared masks")
-        want = tuple(want)
-        for w in want:
-            if w not in self.TOPK_OUTPUTS:
-                raise ValueError(f"want names {w!r}; the outputs are {self.TOPK_OUTPUTS}")
-        if not isinstance(k, int) or not 1 <= k <= self.TOPK_MAX:
-            raise ValueError(f"k must be an integer in 1..{self.TOPK_MAX}, got {k!r}")
+    def _row_block(self, a, logits, vocab, logit_scale, mask_kind, mask, row_mask_id):
+        """The logits and mask fields that glb_topk_args and glb_truncate_args share, checked and written into `a`;
+        returns (n_rows, vocab)."""
         if logits.dim() != 2 or logits.stride(1) != 1:
             raise ValueError("logits must be 2-D with unit inner stride")
         if logits.dtype not in _DT:
@@ -589,10 +589,8 @@ class HipEngine:
         self._check_dev(row_mask_id)
         if mask_kind not in (MASK_NONE, MASK_BITS, MASK_F32):
             raise ValueError(f"bad mask_kind {mask_kind}")
-        a = _lib.TopkArgs()
-        a.struct_size = C.sizeof(_lib.TopkArgs)
         a.logits, a.dtype = logits.data_ptr(), _DT[logits.dtype]
-        a.n_rows, a.vocab, a.logit_scale, a.k = n_rows, V, logit_scale, k
+        a.n_rows, a.vocab, a.logit_scale = n_rows, V, logit_scale
         a.ld = logits.stride(0) if n_rows > 1 else max(width, logits.stride(0))
         a.mask_kind = mask_kind
         if mask_kind != MASK_NONE:
@@ -617,12 +615,70 @@ class HipEngine:
             a.row_mask_id = None if row_mask_id is None else row_mask_id.data_ptr()
         elif mask is not None or row_mask_id is not None:
             raise ValueError("a mask table or row_mask_id given with MASK_NONE")
+        return n_rows, V
+
+    TOPK_OUTPUTS = ("logp", "logp_masked", "lse", "logZ")
+    TOPK_MAX = 64
+
+    def topk_rows(self, logits, k, *, vocab=None, logit_scale=1.0, mask_kind=MASK_NONE, mask=None, row_mask_id=None, want=("logp",)):
+        """The k most probable tokens of every logits row (glb_topk_rows; DESIGN.md §30): with y = logits[r] * logit_scale,
+        m the row's mask and key = y + m, a dict holding "token" int32 [n_rows, k] - the indices of the k largest keys, largest
+        first, equal keys by lower index, -1 beyond the finite keys - and the names in `want`: "logp" = key - lse(y) and
+        "logp_masked" = key - lse(y + m), float32 [n_rows, k] (-inf where the token is -1); "lse" = lse(y) and "logZ" =
+        lse(y + m) - lse(y), float32 [n_rows].  No log-softmax is written.  logits, mask and row_mask_id as `score_rows`
+        takes them - the keywords a constraint's `step_masks(..., by_row=True, ...)` returns."""
+        if isinstance(mask, PreparedMasks) or mask_kind == MASK_PREPARED:
+            raise TypeError("topk_rows reads bit rows or float rows as they lie, not prepared masks")
+        want = tuple(want)
+        for w in want:
+            if w not in self.TOPK_OUTPUTS:
+                raise ValueError(f"want names {w!r}; the outputs are {self.TOPK_OUTPUTS}")
+        if not isinstance(k, int) or not 1 <= k <= self.TOPK_MAX:
+            raise ValueError(f"k must be an integer in 1..{self.TOPK_MAX}, got {k!r}")
+        a = _lib.TopkArgs()
+        a.struct_size = C.sizeof(_lib.TopkArgs)
+        n_rows, _ = self._row_block(a, logits, vocab, logit_scale, mask_kind, mask, row_mask_id)
+        a.k = k
         out = {"token": torch.empty((n_rows, k), dtype=torch.int32, device=self.device)}
         a.out_token = out["token"].data_ptr()
         for w in want:
             out[w] = torch.empty((n_rows, k) if w.startswith("logp") else (n_rows,), dtype=torch.float32, device=self.device)
             setattr(a, "out_" + w, out[w].data_ptr())
         check(self.lib.glb_topk_rows(C.byref(a), self._stream()))
+        return out
+
+    TRUNCATE_OUTPUTS = ("threshold", "kept", "logmass")
+
+    def truncate_rows(self, logits, *, top_k=0, top_p=1.0, min_p=0.0, vocab=None, logit_scale=1.0, mask_kind=MASK_NONE, mask=None,
+                      row_mask_id=None, want=()):
+        """The keep set of top-k, top-p (nucleus) and min-p truncation of every logits row (glb_truncate_rows):
+        with y = logits[r] * logit_scale, m the row's mask and key = y + m, the row keeps {key > -inf, key >= tau}, tau the
+        largest of the top_k-th largest key (top_k = 0: off), the nucleus boundary of mass top_p among those (1: off) and
+        key_max + log(min_p) (0: off); ties at tau are kept.  A dict holding "bits" int32 [n_rows, ceil(vocab / 32)] - raw
+        MASK_BITS rows, one per logits row, as `step`, `score_rows` and `topk_rows` read them - and the names in `want`, each
+        [n_rows]: "threshold" float32 (tau), "kept" int32, "logmass" float32 = log(kept mass / mass of the finite keys).
+        logits, mask and row_mask_id as `topk_rows` takes them - the keywords a constraint's `step_masks(..., by_row=True, ...)`
+        returns."""
+        if isinstance(mask, PreparedMasks) or mask_kind == MASK_PREPARED:
+            raise TypeError("truncate_rows reads bit rows or float rows as they lie, not prepared masks")
+        want = tuple(want)
+        for w in want:
+            if w not in self.TRUNCATE_OUTPUTS:
+                raise ValueError(f"want names {w!r}; the outputs are {self.TRUNCATE_OUTPUTS}")
+        top_k, top_p, log_min_p = check_truncation(top_k, top_p, min_p)
+        a = _lib.TruncateArgs()
+        a.struct_size = C.sizeof(_lib.TruncateArgs)
+        n_rows, V = self._row_block(a, logits, vocab, logit_scale, mask_kind, mask, row_mask_id)
+        if V > 1 << 24:
+            raise ValueError(f"vocab {V} above 2^24")
+        a.top_k, a.top_p, a.log_min_p = top_k, top_p, log_min_p
+        words = (V + 31) // 32
+        out = {"bits": torch.empty((n_rows, words), dtype=torch.int32, device=self.device)}
+        a.out_bits, a.out_ld = out["bits"].data_ptr(), words
+        for w in want:
+            out[w] = torch.empty(n_rows, dtype=torch.int32 if w == "kept" else torch.float32, device=self.device)
+            setattr(a, "out_" + w, out[w].data_ptr())
+        check(self.lib.glb_truncate_rows(C.byref(a), self._stream()))
         return out
 
     def beam_select(self, score, alive, cand_token, cand_logp, width):

@@ -1526,30 +1526,39 @@ class AsyncAmdLM(AsyncLM):
     # ---- sampling (base.py:110-179): a device-resident multi-token loop -----------------------------------------------
     @torch.no_grad()
     def batch_sample_sync(self, prompt_token_ids_list, max_tokens, eos_token_ids, temperature=1.0, seed=None,
-                          sync_every=4):
+                          sync_every=4, top_k=0, top_p=1.0, min_p=0.0):
         """base.py:148-179.  All sequences advance together on the device (sis.DeviceSampler): per-sequence KV slabs,
         softmax(logits / temperature) -> one draw per sequence per forward by the fused step, stop on `eos_token_ids`.
         With a seed every sequence reproduces torch.multinomial under its own torch.Generator().manual_seed(seed)
         (base.py:125-141); without one the draws come from the in-kernel Philox stream.  `sync_every`: how often the
-        loop reads the number of unfinished sequences back (the reference reads every token of every sequence)."""
+        loop reads the number of unfinished sequences back (the reference reads every token of every sequence).
+        top_k (0: off), top_p (1: off), min_p (0: off): every step draws from the distribution truncated after the temperature
+        - top-k, then the nucleus among those, and min-p against the largest probability, ties at the boundary kept
+        (HipEngine.truncate_rows) - and renormalised; with a seed, torch.multinomial of exactly that."""
+        from .engine import check_truncation
         from .sis import DeviceSampler
 
+        check_truncation(top_k, top_p, min_p)
         if not prompt_token_ids_list:
             return []
         if any(len(p) == 0 for p in prompt_token_ids_list):
             raise ValueError("Token ids must not be empty")
         if max_tokens <= 0:
             return [[] for _ in prompt_token_ids_list]
-        smp = DeviceSampler(self, prompt_token_ids_list, max_tokens, eos_token_ids, temperature, seed, sync_every=sync_every)
+        smp = DeviceSampler(self, prompt_token_ids_list, max_tokens, eos_token_ids, temperature, seed, sync_every=sync_every,
+                            top_k=top_k, top_p=top_p, min_p=min_p)
         return [[int(t) for t in row] for row in smp.generate()]
 
-    async def batch_sample(self, prompt_token_ids_list, max_tokens, eos_token_ids, temperature=1.0, seed=None):
-        """base.py:148-179"""
-        return self.batch_sample_sync(prompt_token_ids_list, max_tokens, eos_token_ids, temperature, seed)
+    async def batch_sample(self, prompt_token_ids_list, max_tokens, eos_token_ids, temperature=1.0, seed=None, top_k=0, top_p=1.0,
+                           min_p=0.0):
+        """base.py:148-179; top_k, top_p, min_p as `batch_sample_sync` takes them"""
+        return self.batch_sample_sync(prompt_token_ids_list, max_tokens, eos_token_ids, temperature, seed, top_k=top_k, top_p=top_p,
+                                      min_p=min_p)
 
-    async def sample(self, prompt_token_ids, max_tokens, eos_token_ids, temperature=1.0, seed=None):
-        """base.py:110-146"""
-        return self.batch_sample_sync([prompt_token_ids], max_tokens, eos_token_ids, temperature, seed)[0]
+    async def sample(self, prompt_token_ids, max_tokens, eos_token_ids, temperature=1.0, seed=None, top_k=0, top_p=1.0, min_p=0.0):
+        """base.py:110-146; top_k, top_p, min_p as `batch_sample_sync` takes them"""
+        return self.batch_sample_sync([prompt_token_ids], max_tokens, eos_token_ids, temperature, seed, top_k=top_k, top_p=top_p,
+                                      min_p=min_p)[0]
 
 
 def load_model_by_name(name, backend=None, llm_opts=None):

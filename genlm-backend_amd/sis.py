@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from .cache import KVPrefix
+from .engine import check_truncation
 from .fuse import SplitConv1D, split_gemm_all_rows
 from .kv import PACKED_MAX_KEYS, PrefixTable, PromptGroups, SlabKV, SlabRunner, encode_packed, encode_ragged, packed_supported
 from ._lib import MASK_BITS, MASK_NONE
@@ -916,12 +917,18 @@ class DeviceSampler(DeviceSIS):
     i.e. step t of every sequence races against the SAME Exp(1) row - one host-generated row per step, shared by pitch 0.
     Nothing is read back per token: the active count is fetched every `sync_every` steps."""
 
-    def __init__(self, llm, prompts, max_tokens, eos_token_ids, temperature=1.0, seed=None, sync_every=4):
+    def __init__(self, llm, prompts, max_tokens, eos_token_ids, temperature=1.0, seed=None, sync_every=4, top_k=0, top_p=1.0,
+                 min_p=0.0):
+        top_k, top_p, log_min_p = check_truncation(top_k, top_p, min_p)
         super().__init__(llm, len(prompts), [list(p) for p in prompts], max_tokens, eos_id=-1,
                          seed=0 if seed is None else int(seed), rng="philox", use_particle_kv=True, share_kv=False,
                          kv_graph=max_tokens >= 64)  # (a capture costs a few dozen eager steps: long generations only)
         self.sync_every = max(1, int(sync_every))
         self.temperature = float(temperature)
+        # truncation (DESIGN.md §31): the keep set of every step's rows as bit rows, the draw under them; all off: no such call
+        self.truncation = dict(top_k=top_k, top_p=top_p, min_p=float(min_p))
+        self.truncated = top_k > 0 or top_p < 1.0 or log_min_p > float("-inf")
+        self._row_ids = None
         self.eos = torch.tensor(sorted(set(int(t) for t in eos_token_ids)), dtype=torch.int32, device=self.dev)
         self.seeded = seed is not None
         if not self.seeded:  # unseeded: in-kernel Philox keyed from torch's global generator
@@ -937,6 +944,11 @@ class DeviceSampler(DeviceSIS):
             if self.noise_src is None:
                 self.noise_src = eng.noise_rng(self.seed, V)
             kw["noise"] = self.noise_src.rows(1)
+        if self.truncated:  # after the temperature, as the common samplers order them
+            bits = eng.truncate_rows(logits, vocab=V, logit_scale=1.0 / self.temperature, **self.truncation)["bits"]
+            if self._row_ids is None or self._row_ids.numel() != bits.shape[0]:
+                self._row_ids = torch.arange(bits.shape[0], dtype=torch.int32, device=dev)
+            kw.update(mask_kind=MASK_BITS, mask=bits, row_mask_id=self._row_ids)
         _, _, tok = eng.step(logits, vocab=V, row_of=group_of, rng_mode=mode, seed=self.seed, offset=self.t,
                              logit_scale=1.0 / self.temperature, want_lse=False, **kw)
         act = (self.active > 0) & (tok != -2)  # token -2: a failed launch, never a result (raised at the next copy / results())

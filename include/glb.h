@@ -1906,6 +1906,59 @@ int glb_topk_rows(const glb_topk_args *args, void *hip_stream);
 int glb_beam_select(const float *score, const int32_t *alive, const int32_t *cand_token, const float *cand_logp, int64_t n_groups,
                     int32_t width, int32_t k, int32_t *out_parent, int32_t *out_token, float *out_score, void *hip_stream);
 
+/*
+ * Top-k, top-p (nucleus) and min-p truncation: the keep set of every logits row as a bit row.  Keys as
+ * glb_topk_rows takes them: y_j = fl32(x_j * logit_scale), mask row m (GLB_MASK_NONE, raw GLB_MASK_BITS, GLB_MASK_F32),
+ * key_j = fl32(y_j + m_j), -0 equals +0, a key that is not above -inf is never kept.  The row's threshold is
+ * tau = max(tau_k, tau_p, tau_m):
+ *     tau_k   the top_k-th largest key, counted with multiplicity; -inf when top_k is 0 or the row has no more than top_k finite
+ *             keys.  Exact.
+ *     tau_m   fl32(key_max + log_min_p); log_min_p = -inf: off.  The host passes the float32 log(min_p).  Exact.
+ *     tau_p   over the keys at or above tau_k (top-k first, then top-p: the order of the common samplers): with
+ *             w_j = exp(key_j - key_max) and Z_k their sum over key_j >= tau_k, the largest key t of the row with
+ *             sum over key_j >= t of w_j >= top_p * Z_k; top_p = 1: off.  The device's tau_p is the exact answer for some p'
+ *             with |p' - top_p| <= 1e-4.
+ * The keep set is {j : key_j > -inf and key_j >= tau}: every tie at tau is kept (a row may keep more than top_k tokens), and
+ * the row's largest key is always kept.
+ *     out_bits       uint32 [n_rows, out_ld], required: words 0 .. ceil(vocab / 32) - 1 of every row are written - bit j % 32 of
+ *                    word j / 32 is token j, as glb_mask_f32_to_bits writes them, pad bits 0 - and read as raw GLB_MASK_BITS rows
+ *                    by the fused step, glb_score_rows and glb_topk_rows; words beyond are not touched.
+ *     out_threshold  float32 [n_rows], nullable: tau
+ *     out_kept       int32 [n_rows], nullable: the number of kept tokens
+ *     out_logmass    float32 [n_rows], nullable: log(kept mass / mass of all finite keys), within 1e-4
+ * A row without a finite key (a mask id outside [0, n_masks) allows nothing) gives zero bits, kept 0, tau +inf and logmass -inf,
+ * no NaN.  +inf and NaN inputs and magnitudes beyond 2^21 are not supported (no fault; the results are unspecified).
+ * One launch, one workgroup of four waves per row, no workspace; nothing waits inside the launch, nothing synchronises or
+ * allocates; safe under stream capture.  The row is read once for its maximum, three times for tau_k, three times for tau_p
+ * (twice when tau_k was taken: the first pass is shared) and once to write the bits; an option that is off costs no pass.
+ * A row's outputs are a function of that row's inputs alone - a key's mass is a function of the key and the row's maximum,
+ * every sum of counts and masses is an integer sum (round(w * 2^40) per key, hence vocab <= 2^24) - the same bytes for a row
+ * alone or among others, however the rows are cut into calls, run after run.
+ * GLB_EINVAL before any launch: every rule of glb_topk_args but the one on k, and top_k < 0; top_p NaN, <= 0 or > 1; log_min_p NaN
+ * or > 0; out_bits null or not 4-byte aligned; out_ld < ceil(vocab / 32); vocab > 2^24.
+ */
+typedef struct glb_truncate_args {
+  uint32_t struct_size; /* sizeof this block - ABI guard */
+  const void *logits;   /* [n_rows, ld] device */
+  int32_t dtype;        /* GLB_F32 / GLB_BF16 / GLB_F16 */
+  int64_t n_rows, vocab;
+  int64_t ld; /* row pitch in elements, >= vocab */
+  float logit_scale;
+  int32_t mask_kind;
+  const void *mask; /* [n_masks, mask_ld] device: uint32 words or floats */
+  int64_t mask_ld, n_masks;
+  const int32_t *row_mask_id; /* [n_rows] device, nullable: n_masks == 1 ? 0 : identity */
+  int64_t top_k;              /* 0: off */
+  float top_p;                /* (0, 1]; 1: off */
+  float log_min_p;            /* <= 0; -inf: off */
+  uint32_t *out_bits;         /* [n_rows, out_ld] */
+  int64_t out_ld;             /* row pitch in words, >= ceil(vocab / 32) */
+  float *out_threshold;       /* [n_rows] each, nullable */
+  int32_t *out_kept;
+  float *out_logmass;
+} glb_truncate_args;
+int glb_truncate_rows(const glb_truncate_args *args, void *hip_stream);
+
 /* Philox4x32-10 block function, exposed so hosts can reproduce the device draws. */
 void glb_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 
