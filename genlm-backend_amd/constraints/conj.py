@@ -7,15 +7,15 @@ import ctypes as C
 import numpy as np
 
 from .. import _lib
-from .device import _BIT_BANK, _FLOAT_BANK, _Bank, DeviceConstraint
+from .device import DeviceConstraint
 from .lazy import LazyConstraint
+from .numbered import _Numbered
 from .pda import PDAConstraint
 
-_MAX_TUPLES = 1 << 22
 _CHUNK = 1 << 20  # the particles one chunk of glb_conj_number takes at the most
 
 
-class ConstraintProduct(_Bank):
+class ConstraintProduct(_Numbered):
     """The conjunction of `parts`: a token is allowed exactly where every part allows it, and weighs what the weighted parts
     make it weigh together.
 
@@ -46,11 +46,12 @@ class ConstraintProduct(_Bank):
     in part order.  `n_states`, `tuples()`, `stats()` and `check()` synchronise; nothing else does, and nothing allocates
     after the first call of a given size."""
 
+    _distinct, _beyond = "tuples of the parts' states", "ones"
+    _walks = False  # (the parts walk the vocabulary)
+
     def __init__(self, llm_or_engine, parts, max_states=65536, mask_bank_bytes=256 << 20, on_full="error", *, _hash_mask=0):
-        if on_full not in ("error", "evict"):
-            raise ValueError(f'on_full must be "error" or "evict", got {on_full!r}')
-        if isinstance(max_states, bool) or not isinstance(max_states, (int, np.integer)) or not 1 <= max_states <= _MAX_TUPLES:
-            raise ValueError(f"max_states must be an int in [1, {_MAX_TUPLES}], got {max_states!r}")
+        self._check_on_full(on_full)
+        self._check_max_states(max_states)
         parts = list(parts)
         if not 2 <= len(parts) <= _lib.CONJ_MAX_PARTS:
             raise ValueError(f"a product takes 2 to {_lib.CONJ_MAX_PARTS} parts, got {len(parts)}")
@@ -73,47 +74,20 @@ class ConstraintProduct(_Bank):
                     or not torch.equal(p._bytes, first._bytes):
                 raise ValueError(f"part {k}'s vocabulary bytes differ from part 0's")
         self.parts, self.K, self.W = parts, len(parts), (len(parts) + 1) // 2
-        self.max_states, self.mask_bank_bytes, self.on_full = int(max_states), int(mask_bank_bytes), on_full
         self.weighted = any(p.weighted for p in parts)
         self.start_logw = float(sum(p.start_logw for p in parts))
         self.vocab, self.eos_id, self.words, self.n_bytes = first.vocab, first.eos_id, first.words, first.n_bytes
         self._bytes, self._ptr, self._gathered, self._cus = first._bytes, first._ptr, None, None
-        self._kind = kind = _FLOAT_BANK if self.weighted else _BIT_BANK
-        self.row_elems = kind.row_elems(self.vocab)
-        rows = int(getattr(_lib.load(), kind.rows)(self.mask_bank_bytes, self.vocab, self.max_states))
-        if rows < 3:
-            raise ValueError(f"mask_bank_bytes={mask_bank_bytes} holds no state's mask: a row of this vocabulary takes "
-                             f"{self.row_elems * 4} bytes{' (float32 weights: 32 times a bit row)' if self.weighted else ''} "
-                             "and the bank needs at least three")
+        rows = self._size_bank(self.vocab, max_states, mask_bank_bytes, on_full)
         self.eng, self.dev = eng, eng.device
         self._hash_mask = int(_hash_mask)
         self._start = [int(p.states0(1).item()) for p in parts]  # (DeviceConstraint starts at dfa.start, not at 0)
-        new = lambda dtype, *shape: torch.empty(shape, dtype=dtype, device=self.dev)
-        self._slots = 1 << max(1, (2 * self.max_states - 1).bit_length())
-        self._table = new(torch.int64, self._slots * 12 // 8)
+        new = self._allocate(rows)
         self._tuples, self._rep = new(torch.int64, self.max_states, self.W), new(torch.int32, self.max_states)
-        self._status = torch.zeros(_lib.CONJ_STATUS, dtype=torch.int32, device=self.dev)
-        self._counts = self._part_states = self._claim = self._zeros = None
-        self._row_of_state = new(torch.int32, self.max_states)
-        self._counters = torch.zeros(_lib.DFA_COUNTERS, dtype=torch.int32, device=self.dev)
-        self.bank = torch.zeros((rows, self.row_elems), dtype=getattr(torch, kind.dtype), device=self.dev)
-        self._work = torch.zeros((rows, 2), dtype=torch.int32, device=self.dev)
-        self._evicting = on_full == "evict" and self.max_states + 2 > rows
-        self._evict_tables = self._new_evict_tables() if self._evicting else None
+        self._part_states = self._claim = None
         self._call("glb_conj_init", self._block())
 
     # ---- the blocks ----------------------------------------------------------------------------------------------------
-    def _args(self):
-        """The embedded glb_dfa_args: the vocabulary's size, the bank's bookkeeping; nothing of an automaton."""
-        a = _lib.DfaArgs()
-        a.struct_size = C.sizeof(_lib.DfaArgs)
-        a.n_states, a.start, a.eos_id, a.vocab = self.max_states, 0, self.eos_id, self.vocab
-        if not self.weighted:
-            a.bank, a.bank_ld = self.bank.data_ptr(), self.bank.stride(0)
-        a.capacity = self.bank.shape[0]
-        a.row_of_state, a.work, a.counters = self._row_of_state.data_ptr(), self._work.data_ptr(), self._counters.data_ptr()
-        return a
-
     def _block(self, a=None):
         p = _lib.ConjArgs()
         p.struct_size, p.dfa = C.sizeof(_lib.ConjArgs), self._args() if a is None else a
@@ -158,29 +132,15 @@ class ConstraintProduct(_Bank):
         return [self._part_states[k, :n] for k in range(self.K)]
 
     # ---- states --------------------------------------------------------------------------------------------------------
-    def states0(self, n):
-        import torch
-
-        return torch.zeros(n, dtype=torch.int32, device=self.dev)
-
     def advance(self, states, tokens, frm, to, out=None):
         """The states after tokens[i, frm[i] .. to[i]) (int32 [n, ld], unit inner stride), from states[i] (None: state 0);
         -1 once a part is dead, for a state that is none of the states numbered before the call, and for a tuple that found
         no id below `max_states`.  One launch, the parts' own `advance` calls, five launches (glb_conj_unpack,
         glb_conj_number)."""
-        import torch
-
-        if tokens.dtype != torch.int32 or tokens.dim() != 2 or tokens.device != self.dev:
-            raise ValueError("tokens must be an int32 [n, ld] tensor on the engine's device")
-        tokens = tokens.contiguous()
+        tokens, out = self._check_advance_args(tokens, frm, to, out)
         n = tokens.shape[0]
-        if out is None:
-            out = torch.empty(n, dtype=torch.int32, device=self.dev)
         if n == 0:
             return out
-        for t in (frm, to):
-            if t.dtype != torch.int32 or t.shape != (n,) or t.device != self.dev or not t.is_contiguous():
-                raise ValueError("frm / to must be contiguous int32 [n] tensors on the engine's device")
         for part, s in zip(self.parts, self._unpack(states, n)):
             part.advance(s, tokens, frm, to, out=s)
         a = self._args()
@@ -201,8 +161,7 @@ class ConstraintProduct(_Bank):
         out = torch.empty(n, dtype=torch.int32, device=self.dev)
         if n == 0:
             return out
-        if done is not None and (done.dtype != torch.int32 or done.shape != (n,) or not done.is_contiguous() or done.device != self.dev):
-            raise ValueError("done must be a contiguous int32 [n] tensor on the engine's device")
+        self._check_done(done, n)
         rows = [part.mask_rows(s, done=done) for part, s in zip(self.parts, self._unpack(states, n, done, claim=True))]
         a = self._args()
         a.n, a.state_in, a.out_rows = n, self._states(states).data_ptr(), out.data_ptr()
@@ -233,29 +192,14 @@ class ConstraintProduct(_Bank):
         return total
 
     # ---- inspection (every call synchronises) ------------------------------------------------------------------------------
-    @property
-    def n_states(self):
-        """The tuples numbered so far."""
-        return int(self._status[0].item())
-
     def tuples(self):
         """Host list of K-tuples of part state ids, one for every numbered state."""
         halves = np.ascontiguousarray(self._tuples[:self.n_states].cpu().numpy()).view(np.int32).reshape(-1, 2 * self.W)
         return [tuple(int(v) for v in row[:self.K]) for row in halves]
 
-    def stats(self):
-        """`DeviceConstraint.stats()` and "states": the tuples numbered so far (synchronises)."""
-        return dict(super().stats(), states=self.n_states)
-
     def check(self, word=None):
         """Raises when a tuple found no id below `max_states`, what `DeviceConstraint.check` raises for the product's own bank,
         and then whatever every part's `check()` raises.  Always synchronises, `word` given or not."""
-        flags = int(self._status[1].item())
-        if flags & _lib.CONJ_BUG:
-            raise RuntimeError(f"ConstraintProduct: the table held a reference out of range (flags {flags})")
-        if flags & _lib.CONJ_OVERFLOW:
-            raise RuntimeError(f"the particles reached more than max_states={self.max_states} distinct tuples of the parts' states: "
-                               "the ones beyond got no id, and their particles were served the empty mask.  Raise max_states.")
         super().check(word)
         for part in self.parts:
             part.check()

@@ -18,7 +18,8 @@ _FLOAT_BANK = _BankKind("float32", lambda V: (V + 63) // 64 * 64, lambda V: V, _
 
 
 class _Bank:
-    """What every constraint that serves rows of a bank shares (`DeviceConstraint`, `lazy.LazyConstraint`): the vocabulary on
+    """What every constraint that serves rows of a bank shares - `DeviceConstraint`, and through `numbered._Numbered` the three
+    whose states are numbered on the device, `LazyConstraint`, `PDAConstraint` and `ConstraintProduct`: the vocabulary on
     the device, the bank's row ids as the fused step takes them, its counters and what `check()` says of a full bank.  A
     subclass sets `eng`, `dev`, `bank`, `_kind`, `weighted`, `_counters`, `_evicting`, `_evict_tables`, `mask_bank_bytes` and
     `row_elems`."""

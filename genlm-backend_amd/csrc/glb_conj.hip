@@ -1,29 +1,25 @@
 // glb_conj.hip — the conjunction of K constraints served as one (include/glb.h: glb_conj_*).  A state is the
 // tuple of the K part states, W = ceil(K / 2) <= 4 64-bit words, numbered on the device as glb_lazy.hip numbers a set and
-// glb_pda.hip a configuration: enter, count, scan, number and resolve are those files' kernels, stated a third time here (both
-// are left as they are) - but a LANE per particle, not a wave: a lane packs its tuple from the parts' state arrays, hashes
-// it and compares it by itself, where a wave would keep four lanes of 64 busy.  The bank of rows is glb_dfa_bank.hpp's,
-// unchanged; the fill is the combine: a new row is the AND (with weights: the ordered float32 sum, -inf under a cleared bit)
-// of the parts' rows of one particle that holds the state.  Everything read from device memory is range-checked.
+// glb_pda.hip a configuration: count, scan, number and resolve are glb_number.hpp's kernels over this file's `Conj`, whose
+// store_row packs the tuple once more.  Enter is this file's own: a LANE per particle, not a wave - a lane packs its tuple
+// from the parts' state arrays, hashes it and compares it by itself, where a wave would keep four lanes of 64 busy.  The bank
+// of rows is glb_dfa_bank.hpp's, unchanged; the fill is the combine: a new row is the AND (with weights: the ordered float32
+// sum, -inf under a cleared bit) of the parts' rows of one particle that holds the state.  Everything read from device memory
+// is range-checked.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/glb.h"
 #include "glb_common.hpp"
 #include "glb_dfa_bank.hpp"
+#include "glb_number.hpp"
 #include "glb_set.hpp"
 
 namespace {
 
-enum { P_COUNT = 0, P_FLAGS = 1, P_BASE = 2, P_NEXT = 3 };
-constexpr int CONJ_THREADS = 256;  // a particle a lane; count / number: 256 particles a block; the combine: 1024 words or floats
-constexpr int CONJ_WAVES = CONJ_THREADS / 64;
+constexpr int CONJ_THREADS = NUMBER_THREADS;  // enter: a particle a lane; the combine: 1024 words or floats a block
 constexpr int MAX_K = GLB_CONJ_MAX_PARTS, MAX_W = (GLB_CONJ_MAX_PARTS + 1) / 2;
-constexpr int32_t CONJ_MAX_TUPLES = 1 << 22;
 constexpr int64_t CONJ_MAX_N = (int64_t)1 << 30;
-constexpr int32_t NO_PART = 0x7fffffff;
-constexpr uint32_t REF_PART = 0x80000000u;  // the low half of a slot: this bit and a particle index of the chunk, else a numbered id
-constexpr uint32_t REF_TOMB = 0xffffffffu;  // a tuple that found no id below max_states: never equal to anything, probed past
 
 typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -42,10 +38,11 @@ struct Conj {
   unsigned long long *words;  // [slots]; 0: empty
   int32_t *partmin;           // [slots]; the smallest particle index of the chunk that brought the slot's tuple
   uint64_t mask;              // slots - 1
-  uint64_t *tuples;
+  uint64_t *rows;             // [max_states][W]: the numbered tuples
   int32_t *cnt, *status;
   int32_t *part_states;
   int64_t part_ld;
+  static __device__ void store_row(const Conj &c, int64_t id, int64_t base, int64_t k);
 };
 
 // the parts' rows and banks, by value: indexed under full unrolling only, so that they stay in scalar registers
@@ -55,16 +52,6 @@ struct Parts {
   int64_t ld[MAX_K], capacity[MAX_K];
   int32_t weighted[MAX_K];
 };
-
-__device__ inline int32_t flags_now(const int32_t *status) {
-  return __hip_atomic_load(&status[P_FLAGS], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// the tuples numbered, never more than the rows of `tuples`
-__device__ inline int32_t numbered(const Conj &c, int word) {
-  const int32_t v = c.status[word];
-  return v < 0 ? 0 : v > c.max_states ? c.max_states : v;
-}
 
 // the tuple of particle i, packed; false where a part is dead
 __device__ inline bool pack(const Conj &c, int64_t i, uint64_t t[MAX_W]) {
@@ -101,6 +88,15 @@ __device__ inline bool same(const Conj &c, const uint64_t a[MAX_W], const uint64
   return eq;
 }
 
+// the tuple of a winner (glb_number.hpp, number_kernel) packed once more into `rows`
+__device__ inline void Conj::store_row(const Conj &c, int64_t id, int64_t base, int64_t k) {
+  uint64_t t[MAX_W];
+  pack(c, base + k, t);
+#pragma unroll
+  for (int j = 0; j < MAX_W; ++j)
+    if (j < c.W) c.rows[id * c.W + j] = t[j];
+}
+
 // ---- init ------------------------------------------------------------------------------------------------------------------------
 __global__ void conj_clear_kernel(Conj c, int32_t *rep) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -126,12 +122,12 @@ __global__ void conj_seed_kernel(Conj c, Start start) {
     if (k < c.K) t[k >> 1] |= (uint64_t)(uint32_t)start.part[k] << (32 * (k & 1));
 #pragma unroll
   for (int j = 0; j < MAX_W; ++j)
-    if (j < c.W) c.tuples[j] = t[j];
+    if (j < c.W) c.rows[j] = t[j];
   uint64_t slot;
   uint32_t high;
   tuple_key(c, t, slot, high);
   c.words[slot] = (unsigned long long)high << 32;  // (id 0; the table is empty)
-  c.status[P_COUNT] = c.status[P_BASE] = c.status[P_NEXT] = 1;
+  c.status[N_COUNT] = c.status[N_BASE] = c.status[N_NEXT] = 1;
 }
 
 // ---- unpack: a lane a particle, one gather of W words, K stores ------------------------------------------------------------------------
@@ -140,10 +136,10 @@ __global__ __launch_bounds__(CONJ_THREADS) void conj_unpack_kernel(Conj c, int64
   const int64_t i = (int64_t)blockIdx.x * CONJ_THREADS + threadIdx.x;
   if (i >= n) return;
   const int32_t s = state_in ? state_in[i] : 0;
-  const bool known = s >= 0 && s < numbered(c, P_COUNT);
+  const bool known = s >= 0 && s < numbered(c, N_COUNT);
   uint64_t t[MAX_W];
 #pragma unroll
-  for (int j = 0; j < MAX_W; ++j) t[j] = known && j < c.W ? c.tuples[(int64_t)s * c.W + j] : 0ull;
+  for (int j = 0; j < MAX_W; ++j) t[j] = known && j < c.W ? c.rows[(int64_t)s * c.W + j] : 0ull;
 #pragma unroll
   for (int k = 0; k < MAX_K; ++k)
     if (k < c.K) c.part_states[(int64_t)k * c.part_ld + i] = known ? (int32_t)(uint32_t)(t[k >> 1] >> (32 * (k & 1))) : -1;
@@ -154,18 +150,19 @@ __global__ __launch_bounds__(CONJ_THREADS) void conj_unpack_kernel(Conj c, int64
   }
 }
 
-// ---- number: five launches over the particles [base, base + n) of a call, particle base + k the chunk's k -----------------------------
+// ---- number: five launches over the particles [base, base + n) of a call, particle base + k the chunk's k: enter, then the
+// four of glb_number.hpp
 // enter, a lane per particle: its tuple looked up; state_out = -1 where a part is dead, the id where an earlier call or chunk
-// numbered the tuple, else -2 - slot until conj_resolve_kernel.  A new tuple's slot is claimed by one compare-and-swap of the
+// numbered the tuple, else -2 - slot until number_resolve_kernel.  A new tuple's slot is claimed by one compare-and-swap of the
 // whole word; no lane waits on another's stores.  A chunk that begins with every id taken claims nothing: a tuple not found
 // is -1 and the overflow
 __global__ __launch_bounds__(CONJ_THREADS) void conj_enter_kernel(Conj c, int64_t base, int64_t n, int32_t *state_out) {
-  const bool full = c.status[P_COUNT] >= c.max_states;  // (written by the chunk before, not by this one)
+  const bool full = c.status[N_COUNT] >= c.max_states;  // (written by the chunk before, not by this one)
   const int64_t stride = (int64_t)gridDim.x * CONJ_THREADS;
   for (int64_t k = (int64_t)blockIdx.x * CONJ_THREADS + threadIdx.x; k < n; k += stride) {
     uint64_t target[MAX_W];
     int32_t out = -1;
-    if (pack(c, base + k, target) && !(flags_now(c.status) & GLB_CONJ_BUG)) {
+    if (pack(c, base + k, target) && !(flags_now(c.status) & NUMBER_BUG)) {
       uint64_t slot;
       uint32_t high;
       tuple_key(c, target, slot, high);
@@ -192,11 +189,11 @@ __global__ __launch_bounds__(CONJ_THREADS) void conj_enter_kernel(Conj c, int64_
             if ((int64_t)(ref & 0x7fffffffu) < n) there = pack(c, base + (int64_t)(ref & 0x7fffffffu), other);
           } else if ((int32_t)ref < c.max_states) {
 #pragma unroll
-            for (int j = 0; j < MAX_W; ++j) other[j] = j < c.W ? c.tuples[(int64_t)ref * c.W + j] : 0ull;
+            for (int j = 0; j < MAX_W; ++j) other[j] = j < c.W ? c.rows[(int64_t)ref * c.W + j] : 0ull;
             there = true;
           }
           if (!there) {
-            atomicOr(&c.status[P_FLAGS], GLB_CONJ_BUG);
+            atomicOr(&c.status[N_FLAGS], NUMBER_BUG);
             settled = true;
             break;
           }
@@ -211,101 +208,13 @@ __global__ __launch_bounds__(CONJ_THREADS) void conj_enter_kernel(Conj c, int64_
             break;
           }
         }
-        if ((probe & 31) == 31 && (flags_now(c.status) & GLB_CONJ_BUG)) settled = true;
+        if ((probe & 31) == 31 && (flags_now(c.status) & NUMBER_BUG)) settled = true;
       }
       // not found and nothing claimed: every id is taken (or, a table walked all round, every slot)
-      if (!settled) atomicOr(&c.status[P_FLAGS], GLB_CONJ_OVERFLOW);
+      if (!settled) atomicOr(&c.status[N_FLAGS], NUMBER_OVERFLOW);
     }
     state_out[base + k] = out;
   }
-}
-
-// whether particle k of the chunk is the one that numbers its tuple: the smallest to have ended in it
-__device__ inline bool wins(const Conj &c, int32_t code, int64_t k, int64_t &slot) {
-  slot = -2 - (int64_t)code;
-  return code <= -2 && (uint64_t)slot <= c.mask && c.partmin[slot] == (int32_t)k;
-}
-
-// cnt[b]: the new tuples that the particles [256 b, 256 b + 256) of the chunk number
-__global__ __launch_bounds__(CONJ_THREADS) void conj_count_kernel(Conj c, int64_t base, int64_t n, const int32_t *state_out) {
-  const int64_t nb = (n + CONJ_THREADS - 1) / CONJ_THREADS;
-  for (int64_t b = blockIdx.x; b < nb; b += gridDim.x) {
-    const int64_t k = b * CONJ_THREADS + threadIdx.x;
-    int64_t slot;
-    const bool w = k < n && wins(c, state_out[base + k], k, slot);
-    const int total = __syncthreads_count(w);
-    if (threadIdx.x == 0) c.cnt[b] = total;
-  }
-}
-
-// one block: cnt becomes its exclusive prefix sums; P_NEXT = the tuples after this chunk, at most max_states - past it the
-// overflow flag
-__global__ __launch_bounds__(SCAN_THREADS) void conj_scan_kernel(Conj c, int64_t n) {
-  __shared__ int32_t wave_sum[SCAN_THREADS / 64];
-  __shared__ int32_t carry;
-  const int32_t total = scan_exclusive(c.cnt, (int32_t)((n + CONJ_THREADS - 1) / CONJ_THREADS), wave_sum, &carry);
-  if (threadIdx.x == 0) {
-    const int64_t next = (int64_t)numbered(c, P_COUNT) + total;  // (total <= n <= 2^30)
-    if (next > c.max_states) atomicOr(&c.status[P_FLAGS], GLB_CONJ_OVERFLOW);
-    c.status[P_NEXT] = (int32_t)(next > c.max_states ? c.max_states : next);
-  }
-}
-
-// the winners number their tuples: id = P_COUNT + cnt[b] + the winners of the block at smaller particles; the tuple packed
-// once more into `tuples`, and the slot's reference turned into the id - or, with no id left, into the tombstone
-__global__ __launch_bounds__(CONJ_THREADS) void conj_number_kernel(Conj c, int64_t base, int64_t n, const int32_t *state_out) {
-  __shared__ int32_t wave_n[CONJ_WAVES];
-  const int32_t count = numbered(c, P_COUNT);
-  const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
-  const int64_t nb = (n + CONJ_THREADS - 1) / CONJ_THREADS;
-  for (int64_t b = blockIdx.x; b < nb; b += gridDim.x) {
-    const int64_t k = b * CONJ_THREADS + threadIdx.x;
-    int64_t slot;
-    const bool w = k < n && wins(c, state_out[base + k], k, slot);
-    const unsigned long long ballot = __ballot(w);
-    if (lane == 0) wave_n[wave] = __popcll(ballot);
-    __syncthreads();
-    int32_t rank = __popcll(ballot & ((1ull << lane) - 1ull));
-    for (int v = 0; v < wave; ++v) rank += wave_n[v];
-    if (w) {
-      const int64_t id = (int64_t)count + c.cnt[b] + rank;
-      const unsigned long long high = c.words[slot] & 0xffffffff00000000ull;
-      if (id >= 0 && id < c.max_states) {
-        uint64_t t[MAX_W];
-        pack(c, base + k, t);
-#pragma unroll
-        for (int j = 0; j < MAX_W; ++j)
-          if (j < c.W) c.tuples[id * c.W + j] = t[j];
-        c.words[slot] = high | (unsigned long long)id;
-      } else {
-        c.words[slot] = high | REF_TOMB;
-      }
-    }
-    __syncthreads();
-  }
-}
-
-// state_out of the chunk: -2 - slot becomes the id its slot was given, -1 behind a tombstone.  The chunk's last launch: the
-// count moves on (no launch of the chunk reads it from here), and with the call's last chunk the ids a caller may name
-__global__ void conj_resolve_kernel(Conj c, int64_t base, int64_t n, int32_t *state_out, int last) {
-  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (k == 0) {
-    c.status[P_COUNT] = c.status[P_NEXT];
-    if (last) c.status[P_BASE] = c.status[P_NEXT];
-  }
-  if (k >= n) return;
-  const int32_t code = state_out[base + k];
-  if (code > -2) return;
-  const int64_t slot = -2 - (int64_t)code;
-  int32_t id = -1;
-  bool bug = true;
-  if ((uint64_t)slot <= c.mask) {
-    const uint32_t ref = (uint32_t)c.words[slot];
-    if (ref == REF_TOMB) bug = false;
-    else if (!(ref & REF_PART) && (int32_t)ref < c.max_states) id = (int32_t)ref, bug = false;
-  }
-  if (bug) atomicOr(&c.status[P_FLAGS], GLB_CONJ_BUG);
-  state_out[base + k] = id;
 }
 
 // ---- the combine: the rows of the work entries, from the parts' rows of one particle that holds the state -----------------------------
@@ -431,30 +340,19 @@ __global__ void conj_ids_kernel(Parts p, int32_t K, int32_t max_states, int64_t 
 }
 
 // ---- the host side -----------------------------------------------------------------------------------------------------------------
-constexpr int NEED_N = 1, NEED_BANK = 2, NEED_STATES = 4;
+constexpr int NEED_STATES = 8;  // (beside glb_number.hpp's NEED_N and NEED_BANK, both checked here: a float bank, a bound on n)
 
 int conj_check(const glb_conj_args *a, const char *what, int need) {
-  if (const int rc = glb::block_ok(a, what, "glb_conj_args")) return rc;
+  if (const int rc = number_check(a, what, "glb_conj_args", 0)) return rc;
   const glb_dfa_args *d = &a->dfa;
-  if (const int rc = glb::block_ok(d, what, "glb_dfa_args")) return rc;
   if (a->n_parts < 2 || a->n_parts > GLB_CONJ_MAX_PARTS)
     return glb::api_fail(GLB_EINVAL, "%s: n_parts %d outside [2, %d]", what, a->n_parts, GLB_CONJ_MAX_PARTS);
   if (a->n_words != (a->n_parts + 1) / 2)
     return glb::api_fail(GLB_EINVAL, "%s: n_words %d is not ceil(n_parts / 2) = %d", what, a->n_words, (a->n_parts + 1) / 2);
-  if (a->max_states < 1 || a->max_states > CONJ_MAX_TUPLES)
-    return glb::api_fail(GLB_EINVAL, "%s: max_states %d outside [1, %d]", what, a->max_states, CONJ_MAX_TUPLES);
-  if (a->table_slots < 2 * (int64_t)a->max_states || a->table_slots > ((int64_t)1 << 30) || (a->table_slots & (a->table_slots - 1)))
-    return glb::api_fail(GLB_EINVAL, "%s: table_slots %lld is not a power of two in [2 max_states = %lld, 2^30]", what,
-                         (long long)a->table_slots, 2 * (long long)a->max_states);
-  if (!a->table) return glb::api_fail(GLB_EINVAL, "%s: table is null", what);
-  if ((uintptr_t)a->table & 7) return glb::api_fail(GLB_EINVAL, "%s: table is not aligned to 8 bytes", what);
   if (!a->tuples) return glb::api_fail(GLB_EINVAL, "%s: tuples is null", what);
   if ((uintptr_t)a->tuples & 7) return glb::api_fail(GLB_EINVAL, "%s: tuples is not aligned to 8 bytes", what);
-  if (!a->status) return glb::api_fail(GLB_EINVAL, "%s: status is null", what);
   if (!a->rep) return glb::api_fail(GLB_EINVAL, "%s: rep is null", what);
-  const int tables = !!a->row_state + !!a->row_stamp + !!a->claimants + !!a->victims + !!a->ecounters + !!a->epoch;
-  if (tables != 0 && tables != 6) return glb::api_fail(GLB_EINVAL, "%s: the eviction tables are given in part (%d of 6)", what, tables);
-  if (d->vocab <= 0 || d->vocab > 0x7fffff00ll) return glb::api_fail(GLB_EINVAL, "%s: vocab %lld", what, (long long)d->vocab);
+  const bool tables = a->epoch != nullptr;  // (all six or none)
   if (need & NEED_BANK) {
     const int64_t ld = a->wbank ? a->wbank_ld : d->bank_ld, elems = a->wbank ? d->vocab : (d->vocab + 31) / 32;
     if (ld < elems)
@@ -487,23 +385,6 @@ Parts parts_of(const glb_conj_args *a) {
     p.ld[k] = a->part_bank_ld[k], p.capacity[k] = a->part_capacity[k], p.weighted[k] = a->part_weighted[k];
   }
   return p;
-}
-
-// blocks for a grid that strides over its work: four to a CU, and no more than the work has
-int conj_grid(int64_t items, int per_block, unsigned *blocks) {
-  static std::atomic<int> cus_of_device{0};  // (one kind of device a process)
-  int cus = cus_of_device.load(std::memory_order_relaxed);
-  if (cus <= 0) {
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (e != hipSuccess) return glb::api_hip_fail(e, "conj: the device's CU count");
-    if (cus <= 0) cus = 256;
-    cus_of_device.store(cus, std::memory_order_relaxed);
-  }
-  const int64_t need = (items + per_block - 1) / per_block, most = (int64_t)cus * 4;
-  *blocks = (unsigned)(need < most ? (need > 0 ? need : 1) : most);
-  return GLB_OK;
 }
 
 template <bool FLOAT>
@@ -593,12 +474,9 @@ int glb_conj_number(const glb_conj_args *a, void *stream) {
   for (int64_t base = 0; base < d->n; base += a->cand_rows) {
     const int64_t n = d->n - base < a->cand_rows ? d->n - base : a->cand_rows;
     unsigned blocks = 0;
-    if (const int rc = conj_grid(n, CONJ_THREADS, &blocks)) return rc;
+    if (const int rc = number_grid("conj: the device's CU count", n, CONJ_THREADS, &blocks)) return rc;
     hipLaunchKernelGGL(conj_enter_kernel, dim3(blocks), dim3(CONJ_THREADS), 0, st, c, base, n, d->state_out);
-    hipLaunchKernelGGL(conj_count_kernel, dim3(blocks), dim3(CONJ_THREADS), 0, st, c, base, n, (const int32_t *)d->state_out);
-    hipLaunchKernelGGL(conj_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, st, c, n);
-    hipLaunchKernelGGL(conj_number_kernel, dim3(blocks), dim3(CONJ_THREADS), 0, st, c, base, n, (const int32_t *)d->state_out);
-    hipLaunchKernelGGL(conj_resolve_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, st, c, base, n, d->state_out, base + n >= d->n ? 1 : 0);
+    number_launches(c, blocks, base, n, d->state_out, base + n >= d->n, st);
   }
   return glb::launched("conj_number launch");
 }

@@ -1,31 +1,24 @@
 // glb_lazy.hip — a byte NFA served as a constraint, its subset states made when a particle reaches them (include/glb.h:
 // glb_lazy_*).  A state is a set of important NFA states, W 64-bit words: a wave holds one, a lane a word
 // (glb_set.hpp, shared with glb_nfa_det.hip).  glb_lazy_advance walks every particle's tokens from its state's set, byte by
-// byte, in registers; only the set a particle ends in is looked up in the table of §23 - a slot one word, 31 bits of hash and
-// a reference: the particle of this chunk that claimed it (its row of `cand`, written by the launch before the one that
-// probes: no wave waits for another's stores) or the id of a numbered set (its row of `sets`).  The smallest particle index
-// to end in a new set numbers it, so ids, sets and accepting bits do not depend on the order the atomics take.  The bank of
-// rows is glb_dfa_bank.hpp's, unchanged: only the fill is new - it walks every token from sets[s] where glb_dfa.hip follows
-// delta.  Everything read from device memory is range-checked.
+// byte, in registers; only the set a particle ends in is looked up and numbered, by glb_number.hpp's kernels: enter (a wave per
+// particle), count, scan, number and resolve, over this file's `Lazy`, whose store_row copies the set and derives its
+// accepting bit.  The bank of rows is glb_dfa_bank.hpp's, unchanged: only the fill is new - it walks every token from sets[s]
+// where glb_dfa.hip follows delta.  Everything read from device memory is range-checked.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/glb.h"
 #include "glb_common.hpp"
 #include "glb_dfa_bank.hpp"
+#include "glb_number.hpp"
 #include "glb_set.hpp"
 
 namespace {
 
-enum { L_COUNT = 0, L_FLAGS = 1, L_BASE = 2, L_NEXT = 3 };
-constexpr int LAZY_THREADS = 256;  // four waves, a particle each; count / number: 256 particles a block
-constexpr int LAZY_WAVES = LAZY_THREADS / 64;
-constexpr int32_t LAZY_MAX_STATES = 1 << 22;
+constexpr int LAZY_THREADS = NUMBER_THREADS;  // the walk: four waves, a particle each, as number_enter_wave_kernel has them
+constexpr int LAZY_WAVES = NUMBER_WAVES;
 constexpr int32_t LAZY_MAX_NFA_STATES = 1 << 24;
-constexpr int32_t NO_PART = 0x7fffffff;
-constexpr int32_t PENDING = INT32_MIN;    // state_out between walk and enter: the particle's end set lies in its row of `cand`
-constexpr uint32_t REF_PART = 0x80000000u;  // the low half of a slot: this bit and a particle index of the chunk, else a numbered id
-constexpr uint32_t REF_TOMB = 0xffffffffu;  // a set that found no id below max_states: never equal to anything, probed past
 
 struct Lazy {
   const uint8_t *bytes;
@@ -41,20 +34,11 @@ struct Lazy {
   unsigned long long *words;  // [slots]; 0: empty
   int32_t *partmin;           // [slots]; the smallest particle index of the chunk that brought the slot's set
   uint64_t mask;              // slots - 1
-  uint64_t *cand, *sets;
+  uint64_t *cand, *rows;      // rows [max_states][W]: the numbered sets
   uint8_t *accepting_out;
   int32_t *cnt, *status;
+  static __device__ void store_row(const Lazy &p, int64_t id, int64_t base, int64_t k);
 };
-
-__device__ inline int32_t flags_now(const int32_t *status) {
-  return __hip_atomic_load(&status[L_FLAGS], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// the states numbered, never more than the rows of `sets`
-__device__ inline int32_t numbered(const Lazy &p, int word) {
-  const int32_t c = p.status[word];
-  return c < 0 ? 0 : c > p.max_states ? p.max_states : c;
-}
 
 // whether arc a reads `byte`, and then its target where that is a state of the automaton (else -1)
 __device__ inline int32_t arc_target(const Lazy &p, int32_t a, int byte) {
@@ -139,7 +123,7 @@ __global__ void lazy_clear_kernel(Lazy p) {
 __global__ __launch_bounds__(64) void lazy_seed_kernel(Lazy p, int32_t start) {
   const int lane = (int)threadIdx.x;
   const uint64_t word = lane < p.W ? p.eclose[(int64_t)start * p.W + lane] : 0ull;
-  if (lane < p.W) p.sets[lane] = word;
+  if (lane < p.W) p.rows[lane] = word;
   const bool acc = __any(lane < p.W && (word & p.acc_mask[lane < p.W ? lane : 0]) != 0), some = __any(word != 0);
   uint64_t slot;
   uint32_t high;
@@ -147,18 +131,19 @@ __global__ __launch_bounds__(64) void lazy_seed_kernel(Lazy p, int32_t start) {
   if (lane == 0) {
     p.accepting_out[0] = acc ? 1 : 0;
     if (some) p.words[slot] = (unsigned long long)high << 32;  // (id 0; the table is empty)
-    p.status[L_COUNT] = p.status[L_BASE] = p.status[L_NEXT] = 1;
+    p.status[N_COUNT] = p.status[N_BASE] = p.status[N_NEXT] = 1;
   }
 }
 
-// ---- advance: six launches over the particles [base, base + n) of a call, particle base + k owning row k of `cand` ---------------
+// ---- advance: six launches over the particles [base, base + n) of a call, particle base + k owning row k of `cand`: the walk,
+// then the five of glb_number.hpp
 // walk, a wave per particle: the tokens of its range from its state's set, in registers; state_out = -1 (dead), the state
 // itself (an empty range) or PENDING with the end set in `cand`
 __global__ __launch_bounds__(LAZY_THREADS) void lazy_walk_kernel(Lazy p, int64_t base, int64_t n, const int32_t *tokens, int64_t ld,
                                                                 const int32_t *from, const int32_t *to, const int32_t *state_in,
                                                                 int32_t *state_out) {
   const int lane = (int)threadIdx.x & 63;
-  const int32_t known = numbered(p, L_BASE);
+  const int32_t known = numbered(p, N_BASE);
   const int64_t waves = (int64_t)gridDim.x * LAZY_WAVES;
   for (int64_t k = (int64_t)blockIdx.x * LAZY_WAVES + (threadIdx.x >> 6); k < n; k += waves) {
     const int64_t i = base + k;
@@ -169,7 +154,7 @@ __global__ __launch_bounds__(LAZY_THREADS) void lazy_walk_kernel(Lazy p, int64_t
       if (f == t) {
         code = s;
       } else {
-        uint64_t set = lane < p.W ? p.sets[(int64_t)s * p.W + lane] : 0ull;
+        uint64_t set = lane < p.W ? p.rows[(int64_t)s * p.W + lane] : 0ull;
         bool alive = __any(set != 0);
         for (int64_t j = f; j < t && alive; ++j) {
           set = wave_token(p, set, tokens[i * ld + j], lane);
@@ -185,160 +170,16 @@ __global__ __launch_bounds__(LAZY_THREADS) void lazy_walk_kernel(Lazy p, int64_t
   }
 }
 
-// enter, a wave per particle that is PENDING: its end set looked up; state_out = the id where an earlier call or chunk
-// numbered it, else -2 - slot until lazy_resolve_kernel.  A new set's slot is claimed by one compare-and-swap of the whole word.
-// A chunk that begins with every id taken claims nothing: a set not found is -1 and the overflow
-__global__ __launch_bounds__(LAZY_THREADS) void lazy_enter_kernel(Lazy p, int64_t base, int64_t n, int32_t *state_out) {
-  const int lane = (int)threadIdx.x & 63;
-  const bool full = p.status[L_COUNT] >= p.max_states;  // (written by the chunk before, not by this one)
-  const int64_t waves = (int64_t)gridDim.x * LAZY_WAVES;
-  for (int64_t k = (int64_t)blockIdx.x * LAZY_WAVES + (threadIdx.x >> 6); k < n; k += waves) {
-    if (state_out[base + k] != PENDING) continue;  // (a whole wave)
-    if (flags_now(p.status) & GLB_LAZY_BUG) break;
-    const uint64_t target = lane < p.W ? p.cand[k * p.W + lane] : 0ull;
-    uint64_t slot;
-    uint32_t high;
-    set_key(p.hash_mask, p.mask, target, lane, slot, high);
-    const unsigned long long claim = ((unsigned long long)high << 32) | REF_PART | (uint32_t)k;
-    int32_t out = -1;
-    bool settled = false;
-    for (uint64_t probe = 0; probe <= p.mask && !settled; ++probe, slot = (slot + 1) & p.mask) {
-      unsigned long long cur = word_now(&p.words[slot]);  // (one address: the same in every lane)
-      if (cur == 0ull) {
-        if (full) break;
-        unsigned long long old = 0ull;
-        if (lane == 0) old = atomicCAS(&p.words[slot], 0ull, claim);
-        old = bcast64(old, 0);
-        if (old == 0ull) {  // this wave's: a new set
-          if (lane == 0) atomicMin(&p.partmin[slot], (int32_t)k);
-          out = -2 - (int32_t)slot;
-          settled = true;
-          break;
-        }
-        cur = old;
-      }
-      const uint32_t ref = (uint32_t)cur;
-      if ((uint32_t)(cur >> 32) == high && ref != REF_TOMB) {
-        const uint64_t *row = nullptr;  // the set behind the reference
-        if (ref & REF_PART) {
-          if ((int64_t)(ref & 0x7fffffffu) < n) row = p.cand + (int64_t)(ref & 0x7fffffffu) * p.W;
-        } else if ((int32_t)ref < p.max_states) {
-          row = p.sets + (int64_t)ref * p.W;
-        }
-        if (!row) {
-          if (lane == 0) atomicOr(&p.status[L_FLAGS], GLB_LAZY_BUG);
-          settled = true;
-          break;
-        }
-        const uint64_t other = lane < p.W ? row[lane] : 0ull;
-        if (!__any(other != target)) {
-          if (ref & REF_PART) {
-            if (lane == 0) atomicMin(&p.partmin[slot], (int32_t)k);
-            out = -2 - (int32_t)slot;
-          } else {
-            out = (int32_t)ref;
-          }
-          settled = true;
-          break;
-        }
-      }
-      if ((probe & 31) == 31 && (flags_now(p.status) & GLB_LAZY_BUG)) settled = true;
-    }
-    // not found and nothing claimed: every id is taken (or, a table walked all round, every slot)
-    if (!settled && lane == 0) atomicOr(&p.status[L_FLAGS], GLB_LAZY_OVERFLOW);
-    if (lane == 0) state_out[base + k] = out;
+// the set of a winner (glb_number.hpp, number_kernel) copied from `cand`, and its accepting bit
+__device__ inline void Lazy::store_row(const Lazy &p, int64_t id, int64_t, int64_t k) {
+  const uint64_t *row = p.cand + k * p.W;
+  bool acc = false;
+  for (int j = 0; j < p.W; ++j) {
+    const uint64_t word = row[j];
+    p.rows[id * p.W + j] = word;
+    acc = acc || (word & p.acc_mask[j]) != 0;
   }
-}
-
-// whether particle k of the chunk is the one that numbers its end set: the smallest to have ended in it
-__device__ inline bool wins(const Lazy &p, int32_t code, int64_t k, int64_t &slot) {
-  slot = -2 - (int64_t)code;
-  return code <= -2 && (uint64_t)slot <= p.mask && p.partmin[slot] == (int32_t)k;
-}
-
-// cnt[b]: the new sets that the particles [256 b, 256 b + 256) of the chunk number
-__global__ __launch_bounds__(LAZY_THREADS) void lazy_count_kernel(Lazy p, int64_t base, int64_t n, const int32_t *state_out) {
-  const int64_t nb = (n + LAZY_THREADS - 1) / LAZY_THREADS;
-  for (int64_t b = blockIdx.x; b < nb; b += gridDim.x) {
-    const int64_t k = b * LAZY_THREADS + threadIdx.x;
-    int64_t slot;
-    const bool w = k < n && wins(p, state_out[base + k], k, slot);
-    const int c = __syncthreads_count(w);
-    if (threadIdx.x == 0) p.cnt[b] = c;
-  }
-}
-
-// one block: cnt becomes its exclusive prefix sums; L_NEXT = the states after this chunk, at most max_states - past it the
-// overflow flag
-__global__ __launch_bounds__(SCAN_THREADS) void lazy_scan_kernel(Lazy p, int64_t n) {
-  __shared__ int32_t wave_sum[SCAN_THREADS / 64];
-  __shared__ int32_t carry;
-  const int32_t total = scan_exclusive(p.cnt, (int32_t)((n + LAZY_THREADS - 1) / LAZY_THREADS), wave_sum, &carry);
-  if (threadIdx.x == 0) {
-    const int64_t next = (int64_t)numbered(p, L_COUNT) + total;  // (total <= n <= 2^30)
-    if (next > p.max_states) atomicOr(&p.status[L_FLAGS], GLB_LAZY_OVERFLOW);
-    p.status[L_NEXT] = (int32_t)(next > p.max_states ? p.max_states : next);
-  }
-}
-
-// the winners number their sets: id = L_COUNT + cnt[b] + the winners of the block at smaller particles; the set copied from
-// `cand`, its accepting bit, and the slot's reference turned into the id - or, with no id left, into the tombstone
-__global__ __launch_bounds__(LAZY_THREADS) void lazy_number_kernel(Lazy p, int64_t base, int64_t n, const int32_t *state_out) {
-  __shared__ int32_t wave_n[LAZY_WAVES];
-  const int32_t count = numbered(p, L_COUNT);
-  const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
-  const int64_t nb = (n + LAZY_THREADS - 1) / LAZY_THREADS;
-  for (int64_t b = blockIdx.x; b < nb; b += gridDim.x) {
-    const int64_t k = b * LAZY_THREADS + threadIdx.x;
-    int64_t slot;
-    const bool w = k < n && wins(p, state_out[base + k], k, slot);
-    const unsigned long long ballot = __ballot(w);
-    if (lane == 0) wave_n[wave] = __popcll(ballot);
-    __syncthreads();
-    int32_t rank = __popcll(ballot & ((1ull << lane) - 1ull));
-    for (int v = 0; v < wave; ++v) rank += wave_n[v];
-    if (w) {
-      const int64_t id = (int64_t)count + p.cnt[b] + rank;
-      const unsigned long long high = p.words[slot] & 0xffffffff00000000ull;
-      if (id >= 0 && id < p.max_states) {
-        const uint64_t *row = p.cand + k * p.W;
-        bool acc = false;
-        for (int j = 0; j < p.W; ++j) {
-          const uint64_t word = row[j];
-          p.sets[id * p.W + j] = word;
-          acc = acc || (word & p.acc_mask[j]) != 0;
-        }
-        p.accepting_out[id] = acc ? 1 : 0;
-        p.words[slot] = high | (unsigned long long)id;
-      } else {
-        p.words[slot] = high | REF_TOMB;
-      }
-    }
-    __syncthreads();
-  }
-}
-
-// state_out of the chunk: -2 - slot becomes the id its slot was given, -1 behind a tombstone.  The chunk's last launch: the
-// count moves on (no launch of the chunk reads it from here), and with the call's last chunk the states a caller may name
-__global__ void lazy_resolve_kernel(Lazy p, int64_t base, int64_t n, int32_t *state_out, int last) {
-  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (k == 0) {
-    p.status[L_COUNT] = p.status[L_NEXT];
-    if (last) p.status[L_BASE] = p.status[L_NEXT];
-  }
-  if (k >= n) return;
-  const int32_t code = state_out[base + k];
-  if (code > -2) return;
-  const int64_t slot = -2 - (int64_t)code;
-  int32_t id = -1;
-  bool bug = true;
-  if ((uint64_t)slot <= p.mask) {
-    const uint32_t ref = (uint32_t)p.words[slot];
-    if (ref == REF_TOMB) bug = false;
-    else if (!(ref & REF_PART) && (int32_t)ref < p.max_states) id = (int32_t)ref, bug = false;
-  }
-  if (bug) atomicOr(&p.status[L_FLAGS], GLB_LAZY_BUG);
-  state_out[base + k] = id;
+  p.accepting_out[id] = acc ? 1 : 0;
 }
 
 // ---- the fill: the rows of the work entries, every token walked from sets[s] ----------------------------------------------------
@@ -362,7 +203,7 @@ __global__ __launch_bounds__(FILL_THREADS) void lazy_fill_lane_kernel(Lazy p, in
   const int64_t t = (int64_t)blockIdx.x * FILL_THREADS + threadIdx.x;
   const int64_t w0 = (t >> 6) * 2;
   if (w0 >= words) return;  // (a whole wave past the last word: the ballot wants every lane of the others)
-  const int32_t known = numbered(p, L_COUNT);
+  const int32_t known = numbered(p, N_COUNT);
   for (int32_t e = range[0] + (int32_t)blockIdx.y; e < range[1]; e += (int32_t)gridDim.y) {
     const int32_t s = work[2 * (int64_t)e], r = work[2 * (int64_t)e + 1];
     if (s < 0 || s >= p.max_states || r < 2 || r >= capacity) continue;  // (uniform over the block)
@@ -370,7 +211,7 @@ __global__ __launch_bounds__(FILL_THREADS) void lazy_fill_lane_kernel(Lazy p, in
       if (blockIdx.x == 0 && threadIdx.x == 0) unclaim(row_of_state, row_state, s, r);
       continue;
     }
-    const uint64_t set = p.sets[s];
+    const uint64_t set = p.rows[s];
     bool bit = false;
     if (t < p.vocab) bit = t == p.eos_id ? p.accepting_out[s] != 0 : lane_token(p, set, t) != 0;
     const uint64_t b = __ballot(bit);
@@ -396,7 +237,7 @@ __global__ __launch_bounds__(FILL_THREADS) void lazy_fill_wave_kernel(Lazy p, in
   const int64_t wi = blockIdx.x;
   if (wi >= words) return;  // (uniform)
   const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
-  const int32_t known = numbered(p, L_COUNT);
+  const int32_t known = numbered(p, N_COUNT);
   for (int32_t e = range[0] + (int32_t)blockIdx.y; e < range[1]; e += (int32_t)gridDim.y) {
     const int32_t s = work[2 * (int64_t)e], r = work[2 * (int64_t)e + 1];
     if (s < 0 || s >= p.max_states || r < 2 || r >= capacity) continue;  // (uniform over the block)
@@ -404,7 +245,7 @@ __global__ __launch_bounds__(FILL_THREADS) void lazy_fill_wave_kernel(Lazy p, in
       if (blockIdx.x == 0 && threadIdx.x == 0) unclaim(row_of_state, row_state, s, r);
       continue;
     }
-    const uint64_t set = lane < p.W ? p.sets[(int64_t)s * p.W + lane] : 0ull;
+    const uint64_t set = lane < p.W ? p.rows[(int64_t)s * p.W + lane] : 0ull;
     const bool some = __any(set != 0);
     uint32_t bits = 0;
     for (int j = 0; j < 8; ++j) {
@@ -421,14 +262,8 @@ __global__ __launch_bounds__(FILL_THREADS) void lazy_fill_wave_kernel(Lazy p, in
 }
 
 // ---- the host side -----------------------------------------------------------------------------------------------------------------
-constexpr int NEED_N = 1, NEED_BANK = 2, NEED_WALK = 4;
-
 int lazy_check(const glb_lazy_args *a, const char *what, int need) {
-  if (const int rc = glb::block_ok(a, what, "glb_lazy_args")) return rc;
-  const glb_dfa_args *d = &a->dfa;
-  if (const int rc = glb::block_ok(d, what, "glb_dfa_args")) return rc;
-  if (a->max_states < 1 || a->max_states > LAZY_MAX_STATES)
-    return glb::api_fail(GLB_EINVAL, "%s: max_states %d outside [1, %d]", what, a->max_states, LAZY_MAX_STATES);
+  if (const int rc = number_check(a, what, "glb_lazy_args", need)) return rc;
   if (a->n_nfa_states < 1 || a->n_nfa_states > LAZY_MAX_NFA_STATES)
     return glb::api_fail(GLB_EINVAL, "%s: n_nfa_states %d outside [1, %d]", what, a->n_nfa_states, LAZY_MAX_NFA_STATES);
   if (a->n_important < 0 || a->n_important > GLB_NFA_MAX_IMPORTANT || a->n_important > a->n_nfa_states)
@@ -442,31 +277,8 @@ int lazy_check(const glb_lazy_args *a, const char *what, int need) {
   if (!a->arc_off || !a->arc_dst || !a->arc_bytes) return glb::api_fail(GLB_EINVAL, "%s: arc_off, arc_dst or arc_bytes is null", what);
   if (!a->accepting_mask) return glb::api_fail(GLB_EINVAL, "%s: accepting_mask is null", what);
   if (!a->eclose) return glb::api_fail(GLB_EINVAL, "%s: eclose is null", what);
-  if (a->table_slots < 2 * (int64_t)a->max_states || a->table_slots > ((int64_t)1 << 30) || (a->table_slots & (a->table_slots - 1)))
-    return glb::api_fail(GLB_EINVAL, "%s: table_slots %lld is not a power of two in [2 max_states = %lld, 2^30]", what,
-                         (long long)a->table_slots, 2 * (long long)a->max_states);
-  if (!a->table) return glb::api_fail(GLB_EINVAL, "%s: table is null", what);
-  if ((uintptr_t)a->table & 7) return glb::api_fail(GLB_EINVAL, "%s: table is not aligned to 8 bytes", what);
   if (!a->sets) return glb::api_fail(GLB_EINVAL, "%s: sets is null", what);
   if (!a->accepting_out) return glb::api_fail(GLB_EINVAL, "%s: accepting_out is null", what);
-  if (!a->status) return glb::api_fail(GLB_EINVAL, "%s: status is null", what);
-  const int tables = !!a->row_state + !!a->row_stamp + !!a->claimants + !!a->victims + !!a->ecounters + !!a->epoch;
-  if (tables != 0 && tables != 6) return glb::api_fail(GLB_EINVAL, "%s: the eviction tables are given in part (%d of 6)", what, tables);
-  if (d->vocab <= 0 || d->vocab > 0x7fffff00ll) return glb::api_fail(GLB_EINVAL, "%s: vocab %lld", what, (long long)d->vocab);
-  if (need & NEED_WALK) {
-    if (!d->tok_bytes || !d->tok_ptr || !d->skip || d->n_bytes < 0 || d->n_bytes > 0x7fffffffll)
-      return glb::api_fail(GLB_EINVAL, "%s: vocabulary bytes missing", what);
-  }
-  if (need & NEED_BANK) {
-    if (d->bank_ld < (d->vocab + 31) / 32)
-      return glb::api_fail(GLB_EINVAL, "%s: bank_ld %lld < %lld words", what, (long long)d->bank_ld, (long long)((d->vocab + 31) / 32));
-    if (d->capacity < (tables ? 3 : 2) || d->capacity > (tables ? 65535 : 0x7fffffffll))
-      return glb::api_fail(GLB_EINVAL, "%s: capacity %lld (rows 0 and 1 are the bank's own; an evicting bank: [3, 65535])", what, (long long)d->capacity);
-    if (!d->bank || !d->row_of_state || !d->work || !d->counters) return glb::api_fail(GLB_EINVAL, "%s: null bank pointer", what);
-  }
-  if (need & NEED_N) {
-    if (d->n <= 0) return glb::api_fail(GLB_EINVAL, "%s: n %lld <= 0", what, (long long)d->n);
-  }
   return GLB_OK;
 }
 
@@ -476,23 +288,6 @@ Lazy lazy_of(const glb_lazy_args *a) {
   return Lazy{d->tok_bytes, d->n_bytes, d->tok_ptr, d->skip, d->vocab, d->eos_id, a->n_nfa_states, a->n_important, a->n_words, a->n_arcs,
               a->max_states, a->arc_off, a->arc_dst, a->arc_bytes, a->accepting_mask, a->eclose, a->hash_mask, words,
               (int32_t *)(words + a->table_slots), (uint64_t)a->table_slots - 1, a->cand, a->sets, a->accepting_out, a->counts, a->status};
-}
-
-// blocks for a grid that strides over its work: four to a CU, and no more than the work has
-int lazy_grid(int64_t items, int per_block, unsigned *blocks) {
-  static std::atomic<int> cus_of_device{0};  // (one kind of device a process)
-  int cus = cus_of_device.load(std::memory_order_relaxed);
-  if (cus <= 0) {
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (e != hipSuccess) return glb::api_hip_fail(e, "lazy: the device's CU count");
-    if (cus <= 0) cus = 256;
-    cus_of_device.store(cus, std::memory_order_relaxed);
-  }
-  const int64_t need = (items + per_block - 1) / per_block, most = (int64_t)cus * 4;
-  *blocks = (unsigned)(need < most ? (need > 0 ? need : 1) : most);
-  return GLB_OK;
 }
 
 }  // namespace
@@ -530,15 +325,12 @@ int glb_lazy_advance(const glb_lazy_args *a, void *stream) {
   for (int64_t base = 0; base < d->n; base += a->cand_rows) {
     const int64_t n = d->n - base < a->cand_rows ? d->n - base : a->cand_rows;
     unsigned waves = 0, blocks = 0;
-    if (const int rc = lazy_grid(n, LAZY_WAVES, &waves)) return rc;
-    if (const int rc = lazy_grid(n, LAZY_THREADS, &blocks)) return rc;
+    if (const int rc = number_grid("lazy: the device's CU count", n, LAZY_WAVES, &waves)) return rc;
+    if (const int rc = number_grid("lazy: the device's CU count", n, LAZY_THREADS, &blocks)) return rc;
     hipLaunchKernelGGL(lazy_walk_kernel, dim3(waves), dim3(LAZY_THREADS), 0, st, p, base, n, d->tokens, d->ld, d->from, d->to, d->state_in,
                        d->state_out);
-    hipLaunchKernelGGL(lazy_enter_kernel, dim3(waves), dim3(LAZY_THREADS), 0, st, p, base, n, d->state_out);
-    hipLaunchKernelGGL(lazy_count_kernel, dim3(blocks), dim3(LAZY_THREADS), 0, st, p, base, n, (const int32_t *)d->state_out);
-    hipLaunchKernelGGL(lazy_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, st, p, n);
-    hipLaunchKernelGGL(lazy_number_kernel, dim3(blocks), dim3(LAZY_THREADS), 0, st, p, base, n, (const int32_t *)d->state_out);
-    hipLaunchKernelGGL(lazy_resolve_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, st, p, base, n, d->state_out, base + n >= d->n ? 1 : 0);
+    hipLaunchKernelGGL(number_enter_wave_kernel<Lazy>, dim3(waves), dim3(LAZY_THREADS), 0, st, p, base, n, d->state_out);
+    number_launches(p, blocks, base, n, d->state_out, base + n >= d->n, st);
   }
   return glb::launched("lazy_advance launch");
 }

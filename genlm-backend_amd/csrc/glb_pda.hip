@@ -2,31 +2,27 @@
 // DESIGN.md §25).  A state of the constraint is a configuration - the automaton's state and a bounded stack - of W 64-bit
 // words: a wave holds one, a lane a word (glb_set.hpp's hash and key work on the raw words, every byte above the depth being
 // zero).  glb_pda_advance walks every particle's tokens from its configuration, byte by byte, in registers; the configuration
-// it ends in is looked up and numbered as glb_lazy.hip numbers a set: enter, count, scan, number and resolve are that file's
-// kernels over `configs` in place of `sets`, stated a second time here (glb_lazy.hip is left as it is).  The bank of rows is
-// glb_dfa_bank.hpp's, unchanged: only the fill is new.  Everything read from device memory is range-checked.
+// it ends in is looked up and numbered as glb_lazy.hip numbers a set, by glb_number.hpp's kernels: enter (a wave per
+// particle), count, scan, number and resolve, over this file's `Pda`, whose store_row copies the configuration and derives
+// its accepting byte.  The bank of rows is glb_dfa_bank.hpp's, unchanged: only the fill is new.  Everything read from device
+// memory is range-checked.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/glb.h"
 #include "glb_common.hpp"
 #include "glb_dfa_bank.hpp"
+#include "glb_number.hpp"
 #include "glb_set.hpp"
 
 namespace {
 
-enum { P_COUNT = 0, P_FLAGS = 1, P_BASE = 2, P_NEXT = 3 };
-constexpr int PDA_THREADS = 256;  // four waves, a particle each; count / number: 256 particles a block
-constexpr int PDA_WAVES = PDA_THREADS / 64;
+constexpr int PDA_THREADS = NUMBER_THREADS;  // the walk: four waves, a particle each, as number_enter_wave_kernel has them
+constexpr int PDA_WAVES = NUMBER_WAVES;
 constexpr int PDA_FILL_THREADS = 64;  // the fill: one wave a workgroup, 64 tokens, at most 64 x 504 bytes of private stacks
-constexpr int32_t PDA_MAX_CONFIGS = 1 << 22;
 constexpr int32_t PDA_MAX_AUTOMATON = 1 << 24;
 constexpr int32_t PDA_MAX_SYMBOLS = 126;
 constexpr int PDA_POP = 127;
-constexpr int32_t NO_PART = 0x7fffffff;
-constexpr int32_t PENDING = INT32_MIN;    // state_out between walk and enter: the particle's end configuration lies in its row of `cand`
-constexpr uint32_t REF_PART = 0x80000000u;  // the low half of a slot: this bit and a particle index of the chunk, else a numbered id
-constexpr uint32_t REF_TOMB = 0xffffffffu;  // a configuration that found no id below max_states: never equal to anything, probed past
 
 struct Pda {
   const uint8_t *bytes;
@@ -42,20 +38,11 @@ struct Pda {
   unsigned long long *words;  // [slots]; 0: empty
   int32_t *partmin;           // [slots]; the smallest particle index of the chunk that brought the slot's configuration
   uint64_t mask;              // slots - 1
-  uint64_t *cand, *configs;
+  uint64_t *cand, *rows;      // rows [max_states][W]: the numbered configurations
   uint8_t *accepting_out;
   int32_t *cnt, *status;
+  static __device__ void store_row(const Pda &p, int64_t id, int64_t base, int64_t k);
 };
-
-__device__ inline int32_t flags_now(const int32_t *status) {
-  return __hip_atomic_load(&status[P_FLAGS], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// the configurations numbered, never more than the rows of `configs`
-__device__ inline int32_t numbered(const Pda &p, int word) {
-  const int32_t c = p.status[word];
-  return c < 0 ? 0 : c > p.max_states ? p.max_states : c;
-}
 
 // word 0 of a configuration: whether its state and depth are the automaton's
 __device__ inline bool head_ok(const Pda &p, uint64_t head, int32_t &state, int32_t &depth) {
@@ -156,25 +143,26 @@ __global__ void pda_clear_kernel(Pda p) {
 __global__ __launch_bounds__(64) void pda_seed_kernel(Pda p, int32_t start) {
   const int lane = (int)threadIdx.x;
   const uint64_t word = lane == 0 ? (uint64_t)(uint32_t)start : 0ull;
-  if (lane < p.W) p.configs[lane] = word;
+  if (lane < p.W) p.rows[lane] = word;
   uint64_t slot;
   uint32_t high;
   set_key(p.hash_mask, p.mask, word, lane, slot, high);
   if (lane == 0) {
     p.accepting_out[0] = p.accepting[start] ? 1 : 0;
     p.words[slot] = (unsigned long long)high << 32;  // (id 0; the table is empty)
-    p.status[P_COUNT] = p.status[P_BASE] = p.status[P_NEXT] = 1;
+    p.status[N_COUNT] = p.status[N_BASE] = p.status[N_NEXT] = 1;
   }
 }
 
-// ---- advance: six launches over the particles [base, base + n) of a call, particle base + k owning row k of `cand` ---------------
+// ---- advance: six launches over the particles [base, base + n) of a call, particle base + k owning row k of `cand`: the walk,
+// then the five of glb_number.hpp
 // walk, a wave per particle: the tokens of its range from its configuration, in registers; state_out = -1 (dead), the id
 // itself (an empty range) or PENDING with the end configuration in `cand`
 __global__ __launch_bounds__(PDA_THREADS) void pda_walk_kernel(Pda p, int64_t base, int64_t n, const int32_t *tokens, int64_t ld,
                                                               const int32_t *from, const int32_t *to, const int32_t *state_in,
                                                               int32_t *state_out) {
   const int lane = (int)threadIdx.x & 63;
-  const int32_t known = numbered(p, P_BASE);
+  const int32_t known = numbered(p, N_BASE);
   const int64_t waves = (int64_t)gridDim.x * PDA_WAVES;
   for (int64_t k = (int64_t)blockIdx.x * PDA_WAVES + (threadIdx.x >> 6); k < n; k += waves) {
     const int64_t i = base + k;
@@ -185,7 +173,7 @@ __global__ __launch_bounds__(PDA_THREADS) void pda_walk_kernel(Pda p, int64_t ba
       if (f == t) {
         code = s;
       } else {
-        const uint64_t word = lane < p.W ? p.configs[(int64_t)s * p.W + lane] : 0ull;
+        const uint64_t word = lane < p.W ? p.rows[(int64_t)s * p.W + lane] : 0ull;
         int32_t state, depth;
         bool alive = head_ok(p, bcast64(word, 0), state, depth);
         uint64_t mine = lane == 0 ? 0ull : word;
@@ -201,158 +189,13 @@ __global__ __launch_bounds__(PDA_THREADS) void pda_walk_kernel(Pda p, int64_t ba
   }
 }
 
-// enter, a wave per particle that is PENDING: its end configuration looked up; state_out = the id where an earlier call or
-// chunk numbered it, else -2 - slot until pda_resolve_kernel.  A new configuration's slot is claimed by one compare-and-swap
-// of the whole word.  A chunk that begins with every id taken claims nothing: a configuration not found is -1 and the overflow
-__global__ __launch_bounds__(PDA_THREADS) void pda_enter_kernel(Pda p, int64_t base, int64_t n, int32_t *state_out) {
-  const int lane = (int)threadIdx.x & 63;
-  const bool full = p.status[P_COUNT] >= p.max_states;  // (written by the chunk before, not by this one)
-  const int64_t waves = (int64_t)gridDim.x * PDA_WAVES;
-  for (int64_t k = (int64_t)blockIdx.x * PDA_WAVES + (threadIdx.x >> 6); k < n; k += waves) {
-    if (state_out[base + k] != PENDING) continue;  // (a whole wave)
-    if (flags_now(p.status) & GLB_PDA_BUG) break;
-    const uint64_t target = lane < p.W ? p.cand[k * p.W + lane] : 0ull;
-    uint64_t slot;
-    uint32_t high;
-    set_key(p.hash_mask, p.mask, target, lane, slot, high);
-    const unsigned long long claim = ((unsigned long long)high << 32) | REF_PART | (uint32_t)k;
-    int32_t out = -1;
-    bool settled = false;
-    for (uint64_t probe = 0; probe <= p.mask && !settled; ++probe, slot = (slot + 1) & p.mask) {
-      unsigned long long cur = word_now(&p.words[slot]);  // (one address: the same in every lane)
-      if (cur == 0ull) {
-        if (full) break;
-        unsigned long long old = 0ull;
-        if (lane == 0) old = atomicCAS(&p.words[slot], 0ull, claim);
-        old = bcast64(old, 0);
-        if (old == 0ull) {  // this wave's: a new configuration
-          if (lane == 0) atomicMin(&p.partmin[slot], (int32_t)k);
-          out = -2 - (int32_t)slot;
-          settled = true;
-          break;
-        }
-        cur = old;
-      }
-      const uint32_t ref = (uint32_t)cur;
-      if ((uint32_t)(cur >> 32) == high && ref != REF_TOMB) {
-        const uint64_t *row = nullptr;  // the configuration behind the reference
-        if (ref & REF_PART) {
-          if ((int64_t)(ref & 0x7fffffffu) < n) row = p.cand + (int64_t)(ref & 0x7fffffffu) * p.W;
-        } else if ((int32_t)ref < p.max_states) {
-          row = p.configs + (int64_t)ref * p.W;
-        }
-        if (!row) {
-          if (lane == 0) atomicOr(&p.status[P_FLAGS], GLB_PDA_BUG);
-          settled = true;
-          break;
-        }
-        const uint64_t other = lane < p.W ? row[lane] : 0ull;
-        if (!__any(other != target)) {
-          if (ref & REF_PART) {
-            if (lane == 0) atomicMin(&p.partmin[slot], (int32_t)k);
-            out = -2 - (int32_t)slot;
-          } else {
-            out = (int32_t)ref;
-          }
-          settled = true;
-          break;
-        }
-      }
-      if ((probe & 31) == 31 && (flags_now(p.status) & GLB_PDA_BUG)) settled = true;
-    }
-    // not found and nothing claimed: every id is taken (or, a table walked all round, every slot)
-    if (!settled && lane == 0) atomicOr(&p.status[P_FLAGS], GLB_PDA_OVERFLOW);
-    if (lane == 0) state_out[base + k] = out;
-  }
-}
-
-// whether particle k of the chunk is the one that numbers its end configuration: the smallest to have ended in it
-__device__ inline bool wins(const Pda &p, int32_t code, int64_t k, int64_t &slot) {
-  slot = -2 - (int64_t)code;
-  return code <= -2 && (uint64_t)slot <= p.mask && p.partmin[slot] == (int32_t)k;
-}
-
-// cnt[b]: the new configurations that the particles [256 b, 256 b + 256) of the chunk number
-__global__ __launch_bounds__(PDA_THREADS) void pda_count_kernel(Pda p, int64_t base, int64_t n, const int32_t *state_out) {
-  const int64_t nb = (n + PDA_THREADS - 1) / PDA_THREADS;
-  for (int64_t b = blockIdx.x; b < nb; b += gridDim.x) {
-    const int64_t k = b * PDA_THREADS + threadIdx.x;
-    int64_t slot;
-    const bool w = k < n && wins(p, state_out[base + k], k, slot);
-    const int c = __syncthreads_count(w);
-    if (threadIdx.x == 0) p.cnt[b] = c;
-  }
-}
-
-// one block: cnt becomes its exclusive prefix sums; P_NEXT = the configurations after this chunk, at most max_states - past
-// it the overflow flag
-__global__ __launch_bounds__(SCAN_THREADS) void pda_scan_kernel(Pda p, int64_t n) {
-  __shared__ int32_t wave_sum[SCAN_THREADS / 64];
-  __shared__ int32_t carry;
-  const int32_t total = scan_exclusive(p.cnt, (int32_t)((n + PDA_THREADS - 1) / PDA_THREADS), wave_sum, &carry);
-  if (threadIdx.x == 0) {
-    const int64_t next = (int64_t)numbered(p, P_COUNT) + total;  // (total <= n <= 2^30)
-    if (next > p.max_states) atomicOr(&p.status[P_FLAGS], GLB_PDA_OVERFLOW);
-    p.status[P_NEXT] = (int32_t)(next > p.max_states ? p.max_states : next);
-  }
-}
-
-// the winners number their configurations: id = P_COUNT + cnt[b] + the winners of the block at smaller particles; the
-// configuration copied from `cand`, accepting_out = accepting[state] && depth == 0, and the slot's reference turned into the
-// id - or, with no id left, into the tombstone
-__global__ __launch_bounds__(PDA_THREADS) void pda_number_kernel(Pda p, int64_t base, int64_t n, const int32_t *state_out) {
-  __shared__ int32_t wave_n[PDA_WAVES];
-  const int32_t count = numbered(p, P_COUNT);
-  const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
-  const int64_t nb = (n + PDA_THREADS - 1) / PDA_THREADS;
-  for (int64_t b = blockIdx.x; b < nb; b += gridDim.x) {
-    const int64_t k = b * PDA_THREADS + threadIdx.x;
-    int64_t slot;
-    const bool w = k < n && wins(p, state_out[base + k], k, slot);
-    const unsigned long long ballot = __ballot(w);
-    if (lane == 0) wave_n[wave] = __popcll(ballot);
-    __syncthreads();
-    int32_t rank = __popcll(ballot & ((1ull << lane) - 1ull));
-    for (int v = 0; v < wave; ++v) rank += wave_n[v];
-    if (w) {
-      const int64_t id = (int64_t)count + p.cnt[b] + rank;
-      const unsigned long long high = p.words[slot] & 0xffffffff00000000ull;
-      if (id >= 0 && id < p.max_states) {
-        const uint64_t *row = p.cand + k * p.W;
-        for (int j = 0; j < p.W; ++j) p.configs[id * p.W + j] = row[j];
-        int32_t state, depth;
-        const bool ok = head_ok(p, row[0], state, depth);
-        p.accepting_out[id] = ok && depth == 0 && p.accepting[state] ? 1 : 0;
-        p.words[slot] = high | (unsigned long long)id;
-      } else {
-        p.words[slot] = high | REF_TOMB;
-      }
-    }
-    __syncthreads();
-  }
-}
-
-// state_out of the chunk: -2 - slot becomes the id its slot was given, -1 behind a tombstone.  The chunk's last launch: the
-// count moves on (no launch of the chunk reads it from here), and with the call's last chunk the ids a caller may name
-__global__ void pda_resolve_kernel(Pda p, int64_t base, int64_t n, int32_t *state_out, int last) {
-  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (k == 0) {
-    p.status[P_COUNT] = p.status[P_NEXT];
-    if (last) p.status[P_BASE] = p.status[P_NEXT];
-  }
-  if (k >= n) return;
-  const int32_t code = state_out[base + k];
-  if (code > -2) return;
-  const int64_t slot = -2 - (int64_t)code;
-  int32_t id = -1;
-  bool bug = true;
-  if ((uint64_t)slot <= p.mask) {
-    const uint32_t ref = (uint32_t)p.words[slot];
-    if (ref == REF_TOMB) bug = false;
-    else if (!(ref & REF_PART) && (int32_t)ref < p.max_states) id = (int32_t)ref, bug = false;
-  }
-  if (bug) atomicOr(&p.status[P_FLAGS], GLB_PDA_BUG);
-  state_out[base + k] = id;
+// the configuration of a winner (glb_number.hpp, number_kernel) copied from `cand`; accepting_out = accepting[state] && depth == 0
+__device__ inline void Pda::store_row(const Pda &p, int64_t id, int64_t, int64_t k) {
+  const uint64_t *row = p.cand + k * p.W;
+  for (int j = 0; j < p.W; ++j) p.rows[id * p.W + j] = row[j];
+  int32_t state, depth;
+  const bool ok = head_ok(p, row[0], state, depth);
+  p.accepting_out[id] = ok && depth == 0 && p.accepting[state] ? 1 : 0;
 }
 
 // ---- the fill: the rows of the work entries, every token walked from configs[s] ------------------------------------------------
@@ -375,7 +218,7 @@ __global__ __launch_bounds__(PDA_FILL_THREADS) void pda_fill_kernel(Pda p, int32
   const int64_t t = (int64_t)blockIdx.x * PDA_FILL_THREADS + lane;
   const int64_t w0 = (int64_t)blockIdx.x * 2;
   if (w0 >= words) return;  // (the whole workgroup)
-  const int32_t known = numbered(p, P_COUNT);
+  const int32_t known = numbered(p, N_COUNT);
   for (int32_t e = range[0] + (int32_t)blockIdx.y; e < range[1]; e += (int32_t)gridDim.y) {
     const int32_t s = work[2 * (int64_t)e], r = work[2 * (int64_t)e + 1];
     if (s < 0 || s >= p.max_states || r < 2 || r >= capacity) continue;  // (uniform over the block)
@@ -386,7 +229,7 @@ __global__ __launch_bounds__(PDA_FILL_THREADS) void pda_fill_kernel(Pda p, int32
       }
       continue;
     }
-    const uint64_t *config = p.configs + (int64_t)s * p.W;
+    const uint64_t *config = p.rows + (int64_t)s * p.W;
     int32_t state, depth;
     const bool ok = head_ok(p, config[0], state, depth);  // (uniform)
     __syncthreads();  // (the entry before is read to its end)
@@ -407,14 +250,8 @@ __global__ __launch_bounds__(PDA_FILL_THREADS) void pda_fill_kernel(Pda p, int32
 }
 
 // ---- the host side -----------------------------------------------------------------------------------------------------------------
-constexpr int NEED_N = 1, NEED_BANK = 2, NEED_WALK = 4;
-
 int pda_check(const glb_pda_args *a, const char *what, int need) {
-  if (const int rc = glb::block_ok(a, what, "glb_pda_args")) return rc;
-  const glb_dfa_args *d = &a->dfa;
-  if (const int rc = glb::block_ok(d, what, "glb_dfa_args")) return rc;
-  if (a->max_states < 1 || a->max_states > PDA_MAX_CONFIGS)
-    return glb::api_fail(GLB_EINVAL, "%s: max_states %d outside [1, %d]", what, a->max_states, PDA_MAX_CONFIGS);
+  if (const int rc = number_check(a, what, "glb_pda_args", need)) return rc;
   if (a->n_pda_states < 1 || a->n_pda_states > PDA_MAX_AUTOMATON)
     return glb::api_fail(GLB_EINVAL, "%s: n_pda_states %d outside [1, %d]", what, a->n_pda_states, PDA_MAX_AUTOMATON);
   if (a->n_symbols < 1 || a->n_symbols > PDA_MAX_SYMBOLS)
@@ -428,32 +265,9 @@ int pda_check(const glb_pda_args *a, const char *what, int need) {
   if (a->n_words != W) return glb::api_fail(GLB_EINVAL, "%s: n_words %d is not 1 + ceil(max_depth / 8) = %d", what, a->n_words, W);
   if (!a->delta) return glb::api_fail(GLB_EINVAL, "%s: delta is null", what);
   if (!a->accepting) return glb::api_fail(GLB_EINVAL, "%s: accepting is null", what);
-  if (a->table_slots < 2 * (int64_t)a->max_states || a->table_slots > ((int64_t)1 << 30) || (a->table_slots & (a->table_slots - 1)))
-    return glb::api_fail(GLB_EINVAL, "%s: table_slots %lld is not a power of two in [2 max_states = %lld, 2^30]", what,
-                         (long long)a->table_slots, 2 * (long long)a->max_states);
-  if (!a->table) return glb::api_fail(GLB_EINVAL, "%s: table is null", what);
-  if ((uintptr_t)a->table & 7) return glb::api_fail(GLB_EINVAL, "%s: table is not aligned to 8 bytes", what);
   if (!a->configs) return glb::api_fail(GLB_EINVAL, "%s: configs is null", what);
   if ((uintptr_t)a->configs & 7) return glb::api_fail(GLB_EINVAL, "%s: configs is not aligned to 8 bytes", what);
   if (!a->accepting_out) return glb::api_fail(GLB_EINVAL, "%s: accepting_out is null", what);
-  if (!a->status) return glb::api_fail(GLB_EINVAL, "%s: status is null", what);
-  const int tables = !!a->row_state + !!a->row_stamp + !!a->claimants + !!a->victims + !!a->ecounters + !!a->epoch;
-  if (tables != 0 && tables != 6) return glb::api_fail(GLB_EINVAL, "%s: the eviction tables are given in part (%d of 6)", what, tables);
-  if (d->vocab <= 0 || d->vocab > 0x7fffff00ll) return glb::api_fail(GLB_EINVAL, "%s: vocab %lld", what, (long long)d->vocab);
-  if (need & NEED_WALK) {
-    if (!d->tok_bytes || !d->tok_ptr || !d->skip || d->n_bytes < 0 || d->n_bytes > 0x7fffffffll)
-      return glb::api_fail(GLB_EINVAL, "%s: vocabulary bytes missing", what);
-  }
-  if (need & NEED_BANK) {
-    if (d->bank_ld < (d->vocab + 31) / 32)
-      return glb::api_fail(GLB_EINVAL, "%s: bank_ld %lld < %lld words", what, (long long)d->bank_ld, (long long)((d->vocab + 31) / 32));
-    if (d->capacity < (tables ? 3 : 2) || d->capacity > (tables ? 65535 : 0x7fffffffll))
-      return glb::api_fail(GLB_EINVAL, "%s: capacity %lld (rows 0 and 1 are the bank's own; an evicting bank: [3, 65535])", what, (long long)d->capacity);
-    if (!d->bank || !d->row_of_state || !d->work || !d->counters) return glb::api_fail(GLB_EINVAL, "%s: null bank pointer", what);
-  }
-  if (need & NEED_N) {
-    if (d->n <= 0) return glb::api_fail(GLB_EINVAL, "%s: n %lld <= 0", what, (long long)d->n);
-  }
   return GLB_OK;
 }
 
@@ -463,23 +277,6 @@ Pda pda_of(const glb_pda_args *a) {
   return Pda{d->tok_bytes, d->n_bytes, d->tok_ptr, d->skip, d->vocab, d->eos_id, a->n_pda_states, a->n_symbols, a->max_depth, a->n_words,
              a->max_states, a->delta, a->accepting, a->hash_mask, words, (int32_t *)(words + a->table_slots), (uint64_t)a->table_slots - 1,
              a->cand, a->configs, a->accepting_out, a->counts, a->status};
-}
-
-// blocks for a grid that strides over its work: four to a CU, and no more than the work has
-int pda_grid(int64_t items, int per_block, unsigned *blocks) {
-  static std::atomic<int> cus_of_device{0};  // (one kind of device a process)
-  int cus = cus_of_device.load(std::memory_order_relaxed);
-  if (cus <= 0) {
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (e != hipSuccess) return glb::api_hip_fail(e, "pda: the device's CU count");
-    if (cus <= 0) cus = 256;
-    cus_of_device.store(cus, std::memory_order_relaxed);
-  }
-  const int64_t need = (items + per_block - 1) / per_block, most = (int64_t)cus * 4;
-  *blocks = (unsigned)(need < most ? (need > 0 ? need : 1) : most);
-  return GLB_OK;
 }
 
 }  // namespace
@@ -518,15 +315,12 @@ int glb_pda_advance(const glb_pda_args *a, void *stream) {
   for (int64_t base = 0; base < d->n; base += a->cand_rows) {
     const int64_t n = d->n - base < a->cand_rows ? d->n - base : a->cand_rows;
     unsigned waves = 0, blocks = 0;
-    if (const int rc = pda_grid(n, PDA_WAVES, &waves)) return rc;
-    if (const int rc = pda_grid(n, PDA_THREADS, &blocks)) return rc;
+    if (const int rc = number_grid("pda: the device's CU count", n, PDA_WAVES, &waves)) return rc;
+    if (const int rc = number_grid("pda: the device's CU count", n, PDA_THREADS, &blocks)) return rc;
     hipLaunchKernelGGL(pda_walk_kernel, dim3(waves), dim3(PDA_THREADS), 0, st, p, base, n, d->tokens, d->ld, d->from, d->to, d->state_in,
                        d->state_out);
-    hipLaunchKernelGGL(pda_enter_kernel, dim3(waves), dim3(PDA_THREADS), 0, st, p, base, n, d->state_out);
-    hipLaunchKernelGGL(pda_count_kernel, dim3(blocks), dim3(PDA_THREADS), 0, st, p, base, n, (const int32_t *)d->state_out);
-    hipLaunchKernelGGL(pda_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, st, p, n);
-    hipLaunchKernelGGL(pda_number_kernel, dim3(blocks), dim3(PDA_THREADS), 0, st, p, base, n, (const int32_t *)d->state_out);
-    hipLaunchKernelGGL(pda_resolve_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, st, p, base, n, d->state_out, base + n >= d->n ? 1 : 0);
+    hipLaunchKernelGGL(number_enter_wave_kernel<Pda>, dim3(waves), dim3(PDA_THREADS), 0, st, p, base, n, d->state_out);
+    number_launches(p, blocks, base, n, d->state_out, base + n >= d->n, st);
   }
   return glb::launched("pda_advance launch");
 }
