@@ -517,6 +517,19 @@ class TopkArgs(C.Structure):
     ]
 
 
+class ByteLmArgs(C.Structure):  # glb_bytelm_args
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("width", C.c_int32),
+        ("n_groups", C.c_int64), ("n_nodes", C.c_int64), ("root", C.c_int32),
+        ("child_ptr", C.c_void_p), ("child_idx", C.c_void_p), ("child_sym", C.c_void_p), ("leaf_token", C.c_void_p),
+        ("node", C.c_void_p), ("alive", C.c_void_p), ("u", C.c_void_p), ("w", C.c_void_p),
+        ("sel", C.c_void_p), ("mass", C.c_void_p), ("fresh", C.c_void_p),
+        ("out_parent", C.c_void_p), ("out_token", C.c_void_p), ("out_node", C.c_void_p), ("out_alive", C.c_void_p),
+        ("out_u", C.c_void_p), ("out_w", C.c_void_p), ("out_spawned", C.c_void_p), ("out_n_spawned", C.c_void_p),
+        ("byte", C.c_void_p), ("out_next", C.c_void_p), ("out_logZ", C.c_void_p), ("logp", C.c_void_p),
+    ]
+
+
 class TruncateArgs(C.Structure):
     _fields_ = [
         ("struct_size", C.c_uint32),
@@ -653,6 +666,9 @@ SYMBOLS = {
     "glb_topk_rows": (C.c_int, [C.POINTER(TopkArgs), _vp]),
     "glb_truncate_rows": (C.c_int, [C.POINTER(TruncateArgs), _vp]),
     "glb_beam_select": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "glb_bytelm_children": (C.c_int, [C.POINTER(ByteLmArgs), _vp]),
+    "glb_bytelm_extend": (C.c_int, [C.POINTER(ByteLmArgs), _vp]),
+    "glb_bytelm_next": (C.c_int, [C.POINTER(ByteLmArgs), _vp]),
     "glb_philox4x32_10": (None, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
 }
 

@@ -709,6 +709,83 @@ class HipEngine:
                                        _ptr(parent), _ptr(token), _ptr(out), self._stream()))
         return parent, token, out
 
+    # ---- the byte-level beam's three calls (glb_bytelm_*) ------------------------------------------------------
+    BYTELM_SEL, BYTELM_ROW, BYTELM_LEAVES = 260, 257, 4
+
+    def _bytelm_block(self, trie, node, alive, width, **tensors):
+        """glb_bytelm_args over a trie's device arrays (`bytelm.byte_trie_arrays`: child_ptr, child_idx, child_sym, leaf_token,
+        n_nodes, root) and the slot state; `tensors`: further fields by name, each checked for device and contiguity."""
+        if not isinstance(width, int) or not 1 <= width <= self.TOPK_MAX:
+            raise ValueError(f"width must be an integer in 1..{self.TOPK_MAX}, got {width!r}")
+        n = node.numel()
+        if node.dtype != torch.int32 or node.dim() != 1 or n == 0 or n % width:
+            raise ValueError("node must be an int32 [G * width] tensor, G >= 1")
+        if alive.dtype != torch.int32 or alive.shape != (n,):
+            raise ValueError("alive must be an int32 [G * width] tensor")
+        want = {"u": (torch.float32, (n,)), "w": (torch.float32, (n,)), "sel": (torch.int32, (n, self.BYTELM_SEL)),
+                "mass": (torch.float32, (n, self.BYTELM_SEL)), "fresh": (torch.int32, (n // width,)),
+                "byte": (torch.int32, (n // width,)), "logp": (torch.float32, (n // width,))}
+        a = _lib.ByteLmArgs()
+        a.struct_size = C.sizeof(_lib.ByteLmArgs)
+        a.width, a.n_groups, a.n_nodes, a.root = width, n // width, int(trie["n_nodes"]), int(trie["root"])
+        for k in ("child_ptr", "child_idx", "child_sym", "leaf_token"):
+            self._check_dev(trie[k])
+            setattr(a, k, trie[k].data_ptr())
+        self._check_dev(node, alive)
+        a.node, a.alive = node.data_ptr(), alive.data_ptr()
+        for k, t in tensors.items():
+            if t is None:
+                continue
+            self._check_dev(t)
+            if k in want and (t.dtype != want[k][0] or tuple(t.shape) != want[k][1]):
+                raise ValueError(f"{k} must be a {want[k][0]} tensor of shape {list(want[k][1])}, got {t.dtype} {list(t.shape)}")
+            setattr(a, k, t.data_ptr())
+        return a, n
+
+    def bytelm_children(self, trie, node, alive, width):
+        """The selection rows of a byte beam's slots (glb_bytelm_children): int32 [G * width, 260] - columns 0..255 the byte
+        children of every alive slot's node, 256..259 its leaf children, -1 where there is none and for dead slots - the
+        `nodes` argument of `TokenByteTrie.masses_from_logits`."""
+        sel = torch.empty((node.numel(), self.BYTELM_SEL), dtype=torch.int32, device=self.device)
+        a, _ = self._bytelm_block(trie, node, alive, width, sel=sel)
+        check(self.lib.glb_bytelm_children(C.byref(a), self._stream()))
+        return sel
+
+    def bytelm_extend(self, trie, node, u, w, alive, sel, mass, width, fresh=None):
+        """A byte beam's token boundary (glb_bytelm_extend): per group the `width` largest of the alive candidates' `w` and of
+        u + log(mass) of every leaf child of a candidate that is not at the root; ties by existing before spawned, lower
+        slot, lower leaf.  Kept candidates stay in their slots, spawned survivors fill the lowest freed ones, best first.
+        Returns a dict: parent (the slot itself / the offering slot / -1: empty) and token (the committed token of a spawned
+        slot, else -1), the new state node, u, w, alive, and `spawned` int32 [G * width] (the spawned slots, ascending,
+        then -1) with `n_spawned` int32 [1]."""
+        n = node.numel()
+        out = {k: torch.empty(n, dtype=torch.int32, device=self.device) for k in ("parent", "token", "node", "alive", "spawned")}
+        out["u"], out["w"] = self._f32(n), self._f32(n)
+        out["n_spawned"] = self._i32(1)
+        a, _ = self._bytelm_block(trie, node, alive, width, u=u, w=w, sel=sel, mass=mass, fresh=fresh,
+                                  **{"out_" + k: t for k, t in out.items()})
+        check(self.lib.glb_bytelm_extend(C.byref(a), self._stream()))
+        return out
+
+    def bytelm_next(self, trie, node, u, w, alive, sel, mass, width, byte=None, logp=None, fresh=None):
+        """A byte beam's next-byte rows, or its advance (glb_bytelm_next).  byte None: returns (next float32 [G, 257] - the
+        log-probabilities of the 256 bytes and, in column 256, of EOS; -inf rows for groups without a live candidate - and
+        logZ float32 [G]).  byte int32 [G]: moves every candidate of the groups whose byte is in 0..256 to its child under
+        that byte (node, w, alive are written in place; 256 ends the group), adds the row's entry to `logp` (float32 [G]),
+        marks the groups in `fresh`, and returns None."""
+        if byte is None:
+            G = node.numel() // max(width, 1) if isinstance(width, int) else 0
+            nxt = torch.empty((max(G, 1), self.BYTELM_ROW), dtype=torch.float32, device=self.device)
+            logZ = self._f32(max(G, 1))
+            a, _ = self._bytelm_block(trie, node, alive, width, u=u, w=w, sel=sel, mass=mass, out_next=nxt, out_logZ=logZ)
+            check(self.lib.glb_bytelm_next(C.byref(a), self._stream()))
+            return nxt, logZ
+        if logp is None:
+            raise ValueError("an advance needs logp")
+        a, _ = self._bytelm_block(trie, node, alive, width, u=u, w=w, sel=sel, mass=mass, byte=byte, logp=logp, fresh=fresh)
+        check(self.lib.glb_bytelm_next(C.byref(a), self._stream()))
+        return None
+
     # ---- failed one-launch calls (include/glb.h: glb_workspace_check) ---------------------------------------------
     def error_word(self):
         """int32 [1] device view of the scratch buffer's error word: nonzero after a one-launch call whose waves gave

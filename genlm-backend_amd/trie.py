@@ -14,11 +14,13 @@ from .tokenization import Token
 
 
 class TokenByteTrie:
-    def __init__(self, decode, engine=None):
+    def __init__(self, decode, engine=None, ignore_ids=()):
         """decode: the vocabulary - `Token`s from `decode_vocab`, plain bytes, or other iterables of symbols; the weight
-        of token k is column k of a weight row.  engine: a `HipEngine` (needed for the weight_* methods)."""
+        of token k is column k of a weight row.  engine: a `HipEngine` (needed for the weight_* methods).  ignore_ids:
+        columns whose leaves `flat()["child_sym"]` marks as never selected (-2); the masses are not affected."""
         self.decode = decode
         self.engine = engine
+        self.ignore_ids = frozenset(int(k) for k in ignore_ids)
         # -- build: nodes in creation order, every node keeps its out-edges in insertion order; a token ends in a leaf
         #    of its own hanging off the node of its last byte through the edge (None, k)          (base.py:13-62)
         edges = [[]]          # per node: [(symbol, child)]
@@ -99,7 +101,9 @@ class TokenByteTrie:
     # ---- flattened form for the kernel --------------------------------------------------------------------------
     def flat(self):
         """Host arrays of glb_trie_reduce: leaf of every token, internal nodes by level (level 0 = all children are
-        leaves; a node sits one level above its highest internal child) and the CSR of ascending children."""
+        leaves; a node sits one level above its highest internal child) and the CSR of ascending children.  `child_sym`
+        (int16, parallel to `child_idx`) names every edge for glb_bytelm_children: 0..255 a byte, 256 + j the node's j-th
+        leaf child in ascending order (= token order), -2 the leaf of a token in `ignore_ids`, -1 any other symbol."""
         if self._flat is None:
             n = len(self.children)
             counts = np.fromiter((len(j) for j in self.jump), np.int64, n)
@@ -114,7 +118,21 @@ class TokenByteTrie:
             order = internal[np.argsort(level[internal], kind="stable")]
             n_levels = int(level.max()) + 1
             level_start = np.searchsorted(level[order], np.arange(n_levels + 1))
-            self._flat = dict(vocab=len(self.decode), n_nodes=n, n_levels=n_levels,
+            child_sym = np.full(len(child_idx), -1, np.int16)
+            for x in np.nonzero(counts)[0]:
+                sym_of = {c: sym for sym, c in self.children[x].items()}
+                j = 0
+                for i, c in enumerate(self.jump[x], start=int(child_ptr[x])):
+                    sym = sym_of[int(c)]
+                    if isinstance(sym, tuple) and sym[0] is None:
+                        if sym[1] in self.ignore_ids:
+                            child_sym[i] = -2
+                        else:
+                            child_sym[i] = min(256 + j, 32767)
+                            j += 1
+                    elif isinstance(sym, (int, np.integer)) and 0 <= sym < 256:
+                        child_sym[i] = sym
+            self._flat = dict(vocab=len(self.decode), n_nodes=n, n_levels=n_levels, child_sym=child_sym,
                               leaf_node=self.idx_to_leaf[:, 1].astype(np.int32), level_start=level_start.astype(np.int32),
                               level_nodes=order.astype(np.int32), child_ptr=child_ptr.astype(np.int32),
                               child_idx=child_idx.astype(np.int32))

@@ -1959,6 +1959,84 @@ typedef struct glb_truncate_args {
 } glb_truncate_args;
 int glb_truncate_rows(const glb_truncate_args *args, void *hip_stream);
 
+/*
+ * A byte-level beam over tokenisations: next-byte distributions of a token model, marginalised over the
+ * token sequences that spell a byte prefix.  A candidate is (token context, trie node n, u = log-probability of the committed
+ * tokens, w = u + log mass of n under the context's next-token distribution); n_groups groups of `width` candidates (1 .. 64)
+ * live in slots that never move: group g owns slots g * width .. g * width + width - 1 of node int32, u and w float32, alive
+ * int32.  The trie is TokenByteTrie's CSR (child_ptr int32 [n_nodes + 1], child_idx int32, ascending children) with the edge
+ * symbols child_sym int16 beside child_idx: 0 .. 255 a byte, 256 + j the node's j-th leaf child (a token that ends here;
+ * j < GLB_BYTELM_LEAVES), any other value an edge that is never selected (-2: an ignored token's leaf).  The EOS tokens have
+ * empty byte strings: their leaves are the root's.  leaf_token int32 [n_nodes]: the token a leaf ends, -1 for other nodes.
+ *
+ * glb_bytelm_children  sel int32 [n_slots, GLB_BYTELM_SEL]: columns 0 .. 255 the byte children of the slot's node, 256 .. 259
+ *     its leaf children, -1 where there is none; all -1 for a slot that is not alive or whose node lies outside the trie.  Reads
+ *     node, alive and the CSR.  One wave per slot.  The rows are what glb_trie_rows takes as per-row selections; the masses
+ *     it returns for them are `mass`, float32 [n_slots, GLB_BYTELM_SEL], below (a mass that is not above 0, NaN too, counts as
+ *     none).
+ * glb_bytelm_extend  a token boundary: per group, every alive candidate with a finite w and u is an existing entry of weight
+ *     w; every alive candidate whose node is not the root offers, for each leaf child l (column 256 + j) with mass m > 0,
+ *     a spawned candidate of weight fl32(u + logf(m)) that has committed leaf_token[l].  The `width` largest weights are
+ *     kept: equal weights by existing before spawned, then lower slot, then lower j; -0 equals +0; a weight that is not
+ *     finite is never kept.  A kept existing candidate stays in its slot as it is; the r-th best spawned survivor takes the
+ *     r-th lowest slot of the group that no kept candidate holds, at the root with u = w = its weight.  Per slot:
+ *     out_parent (the slot itself for a kept candidate, the slot of the candidate that offered it for a spawned one, -1
+ *     for an empty slot: alive 0, u = w = -inf, node root), out_token (the committed token of a spawned candidate, else -1),
+ *     out_node, out_alive, out_u, out_w - the new state, which may not lie over the old one.  out_spawned int32 [n_slots]:
+ *     the slots that hold a spawned candidate, ascending, -1 behind them; out_n_spawned int32 [1] their number.  fresh int32
+ *     [n_groups], nullable: a group whose entry is 0 has not moved since it was last extended and offers nothing; the call
+ *     sets the entries to 0.  Reads node, u, w, alive, sel, mass.  One wave per group, then one wave for the list.
+ * glb_bytelm_next  with a = the largest finite u of the group's alive candidates and e_s = expf(u_s - a), in float32:
+ *     num[b] = sum over the slots s in ascending order of e_s * mass[s, b] for the bytes b, num[256] the same sum of
+ *     e_s * (mass[s, 256] + .. + mass[s, 259]) over the candidates at the root, Z = the sum of all 257 in a fixed order.
+ *     byte null: out_next float32 [n_groups, GLB_BYTELM_ROW] = logf(num) - logf(Z), -inf where num is 0; out_logZ float32
+ *     [n_groups] = a + logf(Z).  A group without an alive candidate or without mass gets -inf everywhere, no NaN.
+ *     byte int32 [n_groups] given: nothing of the above is written; a group whose byte is outside 0 .. 256 is left alone;
+ *     else logp[g] += the row's entry for the byte, and every alive candidate moves to sel[s, byte] with
+ *     w = fl32(u + logf(mass[s, byte])), or dies (alive 0, w -inf) when there is no such child, its mass is not above 0, or
+ *     the byte is 256 (EOS ends the group); fresh[g], if given, becomes 1.  Writes node, w, alive, logp in place.
+ *     One wave per group.  A group's outputs depend on that group's inputs alone: the same bytes however groups are batched.
+ * Each call: no workspace beyond its arguments, nothing waits, synchronises or allocates; safe under stream capture.
+ * GLB_EINVAL before any launch: struct_size wrong; width outside 1 .. 64; n_groups or n_nodes not positive; n_groups * width or
+ * n_nodes beyond 31 bits; root outside the trie; a null pointer among those the call reads or writes.
+ */
+#define GLB_BYTELM_SEL 260
+#define GLB_BYTELM_ROW 257
+#define GLB_BYTELM_LEAVES 4
+typedef struct glb_bytelm_args {
+  uint32_t struct_size; /* sizeof this block - ABI guard */
+  int32_t width;        /* 1 .. 64 */
+  int64_t n_groups;
+  int64_t n_nodes;
+  int32_t root;
+  const int32_t *child_ptr; /* [n_nodes + 1] */
+  const int32_t *child_idx;
+  const int16_t *child_sym;
+  const int32_t *leaf_token; /* [n_nodes] */
+  int32_t *node;             /* [n_slots] each */
+  int32_t *alive;
+  const float *u;
+  float *w;
+  int32_t *sel;      /* [n_slots, GLB_BYTELM_SEL] */
+  const float *mass; /* [n_slots, GLB_BYTELM_SEL] */
+  int32_t *fresh;    /* [n_groups], nullable */
+  int32_t *out_parent; /* [n_slots] each */
+  int32_t *out_token;
+  int32_t *out_node;
+  int32_t *out_alive;
+  float *out_u;
+  float *out_w;
+  int32_t *out_spawned;   /* [n_slots] */
+  int32_t *out_n_spawned; /* [1] */
+  const int32_t *byte;    /* [n_groups], nullable */
+  float *out_next;        /* [n_groups, GLB_BYTELM_ROW] */
+  float *out_logZ;        /* [n_groups] */
+  float *logp;            /* [n_groups] */
+} glb_bytelm_args;
+int glb_bytelm_children(const glb_bytelm_args *args, void *hip_stream);
+int glb_bytelm_extend(const glb_bytelm_args *args, void *hip_stream);
+int glb_bytelm_next(const glb_bytelm_args *args, void *hip_stream);
+
 /* Philox4x32-10 block function, exposed so hosts can reproduce the device draws. */
 void glb_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 
