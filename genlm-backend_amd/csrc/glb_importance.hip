@@ -4,13 +4,9 @@
 //     qt(j) ∝ exp(y_j + m_j)      token ~ qt      dlogw = (p_tok - lse(p)) - (y_tok - lse(y + m))
 // Two plain launches on the caller's stream; no wave waits inside a launch for anything another wave writes.
 //   imp_stats_kernel   one wave per (unit, 4096-token chunk) - a unit is a logits row when the masks go by row (or there
-//                      are none), else a particle.  The chunk of p and of q in 16-byte loads (the lane layout of
-//                      glb_chunk.hpp: lane l holds vector i = elements (i * 64 + l) * EPV ..), and for each of p, y and
-//                      y + m: the chunk's binary scale N = exp_n(max) and the sum of t = 2^(x log2 e - N - 1) (the hardware's
-//                      v_exp_f32, glb_math.hpp kExpHw).  A lane adds its 64 terms in float32 as four chains of sixteen in load
-//                      order, the four in a fixed tree; floor(lane sum * 2^40) is summed over the wave as an integer.  Out: one
-//                      64-byte record {N_p, N_y, N_z, -, S_p, S_y, S_z}.  With bit masks and N_z == N_y (nearly always) the
-//                      allowed sum takes the terms of the full one: two exponentials an element pair instead of three.
+//                      are none), else a particle.  The chunk of p and of q, and for each of p, y and y + m the chunk's
+//                      binary scale and integer sum, as glb_rowlse.hpp reads and takes them.  Out: one 64-byte record
+//                      {N_p, N_y, N_z, -, S_p, S_y, S_z}.
 //   imp_finish_kernel  one wave per particle.  Folds its unit's records in double (chunk order, lane l the chunks
 //                      [l B, l B + B)), log-sum-exps by a double logarithm, picks the chunk by R1 / 2^64 over the chunks' masses
 //                      of y + m, reads that one chunk of q again - lane l the 64 CONSECUTIVE elements from 64 l, so that the
@@ -73,7 +69,7 @@ __device__ __forceinline__ bool unit_rows(const ImpParams &a, int u, int &row, i
 template <int DTP, int DTQ>
 __global__ __launch_bounds__(64) void imp_stats_kernel(const ImpParams a) {
   constexpr int DTY = DTQ == kNoProposal ? DTP : DTQ;  // the element type y is read in
-  constexpr int EPVP = ElemTraits<DTP>::EPV, EPVY = ElemTraits<DTY>::EPV, NVY = ElemTraits<DTY>::NVC;
+  constexpr int EPVP = ElemTraits<DTP>::EPV;
   const int lane = threadIdx.x;
   const int u = (int)(blockIdx.x / (uint32_t)a.nch), c = (int)(blockIdx.x % (uint32_t)a.nch);
   const int e_base = c * kChunk, V = a.V;
@@ -86,12 +82,8 @@ __global__ __launch_bounds__(64) void imp_stats_kernel(const ImpParams a) {
     u32x4_t rawp[ElemTraits<DTP>::NVC];
     load_chunk_raw<DTP>(prow, e_base, V, lane, rawp);
     float y[64];
-    if constexpr (DTQ != kNoProposal) {  // both chunks' loads are under way before the first is used
-      u32x4_t rawq[NVY];
-      load_chunk_raw<DTQ>(row_ptr<DTQ>(a.q, row, a.ld_q), e_base, V, lane, rawq);
-#pragma unroll
-      for (int i = 0; i < NVY; ++i) unpack_vec<DTQ>(rawq[i], &y[i * EPVY]);
-    }
+    // (both chunks' loads are under way before the first is used)
+    if constexpr (DTQ != kNoProposal) chunk_scaled<DTQ>(row_ptr<DTQ>(a.q, row, a.ld_q), e_base, V, lane, a.scale, y);
     {
       float x[64];
 #pragma unroll
@@ -100,65 +92,13 @@ __global__ __launch_bounds__(64) void imp_stats_kernel(const ImpParams a) {
       if (Np != kNegInf) Sp = wave_fix_sum(lane_sum64<EPVP>(x, Np));
       if constexpr (DTQ == kNoProposal) {
 #pragma unroll
-        for (int j = 0; j < 64; ++j) y[j] = x[j];
+        for (int j = 0; j < 64; ++j) y[j] = x[j] * a.scale;  // (times 1.0f: the same bits)
       }
     }
-#pragma unroll
-    for (int j = 0; j < 64; ++j) y[j] *= a.scale;  // (times 1.0f: the same bits)
-    Ny = exp_n(wave_max(lane_max64(y)));
-    if (a.mask_kind == GLB_MASK_NONE) {
-      if (Ny != kNegInf) Sy = wave_fix_sum(lane_sum64<EPVY>(y, Ny));
-      Nz = Ny;
-      Sz = Sy;
-    } else if (a.mask_kind == GLB_MASK_BITS) {
-      // the words that hold this lane's bits: vector i covers EPV bits from bit (lane * EPV) % 32 of word
-      // e_base / 32 + i * (64 * EPV / 32) + lane * EPV / 32
-      const uint32_t *mrow = reinterpret_cast<const uint32_t *>(a.mask) + (int64_t)mid * a.mask_ld;
-      const int nw = (V + 31) >> 5, w0 = (e_base >> 5) + ((lane * EPVY) >> 5), sh = (lane * EPVY) & 31;
-      uint32_t mw[NVY];
-#pragma unroll
-      for (int i = 0; i < NVY; ++i) {
-        const int wi = w0 + i * (64 * EPVY / 32);
-        mw[i] = wi < nw ? mrow[wi] >> sh : 0u;
-      }
-      float zm = kNegInf;
-#pragma unroll
-      for (int j = 0; j < 64; ++j) zm = fmaxf(zm, ((mw[j / EPVY] >> (j % EPVY)) & 1u) ? y[j] : kNegInf);
-      Nz = exp_n(wave_max(zm));
-      if (Nz == Ny) {  // the allowed maximum lies in the chunk's top binade: one term serves both sums
-        if (Ny != kNegInf) {
-          const float bias = term_bias<kExpHw>(Ny);
-          float cy[4] = {0.0f, 0.0f, 0.0f, 0.0f}, cz[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-          for (int j = 0; j < 64; ++j) {
-            const float t = chunk_term<kExpHw>(y[j], bias);
-            cy[(j / EPVY) & 3] += t;
-            cz[(j / EPVY) & 3] += ((mw[j / EPVY] >> (j % EPVY)) & 1u) ? t : 0.0f;
-          }
-          Sy = wave_fix_sum((cy[0] + cy[1]) + (cy[2] + cy[3]));
-          Sz = wave_fix_sum((cz[0] + cz[1]) + (cz[2] + cz[3]));
-        }
-      } else {
-        Sy = wave_fix_sum(lane_sum64<EPVY>(y, Ny));  // (Nz < Ny: Ny is finite)
-#pragma unroll
-        for (int j = 0; j < 64; ++j) y[j] = ((mw[j / EPVY] >> (j % EPVY)) & 1u) ? y[j] : kNegInf;
-        if (Nz != kNegInf) Sz = wave_fix_sum(lane_sum64<EPVY>(y, Nz));
-      }
-    } else {  // GLB_MASK_F32: z = y + m, the floats in y's lane layout
-      if (Ny != kNegInf) Sy = wave_fix_sum(lane_sum64<EPVY>(y, Ny));
-      const char *mrow = reinterpret_cast<const char *>(reinterpret_cast<const float *>(a.mask) + (int64_t)mid * a.mask_ld);
-#pragma unroll
-      for (int i = 0; i < NVY; ++i) {
-#pragma unroll
-        for (int h = 0; h < EPVY / 4; ++h) {
-          float m[4];
-          unpack_vec<kDtF32>(load_vec_guarded<kDtF32>(mrow, e_base + (i * 64 + lane) * EPVY + 4 * h, V), m);
-#pragma unroll
-          for (int k = 0; k < 4; ++k) y[i * EPVY + 4 * h + k] += m[k];
-        }
-      }
-      Nz = exp_n(wave_max(lane_max64(y)));
-      if (Nz != kNegInf) Sz = wave_fix_sum(lane_sum64<EPVY>(y, Nz));
+    switch (a.mask_kind) {  // (wave-uniform)
+      case GLB_MASK_NONE: chunk_sums<DTY, GLB_MASK_NONE>(y, true, a.mask, mid, a.mask_ld, e_base, V, lane, Ny, Sy, Nz, Sz); break;
+      case GLB_MASK_BITS: chunk_sums<DTY, GLB_MASK_BITS>(y, true, a.mask, mid, a.mask_ld, e_base, V, lane, Ny, Sy, Nz, Sz); break;
+      default: chunk_sums<DTY, GLB_MASK_F32>(y, true, a.mask, mid, a.mask_ld, e_base, V, lane, Ny, Sy, Nz, Sz); break;
     }
   }
   if (lane == 0) {

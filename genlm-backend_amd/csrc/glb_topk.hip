@@ -2,12 +2,11 @@
 // glb_beam_select).
 //
 // Per logits row, with y = fl32(x * scale), m its mask row and key = fl32(y + m):
-//   topk_rows_kernel    one workgroup of four waves per row, glb_score.hip's geometry: wave w takes the row's 4096-token
-//                       chunks w, w + 4, ... in order - the chunk in 16-byte loads with its mask words or floats, for y and
-//                       y + m the chunk's binary scale and integer sum (glb_rowlse.hpp) folded into the wave's running
-//                       (scale, double sum), and the chunk's keys offered to the wave's sorted list of its k best
-//                       (glb_topk.hpp).  The four lists meet in LDS: an entry's rank is the number of entries above it, ranks
-//                       below k are written.  Thread 0 folds the four waves' sums in wave order.
+//   topk_rows_kernel    one workgroup of four waves per row: wave w takes the row's 4096-token chunks w, w + 4, ... in
+//                       order - the chunk, its sums for y and y + m and every fold are glb_rowlse.hpp's - and offers the
+//                       chunk's keys to the wave's sorted list of its k best (glb_topk.hpp).  The four lists meet in LDS: an
+//                       entry's rank is the number of entries above it, ranks below k are written.  Thread 0 folds the four
+//                       waves' sums in wave order.
 //   beam_select_kernel  one wave per group of B beams: the at most B * k <= 4096 candidates (score + logp of every live beam's
 //                       candidates, a finished beam's own score) are one chunk of the same core, the list's first B entries
 //                       are the group's next beams.
@@ -28,50 +27,23 @@ using namespace glb;
 
 constexpr int kWaves = 4;  // waves per row: part of the reduction tree, not a tuning knob (changing it changes bits)
 
-struct TopkParams {
-  const void *x;
-  int64_t ld;
-  int32_t V, nch;
-  float scale;
-  int64_t n_rows;
-  int32_t n_masks, k;
-  const int32_t *row_mask;  // [n_rows], null = (n_masks == 1 ? 0 : identity)
-  const void *mask;
-  int64_t mask_ld;
+struct TopkParams : RowsParams {
+  int32_t k;
   int32_t *out_token;
   float *out_logp, *out_logp_masked, *out_lse, *out_logZ;
 };
 
-struct alignas(16) WaveAcc {  // what one wave hands to the row's last fold
-  double Wy, Wz;              // sums of the wave's chunks on the scales My, Mz
-  float My, Mz;
-};
-
-// a chunk's (scale, integer sum) into a running (scale, double sum); chunk order is the caller's (glb_score.hip's fold)
-__device__ __forceinline__ void fold_chunk(float N, uint64_t S, float &M, double &W) {
-  if (S == 0) return;
-  if (N > M) {
-    W = W > 0.0 ? ldexp(W, (int)fmaxf(M - N, -4000.0f)) : 0.0;
-    M = N;
-  }
-  W += rec_mass(S, N, M);
-}
-
 template <int DT, int MASK>
 __global__ __launch_bounds__(64 * kWaves) void topk_rows_kernel(const TopkParams a) {
   constexpr int EPV = ElemTraits<DT>::EPV;
-  __shared__ WaveAcc acc[kWaves];
+  __shared__ WaveSums acc[kWaves];
   __shared__ uint64_t lists[kWaves * 64];
   __shared__ double row_lse[2];
   __shared__ int row_has[2];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, V = a.V, k = a.k;
   for (int64_t row = blockIdx.x; row < a.n_rows; row += gridDim.x) {  // (the same trip count for the whole workgroup)
-    int mid = 0;
-    bool mask_ok = true;
-    if constexpr (MASK != GLB_MASK_NONE) {
-      mid = __builtin_amdgcn_readfirstlane(a.row_mask ? a.row_mask[row] : (a.n_masks == 1 ? 0 : (int)row));
-      mask_ok = mid >= 0 && mid < a.n_masks;  // out of range: a row whose mask allows nothing
-    }
+    int mid;
+    const bool mask_ok = row_mask_of<MASK>(a, row, mid);
     const char *xrow = row_ptr<DT>(a.x, row, a.ld);
     float My = kNegInf, Mz = kNegInf;
     double Wy = 0.0, Wz = 0.0;
@@ -80,6 +52,7 @@ __global__ __launch_bounds__(64 * kWaves) void topk_rows_kernel(const TopkParams
       const int e_base = c * kChunk;
       float y[64];
       chunk_scaled<DT>(xrow, e_base, V, lane, a.scale, y);
+      // (not chunk_sums: its one-term form for bit masks costs this kernel scalar registers - profiles/r33)
       const float Ny = exp_n(wave_max(lane_max64(y)));
       float Nz = kNegInf;
       uint64_t Sy = 0, Sz = 0;
@@ -89,7 +62,7 @@ __global__ __launch_bounds__(64 * kWaves) void topk_rows_kernel(const TopkParams
         Sz = Sy;
       } else {
         chunk_add_mask<DT, MASK>(y, mask_ok, a.mask, mid, a.mask_ld, e_base, V, lane);  // y becomes the keys y + m in place
-        Nz =exp_n(wave_max(lane_max64(y)));
+        Nz = exp_n(wave_max(lane_max64(y)));
         if (Nz != kNegInf) Sz = wave_fix_sum(lane_sum64<EPV>(y, Nz));
       }
       fold_chunk(Ny, Sy, My, Wy);
@@ -97,21 +70,12 @@ __global__ __launch_bounds__(64 * kWaves) void topk_rows_kernel(const TopkParams
       select_chunk<EPV>(y, e_base, lane, k, L);
     }
     lists[wave * 64 + lane] = lane < k ? L : 0ull;
-    if (lane == 0) acc[wave] = WaveAcc{Wy, Wz, My, Mz};
+    if (lane == 0) acc[wave] = WaveSums{Wy, Wz, My, Mz};
     __syncthreads();
     if (threadIdx.x == 0) {
-      float Ry = kNegInf, Rz = kNegInf;
-#pragma unroll
-      for (int w = 0; w < kWaves; ++w) {
-        Ry = fmaxf(Ry, acc[w].Wy > 0.0 ? acc[w].My : kNegInf);
-        Rz = fmaxf(Rz, acc[w].Wz > 0.0 ? acc[w].Mz : kNegInf);
-      }
-      double Ty = 0.0, Tz = 0.0;
-#pragma unroll
-      for (int w = 0; w < kWaves; ++w) {  // wave order
-        if (acc[w].Wy > 0.0) Ty += ldexp(acc[w].Wy, (int)fmaxf(acc[w].My - Ry, -4000.0f));
-        if (acc[w].Wz > 0.0) Tz += ldexp(acc[w].Wz, (int)fmaxf(acc[w].Mz - Rz, -4000.0f));
-      }
+      float Ry, Rz;
+      double Ty, Tz;
+      fold_waves(acc, Ty, Ry, Tz, Rz);
       const double lse_y = lse_of(Ty, Ry), lse_z = lse_of(Tz, Rz);
       row_lse[0] = lse_y;
       row_lse[1] = lse_z;
@@ -194,16 +158,6 @@ __global__ __launch_bounds__(64) void beam_select_kernel(const BeamParams a) {
   }
 }
 
-template <int DT>
-void launch_rows(int mask_kind, const TopkParams &p, hipStream_t s) {
-  const dim3 grid((unsigned)(p.n_rows < (1 << 20) ? p.n_rows : (1 << 20))), block(64 * kWaves);
-  switch (mask_kind) {
-    case GLB_MASK_NONE: hipLaunchKernelGGL((topk_rows_kernel<DT, GLB_MASK_NONE>), grid, block, 0, s, p); break;
-    case GLB_MASK_BITS: hipLaunchKernelGGL((topk_rows_kernel<DT, GLB_MASK_BITS>), grid, block, 0, s, p); break;
-    default: hipLaunchKernelGGL((topk_rows_kernel<DT, GLB_MASK_F32>), grid, block, 0, s, p); break;
-  }
-}
-
 }  // namespace
 
 extern "C" {
@@ -214,52 +168,14 @@ int glb_topk_rows(const glb_topk_args *a, void *stream) {
   if (!a->logits) return api_fail(GLB_EINVAL, "%s: logits is null", what);
   if (!a->out_token) return api_fail(GLB_EINVAL, "%s: out_token is null", what);
   if (a->k < 1 || a->k > kTopkMax) return api_fail(GLB_EINVAL, "%s: k %d outside 1..%d", what, a->k, kTopkMax);
-  if (a->dtype < GLB_F32 || a->dtype > GLB_F16) return api_fail(GLB_EINVAL, "%s: bad dtype %d", what, a->dtype);
-  if (a->n_rows <= 0 || a->vocab <= 0)
-    return api_fail(GLB_EINVAL, "%s: n_rows=%lld vocab=%lld must be positive", what, (long long)a->n_rows, (long long)a->vocab);
-  if (a->vocab > 0x7fffff00ll || a->n_rows > 0x7fffffffll) return api_fail(GLB_EINVAL, "%s: vocab / n_rows exceed 31 bits", what);
-  if (a->ld < a->vocab) return api_fail(GLB_EINVAL, "%s: ld %lld < vocab %lld", what, (long long)a->ld, (long long)a->vocab);
-  if (((uintptr_t)a->logits) % (a->dtype == GLB_F32 ? 4 : 2)) return api_fail(GLB_EINVAL, "%s: logits pointer not element aligned", what);
-  if (!(a->logit_scale == a->logit_scale)) return api_fail(GLB_EINVAL, "%s: logit_scale is NaN", what);
-  if (!(a->logit_scale > 0.0f) || a->logit_scale > 3.0e38f)
-    return api_fail(GLB_EINVAL, "%s: logit_scale %g must be positive and finite (0 or a negative scale turns -inf logits into NaN / +inf)", what,
-                    (double)a->logit_scale);
-  if (a->mask_kind == GLB_MASK_PREPARED)
-    return api_fail(GLB_EINVAL, "%s: GLB_MASK_PREPARED is the fused step's layout; give the bit rows (GLB_MASK_BITS)", what);
-  if (a->mask_kind < GLB_MASK_NONE || a->mask_kind > GLB_MASK_F32) return api_fail(GLB_EINVAL, "%s: bad mask_kind %d", what, a->mask_kind);
-  if (a->mask_kind != GLB_MASK_NONE) {
-    if (!a->mask || a->n_masks <= 0) return api_fail(GLB_EINVAL, "%s: mask table missing", what);
-    const int64_t need = a->mask_kind == GLB_MASK_BITS ? (a->vocab + 31) / 32 : a->vocab;
-    if (a->mask_ld < need) return api_fail(GLB_EINVAL, "%s: mask_ld %lld < %lld", what, (long long)a->mask_ld, (long long)need);
-    if (!a->row_mask_id && a->n_masks != 1 && a->n_masks != a->n_rows)
-      return api_fail(GLB_EINVAL, "%s: no mask ids given but n_masks is neither 1 nor the number of rows", what);
-    if (((uintptr_t)a->mask) % 4) return api_fail(GLB_EINVAL, "%s: mask pointer misaligned", what);
-    if (a->n_masks > 0x7fffffffll) return api_fail(GLB_EINVAL, "%s: n_masks exceeds 31 bits", what);
-  }
+  const RowsView v = rows_view(a);
+  if (const int rc = rows_args_ok(what, v)) return rc;
 
-  TopkParams p{};
-  p.x = a->logits;
-  p.ld = a->ld;
-  p.V = (int32_t)a->vocab;
-  p.nch = (int32_t)((a->vocab + kChunk - 1) / kChunk);
-  p.scale = a->logit_scale;
-  p.n_rows = a->n_rows;
-  p.n_masks = (int32_t)a->n_masks;
-  p.k = a->k;
-  p.row_mask = a->mask_kind == GLB_MASK_NONE ? nullptr : a->row_mask_id;
-  p.mask = a->mask;
-  p.mask_ld = a->mask_ld;
-  p.out_token = a->out_token;
-  p.out_logp = a->out_logp;
-  p.out_logp_masked = a->out_logp_masked;
-  p.out_lse = a->out_lse;
-  p.out_logZ = a->out_logZ;
-  hipStream_t s = (hipStream_t)stream;
-  switch (a->dtype) {
-    case GLB_F32: launch_rows<kDtF32>(a->mask_kind, p, s); break;
-    case GLB_BF16: launch_rows<kDtBf16>(a->mask_kind, p, s); break;
-    default: launch_rows<kDtF16>(a->mask_kind, p, s); break;
-  }
+  const TopkParams p{rows_params(v), a->k, a->out_token, a->out_logp, a->out_logp_masked, a->out_lse, a->out_logZ};
+  launch_rows(v, [&](auto dt, auto mk) {
+    hipLaunchKernelGGL((topk_rows_kernel<decltype(dt)::value, decltype(mk)::value>), rows_grid(p.n_rows), dim3(64 * kWaves), 0,
+                       (hipStream_t)stream, p);
+  });
   return glb::launched(what);
 }
 

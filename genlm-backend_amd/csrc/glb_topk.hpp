@@ -3,7 +3,7 @@
 //     (monotone bits of the key << 32) | ~index        0: no entry
 // so that an unsigned maximum yields the largest key and, among equal keys, the lowest index.  -0 is folded into +0 before the
 // bits are taken; a key that is not above -inf (NaN too) packs to 0 and is never selected.
-// select_chunk offers the wave 64 keys a lane (a 4096-index chunk in the lane layout of glb_chunk.hpp, or EPV = 1: index
+// select_chunk offers the wave 64 keys a lane (a 4096-index chunk as glb_rowlse.hpp reads it, or EPV = 1: index
 // j * 64 + lane): the chunk is skipped when no lane's largest key reaches the list's k-th entry; otherwise every lane finds its
 // largest packed value below its ceiling (a statically unrolled pass: no register number depends on data), the wave takes
 // the maxima above the threshold one by one into the list (a lane-neighbour shift), the lanes that gave one lower their ceiling
@@ -13,8 +13,6 @@
 
 #include <cstdint>
 
-#include "../../include/glb.h"
-#include "glb_chunk.hpp"
 #include "glb_rowlse.hpp"
 
 namespace glb {
@@ -37,56 +35,6 @@ __device__ __forceinline__ uint64_t pack_entry(float key, uint32_t nidx) {
 }
 __device__ __forceinline__ int32_t entry_index(uint64_t e) { return (int32_t)~(uint32_t)e; }
 __device__ __forceinline__ float entry_key(uint64_t e) { return mono_key((uint32_t)(e >> 32)); }
-
-// the wave's 64 values a lane of the chunk at e_base: y = fl32(x * scale) (times 1.0f: the same bits), -inf beyond the row
-template <int DT>
-__device__ __forceinline__ void chunk_scaled(const char *xrow, int e_base, int V, int lane, float scale, float (&y)[64]) {
-  constexpr int EPV = ElemTraits<DT>::EPV, NVC = ElemTraits<DT>::NVC;
-  u32x4_t raw[NVC];
-  load_chunk_raw<DT>(xrow, e_base, V, lane, raw);
-#pragma unroll
-  for (int i = 0; i < NVC; ++i) unpack_vec<DT>(raw[i], &y[i * EPV]);
-#pragma unroll
-  for (int j = 0; j < 64; ++j) y[j] *= scale;
-}
-
-// y becomes the keys y + m in place: MASK a GLB_MASK_* kind (raw bit rows or float rows), `mid` the row's mask, !mask_ok a
-// mask that allows nothing
-template <int DT, int MASK>
-__device__ __forceinline__ void chunk_add_mask(float (&y)[64], bool mask_ok, const void *mask, int mid, int64_t mask_ld, int e_base,
-                                               int V, int lane) {
-  constexpr int EPV = ElemTraits<DT>::EPV, NVC = ElemTraits<DT>::NVC;
-  if constexpr (MASK == GLB_MASK_NONE) return;
-  if (!mask_ok) {
-#pragma unroll
-    for (int j = 0; j < 64; ++j) y[j] = kNegInf;
-  } else if constexpr (MASK == GLB_MASK_BITS) {
-    // the words that hold this lane's bits: vector i covers EPV bits from bit (lane * EPV) % 32 of word
-    // e_base / 32 + i * (64 * EPV / 32) + lane * EPV / 32
-    const uint32_t *mrow = reinterpret_cast<const uint32_t *>(mask) + (int64_t)mid * mask_ld;
-    const int nw = (V + 31) >> 5, w0 = (e_base >> 5) + ((lane * EPV) >> 5), sh = (lane * EPV) & 31;
-    uint32_t mw[NVC];
-#pragma unroll
-    for (int i = 0; i < NVC; ++i) {
-      const int wi = w0 + i * (64 * EPV / 32);
-      mw[i] = wi < nw ? mrow[wi] >> sh : 0u;
-    }
-#pragma unroll
-    for (int j = 0; j < 64; ++j) y[j] = ((mw[j / EPV] >> (j % EPV)) & 1u) ? y[j] : kNegInf;
-  } else {  // GLB_MASK_F32: the floats in y's lane layout
-    const char *mrow = reinterpret_cast<const char *>(reinterpret_cast<const float *>(mask) + (int64_t)mid * mask_ld);
-#pragma unroll
-    for (int i = 0; i < NVC; ++i) {
-#pragma unroll
-      for (int h = 0; h < EPV / 4; ++h) {
-        float m[4];
-        unpack_vec<kDtF32>(load_vec_guarded<kDtF32>(mrow, e_base + (i * 64 + lane) * EPV + 4 * h, V), m);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) y[i * EPV + 4 * h + q] += m[q];
-      }
-    }
-  }
-}
 
 // wave maximum of an unsigned 64-bit value, wave-uniform (wave_scan_u64's moves: a lane without a source is offered 0)
 template <int CTRL, int ROW_MASK>

@@ -1,14 +1,14 @@
 // glb_truncate.hip - the keep set of top-k, top-p (nucleus) and min-p truncation as one bit row per logits row (include/glb.h:
 // glb_truncate_rows).
 //
-// Per logits row, with y = fl32(x * scale), m its mask row, key = fl32(y + m) (glb_topk.hpp's keys) and u = key_mono(key), the
+// Per logits row, with y = fl32(x * scale), m its mask row, key = fl32(y + m) (glb_rowlse.hpp's keys) and u = key_mono(key), the
 // keys' order as unsigned order: the row's threshold is the largest of
 //   tau_k   the top_k-th largest key             an exact radix select over u by integer counts
 //   tau_p   the nucleus boundary inside key >= tau_k   the same select weighted by integer masses
 //   tau_m   fl32(key_max + log_min_p)
 // and the keep set {key > -inf, key >= tau} is written as raw GLB_MASK_BITS words.
-// truncate_rows_kernel  one workgroup of four waves per row, glb_topk.hip's geometry: wave w streams the row's 4096-token chunks
-//                       w, w + 4, ... in 16-byte loads, once per pass:
+// truncate_rows_kernel  one workgroup of four waves per row: wave w streams the row's 4096-token chunks w, w + 4, ...
+//                       (glb_rowlse.hpp's reader), once per pass:
 //                         1  the largest key and the number of finite keys
 //                         2  a select, digit by digit (11, 11 and 10 bits of u, most significant first): every key whose higher
 //                            digits equal the chosen prefix adds 1 and its mass to its digit's bin in LDS, wave 0 sums the bins
@@ -47,17 +47,9 @@ constexpr int64_t kVocabMax = 1ll << 24;
 __host__ __device__ constexpr int level_shift(int l) { return l == 0 ? 21 : (l == 1 ? 10 : 0); }
 __host__ __device__ constexpr int level_bits(int l) { return l == 2 ? 10 : 11; }
 
-struct TruncParams {
-  const void *x;
-  int64_t ld;
-  int32_t V, nch;
-  float scale;
-  int64_t n_rows;
-  int32_t n_masks, top_k;  // top_k: 0 = off (the host caps it above any vocab)
+struct TruncParams : RowsParams {
+  int32_t top_k;  // 0 = off (the host caps it above any vocab)
   float top_p, log_min_p;
-  const int32_t *row_mask;  // [n_rows], null = (n_masks == 1 ? 0 : identity)
-  const void *mask;
-  int64_t mask_ld;
   uint32_t *out_bits;
   int64_t out_ld;
   float *out_threshold, *out_logmass;
@@ -121,12 +113,8 @@ __global__ __launch_bounds__(64 * kWaves) void truncate_rows_kernel(const TruncP
   __shared__ Sel s_sel;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, V = a.V, nw = (V + 31) >> 5;
   for (int64_t row = blockIdx.x; row < a.n_rows; row += gridDim.x) {  // (the same trip count for the whole workgroup)
-    int mid = 0;
-    bool mask_ok = true;
-    if constexpr (MASK != GLB_MASK_NONE) {
-      mid = __builtin_amdgcn_readfirstlane(a.row_mask ? a.row_mask[row] : (a.n_masks == 1 ? 0 : (int)row));
-      mask_ok = mid >= 0 && mid < a.n_masks;  // out of range: a row whose mask allows nothing
-    }
+    int mid;
+    const bool mask_ok = row_mask_of<MASK>(a, row, mid);
     const char *xrow = row_ptr<DT>(a.x, row, a.ld);
     uint32_t *orow = a.out_bits + row * a.out_ld;
     auto keys_of = [&](int e_base, float(&y)[64]) {
@@ -295,16 +283,6 @@ __global__ __launch_bounds__(64 * kWaves) void truncate_rows_kernel(const TruncP
   }
 }
 
-template <int DT>
-void launch_rows(int mask_kind, const TruncParams &p, hipStream_t s) {
-  const dim3 grid((unsigned)(p.n_rows < (1 << 20) ? p.n_rows : (1 << 20))), block(64 * kWaves);
-  switch (mask_kind) {
-    case GLB_MASK_NONE: hipLaunchKernelGGL((truncate_rows_kernel<DT, GLB_MASK_NONE>), grid, block, 0, s, p); break;
-    case GLB_MASK_BITS: hipLaunchKernelGGL((truncate_rows_kernel<DT, GLB_MASK_BITS>), grid, block, 0, s, p); break;
-    default: hipLaunchKernelGGL((truncate_rows_kernel<DT, GLB_MASK_F32>), grid, block, 0, s, p); break;
-  }
-}
-
 }  // namespace
 
 extern "C" {
@@ -318,57 +296,19 @@ int glb_truncate_rows(const glb_truncate_args *a, void *stream) {
   if (a->top_k < 0) return api_fail(GLB_EINVAL, "%s: top_k %lld is negative", what, (long long)a->top_k);
   if (!(a->top_p > 0.0f) || a->top_p > 1.0f) return api_fail(GLB_EINVAL, "%s: top_p %g outside (0, 1]", what, (double)a->top_p);
   if (!(a->log_min_p <= 0.0f)) return api_fail(GLB_EINVAL, "%s: log_min_p %g must be at most 0", what, (double)a->log_min_p);
-  if (a->dtype < GLB_F32 || a->dtype > GLB_F16) return api_fail(GLB_EINVAL, "%s: bad dtype %d", what, a->dtype);
-  if (a->n_rows <= 0 || a->vocab <= 0)
-    return api_fail(GLB_EINVAL, "%s: n_rows=%lld vocab=%lld must be positive", what, (long long)a->n_rows, (long long)a->vocab);
   if (a->vocab > kVocabMax) return api_fail(GLB_EINVAL, "%s: vocab %lld above 2^24 (a row's masses are summed in 64 bits)", what, (long long)a->vocab);
   if (a->n_rows > 0x7fffffffll) return api_fail(GLB_EINVAL, "%s: n_rows exceeds 31 bits", what);
-  if (a->ld < a->vocab) return api_fail(GLB_EINVAL, "%s: ld %lld < vocab %lld", what, (long long)a->ld, (long long)a->vocab);
+  const RowsView v = rows_view(a);
+  if (const int rc = rows_args_ok(what, v)) return rc;
   if (a->out_ld < (a->vocab + 31) / 32)
     return api_fail(GLB_EINVAL, "%s: out_ld %lld < %lld words", what, (long long)a->out_ld, (long long)((a->vocab + 31) / 32));
-  if (((uintptr_t)a->logits) % (a->dtype == GLB_F32 ? 4 : 2)) return api_fail(GLB_EINVAL, "%s: logits pointer not element aligned", what);
-  if (!(a->logit_scale == a->logit_scale)) return api_fail(GLB_EINVAL, "%s: logit_scale is NaN", what);
-  if (!(a->logit_scale > 0.0f) || a->logit_scale > 3.0e38f)
-    return api_fail(GLB_EINVAL, "%s: logit_scale %g must be positive and finite (0 or a negative scale turns -inf logits into NaN / +inf)", what,
-                    (double)a->logit_scale);
-  if (a->mask_kind == GLB_MASK_PREPARED)
-    return api_fail(GLB_EINVAL, "%s: GLB_MASK_PREPARED is the fused step's layout; give the bit rows (GLB_MASK_BITS)", what);
-  if (a->mask_kind < GLB_MASK_NONE || a->mask_kind > GLB_MASK_F32) return api_fail(GLB_EINVAL, "%s: bad mask_kind %d", what, a->mask_kind);
-  if (a->mask_kind != GLB_MASK_NONE) {
-    if (!a->mask || a->n_masks <= 0) return api_fail(GLB_EINVAL, "%s: mask table missing", what);
-    const int64_t need = a->mask_kind == GLB_MASK_BITS ? (a->vocab + 31) / 32 : a->vocab;
-    if (a->mask_ld < need) return api_fail(GLB_EINVAL, "%s: mask_ld %lld < %lld", what, (long long)a->mask_ld, (long long)need);
-    if (!a->row_mask_id && a->n_masks != 1 && a->n_masks != a->n_rows)
-      return api_fail(GLB_EINVAL, "%s: no mask ids given but n_masks is neither 1 nor the number of rows", what);
-    if (((uintptr_t)a->mask) % 4) return api_fail(GLB_EINVAL, "%s: mask pointer misaligned", what);
-    if (a->n_masks > 0x7fffffffll) return api_fail(GLB_EINVAL, "%s: n_masks exceeds 31 bits", what);
-  }
 
-  TruncParams p{};
-  p.x = a->logits;
-  p.ld = a->ld;
-  p.V = (int32_t)a->vocab;
-  p.nch = (int32_t)((a->vocab + kChunk - 1) / kChunk);
-  p.scale = a->logit_scale;
-  p.n_rows = a->n_rows;
-  p.n_masks = (int32_t)a->n_masks;
-  p.top_k = (int32_t)(a->top_k < 2 * kVocabMax ? a->top_k : 2 * kVocabMax);  // (at or above the vocabulary: off for every row)
-  p.top_p = a->top_p;
-  p.log_min_p = a->log_min_p;
-  p.row_mask = a->mask_kind == GLB_MASK_NONE ? nullptr : a->row_mask_id;
-  p.mask = a->mask;
-  p.mask_ld = a->mask_ld;
-  p.out_bits = a->out_bits;
-  p.out_ld = a->out_ld;
-  p.out_threshold = a->out_threshold;
-  p.out_kept = a->out_kept;
-  p.out_logmass = a->out_logmass;
-  hipStream_t s = (hipStream_t)stream;
-  switch (a->dtype) {
-    case GLB_F32: launch_rows<kDtF32>(a->mask_kind, p, s); break;
-    case GLB_BF16: launch_rows<kDtBf16>(a->mask_kind, p, s); break;
-    default: launch_rows<kDtF16>(a->mask_kind, p, s); break;
-  }
+  const int32_t top_k = (int32_t)(a->top_k < 2 * kVocabMax ? a->top_k : 2 * kVocabMax);  // (at or above the vocabulary: off for every row)
+  const TruncParams p{rows_params(v), top_k, a->top_p, a->log_min_p, a->out_bits, a->out_ld, a->out_threshold, a->out_logmass, a->out_kept};
+  launch_rows(v, [&](auto dt, auto mk) {
+    hipLaunchKernelGGL((truncate_rows_kernel<decltype(dt)::value, decltype(mk)::value>), rows_grid(p.n_rows), dim3(64 * kWaves), 0,
+                       (hipStream_t)stream, p);
+  });
   return glb::launched(what);
 }
 

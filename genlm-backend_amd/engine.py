@@ -451,15 +451,7 @@ class HipEngine:
         a.row_of = None if row_of is None else row_of.data_ptr()
         a.mask_kind = mask_kind
         if mask_kind != MASK_NONE:
-            if mask.device != self.device:
-                raise ValueError(f"mask on {mask.device}, engine on {self.device}")
-            if mask.dim() != 2 or mask.stride(1) != 1:
-                raise ValueError("mask must be 2-D with unit inner stride (rows may be strided)")
-            want = torch.float32 if mask_kind == MASK_F32 else torch.int32
-            if mask.dtype != want:
-                raise TypeError(f"mask dtype {mask.dtype}, expected {want}")
-            a.mask, a.n_masks = mask.data_ptr(), mask.shape[0]
-            a.mask_ld = mask.stride(0) if mask.shape[0] > 1 else mask.shape[1]
+            self._mask_block(a, mask_kind, mask, V)
             a.mask_id = None if mask_id is None else mask_id.data_ptr()
             a.row_mask_id = None if row_mask_id is None else row_mask_id.data_ptr()
         a.seed, a.offset, a.particle_base = seed, offset, particle_base
@@ -492,54 +484,13 @@ class HipEngine:
         for w in want:
             if w not in self.SCORE_OUTPUTS:
                 raise ValueError(f"want names {w!r}; the outputs are {self.SCORE_OUTPUTS}")
-        if logits.dim() != 2 or logits.stride(1) != 1:
-            raise ValueError("logits must be 2-D with unit inner stride")
-        if logits.dtype not in _DT:
-            raise TypeError(f"unsupported logits dtype {logits.dtype}")
-        if logits.device != self.device:
-            raise ValueError(f"logits on {logits.device}, engine on {self.device}")
-        n_rows, width = logits.shape
-        V = width if vocab is None else vocab
-        if not 0 < V <= width:
-            raise ValueError(f"vocab {V} outside (0, {width}]")
-        if n_rows == 0:
-            raise ValueError("no rows to score")
-        if not 0 < logit_scale < float("inf"):  # (NaN too; 0 or a negative scale would turn -inf logits into NaN / +inf)
-            raise ValueError(f"logit_scale must be positive and finite, got {logit_scale!r}")
-        self._check_dev(tokens, row_mask_id, seq_start)
-        if tokens.dtype != torch.int32 or tokens.shape != (n_rows,) or not tokens.is_contiguous():
-            raise ValueError("tokens must be a contiguous int32 [n_rows] tensor")
-        if mask_kind not in (MASK_NONE, MASK_BITS, MASK_F32):
-            raise ValueError(f"bad mask_kind {mask_kind}")
         a = _lib.ScoreArgs()
         a.struct_size = C.sizeof(_lib.ScoreArgs)
-        a.logits, a.dtype = logits.data_ptr(), _DT[logits.dtype]
-        a.n_rows, a.vocab, a.logit_scale = n_rows, V, logit_scale
-        a.ld = logits.stride(0) if n_rows > 1 else max(width, logits.stride(0))
+        n_rows, _ = self._row_block(a, logits, vocab, logit_scale, mask_kind, mask, row_mask_id, empty="no rows to score")
+        self._check_dev(tokens, seq_start)
+        if tokens.dtype != torch.int32 or tokens.shape != (n_rows,) or not tokens.is_contiguous():
+            raise ValueError("tokens must be a contiguous int32 [n_rows] tensor")
         a.token = tokens.data_ptr()
-        a.mask_kind = mask_kind
-        if mask_kind != MASK_NONE:
-            if mask is None:
-                raise ValueError("mask_kind given without a mask table")
-            if mask.device != self.device:
-                raise ValueError(f"mask on {mask.device}, engine on {self.device}")
-            if mask.dim() != 2 or mask.stride(1) != 1:
-                raise ValueError("mask must be 2-D with unit inner stride (rows may be strided)")
-            want_dt = torch.float32 if mask_kind == MASK_F32 else torch.int32
-            if mask.dtype != want_dt:
-                raise TypeError(f"mask dtype {mask.dtype}, expected {want_dt}")
-            if mask.shape[1] < (V if mask_kind == MASK_F32 else (V + 31) // 32):
-                raise ValueError(f"mask rows of {mask.shape[1]} elements are too short for {V} tokens")
-            if row_mask_id is not None and (row_mask_id.dtype != torch.int32 or row_mask_id.shape != (n_rows,)
-                                            or not row_mask_id.is_contiguous()):
-                raise ValueError("row_mask_id must be a contiguous int32 [n_rows] tensor")
-            if row_mask_id is None and mask.shape[0] not in (1, n_rows):
-                raise ValueError(f"no row_mask_id given but the table has {mask.shape[0]} rows: neither 1 nor {n_rows}")
-            a.mask, a.n_masks = mask.data_ptr(), mask.shape[0]
-            a.mask_ld = mask.stride(0) if mask.shape[0] > 1 else mask.shape[1]
-            a.row_mask_id = None if row_mask_id is None else row_mask_id.data_ptr()
-        elif mask is not None or row_mask_id is not None:
-            raise ValueError("a mask table or row_mask_id given with MASK_NONE")
         out = {w: self._f32(n_rows) for w in want}
         for w in want:
             setattr(a, "out_" + w, out[w].data_ptr())
@@ -569,9 +520,26 @@ class HipEngine:
             check(self.lib.glb_score_seq_sums(_ptr(src), values.numel(), _ptr(seq_start), out.numel(), _ptr(out), self._stream()))
         return out
 
-    def _row_block(self, a, logits, vocab, logit_scale, mask_kind, mask, row_mask_id):
-        """The logits and mask fields that glb_topk_args and glb_truncate_args share, checked and written into `a`;
-        returns (n_rows, vocab)."""
+    def _mask_block(self, a, mask_kind, mask, V):
+        """The mask table's fields (mask, n_masks, mask_ld) of an argument block that reads bit rows or float rows as they
+        lie, checked against `V` tokens and written into `a`; which row reads which mask is the caller's."""
+        if mask is None:
+            raise ValueError("mask_kind given without a mask table")
+        if mask.device != self.device:
+            raise ValueError(f"mask on {mask.device}, engine on {self.device}")
+        if mask.dim() != 2 or mask.stride(1) != 1:
+            raise ValueError("mask must be 2-D with unit inner stride (rows may be strided)")
+        want_dt = torch.float32 if mask_kind == MASK_F32 else torch.int32
+        if mask.dtype != want_dt:
+            raise TypeError(f"mask dtype {mask.dtype}, expected {want_dt}")
+        if mask.shape[1] < (V if mask_kind == MASK_F32 else (V + 31) // 32):
+            raise ValueError(f"mask rows of {mask.shape[1]} elements are too short for {V} tokens")
+        a.mask, a.n_masks = mask.data_ptr(), mask.shape[0]
+        a.mask_ld = mask.stride(0) if mask.shape[0] > 1 else mask.shape[1]
+
+    def _row_block(self, a, logits, vocab, logit_scale, mask_kind, mask, row_mask_id, empty="no rows to select from"):
+        """The logits and mask fields that glb_score_args, glb_topk_args and glb_truncate_args share, checked and written
+        into `a`; returns (n_rows, vocab).  `empty`: what to say of a logits tensor without rows."""
         if logits.dim() != 2 or logits.stride(1) != 1:
             raise ValueError("logits must be 2-D with unit inner stride")
         if logits.dtype not in _DT:
@@ -583,7 +551,7 @@ class HipEngine:
         if not 0 < V <= width:
             raise ValueError(f"vocab {V} outside (0, {width}]")
         if n_rows == 0:
-            raise ValueError("no rows to select from")
+            raise ValueError(empty)
         if not 0 < logit_scale < float("inf"):  # (NaN too; 0 or a negative scale would turn -inf logits into NaN / +inf)
             raise ValueError(f"logit_scale must be positive and finite, got {logit_scale!r}")
         self._check_dev(row_mask_id)
@@ -594,24 +562,12 @@ class HipEngine:
         a.ld = logits.stride(0) if n_rows > 1 else max(width, logits.stride(0))
         a.mask_kind = mask_kind
         if mask_kind != MASK_NONE:
-            if mask is None:
-                raise ValueError("mask_kind given without a mask table")
-            if mask.device != self.device:
-                raise ValueError(f"mask on {mask.device}, engine on {self.device}")
-            if mask.dim() != 2 or mask.stride(1) != 1:
-                raise ValueError("mask must be 2-D with unit inner stride (rows may be strided)")
-            want_dt = torch.float32 if mask_kind == MASK_F32 else torch.int32
-            if mask.dtype != want_dt:
-                raise TypeError(f"mask dtype {mask.dtype}, expected {want_dt}")
-            if mask.shape[1] < (V if mask_kind == MASK_F32 else (V + 31) // 32):
-                raise ValueError(f"mask rows of {mask.shape[1]} elements are too short for {V} tokens")
+            self._mask_block(a, mask_kind, mask, V)
             if row_mask_id is not None and (row_mask_id.dtype != torch.int32 or row_mask_id.shape != (n_rows,)
                                             or not row_mask_id.is_contiguous()):
                 raise ValueError("row_mask_id must be a contiguous int32 [n_rows] tensor")
             if row_mask_id is None and mask.shape[0] not in (1, n_rows):
                 raise ValueError(f"no row_mask_id given but the table has {mask.shape[0]} rows: neither 1 nor {n_rows}")
-            a.mask, a.n_masks = mask.data_ptr(), mask.shape[0]
-            a.mask_ld = mask.stride(0) if mask.shape[0] > 1 else mask.shape[1]
             a.row_mask_id = None if row_mask_id is None else row_mask_id.data_ptr()
         elif mask is not None or row_mask_id is not None:
             raise ValueError("a mask table or row_mask_id given with MASK_NONE")
