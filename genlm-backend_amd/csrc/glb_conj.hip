@@ -474,7 +474,7 @@ int glb_conj_number(const glb_conj_args *a, void *stream) {
   for (int64_t base = 0; base < d->n; base += a->cand_rows) {
     const int64_t n = d->n - base < a->cand_rows ? d->n - base : a->cand_rows;
     unsigned blocks = 0;
-    if (const int rc = number_grid("conj: the device's CU count", n, CONJ_THREADS, &blocks)) return rc;
+    if (const int rc = stride_grid("conj: the device's CU count", &blocks, n, CONJ_THREADS)) return rc;
     hipLaunchKernelGGL(conj_enter_kernel, dim3(blocks), dim3(CONJ_THREADS), 0, st, c, base, n, d->state_out);
     number_launches(c, blocks, base, n, d->state_out, base + n >= d->n, st);
   }

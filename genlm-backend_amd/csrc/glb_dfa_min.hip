@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 #include "../../include/glb.h"
+#include "glb_block.hpp"  // (mix64)
 #include "glb_common.hpp"
 
 namespace {
@@ -29,14 +30,6 @@ struct Min {
   uint64_t mask;             // slots - 1
   int32_t *status;
 };
-
-__device__ inline uint64_t mix64(uint64_t x) {  // (the finaliser of splitmix64)
-  x ^= x >> 30;
-  x *= 0xbf58476d1ce4e5b9ull;
-  x ^= x >> 27;
-  x *= 0x94d049bb133111ebull;
-  return x ^ (x >> 31);
-}
 
 // The lane's share of state s's signature under the classes `src`: succ[k] the class behind byte lane + 64 k (-1: the arc is
 // absent - delta has none, its destination lies outside [0, n_states) or is not kept), w[k] the arc's bits (0 where absent

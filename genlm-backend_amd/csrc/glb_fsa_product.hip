@@ -1,35 +1,29 @@
 // glb_fsa_product.hip — the product of two byte automata on the device (include/glb.h: glb_fsa_product_round / glb_fsa_live;
-// DESIGN.md §22).  A breadth-first search over the pairs of states: a round expands the frontier - the states the round before
-// numbered - a block per state, a thread per byte, so a wave reads 64 consecutive entries of a delta row of either operand.
-// A target pair meets its equals in an open-addressing table keyed by the full 64-bit pair (no collisions to flag); a new
-// pair's slot keeps the smallest arc index (frontier position * 256 + byte) that found it, and a scan over the frontier's
-// winning arcs hands out the ids: the numbering is the host queue search's, whatever order the atomics take.  The frontier's
-// bounds live in the status words and every grid strides over them: no launch depends on a host read.  Then liveness, swept
-// in place to its fixed point.  Everything read from device memory is range-checked.
+// DESIGN.md §22).  A breadth-first search over the pairs of states: the queue search of glb_search.hpp with the whole of the
+// queue a round (chunk = max_states), so a round expands the frontier - the states the round before numbered - a block per
+// state, a thread per byte: a wave reads 64 consecutive entries of a delta row of either operand.  A target pair meets its
+// equals in an open-addressing table keyed by the full 64-bit pair (no collisions to flag); a new pair's slot keeps the
+// smallest arc index (frontier position * 256 + byte) that found it, and count, scan, number, resolve and advance - the
+// shared kernels - hand out the ids: the numbering is the host queue search's, whatever order the atomics take.  This file
+// keeps the table, the expansion and what a pair is.  Then liveness, swept in place to its fixed point.  Everything read
+// from device memory is range-checked.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/glb.h"
 #include "glb_common.hpp"
+#include "glb_search.hpp"
 
 namespace {
 
-// status: the search [0 .. 7], liveness [8 .. 11]
-enum { P_ROUNDS = 0, P_CONVERGED = 1, P_FLAGS = 2, P_COUNT = 3, P_LO = 4, P_HI = 5, P_NEXT = 6, P_REACHED = 7,
-       L_SWEEPS = 8, L_CONVERGED = 9, L_FLAGS = 10, L_CHANGED = 11, P_ENTERED = 12 };
-enum { F_OVERFLOW = 1, F_TABLE = 2 };
-constexpr int FSA_THREADS = 256;      // the 256 bytes of one state; liveness: four waves, a state each
-constexpr int SCAN_THREADS = 1024;
-constexpr int FSA_MAX_ROUNDS = 65536;  // rounds / sweeps one call may enqueue
-constexpr int32_t FSA_MAX_STATES = 1 << 22;  // (an arc index frontier position * 256 + byte stays an int32)
-constexpr int32_t NO_ARC = 0x7fffffff;
+constexpr int FSA_THREADS = SEARCH_THREADS;  // the 256 bytes of one state; liveness: four waves, a state each
 
 struct Prod {
   int32_t op, n_a, n_b;
   const int32_t *delta_a, *delta_b;
   const uint8_t *acc_a, *acc_b, *live_a, *live_b;
   const float *arc_a, *final_a, *arc_b, *final_b;
-  int32_t max_states;
+  int32_t max_states, chunk;  // (chunk = max_states: a round takes all of the queue)
   unsigned long long *keys;  // [slots]; 0: empty
   int32_t *arcmin;           // [slots]; the smallest arc index of the round that brought the key
   int32_t *ids;              // [slots]; -1 until the key's state is numbered
@@ -38,15 +32,17 @@ struct Prod {
   uint8_t *accepting_out;
   float *arc_out, *final_out;
   int32_t *status;
-};
 
-__device__ inline uint64_t mix64(uint64_t x) {  // (the finaliser of splitmix64)
-  x ^= x >> 30;
-  x *= 0xbf58476d1ce4e5b9ull;
-  x ^= x >> 27;
-  x *= 0x94d049bb133111ebull;
-  return x ^ (x >> 31);
-}
+  // the winning arc's target becomes state `id`: the slot's id, and the pair read back from the key
+  static __device__ bool number(const Prod &p, int64_t id, int32_t, int, int64_t slot) {
+    const uint64_t key = p.keys[slot], nb = (uint64_t)p.n_b + 1;
+    p.ids[slot] = (int32_t)id;
+    p.pairs[2 * id] = (int32_t)(key / nb) - 1;
+    p.pairs[2 * id + 1] = (int32_t)(key % nb) - 1;
+    return true;
+  }
+  static __device__ int32_t id_of(const Prod &p, int64_t slot) { return p.ids[slot]; }
+};
 
 // a component that is not a live state of its automaton is out: -1
 __device__ inline int32_t side(int32_t s, int32_t n, const uint8_t *live) { return s >= 0 && s < n && live[s] ? s : -1; }
@@ -55,11 +51,6 @@ __device__ inline int32_t side(int32_t s, int32_t n, const uint8_t *live) { retu
 __device__ inline uint64_t pair_key(const Prod &p, int32_t a, int32_t b) {
   const bool exists = p.op == GLB_FSA_AND ? (a >= 0 && b >= 0) : p.op == GLB_FSA_SUB ? a >= 0 : (a >= 0 || b >= 0);
   return exists ? (uint64_t)(a + 1) * ((uint64_t)p.n_b + 1) + (uint64_t)(b + 1) : 0ull;
-}
-
-// the flag word as it is now, whatever this thread read before (another block of the same launch may have raised a flag)
-__device__ inline int32_t flags_now(const int32_t *status) {
-  return __hip_atomic_load(&status[P_FLAGS], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // the slot of `key`: the first from its hash's own that is empty or holds it, `fresh` where this call put the key there;
@@ -75,19 +66,11 @@ __device__ inline int64_t claim_slot(const Prod &p, uint64_t key, bool &fresh) {
   return -1;
 }
 
-// more than max_states pairs: flag bit 0 and the count that passed it
-__device__ inline void overflow(const Prod &p, int64_t reached) {
-  atomicMax(&p.status[P_REACHED], (int32_t)(reached < 0x7fffffff ? reached : 0x7fffffff));
-  atomicOr(&p.status[P_FLAGS], F_OVERFLOW);
-}
-
 // n more pairs entered; past max_states that is the overflow
 __device__ inline void count_entered(const Prod &p, int32_t n) {
   const int64_t total = (int64_t)atomicAdd(&p.status[P_ENTERED], n) + n;
-  if (total > p.max_states) overflow(p, total);
+  if (total > p.max_states) overflow(p.status, total);
 }
-
-__device__ inline bool stopped(const int32_t *status) { return status[P_CONVERGED] != 0 || status[P_FLAGS] != 0; }
 
 // accepting and the final weight of the pair (a, b), either side -1 when out
 __device__ inline void pair_final(const Prod &p, int32_t a, int32_t b, bool &acc, float &fin) {
@@ -129,7 +112,7 @@ __global__ void fsa_seed_kernel(Prod p, int32_t start_a, int32_t start_b) {
 }
 
 // Every arc of the frontier: the target pair normalised, its weight written, its key entered.  delta_out takes the target's
-// id where an earlier round numbered it, -1 where the arc does not exist, else -2 - slot until fsa_resolve_kernel; thread 0
+// id where an earlier round numbered it, -1 where the arc does not exist, else -2 - slot until search_resolve_kernel; thread 0
 // writes the state's own accepting / final weight.  The pairs entered are counted as they come: a wave adds its own to the
 // block's count in LDS, and the block hands the count on to the status word in steps of 2^shift = max_states / 4096 or so
 // (atomics on one word from every CU cost tens of nanoseconds each: one a wave would double the search's time) and what is
@@ -146,10 +129,11 @@ __global__ __launch_bounds__(FSA_THREADS) void fsa_expand_kernel(Prod p) {
   __syncthreads();
   if (stop) return;
   const int shift = max(0, 19 - __clz(p.max_states));  // (2^shift <= max_states / 4096)
-  const int32_t lo = p.status[P_LO], hi = min(p.status[P_HI], p.max_states);
+  int32_t lo;
+  const int32_t nk = round_states(p, lo);
   const int byte = (int)threadIdx.x;
   const float ninf = -__builtin_inff();
-  for (int32_t k = (int32_t)blockIdx.x; k < hi - lo; k += (int32_t)gridDim.x) {
+  for (int32_t k = (int32_t)blockIdx.x; k < nk; k += (int32_t)gridDim.x) {
     if (flags_now(p.status)) break;
     const int64_t s = (int64_t)lo + k;
     int32_t a = p.pairs[2 * s], b = p.pairs[2 * s + 1];  // (numbered pairs are normalised; checked all the same)
@@ -164,7 +148,7 @@ __global__ __launch_bounds__(FSA_THREADS) void fsa_expand_kernel(Prod p) {
       const int64_t slot = claim_slot(p, key, fresh);
       if (slot < 0) {
         fresh = false;
-        if (slot == -1) overflow(p, (int64_t)p.mask + 1);
+        if (slot == -1) overflow(p.status, (int64_t)p.mask + 1);
       } else {
         const int32_t id = p.ids[slot];  // (no launch of this round has written it)
         if (id >= 0) {
@@ -204,133 +188,17 @@ __global__ __launch_bounds__(FSA_THREADS) void fsa_expand_kernel(Prod p) {
   if (threadIdx.x == 0 && (block_new & ((1 << shift) - 1))) count_entered(p, block_new & ((1 << shift) - 1));
 }
 
-// whether the arc (frontier position k, byte) is the one that numbers its target: the smallest arc of the round to find it
-__device__ inline bool wins(const Prod &p, int32_t code, int32_t arc, int64_t &slot) {
-  slot = -2 - (int64_t)code;
-  return code <= -2 && (uint64_t)slot <= p.mask && p.arcmin[slot] == arc;
-}
-
-// cnt[k]: the states that frontier state k is the first to reach
-__global__ __launch_bounds__(FSA_THREADS) void fsa_count_kernel(Prod p) {
-  if (stopped(p.status)) return;
-  const int32_t lo = p.status[P_LO], hi = min(p.status[P_HI], p.max_states);
-  for (int32_t k = (int32_t)blockIdx.x; k < hi - lo; k += (int32_t)gridDim.x) {
-    int64_t slot;
-    const bool w = wins(p, p.delta_out[((int64_t)lo + k) * 256 + threadIdx.x], k * 256 + (int)threadIdx.x, slot);
-    const int n = __syncthreads_count(w);
-    if (threadIdx.x == 0) p.cnt[k] = n;
-  }
-}
-
-// one block: cnt becomes its exclusive prefix sums over the frontier; P_NEXT = the states after this round; past max_states
-// the overflow flag and the count reached
-__global__ __launch_bounds__(SCAN_THREADS) void fsa_scan_kernel(Prod p) {
-  __shared__ int32_t wave_sum[SCAN_THREADS / 64];
-  __shared__ int32_t carry;
-  if (stopped(p.status)) return;  // (uniform: the block's one writer of the words comes behind the last barrier)
-  const int32_t lo = p.status[P_LO], hi = min(p.status[P_HI], p.max_states);
-  const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
-  if (threadIdx.x == 0) carry = 0;
-  __syncthreads();
-  for (int32_t base = 0; base < hi - lo; base += SCAN_THREADS) {
-    const int32_t k = base + (int32_t)threadIdx.x;
-    const int32_t v = k < hi - lo ? p.cnt[k] : 0;
-    int32_t incl = v;
-    for (int d = 1; d < 64; d <<= 1) {
-      const int32_t up = __shfl_up(incl, d);
-      if (lane >= d) incl += up;
-    }
-    if (lane == 63) wave_sum[wave] = incl;
-    __syncthreads();
-    int32_t before = carry;
-    for (int w = 0; w < wave; ++w) before += wave_sum[w];
-    if (k < hi - lo) p.cnt[k] = before + incl - v;
-    __syncthreads();
-    if (threadIdx.x == SCAN_THREADS - 1) carry = before + incl;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    const int64_t next = (int64_t)hi + carry;  // (carry <= 256 * max_states <= 2^30)
-    if (next > p.max_states) {
-      p.status[P_REACHED] = (int32_t)next;
-      atomicOr(&p.status[P_FLAGS], F_OVERFLOW);
-    } else {
-      p.status[P_NEXT] = (int32_t)next;
-    }
-  }
-}
-
-// the winning arcs number their targets: id = P_HI + cnt[k] + the winners of state k at smaller bytes; pairs from the key
-__global__ __launch_bounds__(FSA_THREADS) void fsa_number_kernel(Prod p) {
-  __shared__ int32_t wave_n[FSA_THREADS / 64];
-  __shared__ int32_t stop;  // (one read for the block: a thread of this launch may raise a flag, and the block meets at barriers)
-  if (threadIdx.x == 0) stop = stopped(p.status);
-  __syncthreads();
-  if (stop) return;
-  const int32_t lo = p.status[P_LO], hi = min(p.status[P_HI], p.max_states);
-  const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
-  for (int32_t k = (int32_t)blockIdx.x; k < hi - lo; k += (int32_t)gridDim.x) {
-    int64_t slot;
-    const bool w = wins(p, p.delta_out[((int64_t)lo + k) * 256 + threadIdx.x], k * 256 + (int)threadIdx.x, slot);
-    const unsigned long long ballot = __ballot(w);
-    if (lane == 0) wave_n[wave] = __popcll(ballot);
-    __syncthreads();
-    int32_t rank = __popcll(ballot & ((1ull << lane) - 1ull));
-    for (int v = 0; v < wave; ++v) rank += wave_n[v];
-    if (w) {
-      const int64_t id = (int64_t)hi + p.cnt[k] + rank;
-      if (id >= 0 && id < p.max_states) {
-        const uint64_t key = p.keys[slot], nb = (uint64_t)p.n_b + 1;
-        p.ids[slot] = (int32_t)id;
-        p.pairs[2 * id] = (int32_t)(key / nb) - 1;
-        p.pairs[2 * id + 1] = (int32_t)(key % nb) - 1;
-      } else {
-        atomicOr(&p.status[P_FLAGS], F_TABLE);
-      }
-    }
-    __syncthreads();
-  }
-}
-
-// delta_out of the frontier: -2 - slot becomes the id its slot was given
-__global__ __launch_bounds__(FSA_THREADS) void fsa_resolve_kernel(Prod p) {
-  if (stopped(p.status)) return;
-  const int32_t lo = p.status[P_LO], hi = min(p.status[P_HI], p.max_states);
-  for (int32_t k = (int32_t)blockIdx.x; k < hi - lo; k += (int32_t)gridDim.x) {
-    int32_t *cell = &p.delta_out[((int64_t)lo + k) * 256 + threadIdx.x];
-    const int32_t code = *cell;
-    if (code > -2) continue;
-    const int64_t slot = -2 - (int64_t)code;
-    int32_t id = -1;
-    if ((uint64_t)slot <= p.mask) id = p.ids[slot];
-    if (id < 0 || id >= p.max_states) {
-      atomicOr(&p.status[P_FLAGS], F_TABLE);
-      id = -1;
-    }
-    *cell = id;
-  }
-}
-
-// the round's last launch, one thread: the states numbered become the frontier; a round that numbered none has converged
-__global__ void fsa_advance_kernel(int32_t *status) {
-  if (stopped(status)) return;
-  status[P_ROUNDS] += 1;
-  status[P_LO] = status[P_HI];
-  status[P_HI] = status[P_COUNT] = status[P_NEXT];
-  if (status[P_LO] == status[P_HI]) status[P_CONVERGED] = 1;
-}
-
 // ---- liveness ---------------------------------------------------------------------------------------------------------------
 __global__ void live_init_kernel(int32_t n, const uint8_t *accepting, uint8_t *live, int32_t *status) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < 4) status[L_SWEEPS + i] = 0;
+  if (i < 4) status[X_SWEEPS + i] = 0;
   if (i < n) live[i] = accepting[i] ? 1 : 0;
 }
 
 // a sweep, a wave per state: a state with a live successor is live.  In place: the rule only ever adds, so whatever a wave
 // sees of the others' stores, the fixed point is the same set
 __global__ __launch_bounds__(FSA_THREADS) void live_sweep_kernel(int32_t n, const int32_t *delta, uint8_t *live, int32_t *status) {
-  if (status[L_CONVERGED]) return;
+  if (status[X_CONVERGED]) return;
   const int lane = (int)threadIdx.x & 63;
   const int64_t waves = (int64_t)gridDim.x * (FSA_THREADS / 64);
   for (int64_t s = (int64_t)blockIdx.x * (FSA_THREADS / 64) + (threadIdx.x >> 6); s < n; s += waves) {
@@ -343,26 +211,18 @@ __global__ __launch_bounds__(FSA_THREADS) void live_sweep_kernel(int32_t n, cons
     }
     if (__any(any) && lane == 0) {
       live[s] = 1;
-      atomicOr(&status[L_CHANGED], 1);
+      atomicOr(&status[X_CHANGED], 1);
     }
   }
 }
 
-__global__ void live_end_kernel(int32_t *status) {
-  if (status[L_CONVERGED]) return;
-  status[L_SWEEPS] += 1;
-  if (!status[L_CHANGED]) status[L_CONVERGED] = 1;
-  status[L_CHANGED] = 0;
-}
-
 int fsa_check(const glb_fsa_product_args *p, const char *what, bool round) {
   if (const int rc = glb::block_ok(p, what, "glb_fsa_product_args")) return rc;
-  if (p->max_states < 1 || p->max_states > FSA_MAX_STATES)
-    return glb::api_fail(GLB_EINVAL, "%s: max_states %d outside [1, %d]", what, p->max_states, FSA_MAX_STATES);
-  if (p->rounds < 1 || p->rounds > FSA_MAX_ROUNDS) return glb::api_fail(GLB_EINVAL, "%s: rounds %d outside [1, %d]", what, p->rounds, FSA_MAX_ROUNDS);
+  if (const int rc = check_max_states(what, p->max_states)) return rc;
+  if (const int rc = check_rounds(what, p->rounds)) return rc;
   if (!p->delta_out) return glb::api_fail(GLB_EINVAL, "%s: delta_out is null", what);
   if (!p->accepting_out) return glb::api_fail(GLB_EINVAL, "%s: accepting_out is null", what);
-  if (!p->status) return glb::api_fail(GLB_EINVAL, "%s: status is null", what);
+  if (const int rc = check_status(what, p->status)) return rc;
   if (!round) {
     if (p->n_states < 1 || p->n_states > p->max_states)
       return glb::api_fail(GLB_EINVAL, "%s: n_states %d outside [1, max_states = %d]", what, p->n_states, p->max_states);
@@ -383,23 +243,9 @@ int fsa_check(const glb_fsa_product_args *p, const char *what, bool round) {
   if (p->arc_a && p->op == GLB_FSA_OR) return glb::api_fail(GLB_EINVAL, "%s: arc_a is given: or takes no weights", what);
   if (!p->arc_out != !(p->arc_a || p->arc_b)) return glb::api_fail(GLB_EINVAL, "%s: arc_out goes with the operands' weights", what);
   if (!p->arc_out != !p->final_out) return glb::api_fail(GLB_EINVAL, "%s: arc_out and final_out go together", what);
-  if (p->table_slots < 2 * (int64_t)p->max_states || p->table_slots > ((int64_t)1 << 30) || (p->table_slots & (p->table_slots - 1)))
-    return glb::api_fail(GLB_EINVAL, "%s: table_slots %lld is not a power of two in [2 max_states = %lld, 2^30]", what,
-                         (long long)p->table_slots, 2 * (long long)p->max_states);
-  if (!p->table) return glb::api_fail(GLB_EINVAL, "%s: table is null", what);
-  if ((uintptr_t)p->table & 7) return glb::api_fail(GLB_EINVAL, "%s: table is not aligned to 8 bytes", what);
+  if (const int rc = check_table(what, p->table_slots, p->max_states, p->table)) return rc;
   if (!p->pairs) return glb::api_fail(GLB_EINVAL, "%s: pairs is null", what);
   if (!p->counts) return glb::api_fail(GLB_EINVAL, "%s: counts is null", what);
-  return GLB_OK;
-}
-
-// blocks for a grid that strides over its work: four to a CU
-int fsa_grid(unsigned *blocks) {
-  int dev = 0, cus = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  if (e != hipSuccess) return glb::api_hip_fail(e, "fsa: the device's CU count");
-  *blocks = (unsigned)(cus > 0 ? cus : 256) * 4u;
   return GLB_OK;
 }
 
@@ -410,12 +256,12 @@ extern "C" {
 int glb_fsa_product_round(const glb_fsa_product_args *a, void *stream) {
   if (const int rc = fsa_check(a, "glb_fsa_product_round", true)) return rc;
   unsigned blocks = 0;
-  if (const int rc = fsa_grid(&blocks)) return rc;
+  if (const int rc = stride_grid("fsa: the device's CU count", &blocks)) return rc;
   const hipStream_t st = (hipStream_t)stream;
   unsigned long long *keys = (unsigned long long *)a->table;
   int32_t *arcmin = (int32_t *)(keys + a->table_slots);
   const Prod p{a->op, a->n_a, a->n_b, a->delta_a, a->delta_b, a->accepting_a, a->accepting_b, a->live_a, a->live_b,
-               a->arc_a, a->final_a, a->arc_b, a->final_b, a->max_states, keys, arcmin, arcmin + a->table_slots,
+               a->arc_a, a->final_a, a->arc_b, a->final_b, a->max_states, a->max_states, keys, arcmin, arcmin + a->table_slots,
                (uint64_t)a->table_slots - 1, a->pairs, a->delta_out, a->counts, a->accepting_out, a->arc_out, a->final_out, a->status};
   const dim3 grid(blocks), block(FSA_THREADS);
   if (a->restart) {
@@ -424,11 +270,7 @@ int glb_fsa_product_round(const glb_fsa_product_args *a, void *stream) {
   }
   for (int32_t j = 0; j < a->rounds; ++j) {
     hipLaunchKernelGGL(fsa_expand_kernel, grid, block, 0, st, p);
-    hipLaunchKernelGGL(fsa_count_kernel, grid, block, 0, st, p);
-    hipLaunchKernelGGL(fsa_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, st, p);
-    hipLaunchKernelGGL(fsa_number_kernel, grid, block, 0, st, p);
-    hipLaunchKernelGGL(fsa_resolve_kernel, grid, block, 0, st, p);
-    hipLaunchKernelGGL(fsa_advance_kernel, dim3(1), dim3(1), 0, st, a->status);
+    round_tail(p, blocks, st);
   }
   return glb::launched("fsa_product_round launch");
 }
@@ -436,16 +278,14 @@ int glb_fsa_product_round(const glb_fsa_product_args *a, void *stream) {
 int glb_fsa_live(const glb_fsa_product_args *a, void *stream) {
   if (const int rc = fsa_check(a, "glb_fsa_live", false)) return rc;
   unsigned blocks = 0;
-  if (const int rc = fsa_grid(&blocks)) return rc;
+  if (const int rc = stride_grid("fsa: the device's CU count", &blocks, a->n_states, FSA_THREADS / 64)) return rc;
   const hipStream_t st = (hipStream_t)stream;
   if (a->restart)
     hipLaunchKernelGGL(live_init_kernel, dim3(blocks_for(a->n_states < 4 ? 4 : a->n_states, 256)), dim3(256), 0, st, a->n_states,
                        a->accepting_out, a->live, a->status);
-  const unsigned need = blocks_for(a->n_states, FSA_THREADS / 64);
   for (int32_t j = 0; j < a->rounds; ++j) {
-    hipLaunchKernelGGL(live_sweep_kernel, dim3(need < blocks ? need : blocks), dim3(FSA_THREADS), 0, st, a->n_states, a->delta_out, a->live,
-                       a->status);
-    hipLaunchKernelGGL(live_end_kernel, dim3(1), dim3(1), 0, st, a->status);
+    hipLaunchKernelGGL(live_sweep_kernel, dim3(blocks), dim3(FSA_THREADS), 0, st, a->n_states, a->delta_out, a->live, a->status);
+    hipLaunchKernelGGL(fixpoint_end_kernel, dim3(1), dim3(1), 0, st, a->status + X_SWEEPS);
   }
   return glb::launched("fsa_live launch");
 }

@@ -325,8 +325,8 @@ int glb_lazy_advance(const glb_lazy_args *a, void *stream) {
   for (int64_t base = 0; base < d->n; base += a->cand_rows) {
     const int64_t n = d->n - base < a->cand_rows ? d->n - base : a->cand_rows;
     unsigned waves = 0, blocks = 0;
-    if (const int rc = number_grid("lazy: the device's CU count", n, LAZY_WAVES, &waves)) return rc;
-    if (const int rc = number_grid("lazy: the device's CU count", n, LAZY_THREADS, &blocks)) return rc;
+    if (const int rc = stride_grid("lazy: the device's CU count", &waves, n, LAZY_WAVES)) return rc;
+    if (const int rc = stride_grid("lazy: the device's CU count", &blocks, n, LAZY_THREADS)) return rc;
     hipLaunchKernelGGL(lazy_walk_kernel, dim3(waves), dim3(LAZY_THREADS), 0, st, p, base, n, d->tokens, d->ld, d->from, d->to, d->state_in,
                        d->state_out);
     hipLaunchKernelGGL(number_enter_wave_kernel<Lazy>, dim3(waves), dim3(LAZY_THREADS), 0, st, p, base, n, d->state_out);

@@ -1,33 +1,28 @@
 // glb_nfa_det.hip — a byte NFA with empty arcs made deterministic on the device (include/glb.h: glb_nfa_closure /
 // glb_nfa_subset_round).  A state of the result is a SET of important NFA states, W = n_words 64-bit words: a
 // wave holds one, a lane a word, lanes >= W zero - so OR-ing a closure row into a set is one load and one OR a lane, equality
-// a compare and a ballot, the hash a wave reduction.  The search is the queue search of glb_fsa_product.hip over chunks of
-// the queue: a round takes the next `chunk` numbered states, seven launches - the target set of every (state, byte group)
-// written to `cand`; every target entered into the table; the winning arcs counted, scanned, numbered; delta_out resolved;
-// the queue moved on.  The table cannot hold a set: a slot is ONE 64-bit word, a 31-bit hash and a reference - the arc of this
-// round that claimed the slot (compare against that arc's row of `cand`, written by the launch BEFORE the one that probes:
-// no wave ever waits for another's stores) or, once numbered, the state's id (compare against sets[id]).  The claimant is
-// fixed by its compare-and-swap; equal hash with unequal set probes on; the smallest arc index to find a new set numbers it,
-// so the arrays do not depend on the order the atomics take.  Everything read from device memory is range-checked.
+// a compare and a ballot, the hash a wave reduction.  The search is the queue search of glb_search.hpp over chunks of the
+// queue: a round takes the next `chunk` numbered states, seven launches - this file's two: the target set of every (state,
+// byte group) written to `cand`, every target entered into the table; then the shared five: the winning arcs counted,
+// scanned, numbered; delta_out resolved; the queue moved on.  The table cannot hold a set: a slot is ONE 64-bit word, a
+// 31-bit hash and a reference - the arc of this round that claimed the slot (compare against that arc's row of `cand`,
+// written by the launch BEFORE the one that probes: no wave ever waits for another's stores) or, once numbered, the state's
+// id (compare against sets[id]).  The claimant is fixed by its compare-and-swap; equal hash with unequal set probes on; the
+// smallest arc index to find a new set numbers it, so the arrays do not depend on the order the atomics take.  Everything
+// read from device memory is range-checked.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/glb.h"
 #include "glb_common.hpp"
+#include "glb_search.hpp"
 #include "glb_set.hpp"
 
 namespace {
 
-// status: the search [0 .. 7] and [12], the closure [8 .. 11]
-enum { P_ROUNDS = 0, P_CONVERGED = 1, P_FLAGS = 2, P_COUNT = 3, P_LO = 4, P_HI = 5, P_NEXT = 6, P_REACHED = 7,
-       C_SWEEPS = 8, C_CONVERGED = 9, C_FLAGS = 10, C_CHANGED = 11, P_ENTERED = 12 };
-enum { F_OVERFLOW = 1, F_TABLE = 2 };
-constexpr int NFA_THREADS = 256;  // four waves, an item each; count / number / resolve: the 256 bytes of one state
+constexpr int NFA_THREADS = SEARCH_THREADS;  // four waves, an item each
 constexpr int NFA_WAVES = NFA_THREADS / 64;
-constexpr int NFA_MAX_ROUNDS = 65536;        // rounds / sweeps one call may enqueue
-constexpr int32_t NFA_MAX_STATES = 1 << 22;  // (an arc index queue position * 256 + byte stays below 2^31)
 constexpr int32_t NFA_MAX_NFA_STATES = 1 << 24;
-constexpr int32_t NO_ARC = 0x7fffffff;
 constexpr uint32_t REF_ARC = 0x80000000u;   // the low half: this bit and an arc index of the round, else the id of a numbered state
 
 struct Det {
@@ -45,33 +40,36 @@ struct Det {
   int32_t *delta_out, *cnt;
   uint8_t *accepting_out;
   int32_t *status;
+
+  // the winning arc's target becomes state `id`: the set copied from `cand`, its accepting bit, and the slot's reference
+  // turned into the id (an arc index is made of its group's lowest byte, so no other byte of the group wins)
+  static __device__ bool number(const Det &p, int64_t id, int32_t k, int byte, int64_t slot) {
+    const int32_t g = p.group_of[byte];
+    if (g < 0 || g >= p.G) return false;
+    const uint64_t *row = p.cand + ((int64_t)k * p.G + g) * p.W;
+    bool acc = false;
+    for (int j = 0; j < p.W; ++j) {
+      const uint64_t word = row[j];
+      p.sets[id * p.W + j] = word;
+      acc = acc || (word & p.acc_mask[j]) != 0;
+    }
+    p.accepting_out[id] = acc ? 1 : 0;
+    p.words[slot] = (p.words[slot] & 0xffffffff00000000ull) | (unsigned long long)id;
+    return true;
+  }
+  // the low half of the slot's word, once it is no arc of the round
+  static __device__ int32_t id_of(const Det &p, int64_t slot) {
+    const uint32_t ref = (uint32_t)p.words[slot];
+    return ref & REF_ARC ? -1 : (int32_t)ref;
+  }
 };
-
-__device__ inline int32_t flags_now(const int32_t *status) {
-  return __hip_atomic_load(&status[P_FLAGS], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ inline bool stopped(const int32_t *status) { return status[P_CONVERGED] != 0 || status[P_FLAGS] != 0; }
-
-// the states of the queue this round takes: [lo, lo + the value returned)
-__device__ inline int32_t round_states(const Det &p, int32_t &lo) {
-  lo = p.status[P_LO];
-  const int32_t hi = min(p.status[P_HI], p.max_states);
-  return lo >= 0 ? max(0, min(hi - lo, p.chunk)) : 0;
-}
-
-// more than max_states sets: flag bit 0 and the count that passed it
-__device__ inline void overflow(const Det &p, int64_t reached) {
-  atomicMax(&p.status[P_REACHED], (int32_t)(reached < 0x7fffffff ? reached : 0x7fffffff));
-  atomicOr(&p.status[P_FLAGS], F_OVERFLOW);
-}
 
 // ---- the closure --------------------------------------------------------------------------------------------------------------
 // eclose[v] = {v} where v is important, else empty; the closure's status words zeroed
 __global__ void closure_init_kernel(Det p) {
   const int64_t total = (int64_t)p.n * p.W;
   const int64_t first = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (first < 4) p.status[C_SWEEPS + first] = 0;
+  if (first < 4) p.status[X_SWEEPS + first] = 0;
   for (int64_t i = first; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     const int32_t b = p.bit_of[i / p.W];
     p.eclose[i] = b >= 0 && b < p.n_imp && (b >> 6) == (int32_t)(i % p.W) ? 1ull << (b & 63) : 0ull;
@@ -82,7 +80,7 @@ __global__ void closure_init_kernel(Det p) {
 // adds, so whatever a wave sees of the others' stores the fixed point is the same - and a sweep that changed no row read
 // nothing but final rows
 __global__ __launch_bounds__(NFA_THREADS) void closure_sweep_kernel(Det p) {
-  if (p.status[C_CONVERGED]) return;
+  if (p.status[X_CONVERGED]) return;
   const int lane = (int)threadIdx.x & 63;
   const int64_t waves = (int64_t)gridDim.x * NFA_WAVES;
   for (int64_t v = (int64_t)blockIdx.x * NFA_WAVES + (threadIdx.x >> 6); v < p.n; v += waves) {
@@ -96,22 +94,15 @@ __global__ __launch_bounds__(NFA_THREADS) void closure_sweep_kernel(Det p) {
       if (u >= 0 && u < p.n && lane < p.W) row |= word_now((const unsigned long long *)p.eclose + (int64_t)u * p.W + lane);
     }
     if (row != old) __hip_atomic_store(mine, row, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (__any(row != old) && lane == 0) atomicOr(&p.status[C_CHANGED], 1);
+    if (__any(row != old) && lane == 0) atomicOr(&p.status[X_CHANGED], 1);
   }
-}
-
-__global__ void closure_end_kernel(int32_t *status) {
-  if (status[C_CONVERGED]) return;
-  status[C_SWEEPS] += 1;
-  if (!status[C_CHANGED]) status[C_CONVERGED] = 1;
-  status[C_CHANGED] = 0;
 }
 
 // ---- the search ---------------------------------------------------------------------------------------------------------------
 // the table emptied and the search's status words zeroed (the closure's stay)
 __global__ void nfa_clear_kernel(Det p) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < GLB_NFA_STATUS && !(i >= C_SWEEPS && i <= C_CHANGED)) p.status[i] = 0;
+  if (i < GLB_NFA_STATUS && !(i >= X_SWEEPS && i <= X_CHANGED)) p.status[i] = 0;
   if (i <= p.mask) {
     p.words[i] = 0;
     p.arcmin[i] = NO_ARC;
@@ -185,7 +176,7 @@ __device__ inline const uint64_t *behind(const Det &p, uint32_t ref, int32_t nk)
 }
 
 // Every target set enters the table, a wave per (k, g): delta_out of the group's bytes takes the set's id where an earlier
-// round numbered it, -1 where the set is empty, else -2 - slot until nfa_resolve_kernel.  A new set's slot is claimed by one
+// round numbered it, -1 where the set is empty, else -2 - slot until search_resolve_kernel.  A new set's slot is claimed by one
 // compare-and-swap and counted; past max_states the overflow flag goes up in the middle of the launch and every wave leaves
 // at its next item or within 32 slots
 __global__ __launch_bounds__(NFA_THREADS) void nfa_enter_kernel(Det p) {
@@ -217,7 +208,7 @@ __global__ __launch_bounds__(NFA_THREADS) void nfa_enter_kernel(Det p) {
             if (lane == 0) {
               atomicMin(&p.arcmin[slot], arc);
               const int64_t total = (int64_t)atomicAdd(&p.status[P_ENTERED], 1) + 1;
-              if (total > p.max_states) overflow(p, total);
+              if (total > p.max_states) overflow(p.status, total);
             }
             out = -2 - (int32_t)slot;
             break;
@@ -244,126 +235,13 @@ __global__ __launch_bounds__(NFA_THREADS) void nfa_enter_kernel(Det p) {
         }
         if ((probe & 31) == 31 && flags_now(p.status)) break;
       }
-      if (probe > p.mask && lane == 0) overflow(p, (int64_t)p.mask + 1);  // (a full table holds >= 2 max_states sets)
+      if (probe > p.mask && lane == 0) overflow(p.status, (int64_t)p.mask + 1);  // (a full table holds >= 2 max_states sets)
     }
     const int64_t s = (int64_t)lo + k;
 #pragma unroll
     for (int j = 0; j < 4; ++j)
       if (p.group_of[lane + 64 * j] == g) p.delta_out[s * 256 + lane + 64 * j] = out;
   }
-}
-
-// whether the arc (queue position k, byte) is the one that numbers its target: the smallest arc of the round to find it (an
-// arc index is made of its group's lowest byte, so no other byte of the group wins)
-__device__ inline bool wins(const Det &p, int32_t code, int32_t arc, int64_t &slot) {
-  slot = -2 - (int64_t)code;
-  return code <= -2 && (uint64_t)slot <= p.mask && p.arcmin[slot] == arc;
-}
-
-// cnt[k]: the states that queue state lo + k is the first to reach
-__global__ __launch_bounds__(NFA_THREADS) void nfa_count_kernel(Det p) {
-  if (stopped(p.status)) return;
-  int32_t lo;
-  const int32_t nk = round_states(p, lo);
-  for (int32_t k = (int32_t)blockIdx.x; k < nk; k += (int32_t)gridDim.x) {
-    int64_t slot;
-    const bool w = wins(p, p.delta_out[((int64_t)lo + k) * 256 + threadIdx.x], k * 256 + (int)threadIdx.x, slot);
-    const int n = __syncthreads_count(w);
-    if (threadIdx.x == 0) p.cnt[k] = n;
-  }
-}
-
-// one block: cnt becomes its exclusive prefix sums over the round's states; P_NEXT = the states after this round; past
-// max_states the overflow flag and the count reached
-__global__ __launch_bounds__(SCAN_THREADS) void nfa_scan_kernel(Det p) {
-  __shared__ int32_t wave_sum[SCAN_THREADS / 64];
-  __shared__ int32_t carry;
-  if (stopped(p.status)) return;  // (uniform: the block's one writer of the words comes behind the last barrier)
-  int32_t lo;
-  const int32_t nk = round_states(p, lo);
-  const int32_t total = scan_exclusive(p.cnt, nk, wave_sum, &carry);
-  if (threadIdx.x == 0) {
-    const int64_t next = (int64_t)p.status[P_COUNT] + total;  // (total <= 256 * chunk <= 2^30)
-    if (next > p.max_states) {
-      atomicMax(&p.status[P_REACHED], (int32_t)next);
-      atomicOr(&p.status[P_FLAGS], F_OVERFLOW);
-    } else {
-      p.status[P_NEXT] = (int32_t)next;
-    }
-  }
-}
-
-// the winning arcs number their targets: id = P_COUNT + cnt[k] + the winners of state k at smaller bytes; the set copied from
-// `cand`, its accepting bit, and the slot's reference turned into the id
-__global__ __launch_bounds__(NFA_THREADS) void nfa_number_kernel(Det p) {
-  __shared__ int32_t wave_n[NFA_WAVES];
-  __shared__ int32_t stop;  // (one read for the block: a thread of this launch may raise a flag, and the block meets at barriers)
-  if (threadIdx.x == 0) stop = stopped(p.status);
-  __syncthreads();
-  if (stop) return;
-  int32_t lo;
-  const int32_t nk = round_states(p, lo), count = p.status[P_COUNT];
-  const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
-  for (int32_t k = (int32_t)blockIdx.x; k < nk; k += (int32_t)gridDim.x) {
-    int64_t slot;
-    const bool w = wins(p, p.delta_out[((int64_t)lo + k) * 256 + threadIdx.x], k * 256 + (int)threadIdx.x, slot);
-    const unsigned long long ballot = __ballot(w);
-    if (lane == 0) wave_n[wave] = __popcll(ballot);
-    __syncthreads();
-    int32_t rank = __popcll(ballot & ((1ull << lane) - 1ull));
-    for (int v = 0; v < wave; ++v) rank += wave_n[v];
-    if (w) {
-      const int64_t id = (int64_t)count + p.cnt[k] + rank;
-      const int32_t g = p.group_of[threadIdx.x];
-      if (id >= 0 && id < p.max_states && g >= 0 && g < p.G) {
-        const uint64_t *row = p.cand + ((int64_t)k * p.G + g) * p.W;
-        bool acc = false;
-        for (int j = 0; j < p.W; ++j) {
-          const uint64_t word = row[j];
-          p.sets[id * p.W + j] = word;
-          acc = acc || (word & p.acc_mask[j]) != 0;
-        }
-        p.accepting_out[id] = acc ? 1 : 0;
-        p.words[slot] = (p.words[slot] & 0xffffffff00000000ull) | (unsigned long long)id;
-      } else {
-        atomicOr(&p.status[P_FLAGS], F_TABLE);
-      }
-    }
-    __syncthreads();
-  }
-}
-
-// delta_out of the round's states: -2 - slot becomes the id its slot was given
-__global__ __launch_bounds__(NFA_THREADS) void nfa_resolve_kernel(Det p) {
-  if (stopped(p.status)) return;
-  int32_t lo;
-  const int32_t nk = round_states(p, lo);
-  for (int32_t k = (int32_t)blockIdx.x; k < nk; k += (int32_t)gridDim.x) {
-    int32_t *cell = &p.delta_out[((int64_t)lo + k) * 256 + threadIdx.x];
-    const int32_t code = *cell;
-    if (code > -2) continue;
-    const int64_t slot = -2 - (int64_t)code;
-    int32_t id = -1;
-    if ((uint64_t)slot <= p.mask) {
-      const uint32_t ref = (uint32_t)p.words[slot];
-      if (!(ref & REF_ARC)) id = (int32_t)ref;
-    }
-    if (id < 0 || id >= p.max_states) {
-      atomicOr(&p.status[P_FLAGS], F_TABLE);
-      id = -1;
-    }
-    *cell = id;
-  }
-}
-
-// the round's last launch, one thread: the queue moves on by the states taken; with nothing left in it the search is over
-__global__ void nfa_advance_kernel(int32_t *status, int32_t chunk) {
-  if (stopped(status)) return;
-  status[P_ROUNDS] += 1;
-  status[P_LO] = status[P_HI];
-  status[P_COUNT] = status[P_NEXT];
-  status[P_HI] = min(status[P_COUNT], status[P_LO] + chunk);
-  if (status[P_LO] >= status[P_COUNT]) status[P_CONVERGED] = 1;
 }
 
 int nfa_check(const glb_nfa_args *p, const char *what, bool round) {
@@ -376,9 +254,9 @@ int nfa_check(const glb_nfa_args *p, const char *what, bool round) {
   const int32_t words = p->n_important > 64 ? (p->n_important + 63) / 64 : 1;
   if (p->n_words != words) return glb::api_fail(GLB_EINVAL, "%s: n_words %d is not max(1, ceil(n_important / 64)) = %d", what, p->n_words, words);
   if (p->start < 0 || p->start >= p->n_states) return glb::api_fail(GLB_EINVAL, "%s: start %d outside [0, n_states = %d)", what, p->start, p->n_states);
-  if (p->rounds < 1 || p->rounds > NFA_MAX_ROUNDS) return glb::api_fail(GLB_EINVAL, "%s: rounds %d outside [1, %d]", what, p->rounds, NFA_MAX_ROUNDS);
+  if (const int rc = check_rounds(what, p->rounds)) return rc;
   if (!p->eclose) return glb::api_fail(GLB_EINVAL, "%s: eclose is null", what);
-  if (!p->status) return glb::api_fail(GLB_EINVAL, "%s: status is null", what);
+  if (const int rc = check_status(what, p->status)) return rc;
   if (!round) {
     if (p->n_eps < 0) return glb::api_fail(GLB_EINVAL, "%s: n_eps %d is negative", what, p->n_eps);
     if (!p->eps_off || !p->eps_to) return glb::api_fail(GLB_EINVAL, "%s: eps_off or eps_to is null", what);
@@ -387,32 +265,17 @@ int nfa_check(const glb_nfa_args *p, const char *what, bool round) {
   }
   if (p->n_arcs < 0) return glb::api_fail(GLB_EINVAL, "%s: n_arcs %d is negative", what, p->n_arcs);
   if (p->n_groups < 1 || p->n_groups > 256) return glb::api_fail(GLB_EINVAL, "%s: n_groups %d outside [1, 256]", what, p->n_groups);
-  if (p->max_states < 1 || p->max_states > NFA_MAX_STATES)
-    return glb::api_fail(GLB_EINVAL, "%s: max_states %d outside [1, %d]", what, p->max_states, NFA_MAX_STATES);
+  if (const int rc = check_max_states(what, p->max_states)) return rc;
   if (p->chunk < 1 || p->chunk > p->max_states) return glb::api_fail(GLB_EINVAL, "%s: chunk %d outside [1, max_states = %d]", what, p->chunk, p->max_states);
   if (!p->arc_off || !p->arc_dst || !p->arc_bytes) return glb::api_fail(GLB_EINVAL, "%s: arc_off, arc_dst or arc_bytes is null", what);
   if (!p->accepting_mask) return glb::api_fail(GLB_EINVAL, "%s: accepting_mask is null", what);
   if (!p->group_of || !p->group_lo) return glb::api_fail(GLB_EINVAL, "%s: group_of or group_lo is null", what);
-  if (p->table_slots < 2 * (int64_t)p->max_states || p->table_slots > ((int64_t)1 << 30) || (p->table_slots & (p->table_slots - 1)))
-    return glb::api_fail(GLB_EINVAL, "%s: table_slots %lld is not a power of two in [2 max_states = %lld, 2^30]", what,
-                         (long long)p->table_slots, 2 * (long long)p->max_states);
-  if (!p->table) return glb::api_fail(GLB_EINVAL, "%s: table is null", what);
-  if ((uintptr_t)p->table & 7) return glb::api_fail(GLB_EINVAL, "%s: table is not aligned to 8 bytes", what);
+  if (const int rc = check_table(what, p->table_slots, p->max_states, p->table)) return rc;
   if (!p->cand) return glb::api_fail(GLB_EINVAL, "%s: cand is null", what);
   if (!p->sets) return glb::api_fail(GLB_EINVAL, "%s: sets is null", what);
   if (!p->delta_out) return glb::api_fail(GLB_EINVAL, "%s: delta_out is null", what);
   if (!p->accepting_out) return glb::api_fail(GLB_EINVAL, "%s: accepting_out is null", what);
   if (!p->counts) return glb::api_fail(GLB_EINVAL, "%s: counts is null", what);
-  return GLB_OK;
-}
-
-// blocks for a grid that strides over its work: four to a CU
-int nfa_grid(unsigned *blocks) {
-  int dev = 0, cus = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  if (e != hipSuccess) return glb::api_hip_fail(e, "nfa: the device's CU count");
-  *blocks = (unsigned)(cus > 0 ? cus : 256) * 4u;
   return GLB_OK;
 }
 
@@ -431,7 +294,7 @@ extern "C" {
 int glb_nfa_closure(const glb_nfa_args *a, void *stream) {
   if (const int rc = nfa_check(a, "glb_nfa_closure", false)) return rc;
   unsigned blocks = 0;
-  if (const int rc = nfa_grid(&blocks)) return rc;
+  if (const int rc = stride_grid("nfa: the device's CU count", &blocks)) return rc;
   const hipStream_t st = (hipStream_t)stream;
   Det p{};
   p.n = a->n_states, p.n_imp = a->n_important, p.W = a->n_words, p.n_eps = a->n_eps;
@@ -441,7 +304,7 @@ int glb_nfa_closure(const glb_nfa_args *a, void *stream) {
   if (a->restart) hipLaunchKernelGGL(closure_init_kernel, dim3(blocks), dim3(256), 0, st, p);
   for (int32_t j = 0; j < a->rounds; ++j) {
     hipLaunchKernelGGL(closure_sweep_kernel, grid, block, 0, st, p);
-    hipLaunchKernelGGL(closure_end_kernel, dim3(1), dim3(1), 0, st, a->status);
+    hipLaunchKernelGGL(fixpoint_end_kernel, dim3(1), dim3(1), 0, st, a->status + X_SWEEPS);
   }
   return glb::launched("nfa_closure launch");
 }
@@ -449,7 +312,7 @@ int glb_nfa_closure(const glb_nfa_args *a, void *stream) {
 int glb_nfa_subset_round(const glb_nfa_args *a, void *stream) {
   if (const int rc = nfa_check(a, "glb_nfa_subset_round", true)) return rc;
   unsigned blocks = 0;
-  if (const int rc = nfa_grid(&blocks)) return rc;
+  if (const int rc = stride_grid("nfa: the device's CU count", &blocks)) return rc;
   const hipStream_t st = (hipStream_t)stream;
   const Det p = det_of(a);
   const dim3 grid(blocks), block(NFA_THREADS);
@@ -460,11 +323,7 @@ int glb_nfa_subset_round(const glb_nfa_args *a, void *stream) {
   for (int32_t j = 0; j < a->rounds; ++j) {
     hipLaunchKernelGGL(nfa_expand_kernel, grid, block, 0, st, p);
     hipLaunchKernelGGL(nfa_enter_kernel, grid, block, 0, st, p);
-    hipLaunchKernelGGL(nfa_count_kernel, grid, block, 0, st, p);
-    hipLaunchKernelGGL(nfa_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, st, p);
-    hipLaunchKernelGGL(nfa_number_kernel, grid, block, 0, st, p);
-    hipLaunchKernelGGL(nfa_resolve_kernel, grid, block, 0, st, p);
-    hipLaunchKernelGGL(nfa_advance_kernel, dim3(1), dim3(1), 0, st, a->status, a->chunk);
+    round_tail(p, blocks, st);
   }
   return glb::launched("nfa_subset_round launch");
 }

@@ -4,7 +4,8 @@
 // that claimed it (written by the launch before the one that probes: no wave waits for another's stores) or the id of a
 // numbered state (its row of `rows`).  The smallest particle index to end in a new state numbers it, so ids and rows do not
 // depend on the order the atomics take.  A chunk of particles [base, base + n) is numbered by five launches: enter, count,
-// scan, number, resolve.
+// scan, number, resolve.  The scan, the rank of a winner among its block's and the launch grid (stride_grid) are
+// glb_block.hpp's.
 //
 // The kernels are templates over the translation unit's parameter struct P, passed by value.  P has: W, max_states,
 // hash_mask, words, partmin, mask, rows, cnt, status - and cand where number_enter_wave_kernel is used - and a
@@ -15,6 +16,7 @@
 #include <stdint.h>
 
 #include "../../include/glb.h"
+#include "glb_block.hpp"
 #include "glb_common.hpp"
 #include "glb_set.hpp"
 
@@ -149,17 +151,12 @@ template <typename P>
 __global__ __launch_bounds__(NUMBER_THREADS) void number_kernel(P p, int64_t base, int64_t n, const int32_t *state_out) {
   __shared__ int32_t wave_n[NUMBER_WAVES];
   const int32_t count = numbered(p, N_COUNT);
-  const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
   const int64_t nb = (n + NUMBER_THREADS - 1) / NUMBER_THREADS;
   for (int64_t b = blockIdx.x; b < nb; b += gridDim.x) {
     const int64_t k = b * NUMBER_THREADS + threadIdx.x;
     int64_t slot;
     const bool w = k < n && wins(p, state_out[base + k], k, slot);
-    const unsigned long long ballot = __ballot(w);
-    if (lane == 0) wave_n[wave] = __popcll(ballot);
-    __syncthreads();
-    int32_t rank = __popcll(ballot & ((1ull << lane) - 1ull));
-    for (int v = 0; v < wave; ++v) rank += wave_n[v];
+    const int32_t rank = block_rank(w, wave_n);
     if (w) {
       const int64_t id = (int64_t)count + p.cnt[b] + rank;
       const unsigned long long high = p.words[slot] & 0xffffffff00000000ull;
@@ -206,23 +203,6 @@ void number_launches(const P &p, unsigned blocks, int64_t base, int64_t n, int32
   hipLaunchKernelGGL(number_scan_kernel<P>, dim3(1), dim3(SCAN_THREADS), 0, st, p, n);
   hipLaunchKernelGGL(number_kernel<P>, dim3(blocks), dim3(NUMBER_THREADS), 0, st, p, base, n, (const int32_t *)state_out);
   hipLaunchKernelGGL(number_resolve_kernel<P>, dim3(blocks_for(n, 256)), dim3(256), 0, st, p, base, n, state_out, last ? 1 : 0);
-}
-
-// blocks for a grid that strides over its work: four to a CU, and no more than the work has; `what` names the failure
-inline int number_grid(const char *what, int64_t items, int per_block, unsigned *blocks) {
-  static std::atomic<int> cus_of_device{0};  // (one kind of device a process)
-  int cus = cus_of_device.load(std::memory_order_relaxed);
-  if (cus <= 0) {
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (e != hipSuccess) return glb::api_hip_fail(e, what);
-    if (cus <= 0) cus = 256;
-    cus_of_device.store(cus, std::memory_order_relaxed);
-  }
-  const int64_t need = (items + per_block - 1) / per_block, most = (int64_t)cus * 4;
-  *blocks = (unsigned)(need < most ? (need > 0 ? need : 1) : most);
-  return GLB_OK;
 }
 
 // What the three blocks (A: glb_lazy_args, glb_pda_args, glb_conj_args) are refused for alike: the block and its glb_dfa_args,

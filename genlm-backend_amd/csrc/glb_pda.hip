@@ -315,8 +315,8 @@ int glb_pda_advance(const glb_pda_args *a, void *stream) {
   for (int64_t base = 0; base < d->n; base += a->cand_rows) {
     const int64_t n = d->n - base < a->cand_rows ? d->n - base : a->cand_rows;
     unsigned waves = 0, blocks = 0;
-    if (const int rc = number_grid("pda: the device's CU count", n, PDA_WAVES, &waves)) return rc;
-    if (const int rc = number_grid("pda: the device's CU count", n, PDA_THREADS, &blocks)) return rc;
+    if (const int rc = stride_grid("pda: the device's CU count", &waves, n, PDA_WAVES)) return rc;
+    if (const int rc = stride_grid("pda: the device's CU count", &blocks, n, PDA_THREADS)) return rc;
     hipLaunchKernelGGL(pda_walk_kernel, dim3(waves), dim3(PDA_THREADS), 0, st, p, base, n, d->tokens, d->ld, d->from, d->to, d->state_in,
                        d->state_out);
     hipLaunchKernelGGL(number_enter_wave_kernel<Pda>, dim3(waves), dim3(PDA_THREADS), 0, st, p, base, n, d->state_out);
