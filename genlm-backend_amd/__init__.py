@@ -21,9 +21,9 @@ def __getattr__(name):
     if name == "DeviceBeam":
         from .beam import DeviceBeam
         return DeviceBeam
-    if name == "ByteBeam":
-        from .bytelm import ByteBeam
-        return ByteBeam
+    if name in ("ByteBeam", "ByteSIS"):
+        from . import bytelm
+        return getattr(bytelm, name)
     if name in ("ByteDFA", "ByteWFSA", "DeviceConstraint", "minimize", "product", "ByteNFA", "determinize", "LazyConstraint", "BytePDA",
                 "PDAConstraint", "ConstraintProduct"):
         from . import constraints

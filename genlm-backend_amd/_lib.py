@@ -530,6 +530,18 @@ class ByteLmArgs(C.Structure):  # glb_bytelm_args
     ]
 
 
+class ByteLmStepArgs(C.Structure):  # glb_bytelm_step_args
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("peek", C.c_int32),
+        ("beam", ByteLmArgs),
+        ("n_states", C.c_int64),
+        ("delta", C.c_void_p), ("accepting", C.c_void_p), ("live", C.c_void_p), ("arc_logw", C.c_void_p), ("final_logw", C.c_void_p),
+        ("state", C.c_void_p), ("ended", C.c_void_p), ("log_weight", C.c_void_p), ("uniform", C.c_void_p),
+        ("seed", C.c_uint64), ("offset", C.c_uint64),
+        ("out_byte", C.c_void_p), ("out_row", C.c_void_p), ("out_logZc", C.c_void_p),
+    ]
+
+
 class TruncateArgs(C.Structure):
     _fields_ = [
         ("struct_size", C.c_uint32),
@@ -669,6 +681,7 @@ SYMBOLS = {
     "glb_bytelm_children": (C.c_int, [C.POINTER(ByteLmArgs), _vp]),
     "glb_bytelm_extend": (C.c_int, [C.POINTER(ByteLmArgs), _vp]),
     "glb_bytelm_next": (C.c_int, [C.POINTER(ByteLmArgs), _vp]),
+    "glb_bytelm_step": (C.c_int, [C.POINTER(ByteLmStepArgs), _vp]),
     "glb_philox4x32_10": (None, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
 }
 

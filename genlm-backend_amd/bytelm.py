@@ -7,8 +7,15 @@ the token -> byte trie.  A candidate's weight is w = u + log M_x[n], M_x the tri
 of x's next-token distribution.  One byte costs two selections' masses, three small kernels (glb_bytelm_children /
 _extend / _next) and a forward over the candidates that just committed a token - the others keep their logits row.
 
-Not here: more than one device, LoRA names, `constraints` (the row is [n, 257]: a byte constraint is a 257-wide mask - a
-follow-up), and pruning by a threshold relative to the best weight."""
+Under a byte automaton (`ByteBeam(constraint=...)`) a state constrains the next byte with one 256-entry row of
+its `delta`: no row bank, no fill, nothing that depends on the tokeniser.  glb_bytelm_step does the row, the automaton's row,
+the renormalisation, the draw and the advance in one launch; `ByteSIS` is sequential importance sampling over bytes on top.
+
+Not here: more than one device, LoRA names, byte-level `BytePDA`s and lazy `ByteNFA`s (determinise an NFA first), token-level
+`*Constraint` objects, one automaton per group, proposals other than the constrained row, and pruning by a threshold
+relative to the best weight."""
+import math
+
 import numpy as np
 import torch
 
@@ -24,6 +31,27 @@ def check_width(width):
     if not isinstance(width, int) or isinstance(width, bool) or not 1 <= width <= MAX_WIDTH:
         raise ValueError(f"width must be an integer in 1..{MAX_WIDTH}, got {width!r}")
     return width
+
+
+def check_constraint(constraint):
+    """`constraint` if a byte beam can serve it - None, a `ByteDFA`, a `ByteWFSA` or a `DeviceTables` with `live` - else
+    ValueError naming its kind.  Touches no device."""
+    from .constraints.automata import ByteDFA
+    from .constraints.nfa import ByteNFA
+    from .constraints.tables import DeviceTables
+
+    if constraint is None or isinstance(constraint, ByteDFA):
+        return constraint
+    if isinstance(constraint, DeviceTables):
+        if constraint.live is None:
+            raise ValueError("constraint is a DeviceTables without `live` (as `minimized` returns them): upload a host automaton")
+        return constraint
+    kind = type(constraint).__name__
+    if isinstance(constraint, ByteNFA):
+        raise ValueError(f"constraint is a {kind}: a byte beam follows one state per group - `determinize` the NFA first and "
+                         f"pass the ByteDFA")
+    raise ValueError(f"constraint must be a ByteDFA, a ByteWFSA or a DeviceTables, got a {kind} (a BytePDA and the token-level "
+                     f"*Constraint objects are not served at byte level; `determinize` a ByteNFA first)")
 
 
 def byte_trie(byte_vocab, eos_ids, ignore_ids=(), engine=None):
@@ -86,13 +114,21 @@ class ByteBeam:
                  normalisation absorbs it; an empty byte string that is in neither list is refused
     prompt_ids   the token context every group starts from (default [bos_token_id] when the tokenizer has one)
     max_bytes    bytes a group may be advanced by; the token capacity of a context is prompt + max_bytes + 1
+    constraint   None, or a byte automaton every group follows from its start state: a `ByteDFA`, a `ByteWFSA` (uploaded
+                 once) or a `DeviceTables`.  Then the rows are constrained and renormalised, and per group there are
+                 `state` int32 [n] (-1 once ended or dead), `ended` int32 [n] (1 after EOS from an accepting state) and
+                 `log_weights` float32 [n]: the sum of what the automaton gave the bytes read (`advance`: the byte's weight,
+                 0 for an allowed byte of a `ByteDFA`, -inf for a forbidden one) and of log Zc for the bytes drawn (`step`).
+                 Without one, none of the three exists.
 
     State per slot (group g owns slots g * width .. g * width + width - 1; a candidate never moves): `node`, `alive` int32,
     `u`, `w` float32, `contexts` int32 [n * width, cap] and `lengths`, the logits row store [n * width, V] in the model's
     logits dtype with `lse`; `logp` float32 [n] per group."""
 
-    def __init__(self, llm, byte_vocab, eos_ids, width=16, n=1, prompt_ids=None, temperature=1.0, max_bytes=256, ignore_ids=()):
+    def __init__(self, llm, byte_vocab, eos_ids, width=16, n=1, prompt_ids=None, temperature=1.0, max_bytes=256, ignore_ids=(),
+                 constraint=None):
         check_width(width)
+        check_constraint(constraint)
         if not isinstance(n, int) or n < 1:
             raise ValueError(f"n must be a positive integer, got {n!r}")
         if not isinstance(max_bytes, int) or max_bytes < 1:
@@ -124,6 +160,11 @@ class ByteBeam:
         self._first_slots = slot[self._first].to(torch.int32).contiguous()
         self.store = self.lse = None
         self.forwarded = 0  # contexts handed to the model so far (equal ones are encoded once: `llm._count`)
+        self.tables = None
+        if constraint is not None:
+            from .constraints.tables import DeviceTables
+
+            self.tables = constraint if isinstance(constraint, DeviceTables) else DeviceTables.upload(self.eng, constraint)
         self.reset()
 
     def reset(self):
@@ -139,6 +180,10 @@ class ByteBeam:
         self.logp = torch.zeros(self.n, dtype=torch.float32, device=dev)
         self.fresh = torch.zeros(self.n, dtype=torch.int32, device=dev)
         self.t = 0
+        if self.tables is not None:
+            self.state = torch.full((self.n,), self.tables.start, dtype=torch.int32, device=dev)
+            self.ended = torch.zeros(self.n, dtype=torch.int32, device=dev)
+            self.log_weights = torch.zeros(self.n, dtype=torch.float32, device=dev)
         self._pending = (self._first_slots, self.n)  # slots whose logits row is still to be fetched
         self._sel = self._mass = self._row = self._logZ = None
 
@@ -195,29 +240,70 @@ class ByteBeam:
             self._masses(wide=True)
 
     # ---- the interface --------------------------------------------------------------------------------------------------------
+    def _step(self, **kw):
+        """glb_bytelm_step over the beam's state as it stands after `_prepare`."""
+        return self.eng.bytelm_step(self._trie, self.node, self.u, self.w, self.alive, self._sel, self._mass, self.width, self.tables,
+                                    self.state, self.ended, self.log_weights, self.logp, fresh=self.fresh, **kw)
+
     def next_byte_logprobs(self):
         """float32 [n, 257] on the device: log p(next byte | the bytes so far) for the 256 bytes and, in column 256, EOS.  A
-        group without a live candidate (ended, or advanced by a byte no tokenisation spells) has a row of -inf.  The same
-        tensor until the next `advance`."""
+        group without a live candidate (ended, or advanced by a byte no tokenisation spells) has a row of -inf.  Under a
+        constraint: the row restricted to what the group's state allows and renormalised - forbidden columns are exactly
+        -inf, a dead group's row is all -inf.  The same tensor until the next `advance` or `step`."""
         if self._row is None:
             self._prepare()
-            self._row, self._logZ = self.eng.bytelm_next(self._trie, self.node, self.u, self.w, self.alive, self._sel, self._mass, self.width)
+            if self.tables is None:
+                self._row, self._logZ = self.eng.bytelm_next(self._trie, self.node, self.u, self.w, self.alive, self._sel, self._mass, self.width)
+            else:
+                out = self._step(peek=True, want_row=True)
+                self._row, self._logZ = out["row"], out["logZc"]
         return self._row
 
-    def advance(self, byte):
-        """Read one byte per group: an int32 [n] device tensor or a list of ints - 0..255, 256 to end the group with EOS, -1 to
-        leave it where it is.  `logp` grows by the row's entry."""
+    def next_byte_logZ(self):
+        """float32 [n] beside `next_byte_logprobs()`: under a constraint log Zc, the log of the mass the unconstrained row
+        (weighted by the automaton's arcs) leaves on what the state allows; without one the log of the candidates' mass."""
+        self.next_byte_logprobs()
+        return self._logZ
+
+    def _bytes(self, byte):
         if not torch.is_tensor(byte):
             byte = torch.tensor([int(b) for b in byte], dtype=torch.int32, device=self.dev)
         if byte.dtype != torch.int32 or byte.shape != (self.n,) or byte.device != self.dev:
             raise ValueError(f"byte must be an int32 [{self.n}] tensor on {self.dev}, or a list of {self.n} ints")
         if self.t >= self.max_bytes:
             raise ValueError(f"max_bytes = {self.max_bytes} bytes have been read")
+        return byte.contiguous()
+
+    def advance(self, byte):
+        """Read one byte per group: an int32 [n] device tensor or a list of ints - 0..255, 256 to end the group with EOS, -1 to
+        leave it where it is.  `logp` grows by the unconstrained row's entry; under a constraint the state moves and
+        `log_weights` grows by the weight the automaton gives the byte (a forbidden byte kills the group: weight -inf)."""
+        byte = self._bytes(byte)
         self._prepare()
-        self.eng.bytelm_next(self._trie, self.node, self.u, self.w, self.alive, self._sel, self._mass, self.width,
-                             byte=byte.contiguous(), logp=self.logp, fresh=self.fresh)
+        if self.tables is None:
+            self.eng.bytelm_next(self._trie, self.node, self.u, self.w, self.alive, self._sel, self._mass, self.width,
+                                 byte=byte, logp=self.logp, fresh=self.fresh)
+        else:
+            self._step(byte=byte)
         self.t += 1
         self._sel = self._mass = self._row = self._logZ = None
+
+    def step(self, seed=None, uniform=None):
+        """Under a constraint: draw one byte per group from the constrained row and read it, one launch after `_prepare()`.
+        `uniform` float32 [n] in [0, 1): the first column whose cumulative probability exceeds it; else one Philox uniform
+        per group from (`seed` (None: 0), the number of bytes read so far, the group).  `log_weights` grows by log Zc.
+        Returns the bytes, int32 [n] on the device: 256 for EOS, -1 for a group that has ended or died."""
+        if self.tables is None:
+            raise ValueError("step() draws under a constraint: this beam has none (generate() draws from the plain rows)")
+        if self.t >= self.max_bytes:
+            raise ValueError(f"max_bytes = {self.max_bytes} bytes have been read")
+        if uniform is not None and (not torch.is_tensor(uniform) or uniform.dtype != torch.float32 or uniform.shape != (self.n,)):
+            raise ValueError(f"uniform must be a float32 [{self.n}] tensor")
+        self._prepare()
+        out = self._step(uniform=uniform, seed=0 if seed is None else int(seed), offset=self.t)
+        self.t += 1
+        self._sel = self._mass = self._row = self._logZ = None
+        return out["byte"]
 
     def prefill(self, prefixes):
         """Advance group g through the bytes object prefixes[g] (shorter ones wait for the longest)."""
@@ -241,12 +327,18 @@ class ByteBeam:
     @torch.no_grad()
     def generate(self, max_bytes=64, seed=0, greedy=False):
         """Draw up to `max_bytes` further bytes per group from the rows (`torch.multinomial` on the [n, 257] matrix; greedy:
-        the most probable entry), stopping a group at EOS.  Returns one bytes object per group."""
+        the most probable entry), stopping a group at EOS.  Returns one bytes object per group.  Under a constraint the draws
+        are `step(seed)`'s, one Philox offset per byte position, and the greedy choice is the constrained row's: every text
+        is a prefix of a string of the language."""
+        steps = min(max_bytes, self.max_bytes - self.t)
+        if self.tables is not None and not greedy:
+            picked = [self.step(seed=seed) for _ in range(steps)]
+            return self._texts(picked)
         gen = torch.Generator(device=self.dev)
         gen.manual_seed(int(seed))
         done = torch.zeros(self.n, dtype=torch.bool, device=self.dev)
         picked = []
-        for _ in range(min(max_bytes, self.max_bytes - self.t)):
+        for _ in range(steps):
             row = self.next_byte_logprobs()
             done = done | ~torch.isfinite(row.max(dim=1).values)
             p = torch.where(done[:, None], torch.ones_like(row), row.exp())  # (a finished group's draw is not used)
@@ -255,7 +347,125 @@ class ByteBeam:
             picked.append(byte)
             self.advance(byte)
             done = done | (byte == EOS)
+        return self._texts(picked)
+
+    def _texts(self, picked):
         if not picked:
             return [b""] * self.n
         host = torch.stack(picked, dim=1).cpu().numpy()
         return [bytes(int(b) for b in host[g] if 0 <= b < 256) for g in range(self.n)]
+
+
+class ByteSIS:
+    """Sequential importance sampling over bytes under a byte automaton: the byte-level twin of `DeviceSIS`.
+
+    A particle is one group of a `ByteBeam(width=width, n=n, constraint=automaton)`.  A step draws every particle's next byte
+    from the model's next-byte row restricted to what the automaton's state allows (weighted by its arcs) and multiplies
+    the particle's weight by the mass Zc that row had before it was renormalised (glb_bytelm_step: one launch a step beside
+    the beam's own).  `run()` steps until every particle has ended (EOS from an accepting state) or died (nothing allowed
+    had mass), or `max_bytes` steps; it reads back one small flag every `CHECK_EVERY` steps (with `resample_ess`: two
+    scalars every step), never a row.  The drawn bytes stay on the device, int32 [n, max_bytes], until `results()`.
+
+    automaton     a `ByteDFA`, a `ByteWFSA` or a `DeviceTables`; a weight of the `ByteWFSA` multiplies the target
+    prefix        bytes every particle reads first (`ByteBeam.prefill`: the automaton moves along, its weights for them count)
+    resample_ess  None: never.  r: after a step, when the effective sample size of the weights is below r * n, ancestors are
+                  drawn systematically (`HipEngine.resample_systematic`, as `DeviceSIS`: ended particles take part, dead ones
+                  have no weight) and every per-group and per-slot tensor is gathered by ancestor - slot j of group g from
+                  slot j of group anc[g] - the logits store included: n * width * V elements copied per resampling
+                  (DESIGN.md §33); the weights become their mean.
+
+    `results()`: (texts, log_weights, finished).  A FINITE returned weight means the text is in the automaton's language and
+    ended with EOS; a particle that died, or that had neither ended nor died after `max_bytes`, is returned with -inf
+    (`sis.log_weights` keeps the raw value) and only an ended particle is `finished`."""
+
+    CHECK_EVERY = 4  # steps between two reads of the stop flag
+
+    def __init__(self, llm, n, automaton, byte_vocab, eos_ids, width=8, prompt_ids=None, prefix=b"", max_bytes=64, temperature=1.0,
+                 seed=0, resample_ess=None, ignore_ids=()):
+        if automaton is None:
+            raise ValueError("ByteSIS needs an automaton: a ByteDFA, a ByteWFSA or a DeviceTables")
+        if not isinstance(max_bytes, int) or max_bytes < 1:
+            raise ValueError(f"max_bytes must be a positive integer, got {max_bytes!r}")
+        if resample_ess is not None and not 0.0 < float(resample_ess) <= 1.0:
+            raise ValueError(f"resample_ess must be None or in (0, 1], got {resample_ess!r}")
+        self.prefix = bytes(prefix)
+        self.beam = ByteBeam(llm, byte_vocab, eos_ids, width=width, n=n, prompt_ids=prompt_ids, temperature=temperature,
+                             max_bytes=len(self.prefix) + max_bytes, ignore_ids=ignore_ids, constraint=automaton)
+        self.n, self.width, self.max_bytes, self.seed, self.resample_ess = n, width, max_bytes, int(seed), resample_ess
+        self.eng, self.dev = self.beam.eng, self.beam.dev
+        self.reset()
+
+    def reset(self):
+        self.beam.reset()
+        if self.prefix:
+            self.beam.prefill([self.prefix] * self.n)
+        self.bytes = torch.full((self.n, self.max_bytes), -1, dtype=torch.int32, device=self.dev)
+        self.t = self.n_resamples = 0
+
+    log_weights = property(lambda self: self.beam.log_weights)
+    logp = property(lambda self: self.beam.logp)
+
+    def _open(self):
+        """bool [n]: the particles that have neither ended nor died."""
+        return (self.beam.ended == 0) & (self.beam.state >= 0)
+
+    @torch.no_grad()
+    def step(self):
+        """One byte per particle; returns whether to go on when that was read back this step (else None)."""
+        self.bytes[:, self.t] = self.beam.step(seed=self.seed)
+        self.t += 1
+        if self.resample_ess is None:
+            return None
+        lw = self.beam.log_weights
+        wt = torch.exp(lw - lw.max().clamp_min(-3.0e38))  # (all dead: zeros)
+        ess, n_open = torch.stack([wt.sum() ** 2 / (wt * wt).sum().clamp_min(1e-30), self._open().sum().float()]).tolist()
+        if n_open and self.t < self.max_bytes and ess < self.resample_ess * self.n:  # (ess 0: no weight left, nothing to draw from)
+            if ess > 0.0:
+                anc, _ = self.eng.resample_systematic(lw, self.seed ^ 0x5eed5a11, self.t)
+                self._resample(anc)
+        return bool(n_open)
+
+    @torch.no_grad()
+    def _resample(self, anc):
+        """Particle g becomes a copy of particle anc[g] (int32 / int64 [n] on the device, or a list): torch indexing only."""
+        b, n, width = self.beam, self.n, self.width
+        if not torch.is_tensor(anc):
+            anc = torch.tensor([int(a) for a in anc], device=self.dev)
+        a = anc.long()
+        if a.shape != (n,):
+            raise ValueError(f"anc must name an ancestor for each of the {n} particles")
+        slots = (a[:, None] * width + torch.arange(width, device=self.dev)[None, :]).reshape(-1)
+        for name in ("contexts", "lengths", "node", "alive", "u", "w", "store", "lse"):
+            t = getattr(b, name)
+            if t is not None:
+                setattr(b, name, t[slots].contiguous())
+        for name in ("fresh", "logp", "state", "ended"):
+            setattr(b, name, getattr(b, name)[a].contiguous())
+        self.bytes = self.bytes[a].contiguous()
+        mean = torch.logsumexp(b.log_weights, 0) - math.log(n)
+        b.log_weights = mean.expand(n).contiguous()
+        b._sel = b._mass = b._row = b._logZ = None  # (they described the slots as they were)
+        self.n_resamples += 1
+
+    @torch.no_grad()
+    def run(self):
+        while self.t < self.max_bytes:
+            go = self.step()
+            if go is None and (self.t % self.CHECK_EVERY == 0):
+                go = bool(self._open().any().item())
+            if go is False:
+                break
+        return self
+
+    def results(self):
+        """(texts, log_weights, finished): the prefix and the drawn bytes of every particle (one copy to the host), float32
+        [n] on the device with -inf for every particle that is not finished, bool [n] on the device."""
+        finished = self.beam.ended != 0
+        lw = torch.where(finished, self.beam.log_weights, torch.full_like(self.beam.log_weights, float("-inf")))
+        host = self.bytes.cpu().numpy()
+        return [self.prefix + bytes(int(v) for v in row if 0 <= v < 256) for row in host], lw, finished
+
+    def log_evidence(self):
+        """logsumexp(the finished particles' log-weights) - log n: a 0-dim device tensor."""
+        lw = self.beam.log_weights
+        return torch.logsumexp(torch.where(self.beam.ended != 0, lw, torch.full_like(lw, float("-inf"))), 0) - math.log(self.n)

@@ -742,6 +742,58 @@ class HipEngine:
         check(self.lib.glb_bytelm_next(C.byref(a), self._stream()))
         return None
 
+    def bytelm_step(self, trie, node, u, w, alive, sel, mass, width, tables, state, ended, log_weight, logp, byte=None, uniform=None,
+                    seed=0, offset=0, fresh=None, want_row=False, peek=False):
+        """One byte step of a byte beam under a byte automaton, one launch (glb_bytelm_step).  `tables`: a
+        `constraints.tables.DeviceTables` on this device; state and ended int32 [G], log_weight and logp float32 [G].  The
+        byte: `byte` int32 [G] given (-1 leaves a group alone), else the first column whose cumulative constrained
+        probability exceeds `uniform` float32 [G], else that rule on one Philox uniform per group from (seed, offset, g).
+        node, w, alive, fresh, logp, state, ended and log_weight are written in place.  Returns a dict: `byte` int32 [G]
+        (the given tensor, or the bytes drawn: -1 for a group that died or had ended), `logZc` float32 [G], and with `want_row` `row` float32 [G, 257], the constrained and renormalised row.
+        peek: only `logZc` and `row` are made, nothing moves and `byte` is None."""
+        from .constraints.tables import DeviceTables
+
+        if not isinstance(tables, DeviceTables):
+            raise ValueError(f"tables must be a DeviceTables, got {type(tables).__name__}")
+        if tables.live is None:
+            raise ValueError("tables without `live` (as `minimized` returns them): upload a host automaton")
+        if byte is not None and uniform is not None:
+            raise ValueError("give byte or uniform, not both")
+        p = _lib.ByteLmStepArgs()
+        p.struct_size, p.peek = C.sizeof(_lib.ByteLmStepArgs), int(bool(peek))
+        p.beam, n = self._bytelm_block(trie, node, alive, width, u=u, w=w, sel=sel, mass=mass, byte=None if peek else byte, logp=logp,
+                                       fresh=fresh)
+        G, S = n // width, int(tables.n_states)
+        want = {"delta": (torch.int32, (S, 256)), "accepting": (torch.uint8, (S,)), "live": (torch.uint8, (S,)),
+                "arc_logw": (torch.float32, (S, 256)), "final_logw": (torch.float32, (S,)), "state": (torch.int32, (G,)),
+                "ended": (torch.int32, (G,)), "log_weight": (torch.float32, (G,)), "uniform": (torch.float32, (G,))}
+        given = dict(delta=tables.delta, accepting=tables.accepting, live=tables.live, arc_logw=tables.arc_logw,
+                     final_logw=tables.final_logw, state=state, ended=ended, log_weight=log_weight, uniform=None if peek else uniform)
+        for k, t in given.items():
+            if t is None:
+                if k not in ("arc_logw", "final_logw", "uniform"):
+                    raise ValueError(f"{k} is missing")
+                continue
+            self._check_dev(t)
+            if t.dtype != want[k][0] or tuple(t.shape) != want[k][1]:
+                raise ValueError(f"{k} must be a {want[k][0]} tensor of shape {list(want[k][1])}, got {t.dtype} {list(t.shape)}")
+            setattr(p, k, t.data_ptr())
+        if logp is None:
+            raise ValueError("logp is missing")
+        p.n_states, p.seed, p.offset = S, int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1)
+        out = {"byte": byte, "logZc": self._f32(G)}
+        if peek:
+            out["byte"] = None
+        elif byte is None:
+            out["byte"] = self._i32(G)
+            p.out_byte = out["byte"].data_ptr()
+        p.out_logZc = out["logZc"].data_ptr()
+        if want_row:
+            out["row"] = torch.empty((G, self.BYTELM_ROW), dtype=torch.float32, device=self.device)
+            p.out_row = out["row"].data_ptr()
+        check(self.lib.glb_bytelm_step(C.byref(p), self._stream()))
+        return out
+
     # ---- failed one-launch calls (include/glb.h: glb_workspace_check) ---------------------------------------------
     def error_word(self):
         """int32 [1] device view of the scratch buffer's error word: nonzero after a one-launch call whose waves gave

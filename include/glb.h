@@ -2037,6 +2037,66 @@ int glb_bytelm_children(const glb_bytelm_args *args, void *hip_stream);
 int glb_bytelm_extend(const glb_bytelm_args *args, void *hip_stream);
 int glb_bytelm_next(const glb_bytelm_args *args, void *hip_stream);
 
+/*
+ * One byte step of the beam under a byte automaton: per group g, in one launch, what glb_bytelm_next, a
+ * mask, a normalisation, a draw and glb_bytelm_next(byte) do.  The automaton's tables are those of the constraint calls: delta
+ * int32 [n_states, 256] (a target outside 0 .. n_states - 1: no arc), accepting and live uint8 [n_states], and - both or
+ * neither - arc_logw float32 [n_states, 256] and final_logw float32 [n_states].  Per group: state int32 (the automaton's state,
+ * -1 once the group has ended or died), ended int32 (1 after EOS was read from an accepting state), log_weight float32.
+ *
+ * A group with ended[g] != 0 is skipped: of the group nothing is written; its out_row and out_logZc are -inf and a drawn step's
+ * out_byte is -1.  Otherwise, with row[0 .. 256] and logZ exactly glb_bytelm_next's and s = state[g]:
+ *     lc[b]   = row[b] + arc_logw[s, b] (+ 0 without weights) where t = delta[s, b] lies in 0 .. n_states - 1 and live[t] != 0,
+ *               else -inf;  lc[256] = row[256] + final_logw[s] (+ 0 without weights) where accepting[s] != 0, else -inf.  A sum
+ *               that is not finite (a weight of -inf, NaN or +inf) is -inf.  s outside 0 .. n_states - 1: all -inf, nothing
+ *               of the tables is read.
+ *     logZc   = m + logf(sum of expf(lc - m)), m the largest lc; the sum in the fixed order of glb_bytelm_next's Z.  -inf where
+ *               every lc is.  out_logZc[g] = logZc; out_row[g, :] (nullable) = lc - logZc, -inf where lc is.
+ *     peek != 0: nothing else happens; beam.byte and uniform are not read.
+ *     the byte  beam.byte given: byte[g]; outside 0 .. 256 the group is left wholly alone, as an ended one.
+ *               uniform float32 [n_groups] given: the first column c in the order 0 .. 256 with lc[c] > -inf whose cumulative
+ *               probability exceeds uniform[g]; the cumulative probability of column q * 64 + l is the sum of the totals of
+ *               the 64-column blocks before block q plus the inclusive scan of expf(out_row) over the block's lanes 0 .. l
+ *               (doubling steps 1, 2, .. 32), all in float32; where none exceeds it, the last column with lc > -inf.
+ *               neither: that rule with uniform = (float)(r0 >> 8) * 2^-24, r0 word 0 of glb_philox4x32_10 with counter
+ *               {low 32 bits of g, high 32 bits of g, low 32 bits of offset, high 32 bits of offset} and key {low 32 bits of
+ *               seed, high 32 bits of seed} - the counter and key of the fused step's draws (g in the particle's place), whose
+ *               draws are integers; this one is the 24 high bits of one word.
+ *     the group dies when every lc is -inf, or when the given byte's lc is -inf: state -1, log_weight -inf, every candidate
+ *               dead (alive 0, w -inf), fresh 1; logp grows by the given byte's row entry, and not at all without a byte;
+ *               out_byte (nullable when the byte is given) gets -1 when the byte was to be drawn, else the given byte.
+ *     otherwise node, w, alive, fresh and logp change exactly as under glb_bytelm_next(byte) - logp by the UNCONSTRAINED row's
+ *               entry; state[g] = delta[s, byte], or -1 after EOS, which also sets ended[g] = 1; log_weight[g] += logZc for a
+ *               drawn byte, and for a given one += what the automaton gives it, lc[byte] - row[byte]: arc_logw[s, byte]
+ *               (final_logw[s] for EOS), 0 without weights; out_byte[g] = the byte.
+ * One wave per group; a group's outputs depend on that group's inputs alone.  No workspace, nothing waits, synchronises or
+ * allocates; safe under stream capture.  GLB_EINVAL before any launch: what glb_bytelm_next refuses for `beam` (its struct_size
+ * included); struct_size wrong; n_states not positive or n_states * 256 beyond 31 bits; null delta, accepting, live, state,
+ * ended or out_logZc; arc_logw without final_logw or the reverse; without peek: null beam.logp or log_weight, and null
+ * out_byte where the byte is drawn.
+ */
+typedef struct glb_bytelm_step_args {
+  uint32_t struct_size; /* sizeof this block - ABI guard */
+  int32_t peek;         /* nonzero: out_row / out_logZc only, nothing moves */
+  glb_bytelm_args beam; /* the beam, as for glb_bytelm_next; beam.byte: the given bytes, nullable */
+  int64_t n_states;
+  const int32_t *delta;     /* [n_states, 256] */
+  const uint8_t *accepting; /* [n_states] */
+  const uint8_t *live;      /* [n_states] */
+  const float *arc_logw;    /* [n_states, 256], nullable (with final_logw) */
+  const float *final_logw;  /* [n_states], nullable */
+  int32_t *state;           /* [n_groups] each */
+  int32_t *ended;
+  float *log_weight;
+  const float *uniform; /* [n_groups], nullable */
+  uint64_t seed;
+  uint64_t offset;
+  int32_t *out_byte; /* [n_groups] */
+  float *out_row;    /* [n_groups, GLB_BYTELM_ROW], nullable */
+  float *out_logZc;  /* [n_groups] */
+} glb_bytelm_step_args;
+int glb_bytelm_step(const glb_bytelm_step_args *args, void *hip_stream);
+
 /* Philox4x32-10 block function, exposed so hosts can reproduce the device draws. */
 void glb_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 
