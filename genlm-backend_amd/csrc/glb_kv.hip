@@ -9,8 +9,11 @@
 #include <hip/hip_runtime.h>
 
 #include <climits>
+#include <initializer_list>
+#include <type_traits>
 
 #include "../../include/glb.h"
+#include "glb_attn.hpp"
 #include "glb_common.hpp"
 
 namespace {
@@ -434,51 +437,9 @@ __global__ __launch_bounds__(kT) void kv_plan_kernel(const PlanArgs a) {
 // position slot keeps its own online softmax (running maximum, denominator, weighted V sum) over the positions it is
 // dealt; the PP slots are merged once at the end.  The new token's K / V come straight from the projection output and
 // are written to their slab position by the wave of the group's first query head (the append of glb_kv_append, fused).
-// float32 accumulation whatever the element type.
+// float32 accumulation whatever the element type.  The wave's shape, the 16-byte vectors and a slot's score are
+// glb_attn.hpp's, for all five attention kernels.
 // ---------------------------------------------------------------------------------------------------------------------
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-template <int DT>
-__device__ __forceinline__ void unpack16(const u32x4 &w, float *x) {
-  const uint32_t v[4] = {w.x, w.y, w.z, w.w};
-  if constexpr (DT == GLB_F32) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) x[k] = __uint_as_float(v[k]);
-  } else if constexpr (DT == GLB_BF16) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      x[2 * k] = __uint_as_float(v[k] << 16);
-      x[2 * k + 1] = __uint_as_float(v[k] & 0xffff0000u);
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      x[2 * k] = (float)__builtin_bit_cast(_Float16, (uint16_t)(v[k] & 0xffffu));
-      x[2 * k + 1] = (float)__builtin_bit_cast(_Float16, (uint16_t)(v[k] >> 16));
-    }
-  }
-}
-
-template <int DT>
-__device__ __forceinline__ u32x4 pack16v(const float *x) {
-  if constexpr (DT == GLB_F32) {
-    return u32x4{__float_as_uint(x[0]), __float_as_uint(x[1]), __float_as_uint(x[2]), __float_as_uint(x[3])};
-  } else {
-    uint32_t w[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      if constexpr (DT == GLB_BF16) {
-        const __bf16 a = (__bf16)x[2 * k], b = (__bf16)x[2 * k + 1];
-        w[k] = (uint32_t)__builtin_bit_cast(uint16_t, a) | ((uint32_t)__builtin_bit_cast(uint16_t, b) << 16);
-      } else {
-        const _Float16 a = (_Float16)x[2 * k], b = (_Float16)x[2 * k + 1];
-        w[k] = (uint32_t)__builtin_bit_cast(uint16_t, a) | ((uint32_t)__builtin_bit_cast(uint16_t, b) << 16);
-      }
-    }
-    return u32x4{w[0], w[1], w[2], w[3]};
-  }
-}
-
 struct AttnArgs {
   const char *q, *k_new, *v_new;
   char *k_slab, *v_slab, *out;
@@ -490,8 +451,8 @@ struct AttnArgs {
 
 template <int DT, int DH>
 __global__ __launch_bounds__(64) void slab_attention_kernel(const AttnArgs a) {
-  constexpr int ES = DT == GLB_F32 ? 4 : 2, EPV = 16 / ES, LP = DH / EPV, PP = 64 / LP;
-  static_assert(LP >= 1 && LP <= 64 && PP * LP == 64, "head_dim / vector width must divide the wave");
+  using W = WaveShape<DT, DH>;
+  constexpr int ES = W::ES, EPV = W::EPV, LP = W::LP, PP = W::PP;
   const int lane = threadIdx.x, j = lane / LP, i = lane - j * LP;
   const int r = blockIdx.x / a.H, h = blockIdx.x - r * a.H;
   const int G = a.H / a.Hkv, hk = h / G;
@@ -522,11 +483,7 @@ __global__ __launch_bounds__(64) void slab_attention_kernel(const AttnArgs a) {
 #pragma unroll
       for (int k = 0; k < EPV; ++k) kf[k] = kn[k], vf[k] = vn[k];
     }
-    float s = 0.0f;
-#pragma unroll
-    for (int k = 0; k < EPV; ++k) s = __builtin_fmaf(qf[k], kf[k], s);
-#pragma unroll
-    for (int o = 1; o < LP; o <<= 1) s += __shfl_xor(s, o, 64);  // the LP lanes of a position end up with its score
+    float s = slot_score<LP, EPV>(qf, kf);
     if (p <= p_new) {
       s *= a.scale;
       const float m2 = fmaxf(m, s), c = __expf(m - m2), w = __expf(s - m2);
@@ -555,22 +512,14 @@ __global__ __launch_bounds__(64) void slab_attention_kernel(const AttnArgs a) {
   }
 }
 
-template <int DT>
-hipError_t launch_attention(const AttnArgs &a, int head_dim, hipStream_t s) {
-  const dim3 grid((unsigned)((int64_t)a.R * a.H)), block(64);
-  if (head_dim == 64) hipLaunchKernelGGL((slab_attention_kernel<DT, 64>), grid, block, 0, s, a);
-  else if (head_dim == 128) hipLaunchKernelGGL((slab_attention_kernel<DT, 128>), grid, block, 0, s, a);
-  else if (head_dim == 32) hipLaunchKernelGGL((slab_attention_kernel<DT, 32>), grid, block, 0, s, a);
-  else if (head_dim == 16) hipLaunchKernelGGL((slab_attention_kernel<DT, 16>), grid, block, 0, s, a);
-  else return hipErrorInvalidValue;
-  return hipGetLastError();
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
 // glb_slab_attention_chunk: up to 16 new tokens per row in one forward.  One wave per (row, query head, new token t): the
-// wave is the one-token kernel above for the query at position pos + t - the same LP lanes a position, PP positions a
-// load, the same position -> slot deal (p = p0 + j), the same online softmax per slot and the same slot merge - so its
-// output carries the bits the t + 1'th of successive glb_slab_attention calls would leave.  Positions below pos come from
+// wave is a query at position pos + t with slab_attention_kernel's WaveShape, its position -> slot deal (p = p0 + j) and its
+// slot_score (glb_attn.hpp), and with that kernel's online-softmax update and slot merge WRITTEN OUT AGAIN below: the two
+// texts are kept equal by hand, and test_slab_attention_chunk holds them to it - the output carries the bits the t + 1'th
+// of successive glb_slab_attention calls would leave.  (One SlotSoftmax for both kept every register count, and all 24
+// forms were timed against the parent's text: 23 inside its spread, slab_attention_kernel<f16, 32> 0.5% outside it on
+// the slow side in five runs of five, so the text stayed: profiles/INDEX.md, r35.)  Positions below pos come from
 // the slab; positions pos .. pos + t from k_new / v_new where the projection left them, NEVER from the slab (no wave
 // reads what another wave of the launch writes: no hand-off inside the launch); the wave of the group's first query head
 // writes its own token's K / V to slab position pos + t.  The T waves of a (row, head) read the same slab positions: the
@@ -589,8 +538,8 @@ struct ChunkAttnArgs {
 
 template <int DT, int DH>
 __global__ __launch_bounds__(64) void slab_attention_chunk_kernel(const ChunkAttnArgs a) {
-  constexpr int ES = DT == GLB_F32 ? 4 : 2, EPV = 16 / ES, LP = DH / EPV, PP = 64 / LP;
-  static_assert(LP >= 1 && LP <= 64 && PP * LP == 64, "head_dim / vector width must divide the wave");
+  using W = WaveShape<DT, DH>;
+  constexpr int ES = W::ES, EPV = W::EPV, LP = W::LP, PP = W::PP;
   const int lane = threadIdx.x, j = lane / LP, i = lane - j * LP;
   const int t = blockIdx.x % a.T, rh = blockIdx.x / a.T;
   const int r = rh / a.H, h = rh - r * a.H;
@@ -634,11 +583,7 @@ __global__ __launch_bounds__(64) void slab_attention_chunk_kernel(const ChunkAtt
       unpack16<DT>(*reinterpret_cast<const u32x4 *>(kb + (int64_t)tn * a.k_sp * ES), kf);
       unpack16<DT>(*reinterpret_cast<const u32x4 *>(vb + (int64_t)tn * a.v_sp * ES), vf);
     }
-    float s = 0.0f;
-#pragma unroll
-    for (int k = 0; k < EPV; ++k) s = __builtin_fmaf(qf[k], kf[k], s);
-#pragma unroll
-    for (int o = 1; o < LP; o <<= 1) s += __shfl_xor(s, o, 64);  // the LP lanes of a position end up with its score
+    float s = slot_score<LP, EPV>(qf, kf);
     if (p <= p_new) {
       s *= a.scale;
       const float m2 = fmaxf(m, s), c = __expf(m - m2), w = __expf(s - m2);
@@ -667,17 +612,6 @@ __global__ __launch_bounds__(64) void slab_attention_chunk_kernel(const ChunkAtt
   }
 }
 
-template <int DT>
-hipError_t launch_attention_chunk(const ChunkAttnArgs &a, int head_dim, hipStream_t s) {
-  const dim3 grid((unsigned)((int64_t)a.n * a.H * a.T)), block(64);
-  if (head_dim == 64) hipLaunchKernelGGL((slab_attention_chunk_kernel<DT, 64>), grid, block, 0, s, a);
-  else if (head_dim == 128) hipLaunchKernelGGL((slab_attention_chunk_kernel<DT, 128>), grid, block, 0, s, a);
-  else if (head_dim == 32) hipLaunchKernelGGL((slab_attention_chunk_kernel<DT, 32>), grid, block, 0, s, a);
-  else if (head_dim == 16) hipLaunchKernelGGL((slab_attention_chunk_kernel<DT, 16>), grid, block, 0, s, a);
-  else return hipErrorInvalidValue;
-  return hipGetLastError();
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
 // glb_short_attention: masked attention of the padded batches of short contexts the hot path feeds the transformer
 // (hf.py:232-281: ragged contexts right-padded to the batch's longest, optionally behind zero-padded cached prefixes) -
@@ -703,8 +637,8 @@ struct ShortArgs {
 
 template <int DT, int DH>
 __global__ __launch_bounds__(64) void short_attention_kernel(const ShortArgs a) {
-  constexpr int ES = DT == GLB_F32 ? 4 : 2, EPV = 16 / ES, LP = DH / EPV, PP = 64 / LP;
-  static_assert(LP >= 1 && LP <= 64 && PP * LP == 64, "head_dim / vector width must divide the wave");
+  using W = WaveShape<DT, DH>;
+  constexpr int ES = W::ES, EPV = W::EPV, LP = W::LP, PP = W::PP;
   const int lane = threadIdx.x, j = lane / LP, i = lane - j * LP;
   const int t = blockIdx.x % a.Lq, uh = blockIdx.x / a.Lq, h = uh % a.H, u = uh / a.H;
   const int hk = h / (a.H / a.Hkv);
@@ -725,11 +659,7 @@ __global__ __launch_bounds__(64) void short_attention_kernel(const ShortArgs a) 
     const int pc = in ? p : last;  // (lanes past the end read the last key and ignore it)
     unpack16<DT>(*reinterpret_cast<const u32x4 *>(kb + (int64_t)pc * a.k_sp * ES), kf);
     unpack16<DT>(*reinterpret_cast<const u32x4 *>(vb + (int64_t)pc * a.v_sp * ES), vf);
-    float s = 0.0f;
-#pragma unroll
-    for (int k = 0; k < EPV; ++k) s = __builtin_fmaf(qf[k], kf[k], s);
-#pragma unroll
-    for (int o = 1; o < LP; o <<= 1) s += __shfl_xor(s, o, 64);
+    float s = slot_score<LP, EPV>(qf, kf);
     if (see) {
       s *= a.scale;
       const float m2 = fmaxf(m, s), c = __expf(m - m2), w = __expf(s - m2);
@@ -766,22 +696,10 @@ __global__ __launch_bounds__(64) void short_attention_kernel(const ShortArgs a) 
 // key's score is one dot product chunk per lane + log2(LP) DPP adds inside the slot, the scores of a query stay in
 // registers, and nothing is ever merged across slots: ~40 instructions a query.  Keys up to KMAX (16 / 32) per call;
 // longer key ranges keep the kernel above.
-template <int LP>
-__device__ __forceinline__ float slot_sum(float v) {
-  // sum over the LP consecutive lanes of a slot, every lane gets it (DPP: quad_perm xor 1, xor 2, row_half_mirror, row_mirror)
-  if constexpr (LP >= 2) v += __uint_as_float((uint32_t)__builtin_amdgcn_update_dpp(0, (int)__float_as_uint(v), 0xB1, 0xf, 0xf, false));
-  if constexpr (LP >= 4) v += __uint_as_float((uint32_t)__builtin_amdgcn_update_dpp(0, (int)__float_as_uint(v), 0x4E, 0xf, 0xf, false));
-  if constexpr (LP >= 8) v += __uint_as_float((uint32_t)__builtin_amdgcn_update_dpp(0, (int)__float_as_uint(v), 0x141, 0xf, 0xf, false));
-  if constexpr (LP >= 16) v += __uint_as_float((uint32_t)__builtin_amdgcn_update_dpp(0, (int)__float_as_uint(v), 0x140, 0xf, 0xf, false));
-  if constexpr (LP >= 32) v += __shfl_xor(v, 16, 64);
-  if constexpr (LP >= 64) v += __shfl_xor(v, 32, 64);
-  return v;
-}
-
 template <int DT, int DH, int KMAX>
 __global__ __launch_bounds__(64) void short_attention_rows_kernel(const ShortArgs a) {
-  constexpr int ES = DT == GLB_F32 ? 4 : 2, EPV = 16 / ES, LP = DH / EPV, PP = 64 / LP;
-  static_assert(LP >= 1 && LP <= 64 && PP * LP == 64, "head_dim / vector width must divide the wave");
+  using W = WaveShape<DT, DH>;
+  constexpr int ES = W::ES, EPV = W::EPV, LP = W::LP, PP = W::PP;
   // up to 16 keys: a lane keeps its chunk of every key in registers (K never passes through LDS: with K and V both read
   // from LDS for every query group the LDS data path - 1 KB a read instruction - took as long as the arithmetic)
   constexpr bool KREG = KMAX * EPV <= 128;
@@ -892,42 +810,18 @@ __global__ __launch_bounds__(64) void short_attention_rows_kernel(const ShortArg
   }
 }
 
-template <int DT, int DH>
-hipError_t launch_short_rows(const ShortArgs &a, hipStream_t s) {
-  const dim3 grid((unsigned)((int64_t)a.U * a.Hkv)), block(64);
-  const size_t lds = (size_t)2 * a.Lk * DH * sizeof(float) + (size_t)a.Lq * sizeof(uint32_t);
-  if (a.Lk <= 16) hipLaunchKernelGGL((short_attention_rows_kernel<DT, DH, 16>), grid, block, lds, s, a);
-  else hipLaunchKernelGGL((short_attention_rows_kernel<DT, DH, 32>), grid, block, lds, s, a);
-  return hipGetLastError();
-}
-
-template <int DT>
-hipError_t launch_short_attention(const ShortArgs &a, int head_dim, hipStream_t s) {
-  if (a.Lk <= 32 && a.Lq <= 2048 && (int64_t)a.U * a.Hkv <= 0x7fffffffll) {  // the (row, KV head) form: K / V in LDS once, slots are queries
-    if (head_dim == 64) return launch_short_rows<DT, 64>(a, s);
-    if (head_dim == 128) return launch_short_rows<DT, 128>(a, s);
-    if (head_dim == 32) return launch_short_rows<DT, 32>(a, s);
-    if (head_dim == 16) return launch_short_rows<DT, 16>(a, s);
-    return hipErrorInvalidValue;
-  }
-  const dim3 grid((unsigned)((int64_t)a.U * a.H * a.Lq)), block(64);
-  if (head_dim == 64) hipLaunchKernelGGL((short_attention_kernel<DT, 64>), grid, block, 0, s, a);
-  else if (head_dim == 128) hipLaunchKernelGGL((short_attention_kernel<DT, 128>), grid, block, 0, s, a);
-  else if (head_dim == 32) hipLaunchKernelGGL((short_attention_kernel<DT, 32>), grid, block, 0, s, a);
-  else if (head_dim == 16) hipLaunchKernelGGL((short_attention_kernel<DT, 16>), grid, block, 0, s, a);
-  else return hipErrorInvalidValue;
-  return hipGetLastError();
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
 // glb_short_attention_packed: short_attention_rows_kernel over a ROW-PACKED batch whose contexts share their prompt's rows.
 // q / k / v are [M, heads, DH] views of one projection output (row and head strides, unit inner stride); segment s of the plan
 // is (pre_start, pre_len, tail_start, tail_len): its tail_len queries are rows tail_start .., its keys 0 .. pre_len - 1 are
 // rows pre_start .. (the shared prompt, computed once for every context behind it), its keys pre_len .. rows tail_start ..;
 // query t sees keys 0 .. pre_len + t.  A prompt itself is a segment without a prefix.  One wave per (segment, KV head); the
-// arithmetic is short_attention_rows_kernel's with Lk = pre_len + tail_len and Lq = tail_len - same key order, same
-// KREG / LDS choice by the call's most keys, same slot_sum, same max-then-exp - so a query's output has the bits
-// glb_short_attention gives it on the right-padded batch (there the keys behind a context's end weigh exactly 0).
+// arithmetic is short_attention_rows_kernel's with Lk = pre_len + tail_len and Lq = tail_len: its WaveShape and slot_sum
+// (glb_attn.hpp), and its body from the first q_raw load to the last store WRITTEN OUT AGAIN with this kernel's row
+// indices - key order, KREG / LDS choice by the call's most keys and max-then-exp are kept equal by hand (one function for
+// both cost the packed forms 2 to 8 VGPRs and a wave of occupancy in six of them), and tests/test_packed_attention_gpu.py
+// holds them to it: a query's output has the bits glb_short_attention gives it on the right-padded batch (there the keys
+// behind a context's end weigh exactly 0).
 // Every index comes from the plan, so every segment is range-checked before an address is formed: one that holds more than
 // `max_keys` keys, no query, or rows outside [0, M) writes nothing and counts in the error word.
 // ---------------------------------------------------------------------------------------------------------------------
@@ -943,10 +837,10 @@ struct PackedArgs {
 
 template <int DT, int DH, int KMAX>
 __global__ __launch_bounds__(64) void short_attention_packed_kernel(const PackedArgs a) {
-  constexpr int ES = DT == GLB_F32 ? 4 : 2, EPV = 16 / ES, LP = DH / EPV, PP = 64 / LP;
-  static_assert(LP >= 1 && LP <= 64 && PP * LP == 64, "head_dim / vector width must divide the wave");
+  using W = WaveShape<DT, DH>;
+  constexpr int ES = W::ES, EPV = W::EPV, LP = W::LP, PP = W::PP;
   constexpr bool KREG = KMAX * EPV <= 128;
-  extern __shared__ float kv_lds[];  // as short_attention_rows_kernel: (K,) V [Lk][DH] float32, then a word per query
+  extern __shared__ float kv_lds[];  // short_attention_rows_kernel's layout: (K,) V [Lk][DH] float32, then a word per query
   const int lane = threadIdx.x, j = lane / LP, i = lane - j * LP;
   const int G = a.H / a.Hkv;
   const int hk = blockIdx.x % a.Hkv, s = blockIdx.x / a.Hkv;
@@ -1054,22 +948,53 @@ __global__ __launch_bounds__(64) void short_attention_packed_kernel(const Packed
   }
 }
 
-template <int DT, int DH>
-hipError_t launch_short_packed_dh(const PackedArgs &a, hipStream_t s) {
-  const dim3 grid((unsigned)((int64_t)a.S * a.Hkv)), block(64);
-  const size_t lds = (size_t)2 * a.max_keys * DH * sizeof(float) + (size_t)a.max_keys * sizeof(uint32_t);
-  if (a.max_keys <= 16) hipLaunchKernelGGL((short_attention_packed_kernel<DT, DH, 16>), grid, block, lds, s, a);
-  else hipLaunchKernelGGL((short_attention_packed_kernel<DT, DH, 32>), grid, block, lds, s, a);
-  return hipGetLastError();
+// ---- the dispatch over the built forms: f gets the element type / the head size as an std::integral_constant ------------
+template <class F>
+hipError_t with_dtype(int32_t dtype, F f) {
+  switch (dtype) {
+    case GLB_F32: return f(std::integral_constant<int, GLB_F32>{});
+    case GLB_BF16: return f(std::integral_constant<int, GLB_BF16>{});
+    default: return f(std::integral_constant<int, GLB_F16>{});
+  }
 }
 
-template <int DT>
-hipError_t launch_short_packed(const PackedArgs &a, int head_dim, hipStream_t s) {
-  if (head_dim == 64) return launch_short_packed_dh<DT, 64>(a, s);
-  if (head_dim == 128) return launch_short_packed_dh<DT, 128>(a, s);
-  if (head_dim == 32) return launch_short_packed_dh<DT, 32>(a, s);
-  if (head_dim == 16) return launch_short_packed_dh<DT, 16>(a, s);
+template <class F>
+hipError_t with_head_dim(int64_t head_dim, F f) {
+  if (head_dim == 64) return f(std::integral_constant<int, 64>{});
+  if (head_dim == 128) return f(std::integral_constant<int, 128>{});
+  if (head_dim == 32) return f(std::integral_constant<int, 32>{});
+  if (head_dim == 16) return f(std::integral_constant<int, 16>{});
   return hipErrorInvalidValue;
+}
+
+// launch(dt, dh) enqueues the kernel of that form; the launch's error
+template <class F>
+hipError_t launch_attention_form(int32_t dtype, int64_t head_dim, F launch) {
+  return with_dtype(dtype, [&](auto dt) {
+    return with_head_dim(head_dim, [&](auto dh) {
+      launch(dt, dh);
+      return hipGetLastError();
+    });
+  });
+}
+
+// What the four attention entries check, around their own size checks: the element type before them ...
+inline int check_dtype(int32_t dtype) {
+  if (dtype < GLB_F32 || dtype > GLB_F16) return glb::api_fail(GLB_EINVAL, "bad dtype %d", dtype);
+  return GLB_OK;
+}
+
+// ... and behind them the head size, then 16-byte alignment of every pointer and every byte stride (`aligned`: what else the
+// entry reports under that message)
+inline int check_head_dim_and_alignment(const char *entry, int32_t dtype, int64_t head_dim, std::initializer_list<const void *> ptrs,
+                                        std::initializer_list<int64_t> strides, bool aligned = true) {
+  if (head_dim != 16 && head_dim != 32 && head_dim != 64 && head_dim != 128)
+    return glb::api_fail(GLB_EUNSUPPORTED, "%s: head_dim %lld (16, 32, 64 and 128 are built)", entry, (long long)head_dim);
+  const int es = dtype == GLB_F32 ? 4 : 2;
+  for (const void *p : ptrs) aligned = aligned && (uintptr_t)p % 16 == 0;
+  for (const int64_t st : strides) aligned = aligned && (st * es) % 16 == 0;
+  if (!aligned) return glb::api_fail(GLB_EINVAL, "%s: pointers and strides must be 16-byte aligned", entry);
+  return GLB_OK;
 }
 
 // ---- KV slab rows: append, gather (moved here from glb_api.hip in round 5) ---------------------------------------------------
@@ -1111,7 +1036,6 @@ __global__ void gather_rows_i32_kernel(const int32_t *src, int64_t src_ld, const
   const int64_t i = gid / width, j = gid % width;
   dst[i * dst_ld + j] = src[(int64_t)row_of[i] * src_ld + j];
 }
-
 
 }  // namespace
 
@@ -1187,23 +1111,18 @@ int glb_gather_rows_i32(const int32_t *src, int64_t src_ld, const int32_t *row_o
   return GLB_OK;
 }
 
-
 int glb_slab_attention(const void *q, int64_t q_stride_row, int64_t q_stride_head, const void *k_new, int64_t k_stride_row,
                        int64_t k_stride_head, const void *v_new, int64_t v_stride_row, int64_t v_stride_head, void *k_slab,
                        void *v_slab, const int32_t *pos,
                        int64_t n_rows, int64_t heads, int64_t kv_heads, int64_t cap, int64_t head_dim, float scale,
                        int32_t dtype, void *out, void *stream) {
   if (!q || !k_new || !v_new || !k_slab || !v_slab || !pos || !out) return glb::api_fail(GLB_EINVAL, "glb_slab_attention: null pointer");
-  if (dtype < GLB_F32 || dtype > GLB_F16) return glb::api_fail(GLB_EINVAL, "bad dtype %d", dtype);
+  if (const int rc = check_dtype(dtype)) return rc;
   if (n_rows <= 0 || heads <= 0 || kv_heads <= 0 || cap <= 0 || heads % kv_heads || n_rows * heads > 0x7fffffffll)
     return glb::api_fail(GLB_EINVAL, "glb_slab_attention: bad sizes");
-  if (head_dim != 16 && head_dim != 32 && head_dim != 64 && head_dim != 128)
-    return glb::api_fail(GLB_EUNSUPPORTED, "glb_slab_attention: head_dim %lld (16, 32, 64 and 128 are built)", (long long)head_dim);
-  const int es = dtype == GLB_F32 ? 4 : 2;
-  if (((uintptr_t)q | (uintptr_t)k_new | (uintptr_t)v_new | (uintptr_t)k_slab | (uintptr_t)v_slab | (uintptr_t)out) % 16 ||
-      (q_stride_row * es) % 16 || (q_stride_head * es) % 16 || (k_stride_row * es) % 16 || (k_stride_head * es) % 16 ||
-      (v_stride_row * es) % 16 || (v_stride_head * es) % 16)
-    return glb::api_fail(GLB_EINVAL, "glb_slab_attention: pointers and strides must be 16-byte aligned");
+  if (const int rc = check_head_dim_and_alignment("glb_slab_attention", dtype, head_dim, {q, k_new, v_new, k_slab, v_slab, out},
+                                                  {q_stride_row, q_stride_head, k_stride_row, k_stride_head, v_stride_row, v_stride_head}))
+    return rc;
   AttnArgs a{};
   a.q = (const char *)q;
   a.k_new = (const char *)k_new;
@@ -1223,12 +1142,10 @@ int glb_slab_attention(const void *q, int64_t q_stride_row, int64_t q_stride_hea
   a.Hkv = (int32_t)kv_heads;
   a.cap = (int32_t)cap;
   a.scale = scale;
-  hipError_t e;
-  switch (dtype) {
-    case GLB_F32: e = launch_attention<GLB_F32>(a, (int)head_dim, (hipStream_t)stream); break;
-    case GLB_BF16: e = launch_attention<GLB_BF16>(a, (int)head_dim, (hipStream_t)stream); break;
-    default: e = launch_attention<GLB_F16>(a, (int)head_dim, (hipStream_t)stream); break;
-  }
+  const dim3 grid((unsigned)((int64_t)a.R * a.H)), block(64);
+  const hipError_t e = launch_attention_form(dtype, head_dim, [&](auto dt, auto dh) {
+    hipLaunchKernelGGL((slab_attention_kernel<decltype(dt)::value, decltype(dh)::value>), grid, block, 0, (hipStream_t)stream, a);
+  });
   if (e != hipSuccess) return glb::api_hip_fail(e, "slab_attention launch");
   return GLB_OK;
 }
@@ -1240,18 +1157,16 @@ int glb_slab_attention_chunk(const void *q, const int64_t q_strides[3], const vo
                              void *out, void *stream) {
   if (!q || !k_new || !v_new || !k_slab || !v_slab || !pos || !n_new || !out || !q_strides || !k_strides || !v_strides)
     return glb::api_fail(GLB_EINVAL, "glb_slab_attention_chunk: null pointer");
-  if (dtype < GLB_F32 || dtype > GLB_F16) return glb::api_fail(GLB_EINVAL, "bad dtype %d", dtype);
+  if (const int rc = check_dtype(dtype)) return rc;
   if (max_new < 1 || max_new > GLB_KV_CHUNK_MAX)
     return glb::api_fail(GLB_EINVAL, "glb_slab_attention_chunk: %lld query positions per row (1 .. %d)", (long long)max_new, GLB_KV_CHUNK_MAX);
   if (n_rows <= 0 || n_slab_rows <= 0 || heads <= 0 || kv_heads <= 0 || cap <= 0 || heads % kv_heads || cap > 0x7fffffffll ||
       n_slab_rows > 0x7fffffffll || n_rows * heads * max_new > 0x7fffffffll)
     return glb::api_fail(GLB_EINVAL, "glb_slab_attention_chunk: bad sizes");
-  if (head_dim != 16 && head_dim != 32 && head_dim != 64 && head_dim != 128)
-    return glb::api_fail(GLB_EUNSUPPORTED, "glb_slab_attention_chunk: head_dim %lld (16, 32, 64 and 128 are built)", (long long)head_dim);
-  const int es = dtype == GLB_F32 ? 4 : 2;
-  bool aligned = (((uintptr_t)q | (uintptr_t)k_new | (uintptr_t)v_new | (uintptr_t)k_slab | (uintptr_t)v_slab | (uintptr_t)out) % 16) == 0;
-  for (int d = 0; d < 3; ++d) aligned = aligned && (q_strides[d] * es) % 16 == 0 && (k_strides[d] * es) % 16 == 0 && (v_strides[d] * es) % 16 == 0;
-  if (!aligned) return glb::api_fail(GLB_EINVAL, "glb_slab_attention_chunk: pointers and strides must be 16-byte aligned");
+  if (const int rc = check_head_dim_and_alignment(
+          "glb_slab_attention_chunk", dtype, head_dim, {q, k_new, v_new, k_slab, v_slab, out},
+          {q_strides[0], q_strides[1], q_strides[2], k_strides[0], k_strides[1], k_strides[2], v_strides[0], v_strides[1], v_strides[2]}))
+    return rc;
   ChunkAttnArgs a{};
   a.q = (const char *)q;
   a.k_new = (const char *)k_new;
@@ -1272,12 +1187,10 @@ int glb_slab_attention_chunk(const void *q, const int64_t q_strides[3], const vo
   a.T = (int32_t)max_new;
   a.n_slab_rows = (int32_t)n_slab_rows;
   a.scale = scale;
-  hipError_t e;
-  switch (dtype) {
-    case GLB_F32: e = launch_attention_chunk<GLB_F32>(a, (int)head_dim, (hipStream_t)stream); break;
-    case GLB_BF16: e = launch_attention_chunk<GLB_BF16>(a, (int)head_dim, (hipStream_t)stream); break;
-    default: e = launch_attention_chunk<GLB_F16>(a, (int)head_dim, (hipStream_t)stream); break;
-  }
+  const dim3 grid((unsigned)((int64_t)a.n * a.H * a.T)), block(64);
+  const hipError_t e = launch_attention_form(dtype, head_dim, [&](auto dt, auto dh) {
+    hipLaunchKernelGGL((slab_attention_chunk_kernel<decltype(dt)::value, decltype(dh)::value>), grid, block, 0, (hipStream_t)stream, a);
+  });
   if (e != hipSuccess) return glb::api_hip_fail(e, "slab_attention_chunk launch");
   return GLB_OK;
 }
@@ -1404,16 +1317,14 @@ int glb_short_attention(const void *q, const int64_t q_strides[3], const void *k
                         int64_t n_rows, int64_t heads, int64_t kv_heads, int64_t q_len, int64_t k_len, int64_t head_dim,
                         float scale, int32_t dtype, void *out, void *stream) {
   if (!q || !k || !v || !out || !q_strides || !k_strides || !v_strides) return glb::api_fail(GLB_EINVAL, "glb_short_attention: null pointer");
-  if (dtype < GLB_F32 || dtype > GLB_F16) return glb::api_fail(GLB_EINVAL, "bad dtype %d", dtype);
+  if (const int rc = check_dtype(dtype)) return rc;
   if (n_rows <= 0 || heads <= 0 || kv_heads <= 0 || q_len <= 0 || k_len <= 0 || heads % kv_heads || k_len < q_len ||
       n_rows * heads * q_len > 0x7fffffffll || k_len > 0x7fffffffll)
     return glb::api_fail(GLB_EINVAL, "glb_short_attention: bad sizes");
-  if (head_dim != 16 && head_dim != 32 && head_dim != 64 && head_dim != 128)
-    return glb::api_fail(GLB_EUNSUPPORTED, "glb_short_attention: head_dim %lld (16, 32, 64 and 128 are built)", (long long)head_dim);
-  const int es = dtype == GLB_F32 ? 4 : 2;
-  bool aligned = (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out) % 16) == 0;
-  for (int d = 0; d < 3; ++d) aligned = aligned && (q_strides[d] * es) % 16 == 0 && (k_strides[d] * es) % 16 == 0 && (v_strides[d] * es) % 16 == 0;
-  if (!aligned) return glb::api_fail(GLB_EINVAL, "glb_short_attention: pointers and strides must be 16-byte aligned");
+  if (const int rc = check_head_dim_and_alignment(
+          "glb_short_attention", dtype, head_dim, {q, k, v, out},
+          {q_strides[0], q_strides[1], q_strides[2], k_strides[0], k_strides[1], k_strides[2], v_strides[0], v_strides[1], v_strides[2]}))
+    return rc;
   ShortArgs a{};
   a.q = (const char *)q;
   a.k = (const char *)k;
@@ -1431,12 +1342,20 @@ int glb_short_attention(const void *q, const int64_t q_strides[3], const void *k
   a.Lq = (int32_t)q_len;
   a.Lk = (int32_t)k_len;
   a.scale = scale;
-  hipError_t e;
-  switch (dtype) {
-    case GLB_F32: e = launch_short_attention<GLB_F32>(a, (int)head_dim, (hipStream_t)stream); break;
-    case GLB_BF16: e = launch_short_attention<GLB_BF16>(a, (int)head_dim, (hipStream_t)stream); break;
-    default: e = launch_short_attention<GLB_F16>(a, (int)head_dim, (hipStream_t)stream); break;
-  }
+  const hipStream_t s = (hipStream_t)stream;
+  const hipError_t e = launch_attention_form(dtype, head_dim, [&](auto dt, auto dh) {
+    constexpr int DT = decltype(dt)::value, DH = decltype(dh)::value;
+    const dim3 block(64);
+    if (a.Lk <= 32 && a.Lq <= 2048 && (int64_t)a.U * a.Hkv <= 0x7fffffffll) {  // the (row, KV head) form: K / V in LDS once, slots are queries
+      const dim3 grid((unsigned)((int64_t)a.U * a.Hkv));
+      const size_t lds = (size_t)2 * a.Lk * DH * sizeof(float) + (size_t)a.Lq * sizeof(uint32_t);
+      if (a.Lk <= 16) hipLaunchKernelGGL((short_attention_rows_kernel<DT, DH, 16>), grid, block, lds, s, a);
+      else hipLaunchKernelGGL((short_attention_rows_kernel<DT, DH, 32>), grid, block, lds, s, a);
+    } else {
+      const dim3 grid((unsigned)((int64_t)a.U * a.H * a.Lq));
+      hipLaunchKernelGGL((short_attention_kernel<DT, DH>), grid, block, 0, s, a);
+    }
+  });
   if (e != hipSuccess) return glb::api_hip_fail(e, "short_attention launch");
   return GLB_OK;
 }
@@ -1447,19 +1366,17 @@ int glb_short_attention_packed(const void *q, int64_t q_stride_row, int64_t q_st
                                int64_t max_keys, int64_t head_dim, float scale, int32_t dtype, void *out, uint32_t *err_word,
                                void *stream) {
   if (!q || !k || !v || !out || !plan || !err_word) return glb::api_fail(GLB_EINVAL, "glb_short_attention_packed: null pointer");
-  if (dtype < GLB_F32 || dtype > GLB_F16) return glb::api_fail(GLB_EINVAL, "bad dtype %d", dtype);
+  if (const int rc = check_dtype(dtype)) return rc;
   if (n_segments <= 0 || n_rows <= 0 || heads <= 0 || kv_heads <= 0 || heads % kv_heads || heads > 0x7fffffffll ||
       n_rows > 0x7fffffffll || n_segments > 0x7fffffffll || n_segments * kv_heads > 0x7fffffffll)
     return glb::api_fail(GLB_EINVAL, "glb_short_attention_packed: bad sizes");
   if (max_keys < 1 || max_keys > 32)
     return glb::api_fail(GLB_EINVAL, "glb_short_attention_packed: %lld keys per context (1 .. 32 are served)", (long long)max_keys);
-  if (head_dim != 16 && head_dim != 32 && head_dim != 64 && head_dim != 128)
-    return glb::api_fail(GLB_EUNSUPPORTED, "glb_short_attention_packed: head_dim %lld (16, 32, 64 and 128 are built)", (long long)head_dim);
-  const int es = dtype == GLB_F32 ? 4 : 2;
-  bool aligned = (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out | (uintptr_t)plan) % 16) == 0 && ((uintptr_t)err_word % 4) == 0;
-  for (int64_t st : {q_stride_row, q_stride_head, k_stride_row, k_stride_head, v_stride_row, v_stride_head})
-    aligned = aligned && st >= 0 && (st * es) % 16 == 0;
-  if (!aligned) return glb::api_fail(GLB_EINVAL, "glb_short_attention_packed: pointers and strides must be 16-byte aligned");
+  const auto strides = {q_stride_row, q_stride_head, k_stride_row, k_stride_head, v_stride_row, v_stride_head};
+  bool word_and_signs = (uintptr_t)err_word % 4 == 0;  // the error word's alignment, and no negative stride
+  for (const int64_t st : strides) word_and_signs = word_and_signs && st >= 0;
+  if (const int rc = check_head_dim_and_alignment("glb_short_attention_packed", dtype, head_dim, {q, k, v, out, plan}, strides, word_and_signs))
+    return rc;
   PackedArgs a{};
   a.q = (const char *)q;
   a.k = (const char *)k;
@@ -1476,12 +1393,13 @@ int glb_short_attention_packed(const void *q, int64_t q_stride_row, int64_t q_st
   a.Hkv = (int32_t)kv_heads;
   a.max_keys = (int32_t)max_keys;
   a.scale = scale;
-  hipError_t e;
-  switch (dtype) {
-    case GLB_F32: e = launch_short_packed<GLB_F32>(a, (int)head_dim, (hipStream_t)stream); break;
-    case GLB_BF16: e = launch_short_packed<GLB_BF16>(a, (int)head_dim, (hipStream_t)stream); break;
-    default: e = launch_short_packed<GLB_F16>(a, (int)head_dim, (hipStream_t)stream); break;
-  }
+  const dim3 grid((unsigned)((int64_t)a.S * a.Hkv)), block(64);
+  const hipError_t e = launch_attention_form(dtype, head_dim, [&](auto dt, auto dh) {
+    constexpr int DT = decltype(dt)::value, DH = decltype(dh)::value;
+    const size_t lds = (size_t)2 * a.max_keys * DH * sizeof(float) + (size_t)a.max_keys * sizeof(uint32_t);
+    if (a.max_keys <= 16) hipLaunchKernelGGL((short_attention_packed_kernel<DT, DH, 16>), grid, block, lds, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL((short_attention_packed_kernel<DT, DH, 32>), grid, block, lds, (hipStream_t)stream, a);
+  });
   if (e != hipSuccess) return glb::api_hip_fail(e, "short_attention_packed launch");
   return GLB_OK;
 }

@@ -2063,6 +2063,39 @@ def test_short_attention_matches_torch(engine, dtype, U, H, Hkv, Lq, Lk, Dh):
         assert not bool(out[~live].any())
 
 
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16])
+def test_short_attention_across_the_hand_over_between_its_two_forms(engine, dtype):
+    """The same right-padded contexts at Lk = 32 (the wave whose slots are queries) and padded one key further to Lk = 33
+    (the wave that is one query), each against a float32 softmax restatement.  The two forms are not bit-equal to each
+    other and are not compared with each other."""
+    dev = engine.device
+    U, H, Hkv, Lq, Dh = 3, 4, 2, 5, 64
+    G, scale = H // Hkv, Dh ** -0.5
+    tol = 2e-5 if dtype == torch.float32 else (2e-2 if dtype == torch.bfloat16 else 3e-3)
+    g = torch.Generator(device=dev)
+    g.manual_seed(3233)
+    q = torch.randn((U, H, Lq, Dh), device=dev, generator=g).to(dtype)
+    k33 = torch.randn((U, Hkv, 33, Dh), device=dev, generator=g).to(dtype)
+    v33 = torch.randn((U, Hkv, 33, Dh), device=dev, generator=g).to(dtype)
+    P = 32 - Lq  # cached positions in front of the Lq new keys; key 32 is padding for every context
+    lens = torch.tensor([Lq, 3, 1], device=dev)
+    ar = torch.arange(33, device=dev)
+    key_ok = ar[None, :] < P + lens[:, None]
+    causal = ar[None, :] <= torch.arange(Lq, device=dev)[:, None] + P
+    mask33 = (key_ok[:, None, None, :] & causal[None, None, :, :]).contiguous()  # [U, 1, Lq, 33]
+    for Lk in (32, 33):
+        k, v, mask = k33[:, :, :Lk].contiguous(), v33[:, :, :Lk].contiguous(), mask33[..., :Lk].contiguous()
+        out = engine.short_attention(q, k, v, mask, scale)
+        torch.cuda.synchronize()
+        s = torch.einsum("uhqd,uhkd->uhqk", q.float(), k.float().repeat_interleave(G, 1)) * scale
+        w = torch.softmax(s.masked_fill(~mask, float("-inf")), dim=-1)
+        want = torch.einsum("uhqk,uhkd->uqhd", w, v.float().repeat_interleave(G, 1))  # [U, Lq, H, Dh]
+        err = (out.float() - want).abs().max().item()
+        print(f"Lk = {Lk}: max |short_attention - softmax| = {err:.3e} (bound {tol})")
+        assert out.shape == (U, Lq, H, Dh) and out.dtype == dtype
+        assert err < tol
+
+
 def test_recorded_gemm_solutions_give_the_librarys_results_within_rounding(engine):
     """gemm_tuning.use_recorded(): on an MI355X with the libraries the file was recorded with, the recorded shapes run by
     their recorded rocBLAS / hipBLASLt solution - the same product up to the order of the additions - and `off()` hands the

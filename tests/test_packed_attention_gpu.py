@@ -26,12 +26,12 @@ def _projection(seed, M, H, Hkv, D, dtype, dev):
     return q, k, v
 
 
-def _padded_reference(engine, q, k, v, seg, n_groups, scale):
-    """glb_short_attention on the right-padded batch of the contexts (segments behind the prompts'): [U, L, H, D] and the
-    packed rows of every context's tokens."""
+def _padded_reference(engine, q, k, v, seg, n_groups, scale, bare=()):
+    """glb_short_attention on the right-padded batch of the contexts (segments behind the prompts') and, behind them, of the
+    prompts `bare` (groups no context stands behind): [U, L, H, D] and the packed rows of every row's tokens."""
     dev = q.device
-    ctx = seg[n_groups:]
-    rows = [list(range(a, a + n)) + list(range(b, b + t)) for a, n, b, t in ctx.tolist()]
+    ctx = seg[n_groups:].tolist() + [seg[g].tolist() for g in bare]  # (a prompt's segment: no prefix, its own rows as the tail)
+    rows = [list(range(a, a + n)) + list(range(b, b + t)) for a, n, b, t in ctx]
     U, L = len(rows), max(len(r) for r in rows)
     idx = torch.zeros((U, L), dtype=torch.long)
     valid = torch.zeros((U, L), dtype=torch.bool)
@@ -55,7 +55,8 @@ def _run_case(engine, dtype, D, H, Hkv, group_lens, grp, tails, seed):
     M, G = sum(group_lens) + sum(tails), len(group_lens)
     q, k, v = _projection(seed, M, H, Hkv, D, dtype, dev)
     scale = D ** -0.5
-    ref, rows = _padded_reference(engine, q, k, v, seg, G, scale)
+    bare = [g for g in range(G) if g not in grp]
+    ref, rows = _padded_reference(engine, q, k, v, seg, G, scale, bare)
     buf = torch.full((M + 2 * PAD, H, D), CANARY, dtype=dtype, device=dev)
     err = torch.zeros(1, dtype=torch.int32, device=dev)
     out = engine.short_attention_packed(q, k, v, torch.from_numpy(seg).to(dev), max(lens), scale, err=err, out=buf[PAD:PAD + M])
@@ -63,13 +64,12 @@ def _run_case(engine, dtype, D, H, Hkv, group_lens, grp, tails, seed):
     assert torch.equal(buf[:PAD], torch.full_like(buf[:PAD], CANARY)) and torch.equal(buf[PAD + M:], torch.full_like(buf[:PAD], CANARY))
     seen = set()
     for u, r in enumerate(rows):
-        P = group_lens[grp[u]]
+        P = group_lens[grp[u]] if u < len(grp) else len(r)  # (behind the contexts: the prompts nobody stands behind)
         # the tail's queries - and the prompt's, which every context of the group computes with the same bits
         assert torch.equal(out[r[P:]], ref[u, P:len(r)]), (u, "tail")
         assert torch.equal(out[r[:P]], ref[u, :P]), (u, "prompt")
         seen.update(r)
-    untouched = [m for m in range(M) if m not in seen]  # the prompt of a group without a context is still served
-    assert all(not torch.equal(out[m], torch.full_like(out[m], CANARY)) for m in untouched)
+    assert seen == set(range(M))  # every packed row was compared
 
 
 @pytest.mark.parametrize("P,t", SIZES)
@@ -90,6 +90,17 @@ def test_packed_unequal_tails(engine, dtype, D):
     """Tails of 1 .. 10 tokens behind prompts of 8, 5 and 1 in one call (9 to 18 keys: both kernel forms' sizes at once)."""
     _run_case(engine, dtype, D, 4, 2, [8, 5, 1], [0, 1, 2, 0, 0, 1, 2], [1, 10, 3, 7, 2, 1, 10], 77)
     _run_case(engine, dtype, D, 2, 2, [8], [0, 0, 0], [3, 1, 2], 78)  # at most 11 keys: the register form alone
+
+
+@pytest.mark.parametrize("keys", [16, 17])
+@pytest.mark.parametrize("D", [16, 128])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16], ids=["f32", "bf16", "f16"])
+def test_packed_at_the_key_count_switch_and_the_edge_head_sizes(engine, dtype, D, keys):
+    """Exactly 16 and exactly 17 keys in the call's longest context (the 16 -> 32-key kernel, for 16-bit types at head size
+    128 also keys in registers -> keys in LDS), at the narrowest and the widest slot (head sizes 16 and 128), grouped query
+    heads: two contexts behind one prompt, and a prompt of `keys` tokens with no context behind it (compared with a row of
+    its own in the padded batch)."""
+    _run_case(engine, dtype, D, 4, 2, [9, keys], [0, 0], [keys - 9, 1], 160 + keys + D)
 
 
 def test_packed_refuses_33_keys(engine):
