@@ -268,6 +268,19 @@ class W4GemmArgs(C.Structure):
     ]
 
 
+class W4TiledArgs(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("dtype", C.c_int32), ("form", C.c_int32),
+        ("m", C.c_int64), ("n", C.c_int64), ("k", C.c_int64),
+        ("x", C.c_void_p), ("ldx", C.c_int64),
+        ("image", C.c_void_p),
+        ("codebook", C.POINTER(C.c_float)),
+        ("bias", C.c_void_p),
+        ("y", C.c_void_p), ("ldy", C.c_int64),
+    ]
+
+
 DFA_COUNTERS = 4  # GLB_DFA_COUNTERS: rows in use, work entries filled, overflow (sticky), private
 
 
@@ -642,6 +655,8 @@ SYMBOLS = {
     "glb_w4_gemm_max_rows": (C.c_int, []),
     "glb_w4_gemm_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "glb_w4_gemm": (C.c_int, [C.POINTER(W4GemmArgs), _vp]),
+    "glb_w4_gemm_tiled_forms": (C.c_int, []),
+    "glb_w4_gemm_tiled": (C.c_int, [C.POINTER(W4TiledArgs), _vp]),
     "glb_dfa_bank_init": (C.c_int, [C.POINTER(DfaArgs), _vp]),
     "glb_dfa_advance": (C.c_int, [C.POINTER(DfaArgs), _vp]),
     "glb_dfa_claim_rows": (C.c_int, [C.POINTER(DfaArgs), _vp]),

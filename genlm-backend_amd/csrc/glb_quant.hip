@@ -29,54 +29,20 @@
 
 #include "../../include/glb.h"
 #include "glb_common.hpp"
+#include "glb_w4.hpp"
 
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
-typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
-
-constexpr int QB = 64;             // elements of a block
-constexpr int UNIT = QB / 2;       // bytes of a block's codes
 constexpr int GEMM_MAX_MF = 8;     // row fragments of 16 a wave can hold
 // Rows glb_w4_gemm serves: the largest M at which it was measured faster than dequantise + library GEMM on any shape of
 // profiles/r09/w4_gemm_ab.txt, rounded up to the 16-row fragment.
 constexpr int GEMM_MAX_ROWS = 128;
 constexpr int GEMM_TARGET_WAVES = 4096;  // 4 per SIMD on 256 CUs
-constexpr int64_t MAX_ELEMS = (int64_t)1 << 34;
 
-struct Codebook {
-  float v[16];
-};
 struct QuantTable {
   float mid[15];     // midpoints of the sorted codebook
   uint64_t code_of;  // nibble i: the code of the i-th smallest entry
 };
-
-__device__ __forceinline__ float load_elem(const void *p, int64_t idx, int dt) {
-  if (dt == GLB_F32) return ((const float *)p)[idx];
-  const uint16_t h = ((const uint16_t *)p)[idx];
-  if (dt == GLB_BF16) return __uint_as_float((uint32_t)h << 16);
-  return __half2float(__ushort_as_half(h));
-}
-
-__device__ __forceinline__ uint16_t bf16_rne(float f) {
-  uint32_t u = __float_as_uint(f);
-  u += 0x7fffu + ((u >> 16) & 1u);  // (finite input: absmax is finite and every codebook entry is)
-  return (uint16_t)(u >> 16);
-}
-
-__device__ __forceinline__ void store_elem(void *p, int64_t idx, int dt, float f) {
-  // (the barrier keeps the f32 product: multiply + convert must not become one v_fma_mix*_f16, a single rounding)
-  asm volatile("" : "+v"(f));
-  if (dt == GLB_F32) ((float *)p)[idx] = f;
-  else if (dt == GLB_BF16) ((uint16_t *)p)[idx] = bf16_rne(f);
-  else ((uint16_t *)p)[idx] = __half_as_ushort(__float2half_rn(f));
-}
 
 __device__ __forceinline__ uint32_t quant_code(float w, float absmax, const QuantTable &q) {
   int cnt = 0;
@@ -180,31 +146,6 @@ __global__ __launch_bounds__(256) void dequantize_cols_kernel(const char *__rest
       store_elem(out, (kb * QB + 8 * i + j) * ldo + n, dt, lut[(words[i] >> (4 * j)) & 15u] * amax);
 }
 
-// eight codes of one word -> lane's B operand (8 values of the 16-bit dtype), each codebook[code] * absmax rounded once
-template <int DT>
-__device__ __forceinline__ u32x4 expand8(uint32_t word, float amax, const float *lut) {
-  u32x4 o;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    float a = lut[(word >> (8 * i)) & 15u] * amax, b = lut[(word >> (8 * i + 4)) & 15u] * amax;
-    if constexpr (DT == GLB_BF16) {
-      o[i] = __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{a, b}, bf16x2));  // v_cvt_pk_bf16_f32 (RNE)
-    } else {
-      asm volatile("" : "+v"(a), "+v"(b));  // (as store_elem: no fused multiply-convert)
-      o[i] = (uint32_t)__half_as_ushort(__float2half_rn(a)) | ((uint32_t)__half_as_ushort(__float2half_rn(b)) << 16);
-    }
-  }
-  return o;
-}
-
-template <int DT>
-__device__ __forceinline__ f32x4 mfma16(u32x4 a, u32x4 b, f32x4 c) {
-  if constexpr (DT == GLB_BF16)
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-
 // One wave per (16 columns, K slice): part[ks][row][col] = sum over the slice of X[row, k] * W'[col, k].
 template <int DT, int MF>
 __global__ __launch_bounds__(256) void w4_gemm_kernel(const uint16_t *__restrict__ x, int64_t ldx, const char *__restrict__ image,
@@ -288,13 +229,6 @@ __global__ __launch_bounds__(256) void w4_reduce_kernel(const float *__restrict_
 
 bool dtype_ok(int32_t dt) { return dt == GLB_F32 || dt == GLB_BF16 || dt == GLB_F16; }
 size_t elem_bytes(int32_t dt) { return dt == GLB_F32 ? 4 : 2; }
-bool shape_served(int64_t n, int64_t k) { return n > 0 && k > 0 && k % QB == 0 && n <= MAX_ELEMS / k; }
-
-bool codebook_ok(const float *cb) {
-  for (int i = 0; i < 16; ++i)
-    if (!std::isfinite(cb[i])) return false;
-  return true;
-}
 
 QuantTable make_table(const float *cb) {
   int order[16];
@@ -315,8 +249,6 @@ int gemm_ksplit(int64_t n, int64_t k) {
   ks = std::min(ks, std::max<int64_t>(1, kb / 2));  // at least two blocks of K per wave
   return (int)std::max<int64_t>(1, ks);
 }
-
-bool gemm_shape_served(int64_t n, int64_t k) { return shape_served(n, k) && n % 16 == 0 && n <= (1 << 24) && k <= (1 << 24); }
 
 int check_quant_args(const glb_w4_args *args, const char *what) {
   if (!args) return glb::api_fail(GLB_EINVAL, "%s: null argument block", what);

@@ -1360,6 +1360,37 @@ class HipEngine:
         check(rc)
         return y if out is not None else y.view(*x.shape[:-1], n)
 
+    def w4_gemm_tiled_forms(self):
+        return self.lib.glb_w4_gemm_tiled_forms()
+
+    def w4_gemm_tiled(self, x, image, n, codebook, bias=None, out=None, form=0):
+        """`w4_gemm` for any number of rows (glb_w4_gemm_tiled: X tiles through LDS, codes expanded in registers, one
+        launch, no workspace).  `form`: 0 lets the library pick a tile shape, 1 .. w4_gemm_tiled_forms() names one - every
+        form gives the same bits.  Returns [..., N] in x's dtype, or None when the call is not served (dtype, shape,
+        alignment): the caller then dequantises and runs its library GEMM."""
+        k = x.shape[-1]
+        x2 = x.reshape(-1, k)
+        m = x2.shape[0]
+        if m == 0 or x2.stride(1) != 1 or x.dtype not in (torch.bfloat16, torch.float16):
+            return None
+        if bias is not None and bias.dtype != x.dtype:
+            return None
+        y = out if out is not None else torch.empty((m, n), dtype=x.dtype, device=self.device)
+        a = _lib.W4TiledArgs()
+        a.struct_size = C.sizeof(_lib.W4TiledArgs)
+        a.dtype, a.form = _DT[x.dtype], int(form)
+        a.m, a.n, a.k = m, n, k
+        a.x, a.ldx = x2.data_ptr(), x2.stride(0)
+        a.image = image.data_ptr()
+        a.codebook = self._codebook(codebook)
+        a.bias = bias.data_ptr() if bias is not None else None
+        a.y, a.ldy = y.data_ptr(), y.stride(0)
+        rc = self.lib.glb_w4_gemm_tiled(C.byref(a), self._stream())
+        if rc == _lib.GLB_EUNSUPPORTED:
+            return None
+        check(rc)
+        return y if out is not None else y.view(*x.shape[:-1], n)
+
     # ---- byte-level DFA constraints (glb_dfa_*: DESIGN.md §17; constraints.DeviceConstraint fills the argument block) ---------
     # the glb_dfa_* entries of `_lib.SYMBOLS` that take (argument block, stream)
     DFA_CALLS = frozenset(name for name, (_, argtypes) in _lib.SYMBOLS.items()

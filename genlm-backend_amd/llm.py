@@ -306,8 +306,9 @@ class AsyncAmdLM(AsyncLM):
         than the library; it keeps a derived bf16 image of each such weight (6 bytes per element: 510 MB for GPT-2 small).
         `gemms` still decides every GEMM this path does not take.  False: not swapped.
         w4_gemm: how the 4-bit layers of a quantised model (quant.W4Linear) multiply - "auto": glb_w4_gemm on the 4-bit image
-        for the row counts where it was measured faster (quant.MIN_ROWS_FUSED), dequantise + library GEMM otherwise;
-        "fused" / "dequant": one path wherever it is able to serve the call (tests, A/Bs).
+        for the row counts where it was measured faster (quant.MIN_ROWS_FUSED), dequantise + library GEMM otherwise,
+        and glb_w4_gemm_tiled in the row ranges of quant.ROWS_TILED; "fused" / "dequant": one path wherever it is able to
+        serve the call (tests, A/Bs); "tiled": glb_w4_gemm_tiled for every 16-bit call beyond "auto"'s few-row rule.
         score_chunk_bytes: the most logits bytes `batch_sequence_logprobs*` hold at a time (never above logprob_budget_bytes;
         always at least one row)."""
         if score_chunk_bytes <= 0:

@@ -2,15 +2,16 @@
 
 `bitsandbytes` itself is not needed: the block format is restated here (blocks of 64 along the input features, one float32
 absmax and 64 four-bit codes into a 16-entry codebook each, no double quantisation) and everything hot about it is
-glb_w4_quantize / glb_w4_dequantize / glb_w4_gemm (csrc/glb_quant.hip).
+glb_w4_quantize / glb_w4_dequantize / glb_w4_gemm (csrc/glb_quant.hip) and glb_w4_gemm_tiled (csrc/glb_quant_tiled.hip).
 
   * `parse_opts` builds `transformers.BitsAndBytesConfig(**opts)` as the reference does (hf.py:80-112) and turns it into a
     `W4Config`; what this backend does not serve raises NotImplementedError naming the option.
   * `quantize_model` replaces the `nn.Linear` / `Conv1D` modules of a model by `W4Linear`, one glb_w4_quantize launch each,
     and lets the full-precision weight go as it does.  The peak is still the full-precision model: loading shard by shard is
     out of scope.
-  * `W4Linear.forward`: few rows go through glb_w4_gemm, which reads the 4-bit image directly; everything else dequantises the
-    layer into a scratch buffer shared by all layers of the model and runs `torch.nn.functional.linear` on it.
+  * `W4Linear.forward`: few rows go through glb_w4_gemm and the row ranges of `ROWS_TILED` through glb_w4_gemm_tiled, which
+    read the 4-bit image directly; everything else dequantises the layer into a scratch buffer shared by all layers of the
+    model and runs `torch.nn.functional.linear` on it.
 
 The codebooks below are written from the published description of the format; equality with bitsandbytes' own tables has not
 been checked against an installation of it.
@@ -27,7 +28,7 @@ _FP4_HALF = tuple(float(np.float32(v) / np.float32(12.0)) for v in (0.0, 0.0625,
 FP4 = _FP4_HALF + tuple(-v for v in _FP4_HALF)  # bit 3 is the sign
 CODEBOOKS = {"nf4": NF4, "fp4": FP4}
 
-W4_GEMM_MODES = ("auto", "fused", "dequant")
+W4_GEMM_MODES = ("auto", "fused", "tiled", "dequant")
 
 # The fused kernel's dispatch rule: per (N, K) of a projection, the most rows (tokens of a forward) at which glb_w4_gemm
 # runs under w4_gemm="auto", from the A/B of profiles/r09/w4_gemm_ab.txt (tools/w4_gemm_ab.py: fused kernel vs dequantise +
@@ -44,6 +45,25 @@ MIN_ROWS_FUSED = {
     (4096, 14336): 64,   # 8B down: 0.24-0.44x up to 32, 0.64x at 64; 0.98x at 128 is inside the noise and left to (b)
 }
 min_rows_fused = MIN_ROWS_FUSED
+
+# The many-row kernel's dispatch rule under w4_gemm="auto": per (N, K), the inclusive row range (lo, hi) in which
+# glb_w4_gemm_tiled runs, from profiles/r34/w4_tiled_ab.txt (tools/w4_gemm_ab.py, arm (d) at form 0 against arm (b), two
+# runs in one session): only ranges where (d) beat (b) by more than the spread between the two runs of the same arm, in
+# both runs.  The comments give the time of (d) over (b), bfloat16 NF4, lowest to highest over both runs.  hi is the last
+# measured M of an unbroken run of wins; the few-row rule above is asked first, so lo matters only where it ends.  Not
+# listed (dequantise + F.linear as before): 1B down (2048, 8192), 8B q / o (4096, 4096), 8B k / v (1024, 4096), 8B down
+# (4096, 14336) and GPT-2's mlp.c_proj (768, 3072), where (d) takes 1.09-2.36x the time of (b) at every M - its K loop
+# exposes one memory latency per block of 64.
+ROWS_TILED = {
+    (2048, 2048): (1, 512),    # 1B q / o: 0.78-0.86x up to 512 rows; 0.97-1.00x at 1024 is left to (b); 1.35-1.37x at 2048
+    (512, 2048): (1, 4096),    # 1B k / v: 0.77-0.85x up to 2048, 0.95-0.96x at 4096 (1.3 us, spread 0.1 us)
+    (8192, 2048): (1, 256),    # 1B gate / up: 0.71-0.79x up to 256; 1.03-1.05x at 512, 2.02x at 4096
+    (14336, 4096): (1, 256),   # 8B gate / up: 0.53-0.62x up to 128, 0.75-0.76x at 256; 0.99x at 512 is left to (b); 1.97-1.99x at 4096
+    (2304, 768): (1, 2048),    # GPT-2 c_attn: 0.36-0.45x up to 512, 0.50-0.55x at 1024, 0.76-0.80x at 2048; 1.19-1.27x at 4096
+    (768, 768): (1, 4096),     # GPT-2 attn.c_proj: 0.35-0.40x up to 1024, 0.43-0.46x at 2048, 0.51-0.55x at 4096
+    (3072, 768): (1, 2048),    # GPT-2 c_fc: 0.36-0.45x up to 512, 0.53-0.55x at 1024, 0.82-0.87x at 2048; 1.41x at 4096
+}
+rows_tiled = ROWS_TILED
 
 
 def w4_bytes(n, k):
@@ -146,6 +166,18 @@ class W4Linear(torch.nn.Module):
         b = self.bias
         return b if b is None or b.dtype == dtype else b.to(dtype)
 
+    def _gemm_paths(self, eng, rows):
+        """The kernels that read the image directly, in the order a 16-bit call of `rows` rows tries them; one that does
+        not serve the call returns None and the next is asked, then the layer dequantises."""
+        if self.mode == "fused":
+            return (eng.w4_gemm,)
+        tiled = getattr(eng, "w4_gemm_tiled", None)  # (an engine without the many-row kernel works under every mode)
+        shape = (self.out_features, self.in_features)
+        if rows <= min_rows_fused.get(shape, 0):  # the few-row rule of "auto" holds under "tiled" too
+            return (eng.w4_gemm,) if self.mode == "auto" or tiled is None else (eng.w4_gemm, tiled)
+        lo, hi = rows_tiled.get(shape, (1, 0))
+        return (tiled,) if tiled is not None and (self.mode == "tiled" or lo <= rows <= hi) else ()
+
     def forward(self, x):
         if torch.is_grad_enabled() and x.requires_grad:
             raise RuntimeError("W4Linear is inference only: run it under torch.no_grad() (4-bit weights have no gradient)")
@@ -154,11 +186,11 @@ class W4Linear(torch.nn.Module):
         cd = self.compute_dtype or x.dtype
         rows = x.shape[:-1].numel()
         with torch.no_grad():
-            if (self.mode != "dequant" and cd in (torch.bfloat16, torch.float16) and x.device == eng.device
-                    and (self.mode == "fused" or rows <= min_rows_fused.get((n, k), 0))):
-                y = eng.w4_gemm(x if x.dtype == cd else x.to(cd), self.image, n, self.codebook, self._bias(cd))
-                if y is not None:
-                    return y if y.dtype == x.dtype else y.to(x.dtype)
+            if self.mode != "dequant" and cd in (torch.bfloat16, torch.float16) and x.device == eng.device:
+                for gemm in self._gemm_paths(eng, rows):
+                    y = gemm(x if x.dtype == cd else x.to(cd), self.image, n, self.codebook, self._bias(cd))
+                    if y is not None:
+                        return y if y.dtype == x.dtype else y.to(x.dtype)
             w = self._glb_scratch.get(cd)[:n * k].view(n, k)
             eng.w4_dequantize(self.image, n, k, self.codebook, out=w)
             y = torch.nn.functional.linear(x if x.dtype == cd else x.to(cd), w, self._bias(cd))

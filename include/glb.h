@@ -968,6 +968,19 @@ int glb_lora_rows(const glb_lora_rows_args *args, void *hip_stream);
  * A NaN or an infinity in X makes only its own row of Y non-finite; a block whose W' is infinite in the 16-bit dtype (a
  * float32 absmax beyond the dtype's range) or zero touches only its own column; finite operands whose sum leaves the
  * dtype's range give +-inf as IEEE addition does.  A -0 of W' reaches Y as +0 (the sums start at +0).
+ *
+ * glb_w4_gemm_tiled is the many-row form of the same product: any m >= 1, n % 16 == 0, k % 64 == 0, X, ldx and the image
+ * 16-byte aligned (the few-row kernel's conditions without the row cap); everything else returns GLB_EUNSUPPORTED.  One
+ * launch on the given stream, no workspace, no atomics, nothing allocated: it may be captured into a hipGraph.  A workgroup
+ * owns a tile of rows x columns over the whole of K (X through LDS once per workgroup, codes expanded in registers);
+ * `form` 1 .. the forms count names one tile shape, 0 lets the library pick by (m, n, k) and the device's CU count.
+ * Arithmetic: every element of W' is glb_w4_dequantize's 16-bit element; every element of Y is ONE float32 accumulator
+ * started at +0, fed by the K blocks of 64 in ascending order (two MFMAs of 32 each, in order), then one float32 addition
+ * of the bias and one rounding to the dtype.  There is no K split, so an element's bits depend on its row of X, its row of
+ * W' and its bias alone - not on m, the row's position, the other rows and columns or the form (the choice of form is a
+ * speed choice only) - and equal glb_w4_gemm's wherever that kernel uses a single K slice.  Containment is glb_w4_gemm's:
+ * only X[0 .. m-1][0 .. k-1] is read, only Y[0 .. m-1][0 .. n-1] written.  Argument errors (null pointers, struct_size, a
+ * dtype that is not 16-bit, a form out of range, ldx < k, ldy < n) return GLB_EINVAL before any GPU work.
  */
 typedef struct glb_w4_args {
   uint32_t struct_size; /* sizeof(glb_w4_args) - ABI guard */
@@ -1000,6 +1013,21 @@ int glb_w4_dequantize(const glb_w4_args *args, void *hip_stream);
 int glb_w4_gemm_max_rows(void);
 size_t glb_w4_gemm_workspace_bytes(int64_t m, int64_t n, int64_t k);
 int glb_w4_gemm(const glb_w4_gemm_args *args, void *hip_stream);
+typedef struct glb_w4_tiled_args {
+  uint32_t struct_size; /* sizeof(glb_w4_tiled_args) - ABI guard */
+  int32_t dtype;        /* GLB_BF16 / GLB_F16: x, bias and y */
+  int32_t form;         /* 0: the library's choice; 1 .. the forms count: that tile form */
+  int64_t m, n, k;
+  const void *x;
+  int64_t ldx;
+  const void *image;
+  const float *codebook; /* host, 16 entries */
+  const void *bias;      /* [n], nullable */
+  void *y;
+  int64_t ldy;
+} glb_w4_tiled_args;
+int glb_w4_gemm_tiled_forms(void);
+int glb_w4_gemm_tiled(const glb_w4_tiled_args *args, void *hip_stream);
 
 /*
  * Byte-level DFA constraints: token masks made on the device from an automaton over bytes.

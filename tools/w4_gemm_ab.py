@@ -1,16 +1,20 @@
 """A/B of the 4-bit projection paths per (N, K) of Llama-3.2-1B's and Llama-3-8B's projections and row count M, in one
-process, the arms alternating round by round (median of the rounds), HIP events around `iters` calls:
+process, the arms alternating round by round in an order shuffled anew for each round (median of the rounds), HIP events
+around `iters` calls:
   (a) glb_w4_gemm on the 4-bit image                   (quant.W4Linear's fused path)
   (b) glb_w4_dequantize into a scratch + F.linear      (its other path)
   (c) F.linear on the 16-bit weight                    (an unquantised model)
+  (d) glb_w4_gemm_tiled on the 4-bit image             (the many-row kernel: form 0 = the library's choice, then every form)
 Every call takes the next of a ring of weight buffers that together exceed the 256 MB Infinity Cache, so weights come from
 HBM.  Then glb_w4_quantize / glb_w4_dequantize on their own, as fractions of 8 TB/s on the bytes they move, and the time to
-quantise a Llama-3-8B-shaped model.  What quant.MIN_ROWS_FUSED and glb_w4_gemm_max_rows() are read from.
+quantise a Llama-3-8B-shaped model.  What quant.MIN_ROWS_FUSED, glb_w4_gemm_max_rows(), quant.ROWS_TILED and the form = 0
+rule of glb_w4_gemm_tiled are read from.
 
     python tools/w4_gemm_ab.py [--rounds 5] [--iters 20] [--rows 1,2,4,...] [--dtype bfloat16]
 """
 import argparse
 import os
+import random
 import statistics
 import sys
 
@@ -22,7 +26,8 @@ from genlm_backend_amd.engine import HipEngine  # noqa: E402
 from genlm_backend_amd.quant import CODEBOOKS  # noqa: E402
 
 SHAPES = [("1B q/o", 2048, 2048), ("1B k/v", 512, 2048), ("1B gate/up", 8192, 2048), ("1B down", 2048, 8192),
-          ("8B q/o", 4096, 4096), ("8B k/v", 1024, 4096), ("8B gate/up", 14336, 4096), ("8B down", 4096, 14336)]
+          ("8B q/o", 4096, 4096), ("8B k/v", 1024, 4096), ("8B gate/up", 14336, 4096), ("8B down", 4096, 14336),
+          ("gpt2 c_attn", 2304, 768), ("gpt2 c_proj", 768, 768), ("gpt2 c_fc", 3072, 768), ("gpt2 mlp.proj", 768, 3072)]
 LLAMA_8B = {(4096, 4096): 2, (1024, 4096): 2, (14336, 4096): 2, (4096, 14336): 1}  # matrices per layer, 32 layers
 RING_BYTES = 320 << 20
 PEAK = 8e12
@@ -51,7 +56,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--rows", default="1,2,4,8,16,32,64,128,256,512,1024")
+    ap.add_argument("--rows", default="1,2,4,8,16,32,64,128,256,512,1024,2048,4096")
     ap.add_argument("--dtype", default="bfloat16")
     args = ap.parse_args()
     dtype = getattr(torch, args.dtype)
@@ -59,10 +64,11 @@ def main():
     cb = CODEBOOKS["nf4"]
     g = torch.Generator(device="cuda").manual_seed(0)
     rows = [int(r) for r in args.rows.split(",")]
+    forms = list(range(eng.w4_gemm_tiled_forms() + 1))  # 0: the library's choice
     print(f"# {torch.cuda.get_device_name(0)}; {args.dtype}; rounds {args.rounds} x {args.iters} calls, median us per call; "
           f"glb_w4_gemm_max_rows() = {eng.w4_gemm_max_rows()}; weight rings of {RING_BYTES >> 20} MB")
     print(f"{'shape':11s} {'N':>6s} {'K':>6s} {'M':>5s} {'(a) fused':>10s} {'(b) deq+lin':>11s} {'(c) 16-bit':>10s} {'a/b':>6s} {'a/c':>6s} "
-          f"{'(a) of 8TB/s':>12s}")
+          f"{'(a) of 8TB/s':>12s} " + " ".join(f"{'(d) form ' + str(f):>10s}" for f in forms) + f" {'d0/b':>6s} {'d0/c':>6s}")
     quant_us = {}
     for name, n, k in SHAPES:
         img_bytes = eng.w4_bytes(n, k)
@@ -87,22 +93,28 @@ def main():
             def lib():
                 return torch.nn.functional.linear(x, ws.next(), bias)
 
+            def tiled(form):
+                return lambda: eng.w4_gemm_tiled(x, imgs.next(), n, cb, bias, out=out, form=form)
+
             has_fused = fused() is not None
             deq(), lib()
+            for f in forms:
+                assert tiled(f)() is not None
             torch.cuda.synchronize()
-            ta, tb, tc = [], [], []
-            for _ in range(args.rounds):
-                if has_fused:
-                    ta.append(_time(fused, args.iters))
-                tb.append(_time(deq, args.iters))
-                tc.append(_time(lib, args.iters))
+            ta, tb, tc, td = [], [], [], [[] for _ in forms]
+            arms = ([(ta, fused)] if has_fused else []) + [(tb, deq), (tc, lib)] + [(td[f], tiled(f)) for f in forms]
+            for rnd in range(args.rounds):  # a new order every round: no arm always follows the same one
+                for ts, fn in random.Random(rnd).sample(arms, len(arms)):
+                    ts.append(_time(fn, args.iters))
             mb, mc = statistics.median(tb), statistics.median(tc)
+            md = [statistics.median(t) for t in td]
+            tail = " " + " ".join(f"{v:10.1f}" for v in md) + f" {md[0] / mb:6.2f} {md[0] / mc:6.2f}"
             if has_fused:
                 ma = statistics.median(ta)
                 print(f"{name:11s} {n:6d} {k:6d} {m:5d} {ma:10.1f} {mb:11.1f} {mc:10.1f} {ma / mb:6.2f} {ma / mc:6.2f} "
-                      f"{img_bytes / (ma * 1e-6) / PEAK:12.3f}", flush=True)
+                      f"{img_bytes / (ma * 1e-6) / PEAK:12.3f}" + tail, flush=True)
             else:
-                print(f"{name:11s} {n:6d} {k:6d} {m:5d} {'-':>10s} {mb:11.1f} {mc:10.1f} {'-':>6s} {'-':>6s} {'-':>12s}", flush=True)
+                print(f"{name:11s} {n:6d} {k:6d} {m:5d} {'-':>10s} {mb:11.1f} {mc:10.1f} {'-':>6s} {'-':>6s} {'-':>12s}" + tail, flush=True)
         # the format kernels on their own (the source / destination ring defeats the cache as above)
         img = imgs.items[0]
         tq = statistics.median(_time(lambda: eng.w4_quantize(ws.next(), cb, out=img), args.iters) for _ in range(args.rounds))
