@@ -157,6 +157,7 @@ class KvPlanChunkArgs(C.Structure):
 
 
 KV_CHUNK_MAX = 16  # GLB_KV_CHUNK_MAX
+KV_TILE_MAX = 128  # GLB_KV_TILE_MAX
 
 
 class MT19937(C.Structure):
@@ -614,6 +615,8 @@ SYMBOLS = {
     "glb_kv_plan_chunk": (C.c_int, [C.POINTER(KvPlanChunkArgs), _vp]),
     "glb_slab_attention_chunk": (C.c_int, [_vp, C.POINTER(C.c_int64), _vp, C.POINTER(C.c_int64), _vp, C.POINTER(C.c_int64), _vp, _vp,
                                            _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _i32, _vp, _vp]),
+    "glb_slab_attention_tile": (C.c_int, [_vp, C.POINTER(C.c_int64), _vp, C.POINTER(C.c_int64), _vp, C.POINTER(C.c_int64), _vp, _vp,
+                                          _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _i32, _vp, _vp]),
     "glb_trie_workspace": (_sz, [_i64, _i64]),
     "glb_trie_reduce": (C.c_int, [_vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _sz,
                                   _vp]),

@@ -18,7 +18,8 @@ as long as the tokens behind the shared prefix are at most K: glb_match_prefix_r
 prefix (`keep` tokens), glb_kv_plan_chunk feeds the context its last L - keep tokens in one forward
 (glb_slab_attention_chunk) - a context that grew by several tokens, shrank and grew again, or forks off a longer one.  A
 row that holds more than keep + 1 tokens is never truncated: the context takes a copy of the shared prefix.  K = 1 is the
-lookup and the plan above, unchanged.
+lookup and the plan above, unchanged.  With `span` = M (auto_kv_span, 17 .. 128) the limit is max(K, M) tokens:
+forwards that feed a row more than 16 run glb_slab_attention_tile.
 
 Lookup and block table run on the device (glb_match_rows, glb_kv_plan: one launch each), like `DeviceSIS._step_shared_kv`;
 the host reads the numbers of rows of each kind from the call's one D2H copy and launches the forwards (kv.SlabRunner).
@@ -29,9 +30,11 @@ from .kv import SlabRunner
 
 
 class AutoKV:
-    def __init__(self, llm, rows, cap=64, in_place=0.75, graph=True, chunk=1):
+    def __init__(self, llm, rows, cap=64, in_place=0.75, graph=True, chunk=1, span=None):
         self.llm, self.eng, self.dev = llm, llm.engine, llm.device
         self.R, self.cap, self.chunk = int(rows), int(cap), int(chunk)
+        # the most tokens fed to a row that shares a prefix: `chunk`, or with `span` (AsyncAmdLM's auto_kv_span) the larger
+        self.span = None if span is None else max(int(span), self.chunk)
         self.kv = SlabRunner(llm, rows, cap, in_place, graph)  # the slabs (they outlive a reset) and the forwards over them
         self.reset()
 
@@ -60,7 +63,7 @@ class AutoKV:
         # the row that holds every distinct context, or its first L - 1 tokens (every candidate's tokens are compared:
         # a hash never decides alone), then the block table - both on the device, one launch each
         self.t += 1
-        if self.chunk > 1:
+        if self.chunk > 1 or self.span is not None:
             return self._logits_chunk(tok_d, st_d, ln_d, group_of, rep, ng, extra_head)
         old, gh = eng.match_rows(tok_d, st_d, ln_d, rep, ng, self.row_tok, self.row_len, self.row_hash)
         plan = eng.kv_plan(group_of, rep, ng, old, ln_d, R, cap, stamps=self.stamp, call_no=self.t,
@@ -70,9 +73,11 @@ class AutoKV:
         return self._forwards(plan, counts, (0, 0), 0, extra, tok_d, st_d, ln_d)
 
     def _logits_chunk(self, tok_d, st_d, ln_d, group_of, rep, ng, extra_head):
-        """`logits` with auto_kv_chunk > 1: the row with the longest shared prefix, up to `chunk` tokens fed per row."""
+        """`logits` with auto_kv_chunk > 1 or auto_kv_span: the row with the longest shared prefix, up to `chunk` (`span`)
+        tokens fed per row."""
         eng, R, cap = self.eng, self.R, self.cap
-        old, keep, gh = eng.match_prefix_rows(tok_d, st_d, ln_d, rep, ng, self.row_tok, self.row_len, self.row_hash, self.chunk)
+        most = self.chunk if self.span is None else self.span
+        old, keep, gh = eng.match_prefix_rows(tok_d, st_d, ln_d, rep, ng, self.row_tok, self.row_len, self.row_hash, most)
         plan = eng.kv_plan_chunk(group_of, rep, ng, old, keep, ln_d, R, cap, stamps=self.stamp, call_no=self.t,
                                  table=(self.row_tok, self.row_len, self.row_hash, gh, tok_d, st_d))
         fed = plan["n_new_of_row"]

@@ -1,4 +1,5 @@
-// glb_attn.hpp - what the five attention kernels of glb_kv.hip share; included there only.
+// glb_attn.hpp - what the five attention kernels of glb_kv.hip share; included there, and by
+// glb_attn_tile.hip for the 16-byte vector and pack16v.
 //   WaveShape<DT, DH>   a 16-byte vector is EPV elements, LP = head_dim / EPV lanes are one slot, PP = 64 / LP slots a wave
 //   unpack16 / pack16v  a 16-byte vector as float32 and back
 //   slot_score          q . k over a slot through __shfl_xor: the wave that is one query (slab, chunk, short)

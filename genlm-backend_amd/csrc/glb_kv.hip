@@ -210,7 +210,7 @@ __global__ __launch_bounds__(kT) void kv_plan_kernel(const PlanArgs a) {
     int claim = u;
     if (a.old_keep && o >= 0) {
       const int keep = keep_of(u, L);
-      if (keep < 0 || keep > L - 1 || L - keep > GLB_KV_CHUNK_MAX) o = -1;  // (not a prefix of this context, or more tokens behind it than one forward feeds: encoded)
+      if (keep < 0 || keep > L - 1 || L - keep > GLB_KV_TILE_MAX) o = -1;  // (not a prefix of this context, or more tokens behind it than one forward feeds: encoded)
       // a row that holds more than keep + 1 tokens is never truncated in place: it stays as it is - pinned, so that it
       // is not handed out as a free row either - and the group takes a copy of its keep tokens
       else if (a.row_len[o] > keep + 1) claim = kPinned;
@@ -1219,8 +1219,8 @@ int glb_match_prefix_rows(const int32_t *tokens, const int64_t *starts, const in
     return glb::api_fail(GLB_EINVAL, "glb_match_prefix_rows: null pointer");
   if (n <= 0 || n_rows <= 0 || cap <= 0 || n > 0x7fffffffll || n_rows > 0x3fffffffll || cap > 0x3fffffffll)
     return glb::api_fail(GLB_EINVAL, "glb_match_prefix_rows: bad sizes");
-  if (max_new < 1 || max_new > GLB_KV_CHUNK_MAX)
-    return glb::api_fail(GLB_EINVAL, "glb_match_prefix_rows: max_new %d outside 1 .. %d", max_new, GLB_KV_CHUNK_MAX);
+  if (max_new < 1 || max_new > GLB_KV_TILE_MAX)
+    return glb::api_fail(GLB_EINVAL, "glb_match_prefix_rows: max_new %d outside 1 .. %d", max_new, GLB_KV_TILE_MAX);
   hipLaunchKernelGGL(match_prefix_rows_kernel, dim3((unsigned)n), dim3(64), 0, (hipStream_t)stream, tokens, starts, lengths,
                      rep, n_groups, row_tok, row_len, (int32_t)n_rows, (int32_t)cap, max_new, out_old, out_keep, out_hash);
   const hipError_t e = hipGetLastError();

@@ -1687,6 +1687,27 @@ class HipEngine:
     def slab_attention_chunk_supports(dtype, head_dim):
         return dtype in _DT and head_dim in (16, 32, 64, 128)
 
+    def slab_attention_tile(self, query, k_new, v_new, k_slab, v_slab, pos, n_new, scale, rows=None):
+        """`slab_attention_chunk` for forwards of up to 128 new tokens per row (glb_slab_attention_tile: the K / V of a (row,
+        KV head) on chip once per 64 queries, both products on MFMA).  The same arguments and result; the output is within
+        the chunk kernel's accuracy, not its bits."""
+        n, H, T, Dh = query.shape
+        R, Hkv, cap = k_slab.shape[0], k_slab.shape[1], k_slab.shape[2]
+        assert query.stride(3) == 1 and k_new.stride(3) == 1 and v_new.stride(3) == 1 and k_slab.is_contiguous() and v_slab.is_contiguous()
+        assert k_new.dtype == v_new.dtype == query.dtype == k_slab.dtype == v_slab.dtype
+        assert k_new.shape == v_new.shape == (n, Hkv, T, Dh) and (rows is not None or n == R)
+        out = torch.empty((n, T, H, Dh), dtype=query.dtype, device=self.device)
+        i64x3 = C.c_int64 * 3
+        check(self.lib.glb_slab_attention_tile(_ptr(query), i64x3(*query.stride()[:3]), _ptr(k_new), i64x3(*k_new.stride()[:3]),
+                                               _ptr(v_new), i64x3(*v_new.stride()[:3]), _ptr(k_slab), _ptr(v_slab), _ptr(pos),
+                                               _ptr(n_new), _ptr(rows), n, R, H, Hkv, cap, Dh, T, float(scale), _DT[query.dtype],
+                                               _ptr(out), self._stream()))
+        return out
+
+    @staticmethod
+    def slab_attention_tile_supports(dtype, head_dim):
+        return dtype in _DT and head_dim in (64, 128)
+
     def resample_systematic(self, log_weights, seed, offset):
         """Ancestors of a systematic resampling step over `log_weights` (the gathered population), int32 [n]
         (glb_resample_systematic); also returns logsumexp of the weights as a 1-element tensor."""

@@ -35,6 +35,7 @@ from transformers.cache_utils import Cache, CacheLayerMixin, DynamicCache
 # layer of a running in-place forward on the key tensor `Cache.update` returned (`_glb_layer`).
 _ATTN_NAME = "glb"
 SHORT_ATTENTION_MAX = 4096  # q_len * k_len up to which glb_short_attention is used
+CHUNK_KERNEL_MAX = 16  # tokens per row of a chunk forward glb_slab_attention_chunk takes; more: glb_slab_attention_tile
 
 
 def _glb_attention_forward(module, query, key, value, attention_mask, dropout=0.0, scaling=None, **kwargs):
@@ -49,7 +50,9 @@ def _glb_attention_forward(module, query, key, value, attention_mask, dropout=0.
         k_new, v_new, layer._new_k, layer._new_v = layer._new_k, layer._new_v, None, None
         o = layer.owner
         scale = scaling if scaling is not None else query.shape[-1] ** -0.5
-        return o.engine.slab_attention_chunk(query, k_new, v_new, layer.keys, layer.values, o.pos, o.n_new, scale, rows=o.rows), None
+        # (more than 16 tokens per row: the MFMA tile kernel - SlabRunner._chunk_fused asked for it before the forward ran)
+        attend = o.engine.slab_attention_chunk if query.shape[2] <= CHUNK_KERNEL_MAX else o.engine.slab_attention_tile
+        return attend(query, k_new, v_new, layer.keys, layer.values, o.pos, o.n_new, scale, rows=o.rows), None
     if layer is not None and layer._new_k is not None:
         # an in-place forward whose append is this kernel's job: the new token's K / V are only in the stash
         if key is not layer.keys or value is not layer.values or query.shape[2] != 1:
@@ -475,12 +478,14 @@ class SlabRunner:
         return fwd
 
     @torch.no_grad()
-    def _chunk_fused(self):
-        """Whether glb_slab_attention_chunk serves a chunk forward over these slabs (SlabForward.fused's conditions)."""
+    def _chunk_fused(self, t_max=1):
+        """Whether a kernel of this library serves a chunk forward of up to t_max tokens per row over these slabs
+        (SlabForward.fused's conditions): glb_slab_attention_chunk up to 16 tokens, glb_slab_attention_tile beyond."""
         pkv, cfg, eng = self.pkv, getattr(self.llm._body, "config", None), self.llm.engine
         k0 = pkv.layers[0].keys if pkv.layers and getattr(pkv.layers[0], "is_initialized", False) else None
-        return bool(cfg is not None and k0 is not None and k0.is_cuda and hasattr(eng, "slab_attention_chunk")
-                    and eng.slab_attention_chunk_supports(k0.dtype, k0.shape[-1])
+        name = "slab_attention_chunk" if t_max <= CHUNK_KERNEL_MAX else "slab_attention_tile"
+        return bool(cfg is not None and k0 is not None and k0.is_cuda and hasattr(eng, name)
+                    and getattr(eng, name + "_supports")(k0.dtype, k0.shape[-1])
                     and getattr(cfg, "_attn_implementation", None) == _ATTN_NAME and getattr(cfg, "_glb_engine", None) is eng)
 
     def _run_chunk(self, plan, lo, hi, t_max, token_at, pad_id):
@@ -497,7 +502,7 @@ class SlabRunner:
         at = torch.where(valid, pos[:, None] + ar[None, :], pos[:, None]).long()  # (padding: a position the row has, its token unused)
         ids = token_at(ctx[:, None].expand(-1, t_max), at).long()
         ids = torch.where(valid, ids, torch.full_like(ids, pad_id))
-        fused = self._chunk_fused()
+        fused = self._chunk_fused(t_max)
         pkv.set_forward_chunk(rows, pos, nn, fused)
         try:
             if fused:

@@ -271,7 +271,7 @@ class AsyncAmdLM(AsyncLM):
     @torch.no_grad()
     def __init__(self, hf_model, hf_tokenizer, batch_size=20, timeout=0.02, engine=None, fuse_activations=True,
                  kv_budget_bytes=8 << 30, logprob_budget_bytes=16 << 30, auto_kv_rows=0, auto_kv_cap=64,
-                 auto_kv_chunk=1, logprob_dtype="float32", glb_attention=True, merge_mlp=True, contract=None, gemms="library",
+                 auto_kv_chunk=1, auto_kv_span=None, logprob_dtype="float32", glb_attention=True, merge_mlp=True, contract=None, gemms="library",
                  split_gemms=True, w4_gemm="auto", score_chunk_bytes=1 << 30):
         """The caller's `hf_model` is never modified (hf.py:114-140 leaves it alone too): with `fuse_activations` or
         `glb_attention` the forwards of this backend run on a private SHADOW of its module tree that shares every weight
@@ -294,6 +294,11 @@ class AsyncAmdLM(AsyncLM):
         row ends up holding the whole context (contexts that grew by several tokens, shrank and grew, or fork off a longer
         one; the reference's per-token KV, cache.py:103-191).  Everything else is encoded as before; 1 (default) is the
         one-token behaviour in every respect.  `_auto_kv.stats` counts `chunk_rows` / `chunk_tokens`.
+        auto_kv_span = M, 17 .. 128 (needs auto_kv_rows; None: off): a context is served by a row when at most
+        max(auto_kv_chunk, M) tokens lie behind its longest shared prefix - a phrase-level proposal, sentences appended between
+        calls, a fork off a long prompt.  Forwards that feed a row more than 16 tokens run glb_slab_attention_tile (MFMA; float32
+        / bfloat16 / float16, head_dim 64 / 128; other shapes: SDPA with the explicit mask); its rows are within the
+        accuracy of one-token calls, not their bits.
         contract: "poly" / "hw" / "auto" - the arithmetic of the fused step's terms (HipEngine; None: the engine's own, "auto"
         for an engine made here: the hardware exponential for 16-bit logits, the polynomial for float32).
         gemms: "library" (default: PyTorch picks the GEMM kernels as it always does) or "recorded" - the forward's GEMM
@@ -386,10 +391,15 @@ class AsyncAmdLM(AsyncLM):
             raise ValueError(f"auto_kv_chunk must be an integer from 1 to 16, got {auto_kv_chunk!r}")
         if auto_kv_chunk > 1 and not auto_kv_rows:
             raise ValueError("auto_kv_chunk > 1 needs auto_kv_rows: there are no KV rows to share prefixes in")
+        if auto_kv_span is not None:
+            if isinstance(auto_kv_span, bool) or not isinstance(auto_kv_span, int) or not 17 <= auto_kv_span <= 128:
+                raise ValueError(f"auto_kv_span must be None or an integer from 17 to 128, got {auto_kv_span!r}")
+            if not auto_kv_rows:
+                raise ValueError("auto_kv_span needs auto_kv_rows: there are no KV rows to share prefixes in")
         if auto_kv_rows:
             from .autokv import AutoKV
 
-            self._auto_kv = AutoKV(self, auto_kv_rows, auto_kv_cap, chunk=auto_kv_chunk)
+            self._auto_kv = AutoKV(self, auto_kv_rows, auto_kv_cap, chunk=auto_kv_chunk, span=auto_kv_span)
         # fused-step state
         self.masks = RegisteredMasks(self.engine)  # what register_masks was given (masks.py)
         self._rng_mode = RNG_PHILOX

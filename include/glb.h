@@ -401,7 +401,7 @@ int glb_kv_plan(const glb_kv_plan_args *args, void *hip_stream);
  * a context finds the longest prefix it shares with anything cached).  Three additions; the entry points above keep their
  * outputs bit for bit.
  *
- * glb_match_prefix_rows: glb_match_rows' inputs plus max_new (1 .. GLB_KV_CHUNK_MAX).  For a group's context of L tokens and a
+ * glb_match_prefix_rows: glb_match_rows' inputs plus max_new (1 .. GLB_KV_TILE_MAX).  For a group's context of L tokens and a
  *   row r with row_len[r] > 0, let c be the length of the common prefix of the row's tokens and the context's and
  *   keep = min(c, L - 1).  r is a candidate when keep >= 1, L - keep <= max_new and L <= cap.  out_old_row[g]: the candidate
  *   with the largest keep - among equals a row that holds exactly the context, then the smallest row index - or -1;
@@ -417,7 +417,7 @@ int glb_kv_plan(const glb_kv_plan_args *args, void *hip_stream);
  *   most keep + 1 tokens (the parent, the context itself, a sibling).  A longer row is never truncated in place - the
  *   group takes a copy of its keep tokens into a free row and the long row stays as it is, not free in this call (its stamp
  *   is renewed).  The first group (by id) that may keep a row in place keeps it.  A group whose keep is outside
- *   0 .. L - 1, or with more than GLB_KV_CHUNK_MAX tokens behind it, reads as a group without a row.  The row table (plan.row_tok ...) is required.  plan.out_head has TEN words:
+ *   0 .. L - 1, or with more than GLB_KV_TILE_MAX tokens behind it, reads as a group without a row.  The row table (plan.row_tok ...) is required.  plan.out_head has TEN words:
  *   the eight of glb_kv_plan (head[1] counts every row with a prefix), head[8] the rows fed more than one token, head[9]
  *   the largest number of tokens fed to a row.  With old_keep[g] == L - 1 for every group and matched rows of L - 1 or L
  *   tokens every output shared with glb_kv_plan equals it (one kernel serves both entries).
@@ -452,6 +452,29 @@ int glb_slab_attention_chunk(const void *q, const int64_t q_strides[3], const vo
                              const int32_t *n_new, const int32_t *row_of, int64_t n_rows, int64_t n_slab_rows, int64_t heads,
                              int64_t kv_heads, int64_t cap, int64_t head_dim, int64_t max_new, float scale, int32_t dtype,
                              void *out, void *hip_stream);
+
+/*
+ * glb_slab_attention_tile: glb_slab_attention_chunk's contract for max_new in 1 .. GLB_KV_TILE_MAX: the same
+ *   arguments, strides, row_of and output [n_rows, max_new, heads, head_dim]; query t < n_new[r] attends positions
+ *   0 .. pos[r] + t - below pos[r] from the slab, from pos[r] on from k_new / v_new, never from what the slab held there; the
+ *   new K / V are written to the slab once per (row, KV head); outputs of t >= n_new[r] are zeros; a chunk outside its row
+ *   (pos < 0, pos + n_new > cap, n_new outside 1 .. max_new, a slab row outside the slab): NaN for that row, nothing
+ *   appended, the other rows unaffected.  No atomics, no workspace, no allocation: fit for a captured graph.
+ *   One workgroup per (row, KV head, 64 query rows) brings the K / V on chip once and runs both products on MFMA
+ *   (v_mfma_f32_16x16x32_{bf16,f16}; float32 rows on v_mfma_f32_16x16x4f32, inputs unrounded), softmax in float32; for the
+ *   16-bit types the probabilities are rounded to the element type as the second product's operand.
+ *   NOT promised: the bits of successive one-token calls (glb_slab_attention_chunk's promise) - this kernel sums in MFMA
+ *   order; the slab afterwards is bit-equal to what those calls leave.  float32 / bfloat16 / float16; head_dim 64 / 128
+ *   (GLB_EUNSUPPORTED otherwise); any heads / kv_heads; pointers and strides multiples of 16 bytes.
+ *   glb_match_prefix_rows takes max_new up to GLB_KV_TILE_MAX and glb_kv_plan_chunk feeds a row up to GLB_KV_TILE_MAX tokens;
+ *   GLB_KV_CHUNK_MAX still bounds glb_slab_attention_chunk.
+ */
+#define GLB_KV_TILE_MAX 128
+int glb_slab_attention_tile(const void *q, const int64_t q_strides[3], const void *k_new, const int64_t k_strides[3],
+                            const void *v_new, const int64_t v_strides[3], void *k_slab, void *v_slab, const int32_t *pos,
+                            const int32_t *n_new, const int32_t *row_of, int64_t n_rows, int64_t n_slab_rows, int64_t heads,
+                            int64_t kv_heads, int64_t cap, int64_t head_dim, int64_t max_new, float scale, int32_t dtype,
+                            void *out, void *hip_stream);
 
 /*
  * Attention of a one-token forward over KV slab rows where they lie (the read side of the device-resident KV, SURVEY.md

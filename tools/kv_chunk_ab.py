@@ -13,6 +13,12 @@ Infinity Cache, so the K / V come from HBM; the fraction of 8 TB/s is on the byt
 once per KV head, the new K / V read and written, q and the output).
 
     python tools/kv_chunk_ab.py [--rounds 5] [--calls 4] [--no-step] [--no-kernel]
+
+--tile runs the arms of glb_slab_attention_tile / auto_kv_span instead.  Kernel: the tile kernel against SDPA
+with the explicit mask, T in {16, 32, 64, 128}, 128 rows of 256 positions with 64 cached, and against the chunk kernel at
+T = 16; the three arms alternate round by round, median (min .. max).  Step: 128 contexts grow by 32 tokens per call from a
+16-token prompt through auto_kv_span=32 (every context is fed its 32 tokens over its row), through rows without it (every
+call re-encodes) and without rows.
 """
 import argparse
 import os
@@ -141,6 +147,94 @@ def kernel_ab(eng, rounds, iters):
             print(f"{name:22s} {T:3d} {a:9.1f} {b:9.1f} {a / b:6.2f} {moved / (a * 1e-6) / PEAK:9.3f}")
 
 
+def tile_kernel_ab(eng, rounds, iters):
+    n, cap, keep = 128, 256, 64
+    g = torch.Generator(device="cuda").manual_seed(0)
+    print(f"# glb_slab_attention_tile vs SDPA + explicit mask (and glb_slab_attention_chunk at T = 16); {n} rows, cap {cap}, "
+          f"{keep} cached positions; us, median (min .. max) of {rounds} alternating rounds x {iters} calls")
+    print(f"{'shape':22s} {'T':>3s} {'tile':>26s} {'sdpa':>26s} {'chunk':>26s} {'t/s':>6s} {'of 8TB/s':>9s}")
+    for name, H, Hkv, Dh, dtype in (("gpt2 12/12 x64 fp32", 12, 12, 64, torch.float32), ("1B 32/8 x64 bf16", 32, 8, 64, torch.bfloat16),
+                                    ("8B 32/8 x128 bf16", 32, 8, 128, torch.bfloat16)):
+        es = 4 if dtype == torch.float32 else 2
+        per = 2 * n * Hkv * cap * Dh * es
+        n_buf = max(2, -(-RING_BYTES // per))
+        slabs = [(torch.randn((n, Hkv, cap, Dh), device="cuda", generator=g).to(dtype), torch.randn((n, Hkv, cap, Dh), device="cuda", generator=g).to(dtype))
+                 for _ in range(n_buf)]
+        pos = torch.full((n,), keep, dtype=torch.int32, device="cuda")
+        for T in (16, 32, 64, 128):
+            nn = torch.full((n,), T, dtype=torch.int32, device="cuda")
+            proj = torch.randn((n, T, (H + 2 * Hkv) * Dh), device="cuda", generator=g).to(dtype)
+            q = proj[..., :H * Dh].view(n, T, H, Dh).transpose(1, 2)
+            kn = proj[..., H * Dh:(H + Hkv) * Dh].view(n, T, Hkv, Dh).transpose(1, 2)
+            vn = proj[..., (H + Hkv) * Dh:].view(n, T, Hkv, Dh).transpose(1, 2)
+            ar = torch.arange(cap, device="cuda")
+            mask = (ar[None, None, None, :] <= (keep + torch.arange(T, device="cuda"))[None, None, :, None]).expand(n, 1, T, cap)
+            state = {"i": 0}
+
+            def slab():
+                state["i"] = (state["i"] + 1) % n_buf
+                return slabs[state["i"]]
+
+            def sdpa():  # what the fall-through does per layer: append the new K / V, dense attention under the mask
+                ks, vs = slab()
+                ks[:, :, keep:keep + T] = kn
+                vs[:, :, keep:keep + T] = vn
+                torch.nn.functional.scaled_dot_product_attention(q, ks, vs, attn_mask=mask, enable_gqa=H != Hkv)
+
+            arms = {"tile": lambda: eng.slab_attention_tile(q, kn, vn, *slab(), pos, nn, Dh ** -0.5), "sdpa": sdpa}
+            if T <= 16:
+                arms["chunk"] = lambda: eng.slab_attention_chunk(q, kn, vn, *slab(), pos, nn, Dh ** -0.5)
+            us = {k: [] for k in arms}
+            for fn in arms.values():
+                fn()
+            for _ in range(rounds):
+                for k, fn in arms.items():
+                    us[k].append(_time(fn, iters))
+            cell = {k: f"{statistics.median(v):9.1f} ({min(v):.1f} .. {max(v):.1f})" for k, v in us.items()}
+            a, b = statistics.median(us["tile"]), statistics.median(us["sdpa"])
+            moved = n * (2 * Hkv * keep * Dh + 2 * 2 * Hkv * T * Dh + 2 * H * T * Dh) * es
+            print(f"{name:22s} {T:3d} {cell['tile']:>26s} {cell['sdpa']:>26s} {cell.get('chunk', '-'):>26s} {a / b:6.2f} {moved / (a * 1e-6) / PEAK:9.3f}")
+        del slabs
+        torch.cuda.empty_cache()
+
+
+def tile_step_ab(rounds, calls, grow=32, n=128):
+    for name, _, model in models():
+        V = model.config.vocab_size
+        cap = 16 + grow * (calls + 1) + 8
+        rows = dict(auto_kv_rows=n + n // 4, auto_kv_cap=cap)
+        arms = {"rows": rows, f"span={grow}": dict(rows, auto_kv_span=grow), "no rows": {}}
+        ms, kinds, llms = {k: [] for k in arms}, {}, {}
+        for k, kw in arms.items():
+            llms[k] = AsyncAmdLM(model, None, batch_size=n, **kw)
+            llms[k].tokenizer = Tok()
+        rnd = np.random.default_rng(0)
+        for rd in range(rounds + 1):  # (round 0 warms every arm up)
+            seqs = [rnd.integers(1, V, 16 + grow * (calls + 1)).tolist() for _ in range(n)]
+            for k, m in llms.items():
+                m.clear_cache()
+                m.set_rng("philox", rd)
+                m.batch_next_token_step_sync([s[:16] for s in seqs], [0] * n)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for c in range(1, calls + 1):
+                    m.batch_next_token_step_sync([s[:16 + grow * c] for s in seqs], [0] * n)
+                torch.cuda.synchronize()
+                if rd:
+                    ms[k].append((time.perf_counter() - t0) * 1e3 / calls)
+                if m._auto_kv is not None:
+                    kinds[k] = dict(m._auto_kv.stats)
+        print(f"## {name}, {n} contexts, +{grow} tokens per call, {rounds} alternating rounds x {calls} calls (median, min .. max ms per call)")
+        for k in arms:
+            st = kinds.get(k, {})
+            print(f"  {k:8s} {statistics.median(ms[k]):8.2f} ms  ({min(ms[k]):.2f} .. {max(ms[k]):.2f})   "
+                  + " ".join(f"{q}={st[q]}" for q in ("one_token_rows", "chunk_rows", "chunk_tokens", "encoded_rows", "copied_rows") if q in st))
+        for m in llms.values():
+            m.close()
+        del llms, model
+        torch.cuda.empty_cache()
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
@@ -149,8 +243,15 @@ if __name__ == "__main__":
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--no-step", action="store_true")
     ap.add_argument("--no-kernel", action="store_true")
+    ap.add_argument("--tile", action="store_true")
     a = ap.parse_args()
     print(f"# {torch.cuda.get_device_name(0)}")
+    if a.tile:
+        if not a.no_kernel:
+            tile_kernel_ab(HipEngine("cuda:0"), a.rounds, a.iters)
+        if not a.no_step:
+            tile_step_ab(a.rounds, a.calls)
+        sys.exit(0)
     if not a.no_kernel:
         kernel_ab(HipEngine("cuda:0"), a.rounds, a.iters)
     if not a.no_step:
