@@ -1,5 +1,6 @@
-// glb_attn.hpp - what the five attention kernels of glb_kv.hip share; included there, and by
-// glb_attn_tile.hip for the 16-byte vector and pack16v.
+// glb_attn.hpp - the DEVICE side the five attention kernels of glb_kv.hip share; included there, and by
+// glb_attn_tile.hip for the 16-byte vector and pack16v.  The host side of the five entries - dispatch, checks, the chunk-shaped
+// argument block - is glb_attn_host.hpp.
 //   WaveShape<DT, DH>   a 16-byte vector is EPV elements, LP = head_dim / EPV lanes are one slot, PP = 64 / LP slots a wave
 //   unpack16 / pack16v  a 16-byte vector as float32 and back
 //   slot_score          q . k over a slot through __shfl_xor: the wave that is one query (slab, chunk, short)

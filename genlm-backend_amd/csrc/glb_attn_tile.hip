@@ -41,6 +41,7 @@
 
 #include "../../include/glb.h"
 #include "glb_attn.hpp"
+#include "glb_attn_host.hpp"
 #include "glb_common.hpp"
 
 namespace {
@@ -280,13 +281,6 @@ __global__ __launch_bounds__(THREADS) void slab_attention_tile_kernel(const Tile
   }
 }
 
-template <int DT>
-hipError_t launch_tile(int64_t head_dim, dim3 grid, hipStream_t s, const TileArgs &a) {
-  if (head_dim == 64) hipLaunchKernelGGL((slab_attention_tile_kernel<DT, 64>), grid, dim3(THREADS), 0, s, a);
-  else hipLaunchKernelGGL((slab_attention_tile_kernel<DT, 128>), grid, dim3(THREADS), 0, s, a);
-  return hipGetLastError();
-}
-
 }  // namespace
 
 extern "C" int glb_slab_attention_tile(const void *q, const int64_t q_strides[3], const void *k_new, const int64_t k_strides[3],
@@ -294,49 +288,20 @@ extern "C" int glb_slab_attention_tile(const void *q, const int64_t q_strides[3]
                                        const int32_t *pos, const int32_t *n_new, const int32_t *row_of, int64_t n_rows,
                                        int64_t n_slab_rows, int64_t heads, int64_t kv_heads, int64_t cap, int64_t head_dim,
                                        int64_t max_new, float scale, int32_t dtype, void *out, void *stream) {
-  if (!q || !k_new || !v_new || !k_slab || !v_slab || !pos || !n_new || !out || !q_strides || !k_strides || !v_strides)
-    return glb::api_fail(GLB_EINVAL, "glb_slab_attention_tile: null pointer");
-  if (dtype < GLB_F32 || dtype > GLB_F16) return glb::api_fail(GLB_EINVAL, "bad dtype %d", dtype);
-  if (max_new < 1 || max_new > GLB_KV_TILE_MAX)
-    return glb::api_fail(GLB_EINVAL, "glb_slab_attention_tile: %lld query positions per row (1 .. %d)", (long long)max_new, GLB_KV_TILE_MAX);
-  if (n_rows <= 0 || n_slab_rows <= 0 || heads <= 0 || kv_heads <= 0 || cap <= 0 || heads % kv_heads || cap > 0x7fffffffll ||
-      n_slab_rows > 0x7fffffffll || n_rows > 0x7fffffffll || heads > 0xffffffll)
-    return glb::api_fail(GLB_EINVAL, "glb_slab_attention_tile: bad sizes");
+  TileArgs a{};
+  if (const int rc = fill_chunk_args("glb_slab_attention_tile", GLB_KV_TILE_MAX, kTileHeadDims, q, q_strides, k_new, k_strides, v_new,
+                                     v_strides, k_slab, v_slab, pos, n_new, row_of, n_rows, n_slab_rows, heads, kv_heads, cap, head_dim,
+                                     max_new, scale, dtype, out, a))
+    return rc;
+  // one workgroup per (row, KV head, block of QROWS query rows): bounded factors first, then their product
+  if (n_rows > 0x7fffffffll || heads > 0xffffffll) return glb::api_fail(GLB_EINVAL, "glb_slab_attention_tile: bad sizes");
   const int64_t q_blocks = (max_new * (heads / kv_heads) + QROWS - 1) / QROWS;
   if (n_rows * kv_heads * q_blocks > 0x7fffffffll) return glb::api_fail(GLB_EINVAL, "glb_slab_attention_tile: bad sizes");
-  if (head_dim != 64 && head_dim != 128)
-    return glb::api_fail(GLB_EUNSUPPORTED, "glb_slab_attention_tile: head_dim %lld (64 and 128 are built)", (long long)head_dim);
-  const int es = dtype == GLB_F32 ? 4 : 2;
-  bool aligned = true;
-  for (const void *p : {q, k_new, v_new, (const void *)k_slab, (const void *)v_slab, (const void *)out}) aligned = aligned && (uintptr_t)p % 16 == 0;
-  for (const int64_t *st : {q_strides, k_strides, v_strides})
-    for (int i = 0; i < 3; ++i) aligned = aligned && (st[i] * es) % 16 == 0;
-  if (!aligned) return glb::api_fail(GLB_EINVAL, "glb_slab_attention_tile: pointers and strides must be 16-byte aligned");
-  TileArgs a{};
-  a.q = (const char *)q;
-  a.k_new = (const char *)k_new;
-  a.v_new = (const char *)v_new;
-  a.k_slab = (char *)k_slab;
-  a.v_slab = (char *)v_slab;
-  a.out = (char *)out;
-  a.pos = pos;
-  a.n_new = n_new;
-  a.row_of = row_of;
-  a.q_sr = q_strides[0], a.q_sh = q_strides[1], a.q_sp = q_strides[2];
-  a.k_sr = k_strides[0], a.k_sh = k_strides[1], a.k_sp = k_strides[2];
-  a.v_sr = v_strides[0], a.v_sh = v_strides[1], a.v_sp = v_strides[2];
-  a.n = (int32_t)n_rows;
-  a.H = (int32_t)heads;
-  a.Hkv = (int32_t)kv_heads;
-  a.cap = (int32_t)cap;
-  a.T = (int32_t)max_new;
-  a.n_slab_rows = (int32_t)n_slab_rows;
   a.QB = (int32_t)q_blocks;
-  a.scale = scale;
   const dim3 grid((unsigned)(n_rows * kv_heads * q_blocks));
-  const hipStream_t s = (hipStream_t)stream;
-  const hipError_t e = dtype == GLB_F32 ? launch_tile<GLB_F32>(head_dim, grid, s, a)
-                                        : (dtype == GLB_BF16 ? launch_tile<GLB_BF16>(head_dim, grid, s, a) : launch_tile<GLB_F16>(head_dim, grid, s, a));
+  const hipError_t e = launch_attention_form(kTileHeadDims, dtype, head_dim, [&](auto dt, auto dh) {
+    hipLaunchKernelGGL((slab_attention_tile_kernel<decltype(dt)::value, decltype(dh)::value>), grid, dim3(THREADS), 0, (hipStream_t)stream, a);
+  });
   if (e != hipSuccess) return glb::api_hip_fail(e, "slab_attention_tile launch");
   return GLB_OK;
 }

@@ -14,6 +14,7 @@
 
 #include "../../include/glb.h"
 #include "glb_attn.hpp"
+#include "glb_attn_host.hpp"
 #include "glb_common.hpp"
 
 namespace {
@@ -948,55 +949,6 @@ __global__ __launch_bounds__(64) void short_attention_packed_kernel(const Packed
   }
 }
 
-// ---- the dispatch over the built forms: f gets the element type / the head size as an std::integral_constant ------------
-template <class F>
-hipError_t with_dtype(int32_t dtype, F f) {
-  switch (dtype) {
-    case GLB_F32: return f(std::integral_constant<int, GLB_F32>{});
-    case GLB_BF16: return f(std::integral_constant<int, GLB_BF16>{});
-    default: return f(std::integral_constant<int, GLB_F16>{});
-  }
-}
-
-template <class F>
-hipError_t with_head_dim(int64_t head_dim, F f) {
-  if (head_dim == 64) return f(std::integral_constant<int, 64>{});
-  if (head_dim == 128) return f(std::integral_constant<int, 128>{});
-  if (head_dim == 32) return f(std::integral_constant<int, 32>{});
-  if (head_dim == 16) return f(std::integral_constant<int, 16>{});
-  return hipErrorInvalidValue;
-}
-
-// launch(dt, dh) enqueues the kernel of that form; the launch's error
-template <class F>
-hipError_t launch_attention_form(int32_t dtype, int64_t head_dim, F launch) {
-  return with_dtype(dtype, [&](auto dt) {
-    return with_head_dim(head_dim, [&](auto dh) {
-      launch(dt, dh);
-      return hipGetLastError();
-    });
-  });
-}
-
-// What the four attention entries check, around their own size checks: the element type before them ...
-inline int check_dtype(int32_t dtype) {
-  if (dtype < GLB_F32 || dtype > GLB_F16) return glb::api_fail(GLB_EINVAL, "bad dtype %d", dtype);
-  return GLB_OK;
-}
-
-// ... and behind them the head size, then 16-byte alignment of every pointer and every byte stride (`aligned`: what else the
-// entry reports under that message)
-inline int check_head_dim_and_alignment(const char *entry, int32_t dtype, int64_t head_dim, std::initializer_list<const void *> ptrs,
-                                        std::initializer_list<int64_t> strides, bool aligned = true) {
-  if (head_dim != 16 && head_dim != 32 && head_dim != 64 && head_dim != 128)
-    return glb::api_fail(GLB_EUNSUPPORTED, "%s: head_dim %lld (16, 32, 64 and 128 are built)", entry, (long long)head_dim);
-  const int es = dtype == GLB_F32 ? 4 : 2;
-  for (const void *p : ptrs) aligned = aligned && (uintptr_t)p % 16 == 0;
-  for (const int64_t st : strides) aligned = aligned && (st * es) % 16 == 0;
-  if (!aligned) return glb::api_fail(GLB_EINVAL, "%s: pointers and strides must be 16-byte aligned", entry);
-  return GLB_OK;
-}
-
 // ---- KV slab rows: append, gather (moved here from glb_api.hip in round 5) ---------------------------------------------------
 
 // slab[row_of[i] (or i), h, pos[i], :] = rows[i, h, :]  (one new token per forward row; rows may be a strided view)
@@ -1120,7 +1072,7 @@ int glb_slab_attention(const void *q, int64_t q_stride_row, int64_t q_stride_hea
   if (const int rc = check_dtype(dtype)) return rc;
   if (n_rows <= 0 || heads <= 0 || kv_heads <= 0 || cap <= 0 || heads % kv_heads || n_rows * heads > 0x7fffffffll)
     return glb::api_fail(GLB_EINVAL, "glb_slab_attention: bad sizes");
-  if (const int rc = check_head_dim_and_alignment("glb_slab_attention", dtype, head_dim, {q, k_new, v_new, k_slab, v_slab, out},
+  if (const int rc = check_head_dim_and_alignment("glb_slab_attention", kWaveHeadDims, dtype, head_dim, {q, k_new, v_new, k_slab, v_slab, out},
                                                   {q_stride_row, q_stride_head, k_stride_row, k_stride_head, v_stride_row, v_stride_head}))
     return rc;
   AttnArgs a{};
@@ -1143,7 +1095,7 @@ int glb_slab_attention(const void *q, int64_t q_stride_row, int64_t q_stride_hea
   a.cap = (int32_t)cap;
   a.scale = scale;
   const dim3 grid((unsigned)((int64_t)a.R * a.H)), block(64);
-  const hipError_t e = launch_attention_form(dtype, head_dim, [&](auto dt, auto dh) {
+  const hipError_t e = launch_attention_form(kWaveHeadDims, dtype, head_dim, [&](auto dt, auto dh) {
     hipLaunchKernelGGL((slab_attention_kernel<decltype(dt)::value, decltype(dh)::value>), grid, block, 0, (hipStream_t)stream, a);
   });
   if (e != hipSuccess) return glb::api_hip_fail(e, "slab_attention launch");
@@ -1155,40 +1107,14 @@ int glb_slab_attention_chunk(const void *q, const int64_t q_strides[3], const vo
                              const int32_t *n_new, const int32_t *row_of, int64_t n_rows, int64_t n_slab_rows, int64_t heads,
                              int64_t kv_heads, int64_t cap, int64_t head_dim, int64_t max_new, float scale, int32_t dtype,
                              void *out, void *stream) {
-  if (!q || !k_new || !v_new || !k_slab || !v_slab || !pos || !n_new || !out || !q_strides || !k_strides || !v_strides)
-    return glb::api_fail(GLB_EINVAL, "glb_slab_attention_chunk: null pointer");
-  if (const int rc = check_dtype(dtype)) return rc;
-  if (max_new < 1 || max_new > GLB_KV_CHUNK_MAX)
-    return glb::api_fail(GLB_EINVAL, "glb_slab_attention_chunk: %lld query positions per row (1 .. %d)", (long long)max_new, GLB_KV_CHUNK_MAX);
-  if (n_rows <= 0 || n_slab_rows <= 0 || heads <= 0 || kv_heads <= 0 || cap <= 0 || heads % kv_heads || cap > 0x7fffffffll ||
-      n_slab_rows > 0x7fffffffll || n_rows * heads * max_new > 0x7fffffffll)
-    return glb::api_fail(GLB_EINVAL, "glb_slab_attention_chunk: bad sizes");
-  if (const int rc = check_head_dim_and_alignment(
-          "glb_slab_attention_chunk", dtype, head_dim, {q, k_new, v_new, k_slab, v_slab, out},
-          {q_strides[0], q_strides[1], q_strides[2], k_strides[0], k_strides[1], k_strides[2], v_strides[0], v_strides[1], v_strides[2]}))
-    return rc;
   ChunkAttnArgs a{};
-  a.q = (const char *)q;
-  a.k_new = (const char *)k_new;
-  a.v_new = (const char *)v_new;
-  a.k_slab = (char *)k_slab;
-  a.v_slab = (char *)v_slab;
-  a.out = (char *)out;
-  a.pos = pos;
-  a.n_new = n_new;
-  a.row_of = row_of;
-  a.q_sr = q_strides[0], a.q_sh = q_strides[1], a.q_sp = q_strides[2];
-  a.k_sr = k_strides[0], a.k_sh = k_strides[1], a.k_sp = k_strides[2];
-  a.v_sr = v_strides[0], a.v_sh = v_strides[1], a.v_sp = v_strides[2];
-  a.n = (int32_t)n_rows;
-  a.H = (int32_t)heads;
-  a.Hkv = (int32_t)kv_heads;
-  a.cap = (int32_t)cap;
-  a.T = (int32_t)max_new;
-  a.n_slab_rows = (int32_t)n_slab_rows;
-  a.scale = scale;
+  if (const int rc = fill_chunk_args("glb_slab_attention_chunk", GLB_KV_CHUNK_MAX, kWaveHeadDims, q, q_strides, k_new, k_strides, v_new,
+                                     v_strides, k_slab, v_slab, pos, n_new, row_of, n_rows, n_slab_rows, heads, kv_heads, cap, head_dim,
+                                     max_new, scale, dtype, out, a))
+    return rc;
+  if (n_rows * heads * max_new > 0x7fffffffll) return glb::api_fail(GLB_EINVAL, "glb_slab_attention_chunk: bad sizes");  // one wave each
   const dim3 grid((unsigned)((int64_t)a.n * a.H * a.T)), block(64);
-  const hipError_t e = launch_attention_form(dtype, head_dim, [&](auto dt, auto dh) {
+  const hipError_t e = launch_attention_form(kWaveHeadDims, dtype, head_dim, [&](auto dt, auto dh) {
     hipLaunchKernelGGL((slab_attention_chunk_kernel<decltype(dt)::value, decltype(dh)::value>), grid, block, 0, (hipStream_t)stream, a);
   });
   if (e != hipSuccess) return glb::api_hip_fail(e, "slab_attention_chunk launch");
@@ -1322,7 +1248,7 @@ int glb_short_attention(const void *q, const int64_t q_strides[3], const void *k
       n_rows * heads * q_len > 0x7fffffffll || k_len > 0x7fffffffll)
     return glb::api_fail(GLB_EINVAL, "glb_short_attention: bad sizes");
   if (const int rc = check_head_dim_and_alignment(
-          "glb_short_attention", dtype, head_dim, {q, k, v, out},
+          "glb_short_attention", kWaveHeadDims, dtype, head_dim, {q, k, v, out},
           {q_strides[0], q_strides[1], q_strides[2], k_strides[0], k_strides[1], k_strides[2], v_strides[0], v_strides[1], v_strides[2]}))
     return rc;
   ShortArgs a{};
@@ -1343,7 +1269,7 @@ int glb_short_attention(const void *q, const int64_t q_strides[3], const void *k
   a.Lk = (int32_t)k_len;
   a.scale = scale;
   const hipStream_t s = (hipStream_t)stream;
-  const hipError_t e = launch_attention_form(dtype, head_dim, [&](auto dt, auto dh) {
+  const hipError_t e = launch_attention_form(kWaveHeadDims, dtype, head_dim, [&](auto dt, auto dh) {
     constexpr int DT = decltype(dt)::value, DH = decltype(dh)::value;
     const dim3 block(64);
     if (a.Lk <= 32 && a.Lq <= 2048 && (int64_t)a.U * a.Hkv <= 0x7fffffffll) {  // the (row, KV head) form: K / V in LDS once, slots are queries
@@ -1375,7 +1301,8 @@ int glb_short_attention_packed(const void *q, int64_t q_stride_row, int64_t q_st
   const auto strides = {q_stride_row, q_stride_head, k_stride_row, k_stride_head, v_stride_row, v_stride_head};
   bool word_and_signs = (uintptr_t)err_word % 4 == 0;  // the error word's alignment, and no negative stride
   for (const int64_t st : strides) word_and_signs = word_and_signs && st >= 0;
-  if (const int rc = check_head_dim_and_alignment("glb_short_attention_packed", dtype, head_dim, {q, k, v, out, plan}, strides, word_and_signs))
+  if (const int rc = check_head_dim_and_alignment("glb_short_attention_packed", kWaveHeadDims, dtype, head_dim, {q, k, v, out, plan},
+                                                  strides, word_and_signs))
     return rc;
   PackedArgs a{};
   a.q = (const char *)q;
@@ -1394,7 +1321,7 @@ int glb_short_attention_packed(const void *q, int64_t q_stride_row, int64_t q_st
   a.max_keys = (int32_t)max_keys;
   a.scale = scale;
   const dim3 grid((unsigned)((int64_t)a.S * a.Hkv)), block(64);
-  const hipError_t e = launch_attention_form(dtype, head_dim, [&](auto dt, auto dh) {
+  const hipError_t e = launch_attention_form(kWaveHeadDims, dtype, head_dim, [&](auto dt, auto dh) {
     constexpr int DT = decltype(dt)::value, DH = decltype(dh)::value;
     const size_t lds = (size_t)2 * a.max_keys * DH * sizeof(float) + (size_t)a.max_keys * sizeof(uint32_t);
     if (a.max_keys <= 16) hipLaunchKernelGGL((short_attention_packed_kernel<DT, DH, 16>), grid, block, lds, (hipStream_t)stream, a);

@@ -1665,11 +1665,8 @@ class HipEngine:
         return self.kv_plan(group_of, rep, n_groups, old_row, lengths, n_rows, cap, stamps=stamps, call_no=call_no,
                             table=table, old_keep=old_keep)
 
-    def slab_attention_chunk(self, query, k_new, v_new, k_slab, v_slab, pos, n_new, scale, rows=None):
-        """Attention of a forward with up to 16 new tokens per row over slab rows where they lie, the new K / V appended on
-        the way (glb_slab_attention_chunk).  query [n, H, T, Dh], k_new / v_new [n, H_kv, T, Dh] (unit inner stride), slabs
-        [R, H_kv, cap, Dh] contiguous, pos / n_new int32 [n]: first new position and number of new tokens of every row,
-        rows: int32 [n] slab row of forward row i (None: i).  Returns [n, T, H, Dh]; queries t >= n_new[i] give zeros."""
+    def _slab_attention_chunk_shaped(self, entry, query, k_new, v_new, k_slab, v_slab, pos, n_new, scale, rows):
+        """`slab_attention_chunk` / `slab_attention_tile`: the two entries share one signature and one contract."""
         n, H, T, Dh = query.shape
         R, Hkv, cap = k_slab.shape[0], k_slab.shape[1], k_slab.shape[2]
         assert query.stride(3) == 1 and k_new.stride(3) == 1 and v_new.stride(3) == 1 and k_slab.is_contiguous() and v_slab.is_contiguous()
@@ -1677,11 +1674,17 @@ class HipEngine:
         assert k_new.shape == v_new.shape == (n, Hkv, T, Dh) and (rows is not None or n == R)
         out = torch.empty((n, T, H, Dh), dtype=query.dtype, device=self.device)
         i64x3 = C.c_int64 * 3
-        check(self.lib.glb_slab_attention_chunk(_ptr(query), i64x3(*query.stride()[:3]), _ptr(k_new), i64x3(*k_new.stride()[:3]),
-                                                _ptr(v_new), i64x3(*v_new.stride()[:3]), _ptr(k_slab), _ptr(v_slab), _ptr(pos),
-                                                _ptr(n_new), _ptr(rows), n, R, H, Hkv, cap, Dh, T, float(scale), _DT[query.dtype],
-                                                _ptr(out), self._stream()))
+        check(getattr(self.lib, entry)(_ptr(query), i64x3(*query.stride()[:3]), _ptr(k_new), i64x3(*k_new.stride()[:3]), _ptr(v_new),
+                                       i64x3(*v_new.stride()[:3]), _ptr(k_slab), _ptr(v_slab), _ptr(pos), _ptr(n_new), _ptr(rows), n, R,
+                                       H, Hkv, cap, Dh, T, float(scale), _DT[query.dtype], _ptr(out), self._stream()))
         return out
+
+    def slab_attention_chunk(self, query, k_new, v_new, k_slab, v_slab, pos, n_new, scale, rows=None):
+        """Attention of a forward with up to 16 new tokens per row over slab rows where they lie, the new K / V appended on
+        the way (glb_slab_attention_chunk).  query [n, H, T, Dh], k_new / v_new [n, H_kv, T, Dh] (unit inner stride), slabs
+        [R, H_kv, cap, Dh] contiguous, pos / n_new int32 [n]: first new position and number of new tokens of every row,
+        rows: int32 [n] slab row of forward row i (None: i).  Returns [n, T, H, Dh]; queries t >= n_new[i] give zeros."""
+        return self._slab_attention_chunk_shaped("glb_slab_attention_chunk", query, k_new, v_new, k_slab, v_slab, pos, n_new, scale, rows)
 
     @staticmethod
     def slab_attention_chunk_supports(dtype, head_dim):
@@ -1691,18 +1694,7 @@ class HipEngine:
         """`slab_attention_chunk` for forwards of up to 128 new tokens per row (glb_slab_attention_tile: the K / V of a (row,
         KV head) on chip once per 64 queries, both products on MFMA).  The same arguments and result; the output is within
         the chunk kernel's accuracy, not its bits."""
-        n, H, T, Dh = query.shape
-        R, Hkv, cap = k_slab.shape[0], k_slab.shape[1], k_slab.shape[2]
-        assert query.stride(3) == 1 and k_new.stride(3) == 1 and v_new.stride(3) == 1 and k_slab.is_contiguous() and v_slab.is_contiguous()
-        assert k_new.dtype == v_new.dtype == query.dtype == k_slab.dtype == v_slab.dtype
-        assert k_new.shape == v_new.shape == (n, Hkv, T, Dh) and (rows is not None or n == R)
-        out = torch.empty((n, T, H, Dh), dtype=query.dtype, device=self.device)
-        i64x3 = C.c_int64 * 3
-        check(self.lib.glb_slab_attention_tile(_ptr(query), i64x3(*query.stride()[:3]), _ptr(k_new), i64x3(*k_new.stride()[:3]),
-                                               _ptr(v_new), i64x3(*v_new.stride()[:3]), _ptr(k_slab), _ptr(v_slab), _ptr(pos),
-                                               _ptr(n_new), _ptr(rows), n, R, H, Hkv, cap, Dh, T, float(scale), _DT[query.dtype],
-                                               _ptr(out), self._stream()))
-        return out
+        return self._slab_attention_chunk_shaped("glb_slab_attention_tile", query, k_new, v_new, k_slab, v_slab, pos, n_new, scale, rows)
 
     @staticmethod
     def slab_attention_tile_supports(dtype, head_dim):

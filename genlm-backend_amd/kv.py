@@ -38,30 +38,59 @@ SHORT_ATTENTION_MAX = 4096  # q_len * k_len up to which glb_short_attention is u
 CHUNK_KERNEL_MAX = 16  # tokens per row of a chunk forward glb_slab_attention_chunk takes; more: glb_slab_attention_tile
 
 
+def _chunk_kernel(t):
+    """The engine method that takes a chunk forward of t tokens per row: asked for before the forward runs
+    (`SlabRunner._chunk_fused`) and called in it (`_glb_attention_forward`)."""
+    return "slab_attention_chunk" if t <= CHUNK_KERNEL_MAX else "slab_attention_tile"
+
+
+def _kernel_serves(engine, name, pkv, body):
+    """Whether this library's kernel `engine.<name>` may serve the slabs of `pkv` under `body`: slabs that exist on a HIP
+    device in a form the kernel is built for, and a body whose attention goes through the "glb" entry with this engine."""
+    cfg = getattr(body, "config", None)
+    k0 = pkv.layers[0].keys if pkv.layers and getattr(pkv.layers[0], "is_initialized", False) else None
+    return bool(cfg is not None and k0 is not None and k0.is_cuda and hasattr(engine, name)
+                and getattr(engine, name + "_supports")(k0.dtype, k0.shape[-1])
+                and getattr(cfg, "_attn_implementation", None) == _ATTN_NAME and getattr(cfg, "_glb_engine", None) is engine)
+
+
+def _fused_forward(pkv, body, entry, lost, **inputs):
+    """One forward of `body` over `pkv` whose attention AND append are this library's kernel `entry` (no mask: the kernel
+    attends to the positions a row holds and its new ones, nothing else).  Whatever happens, the slabs are left with the
+    flag down and no stash; a layer whose stash nobody took bypassed the attention interface: `lost` is what that cost."""
+    pkv.fused_attention = True
+    try:
+        out = body(attention_mask=None, past_key_values=pkv, use_cache=True, **inputs)
+    finally:
+        pkv.fused_attention = False
+        stale = [i for i, ly in enumerate(pkv.layers) if ly._new_k is not None]
+        for i in stale:
+            pkv.layers[i]._new_k = pkv.layers[i]._new_v = None
+    if stale:
+        raise RuntimeError(f"{entry} was not reached in layers {stale}: {lost}")
+    return out
+
+
 def _glb_attention_forward(module, query, key, value, attention_mask, dropout=0.0, scaling=None, **kwargs):
     from transformers.integrations.sdpa_attention import sdpa_attention_forward
 
     layer = getattr(key, "_glb_layer", None)
-    if layer is not None and layer._new_k is not None and getattr(layer.owner, "n_new", None) is not None:
-        # a chunk forward over slab rows (SharedSlabKV.set_forward_chunk): up to 16 new tokens per row, appended by the kernel
-        if key is not layer.keys or value is not layer.values:
-            raise RuntimeError("glb_slab_attention_chunk: the attention module changed the key / value tensors the KV slab "
-                               "handed out: the new tokens were never appended")
-        k_new, v_new, layer._new_k, layer._new_v = layer._new_k, layer._new_v, None, None
-        o = layer.owner
-        scale = scaling if scaling is not None else query.shape[-1] ** -0.5
-        # (more than 16 tokens per row: the MFMA tile kernel - SlabRunner._chunk_fused asked for it before the forward ran)
-        attend = o.engine.slab_attention_chunk if query.shape[2] <= CHUNK_KERNEL_MAX else o.engine.slab_attention_tile
-        return attend(query, k_new, v_new, layer.keys, layer.values, o.pos, o.n_new, scale, rows=o.rows), None
     if layer is not None and layer._new_k is not None:
-        # an in-place forward whose append is this kernel's job: the new token's K / V are only in the stash
-        if key is not layer.keys or value is not layer.values or query.shape[2] != 1:
+        # a fused forward over slab rows (_fused_forward): the new tokens' K / V are only in the stash, the kernel appends them
+        o = layer.owner
+        chunk = getattr(o, "n_new", None) is not None  # (SharedSlabKV.set_forward_chunk: up to 128 new tokens per row)
+        if key is not layer.keys or value is not layer.values or (not chunk and query.shape[2] != 1):
+            if chunk:
+                raise RuntimeError("glb_slab_attention_chunk: the attention module changed the key / value tensors the KV slab "
+                                   "handed out: the new tokens were never appended")
             raise RuntimeError("glb_slab_attention: the attention module changed the key / value tensors the KV slab handed "
                                "out (or feeds more than one token): the new token was never appended - run this model with "
                                "SlabForward(fused_attention=False)")
         k_new, v_new, layer._new_k, layer._new_v = layer._new_k, layer._new_v, None, None
-        o = layer.owner
         scale = scaling if scaling is not None else query.shape[-1] ** -0.5
+        if chunk:
+            attend = getattr(o.engine, _chunk_kernel(query.shape[2]))
+            return attend(query, k_new, v_new, layer.keys, layer.values, o.pos, o.n_new, scale, rows=o.rows), None
         return o.engine.slab_attention(query, k_new, v_new, layer.keys, layer.values, o.pos, scale), None
     packed = getattr(key, "_glb_packed", None)
     if packed is not None:
@@ -145,12 +174,16 @@ class _SlabLayer(CacheLayerMixin):
         o = self.owner
         if key_states.shape[0] != o.n or key_states.shape[-2] != 1:
             raise ValueError("SlabKV takes one new token for every particle per forward")
-        if o.fused_attention:  # glb_slab_attention appends: it gets the new K / V where the projection left them
-            self._new_k, self._new_v = key_states, value_states
-            self.keys._glb_layer = self  # (how the attention entry finds this layer: no module-level state)
-            return self.keys, self.values
+        if o.fused_attention:
+            return self._stash(key_states, value_states)
         o.engine.kv_append(self.keys, key_states, o.pos)
         o.engine.kv_append(self.values, value_states, o.pos)
+        return self.keys, self.values
+
+    def _stash(self, key_states, value_states):
+        """A fused forward: the attention kernel appends, and gets the new K / V where the projection left them."""
+        self._new_k, self._new_v = key_states, value_states
+        self.keys._glb_layer = self  # (how the attention entry finds this layer: no module-level state)
         return self.keys, self.values
 
     def get_mask_sizes(self, query_length):
@@ -232,9 +265,7 @@ class _SharedLayer(_SlabLayer):
             if key_states.shape[0] != o.n or key_states.shape[-2] != 1:
                 raise ValueError("an in-place forward takes one token for every slab row")
             if o.fused_attention:
-                self._new_k, self._new_v = key_states, value_states
-                self.keys._glb_layer = self
-                return self.keys, self.values
+                return self._stash(key_states, value_states)
             eng.kv_append(self.keys, key_states, o.pos)
             eng.kv_append(self.values, value_states, o.pos)
             return self.keys, self.values
@@ -244,9 +275,7 @@ class _SharedLayer(_SlabLayer):
             if key_states.shape[0] != U:
                 raise ValueError("a chunk forward takes the rows SharedSlabKV.set_forward_chunk named")
             if o.fused_attention:  # glb_slab_attention_chunk appends and reads the rows where they lie
-                self._new_k, self._new_v = key_states, value_states
-                self.keys._glb_layer = self
-                return self.keys, self.values
+                return self._stash(key_states, value_states)
             for t in range(T):  # (a position of -1 appends nothing: the padding behind a row's last new token)
                 at = torch.where(o.n_new > t, o.pos + t, torch.full_like(o.pos, -1))
                 for slab, stage, new in ((self.keys, self.stage_keys, key_states), (self.values, self.stage_values, value_states)):
@@ -366,15 +395,9 @@ class SlabForward:
         self._watched_version = self._weights_version()
         # glb_slab_attention instead of two appends + a mask + a dense SDPA call per layer: for models whose attention
         # goes through transformers' attention interface with plain softmax(q k^T * scale) v semantics on a HIP device
-        cfg = getattr(body, "config", None)
-        k0 = pkv.layers[0].keys if pkv.layers and getattr(pkv.layers[0], "is_initialized", False) else None
         # (the body is AsyncAmdLM's shadow of the model, already pointed at the "glb" attention entry when glb_attention is on;
         # a body that is not - the caller's own model, glb_attention=False - keeps appends + mask + SDPA)
-        self.fused = bool(fused_attention and cfg is not None and k0 is not None and k0.is_cuda
-                          and hasattr(pkv.engine, "slab_attention")
-                          and pkv.engine.slab_attention_supports(k0.dtype, k0.shape[-1])
-                          and getattr(cfg, "_attn_implementation", None) == _ATTN_NAME
-                          and getattr(cfg, "_glb_engine", None) is pkv.engine)
+        self.fused = bool(fused_attention) and _kernel_serves(pkv.engine, "slab_attention", pkv, body)
 
     def _weights_version(self):
         return sum(t._version for t in self._watched)
@@ -383,18 +406,8 @@ class SlabForward:
         pkv = self.pkv
         pkv.set_forward_in_place(pos)
         if self.fused:
-            pkv.fused_attention = True
-            try:  # (no mask: the kernel attends to positions 0 .. pos[r] and nothing else)
-                out = self.body(input_ids=ids, position_ids=pos.view(-1, 1).long(), attention_mask=None,
-                                past_key_values=pkv, use_cache=True)
-            finally:
-                pkv.fused_attention = False
-                stale = [i for i, ly in enumerate(pkv.layers) if ly._new_k is not None]
-                for i in stale:
-                    pkv.layers[i]._new_k = pkv.layers[i]._new_v = None
-            if stale:  # an attention module that bypassed the attention interface: its token was never appended
-                raise RuntimeError(f"glb_slab_attention was not reached in layers {stale}: the new token's K / V were not "
-                                   "appended - run this model with SlabForward(fused_attention=False)")
+            out = _fused_forward(pkv, self.body, "glb_slab_attention", "the new token's K / V were not appended - run this model "
+                                 "with SlabForward(fused_attention=False)", input_ids=ids, position_ids=pos.view(-1, 1).long())
             return out.last_hidden_state[:, 0]
         out = self.body(input_ids=ids, position_ids=pos.view(-1, 1).long(), attention_mask=pkv.attention_mask(pos),
                         past_key_values=pkv, use_cache=True)
@@ -481,12 +494,7 @@ class SlabRunner:
     def _chunk_fused(self, t_max=1):
         """Whether a kernel of this library serves a chunk forward of up to t_max tokens per row over these slabs
         (SlabForward.fused's conditions): glb_slab_attention_chunk up to 16 tokens, glb_slab_attention_tile beyond."""
-        pkv, cfg, eng = self.pkv, getattr(self.llm._body, "config", None), self.llm.engine
-        k0 = pkv.layers[0].keys if pkv.layers and getattr(pkv.layers[0], "is_initialized", False) else None
-        name = "slab_attention_chunk" if t_max <= CHUNK_KERNEL_MAX else "slab_attention_tile"
-        return bool(cfg is not None and k0 is not None and k0.is_cuda and hasattr(eng, name)
-                    and getattr(eng, name + "_supports")(k0.dtype, k0.shape[-1])
-                    and getattr(cfg, "_attn_implementation", None) == _ATTN_NAME and getattr(cfg, "_glb_engine", None) is eng)
+        return _kernel_serves(self.llm.engine, _chunk_kernel(t_max), self.pkv, self.llm._body)
 
     def _run_chunk(self, plan, lo, hi, t_max, token_at, pad_id):
         """Forward rows lo .. hi - 1 of the plan, fed up to t_max tokens each (right-padded with pad_id) over the slab rows
@@ -506,17 +514,8 @@ class SlabRunner:
         pkv.set_forward_chunk(rows, pos, nn, fused)
         try:
             if fused:
-                pkv.fused_attention = True
-                try:  # (no mask: the kernel attends to positions 0 .. pos + t and nothing else)
-                    out = llm._body(input_ids=ids, position_ids=at, attention_mask=None, past_key_values=pkv, use_cache=True)
-                finally:
-                    pkv.fused_attention = False
-                    stale = [i for i, ly in enumerate(pkv.layers) if ly._new_k is not None]
-                    for i in stale:
-                        pkv.layers[i]._new_k = pkv.layers[i]._new_v = None
-                if stale:
-                    raise RuntimeError(f"glb_slab_attention_chunk was not reached in layers {stale}: the new tokens' K / V "
-                                       "were not appended")
+                out = _fused_forward(pkv, llm._body, "glb_slab_attention_chunk", "the new tokens' K / V were not appended",
+                                     input_ids=ids, position_ids=at)
             else:
                 impl = getattr(getattr(llm._body, "config", None), "_attn_implementation", None)
                 add = None if impl in ("sdpa", _ATTN_NAME) else pkv.layers[0].keys.dtype

@@ -1,8 +1,12 @@
 """glb_slab_attention_tile on the MI355X: the MFMA tile kernel against torch in float64, against the chunk
 kernel where both apply, and auto_kv_span end to end."""
+import ctypes as C
+
 import numpy as np
 import pytest
 import torch
+
+from genlm_backend_amd import _lib
 
 pytestmark = pytest.mark.gpu
 
@@ -151,3 +155,73 @@ def test_span_rows_match_a_backend_without_rows(engine):
     st = span._auto_kv.stats
     print("auto_kv_span=48 stats:", st)
     assert st["chunk_rows"] == 12 and st["chunk_tokens"] >= 20 * 12 and st["encoded_rows"] == 4
+
+
+@pytest.fixture(scope="module")
+def tiny(engine):
+    """The smallest valid call of the two chunk-shaped entries, as their C arguments by name (float32, two forward rows over
+    rows 2 and 0 of a three-row slab), and the tensors behind them."""
+    dev, n, R, H, Hkv, cap, Dh, T = engine.device, 2, 3, 2, 1, 8, 64, 2
+    g = torch.Generator(device=dev)
+    g.manual_seed(11)
+    t = {name: torch.randn(shape, device=dev, generator=g) for name, shape in
+         (("k_slab", (R, Hkv, cap, Dh)), ("v_slab", (R, Hkv, cap, Dh)), ("q", (n, H, T, Dh)), ("k_new", (n, Hkv, T, Dh)),
+          ("v_new", (n, Hkv, T, Dh)))}
+    t["pos"] = torch.tensor([3, 0], dtype=torch.int32, device=dev)
+    t["n_new"] = torch.tensor([2, 1], dtype=torch.int32, device=dev)
+    t["row_of"] = torch.tensor([2, 0], dtype=torch.int32, device=dev)
+    t["out"] = torch.full((n, T, H, Dh), 7.0, device=dev)
+    args = {name: C.c_void_p(x.data_ptr()) for name, x in t.items()}
+    for name in ("q", "k_new", "v_new"):
+        args[name[0] + "_strides"] = (C.c_int64 * 3)(*t[name].stride()[:3])
+    args.update(n_rows=n, n_slab_rows=R, heads=H, kv_heads=Hkv, cap=cap, head_dim=Dh, max_new=T, scale=Dh ** -0.5, dtype=_lib.F32,
+                stream=engine._stream())
+    return args, t
+
+
+_ARG_ORDER = ("q", "q_strides", "k_new", "k_strides", "v_new", "v_strides", "k_slab", "v_slab", "pos", "n_new", "row_of", "n_rows",
+              "n_slab_rows", "heads", "kv_heads", "cap", "head_dim", "max_new", "scale", "dtype", "out", "stream")
+
+
+@pytest.mark.parametrize("entry,limit,built", [("glb_slab_attention_chunk", _lib.KV_CHUNK_MAX, "16, 32, 64 and 128"),
+                                               ("glb_slab_attention_tile", _lib.KV_TILE_MAX, "64 and 128")], ids=["chunk", "tile"])
+def test_bad_arguments_are_refused_before_any_launch(engine, tiny, entry, limit, built):
+    args, t = tiny
+    call = lambda **change: getattr(engine.lib, entry)(*({**args, **change}[name] for name in _ARG_ORDER))
+    before = {name: x.clone() for name, x in t.items()}
+    cases = [(dict(dtype=7), _lib.GLB_EINVAL, "bad dtype 7"),  # (the one message without the entry's name)
+             (dict(max_new=0), _lib.GLB_EINVAL, f"{entry}: 0 query positions per row (1 .. {limit})"),
+             (dict(max_new=limit + 1), _lib.GLB_EINVAL, f"{entry}: {limit + 1} query positions per row (1 .. {limit})"),
+             (dict(kv_heads=3), _lib.GLB_EINVAL, f"{entry}: bad sizes"),  # heads = 2 is no multiple of it
+             (dict(head_dim=48), _lib.GLB_EUNSUPPORTED, f"{entry}: head_dim 48 ({built} are built)"),
+             (dict(q=C.c_void_p(t["q"].data_ptr() + 4)), _lib.GLB_EINVAL, f"{entry}: pointers and strides must be 16-byte aligned"),
+             (dict(q_strides=(C.c_int64 * 3)(t["q"].stride(0), t["q"].stride(1), 3)), _lib.GLB_EINVAL,
+              f"{entry}: pointers and strides must be 16-byte aligned"),
+             (dict(pos=None), _lib.GLB_EINVAL, f"{entry}: null pointer")]
+    if entry == "glb_slab_attention_tile":
+        cases.append((dict(head_dim=32), _lib.GLB_EUNSUPPORTED, f"{entry}: head_dim 32 ({built} are built)"))
+    for change, code, message in cases:
+        assert call(**change) == code != 0 and _lib.last_error() == message, (change, _lib.last_error())
+    torch.cuda.synchronize()
+    for name, x in t.items():  # nothing was enqueued: the output keeps its fill, the slabs their values
+        assert torch.equal(x, before[name]), name
+    # ... and the same tensors, unchanged, are served: torch's SDPA in float64 on the rows after the append
+    assert call() == _lib.GLB_OK
+    torch.cuda.synchronize()
+    rows, pos, nn, T, cap = t["row_of"].long(), t["pos"], t["n_new"], t["q"].shape[2], t["k_slab"].shape[2]
+    k_ref, v_ref = before["k_slab"].clone(), before["v_slab"].clone()
+    for r in range(2):
+        p, c = int(pos[r]), int(nn[r])
+        k_ref[rows[r], :, p:p + c], v_ref[rows[r], :, p:p + c] = t["k_new"][r, :, :c], t["v_new"][r, :, :c]
+    assert torch.equal(t["k_slab"], k_ref) and torch.equal(t["v_slab"], v_ref)
+    last = pos[:, None] + torch.arange(T, device=pos.device)[None, :]
+    see = (torch.arange(cap, device=pos.device)[None, None, None, :] <= last[:, None, :, None])
+    G = t["q"].shape[1] // k_ref.shape[1]
+    ref = torch.nn.functional.scaled_dot_product_attention(
+        t["q"].double(), k_ref[rows].double().repeat_interleave(G, dim=1), v_ref[rows].double().repeat_interleave(G, dim=1),
+        attn_mask=see, scale=args["scale"]).transpose(1, 2)
+    valid = torch.arange(T, device=pos.device)[None, :] < nn[:, None]
+    err = (t["out"].double() - ref)[valid].abs().max().item()
+    print(f"{entry}: max |out - float64| = {err:.3e} (bound {TOL[torch.float32]})")
+    assert err < TOL[torch.float32] and not t["out"][~valid].any()
+    t["k_slab"].copy_(before["k_slab"]), t["v_slab"].copy_(before["v_slab"]), t["out"].copy_(before["out"])  # (for the other entry)
