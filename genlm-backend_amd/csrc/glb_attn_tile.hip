@@ -37,45 +37,14 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <type_traits>
 
 #include "../../include/glb.h"
 #include "glb_attn.hpp"
 #include "glb_attn_host.hpp"
+#include "glb_attn_mfma.hpp"
 #include "glb_common.hpp"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-
-constexpr int KT = 32;          // key positions of a tile
-constexpr int THREADS = 256;    // 4 waves
-constexpr int QROWS = 64;       // query rows of a block: one 16-row fragment per wave
-
-template <int DT, int DH>
-struct TileShape {
-  static constexpr bool F32 = DT == GLB_F32;
-  static constexpr int ES = F32 ? 4 : 2, EPV = 16 / ES;  // element size; elements of a 16-byte vector
-  static constexpr int VPR = DH / EPV;                   // vectors of a key's row
-  static constexpr int KPITCH = DH * ES + 16;            // bytes of a K row in LDS (float32: of a V row too)
-  static constexpr int VTPITCH = KT * 2 + 16;            // bytes of a row of V^T [dim][key] (16-bit types)
-  static constexpr int K_BYTES = KT * KPITCH, V_BYTES = F32 ? KT * KPITCH : DH * VTPITCH;
-  static constexpr int NQ = F32 ? DH / 16 : DH / 32;     // Q operand vectors of a lane
-  static constexpr int NK = KT * VPR / THREADS;          // K vectors a thread moves per tile (float32: V vectors too)
-  static constexpr int NV = F32 ? NK : 2;                // 16-bit V: two keys of one 8-dim chunk
-  static_assert(NK >= 1 && NK * THREADS == KT * VPR && (F32 || (KT / 2) * VPR <= THREADS), "a tile must deal out evenly");
-};
-
-template <int DT>
-__device__ __forceinline__ f32x4 mfma16(u32x4 a, u32x4 b, f32x4 c) {
-  if constexpr (DT == GLB_BF16)
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
 
 struct TileArgs {
   const char *q, *k_new, *v_new;
@@ -86,23 +55,11 @@ struct TileArgs {
   float scale;
 };
 
-// four consecutive output dims of one query
-template <int DT>
-__device__ __forceinline__ void store4(char *p, const float (&x)[4]) {
-  if constexpr (DT == GLB_F32) {
-    *reinterpret_cast<f32x4 *>(p) = f32x4{x[0], x[1], x[2], x[3]};
-  } else {
-    const float y[8] = {x[0], x[1], x[2], x[3], 0.0f, 0.0f, 0.0f, 0.0f};
-    const u32x4 w = pack16v<DT>(y);
-    *reinterpret_cast<u32x2 *>(p) = u32x2{w.x, w.y};
-  }
-}
-
 template <int DT, int DH>
 __global__ __launch_bounds__(THREADS) void slab_attention_tile_kernel(const TileArgs a) {
   using S = TileShape<DT, DH>;
   constexpr bool F32 = S::F32;
-  constexpr int ES = S::ES, VPR = S::VPR, KPITCH = S::KPITCH, VTPITCH = S::VTPITCH, NQ = S::NQ, NK = S::NK, NV = S::NV, ND = DH / 16;
+  constexpr int ES = S::ES, VPR = S::VPR, NQ = S::NQ, NK = S::NK, NV = S::NV, ND = S::ND;
   __shared__ __attribute__((aligned(16))) char k_lds[S::K_BYTES];
   __shared__ __attribute__((aligned(16))) char v_lds[S::V_BYTES];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 15, quad = lane >> 4;
@@ -159,9 +116,7 @@ __global__ __launch_bounds__(THREADS) void slab_attention_tile_kernel(const Tile
     if (append && p < kend) *reinterpret_cast<u32x4 *>(slab + ((slab_row + p) * DH) * ES + ch * 16) = v;
     return v;
   };
-  // 16-bit V: thread x < 16 VPR moves chunk x % VPR of the keys in operand slots 2 j, 2 j + 1 (j = x / VPR)
-  const int vj = tid / VPR, vch = tid - vj * VPR;
-  const int vkey = 16 * ((2 * vj & 7) >> 2) + 4 * (vj >> 2) + (2 * vj & 3);  // the key in slot 2 j; slot 2 j + 1 holds the next
+  const int vkey = S::v_key(tid), vch = tid % VPR;  // 16-bit V: this thread's two keys of a tile and its chunk of them
   u32x4 kreg[NK], vreg[NV];
   const auto load_tile = [&](int tile0) {
 #pragma unroll
@@ -177,25 +132,6 @@ __global__ __launch_bounds__(THREADS) void slab_attention_tile_kernel(const Tile
       }
     }
   };
-  const auto store_tile = [&]() {
-#pragma unroll
-    for (int i = 0; i < NK; ++i) {
-      const int x = tid + i * THREADS, key = x / VPR, ch = x - key * VPR;
-      *reinterpret_cast<u32x4 *>(k_lds + key * KPITCH + ch * 16) = kreg[i];
-      if constexpr (F32) *reinterpret_cast<u32x4 *>(v_lds + key * KPITCH + ch * 16) = vreg[i];
-    }
-    if constexpr (!F32) {
-      if (tid < (KT / 2) * VPR) {
-        const uint32_t lo[4] = {vreg[0].x, vreg[0].y, vreg[0].z, vreg[0].w}, hi[4] = {vreg[1].x, vreg[1].y, vreg[1].z, vreg[1].w};
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {  // dim 8 ch + e of both keys as one word
-          const uint32_t x0 = (lo[e >> 1] >> (16 * (e & 1))) & 0xffffu, x1 = (hi[e >> 1] >> (16 * (e & 1))) & 0xffffu;
-          *reinterpret_cast<uint32_t *>(v_lds + (vch * 8 + e) * VTPITCH + vj * 4) = x0 | (x1 << 16);
-        }
-      }
-    }
-  };
-
   float m = -__builtin_huge_valf(), l = 0.0f;  // the lane's query: running maximum (the same in its four lanes); the lane's share of the sum
   f32x4 o[ND];
 #pragma unroll
@@ -205,29 +141,13 @@ __global__ __launch_bounds__(THREADS) void slab_attention_tile_kernel(const Tile
   for (int tile = 0; tile < n_tiles; ++tile) {
     const int tile0 = tile * KT;
     __syncthreads();  // every wave is done with the tile before
-    store_tile();
+    stage_tile<DT, DH>(k_lds, v_lds, kreg, vreg, tid);
     __syncthreads();
     if (tile + 1 < n_tiles) load_tile(tile0 + KT);  // travels while this tile is worked on
     if (tile0 > pos + t_hi) continue;               // (wave-uniform) wholly behind the fragment; tile 0 never is
     // ---- S^T = K . Q^T: s[half][v] = score of key tile0 + 16 half + 4 quad + v for this lane's query
     f32x4 s[2];
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {
-      s[half] = f32x4{0.f, 0.f, 0.f, 0.f};
-      const char *kp = k_lds + (16 * half + col) * KPITCH + quad * 16;
-#pragma unroll
-      for (int c = 0; c < NQ; ++c) {
-        const u32x4 kv = *reinterpret_cast<const u32x4 *>(kp + c * 64);
-        if constexpr (F32) {
-          const uint32_t kw[4] = {kv.x, kv.y, kv.z, kv.w}, qw[4] = {qv[c].x, qv[c].y, qv[c].z, qv[c].w};
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            s[half] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(kw[e]), __uint_as_float(qw[e]), s[half], 0, 0, 0);
-        } else {
-          s[half] = mfma16<DT>(kv, qv[c], s[half]);
-        }
-      }
-    }
+    tile_scores<DT, DH>(k_lds, qv, s, col, quad);
     // ---- online softmax on the accumulator layout
     const bool full = tile0 + KT - 1 <= pos + t_lo;  // (wave-uniform) every key of the tile is seen by every query of the fragment
     float p[8], tm = -__builtin_huge_valf();
@@ -253,20 +173,7 @@ __global__ __launch_bounds__(THREADS) void slab_attention_tile_kernel(const Tile
 #pragma unroll
     for (int dt = 0; dt < ND; ++dt) o[dt] *= c;
     // ---- O^T += V^T . P^T: o[dt][v] = dim 16 dt + 4 quad + v of this lane's query
-    if constexpr (F32) {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const char *vp = v_lds + (16 * (i >> 2) + 4 * quad + (i & 3)) * KPITCH + col * 4;
-#pragma unroll
-        for (int dt = 0; dt < ND; ++dt)
-          o[dt] = __builtin_amdgcn_mfma_f32_16x16x4f32(*reinterpret_cast<const float *>(vp + dt * 64), p[i], o[dt], 0, 0, 0);
-      }
-    } else {
-      const u32x4 pb = pack16v<DT>(p);  // slots 8 quad + 4 half + v: the order V^T is stored in
-#pragma unroll
-      for (int dt = 0; dt < ND; ++dt)
-        o[dt] = mfma16<DT>(*reinterpret_cast<const u32x4 *>(v_lds + (16 * dt + col) * VTPITCH + quad * 16), pb, o[dt]);
-    }
+    tile_pv<DT, DH>(v_lds, p, o, col, quad);
   }
   l += __shfl_xor(l, 16, 64);
   l += __shfl_xor(l, 32, 64);

@@ -1502,6 +1502,31 @@ class HipEngine:
                                            _DT[query.dtype], _ptr(out), self._stream()))
         return out
 
+    def batch_attention_tile(self, query, key, value, mask, scale):
+        """`short_attention` for contexts of any length (glb_batch_attention_tile: MFMA): the same argument
+        shapes - query [U, H, Lq, Dh], key / value [U, H_kv, Lk, Dh] (unit inner stride), mask: bool [U or 1, 1, Lq or 1, Lk]
+        (true = attend) or None (causal), 1 <= Lq <= Lk <= 65536 - and the same [U, Lq, H, Dh]; a query that sees no key gives
+        zeros.  float32 / bfloat16 / float16, head_dim 64 / 128 (`batch_attention_tile_supports`)."""
+        U, H, Lq, Dh = query.shape
+        Hkv, Lk = key.shape[1], key.shape[2]
+        assert query.stride(3) == 1 and key.stride(3) == 1 and value.stride(3) == 1 and key.dtype == value.dtype == query.dtype
+        assert key.shape == value.shape == (U, Hkv, Lk, Dh)
+        out = torch.empty((U, Lq, H, Dh), dtype=query.dtype, device=self.device)
+        i64x3 = C.c_int64 * 3
+        m_ptr, m_sr, m_sq = None, 0, 0
+        if mask is not None:
+            assert mask.dtype == torch.bool and mask.dim() == 4 and mask.shape[-1] == Lk and mask.stride(3) == 1 and mask.shape[1] == 1
+            assert mask.shape[0] in (1, U) and mask.shape[2] in (1, Lq)
+            m_ptr, m_sr, m_sq = _ptr(mask), (mask.stride(0) if mask.shape[0] > 1 else 0), (mask.stride(2) if mask.shape[2] > 1 else 0)
+        check(self.lib.glb_batch_attention_tile(_ptr(query), i64x3(*query.stride()[:3]), _ptr(key), i64x3(*key.stride()[:3]), _ptr(value),
+                                                i64x3(*value.stride()[:3]), m_ptr, m_sr, m_sq, U, H, Hkv, Lq, Lk, Dh, float(scale),
+                                                _DT[query.dtype], _ptr(out), self._stream()))
+        return out
+
+    @staticmethod
+    def batch_attention_tile_supports(dtype, head_dim):
+        return dtype in _DT and head_dim in (64, 128)
+
     def short_attention_packed(self, query, key, value, plan, max_keys, scale, err=None, out=None):
         """Attention of a row-packed batch whose contexts share their prompt's rows (glb_short_attention_packed).  query
         [M, H, Dh], key / value [M, H_kv, Dh] (unit inner stride: views of the projection output), plan int32 [S, 4] on the

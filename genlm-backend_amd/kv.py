@@ -31,8 +31,11 @@ from transformers.cache_utils import Cache, CacheLayerMixin, DynamicCache
 # one-token forward over KV slab rows (glb_slab_attention: append fused, no mask tensor) and the padded batches of short
 # contexts (glb_short_attention: a dozen tokens per row, where the library SDPA kernels spend a fifth of the step) - and
 # everything else (long sequences, dropout, training / autograd, exotic masks, CPU runs) goes to transformers' own SDPA
-# path exactly as before.  No module-level state: the engine rides on the shadow configuration (`_glb_engine`), the slab
-# layer of a running in-place forward on the key tensor `Cache.update` returned (`_glb_layer`).
+# path exactly as before - except that a backend made with long_attention=True (`_glb_long_attention` on the shadow
+# configuration) sends the padded batches past the short kernel's range to glb_batch_attention_tile (MFMA; float32 / bfloat16 /
+# float16, head_dim 64 / 128) under every other condition of the short path.  No module-level state: the
+# engine rides on the shadow configuration (`_glb_engine`), the slab layer of a running in-place forward on the key tensor
+# `Cache.update` returned (`_glb_layer`).
 _ATTN_NAME = "glb"
 SHORT_ATTENTION_MAX = 4096  # q_len * k_len up to which glb_short_attention is used
 CHUNK_KERNEL_MAX = 16  # tokens per row of a chunk forward glb_slab_attention_chunk takes; more: glb_slab_attention_tile
@@ -107,8 +110,12 @@ def _glb_attention_forward(module, query, key, value, attention_mask, dropout=0.
     Lq, Lk = query.shape[2], key.shape[2]
     # the kernels write into fresh tensors outside autograd: a forward that may be differentiated keeps the SDPA path
     wants_grad = torch.is_grad_enabled() and (query.requires_grad or key.requires_grad or value.requires_grad)
+    short = Lq * Lk <= SHORT_ATTENTION_MAX
+    # past the short kernel's range: the MFMA tile kernel where the backend asked for it (long_attention) and it is built
+    long_ok = (not short and eng is not None and getattr(module.config, "_glb_long_attention", False)
+               and hasattr(eng, "batch_attention_tile") and eng.batch_attention_tile_supports(query.dtype, query.shape[-1]))
     if (eng is not None and query.is_cuda and not dropout and not wants_grad and not getattr(module, "training", False)
-            and Lq * Lk <= SHORT_ATTENTION_MAX and Lk >= Lq
+            and (short or long_ok) and Lk >= Lq
             and eng.slab_attention_supports(query.dtype, query.shape[-1]) and key.dtype == query.dtype == value.dtype
             and query.stride(3) == 1 and key.stride(3) == 1 and value.stride(3) == 1
             and kwargs.get("is_causal", True) is not False and not kwargs.get("softcap") and not kwargs.get("sliding_window")
@@ -119,7 +126,8 @@ def _glb_attention_forward(module, query, key, value, attention_mask, dropout=0.
             and all((st * query.element_size()) % 16 == 0 for t in (query, key, value) for st in t.stride()[:3])
             and all(t.data_ptr() % 16 == 0 for t in (query, key, value))):
         scale = scaling if scaling is not None else query.shape[-1] ** -0.5
-        return eng.short_attention(query, key, value, attention_mask, scale), None
+        attend = eng.short_attention if short else eng.batch_attention_tile
+        return attend(query, key, value, attention_mask, scale), None
     return sdpa_attention_forward(module, query, key, value, attention_mask, dropout=dropout, scaling=scaling, **kwargs)
 
 
@@ -132,12 +140,13 @@ def _register_attention():
         ALL_MASK_ATTENTION_FUNCTIONS.register(_ATTN_NAME, ALL_MASK_ATTENTION_FUNCTIONS["sdpa"])
 
 
-def use_glb_attention(shadow, engine):
+def use_glb_attention(shadow, engine, long_attention=False):
     """Point a SHADOW of a transformers model (fuse.shadow_model: its configuration is a private copy) whose attention goes
-    through the attention interface as "sdpa" at this library's attention kernels; returns whether it was done."""
+    through the attention interface as "sdpa" at this library's attention kernels; returns whether it was done.
+    long_attention: padded batches past SHORT_ATTENTION_MAX go to glb_batch_attention_tile instead of SDPA."""
     cfg = getattr(shadow, "config", None)
     if cfg is not None and getattr(cfg, "_attn_implementation", None) == _ATTN_NAME:
-        return getattr(cfg, "_glb_engine", None) is engine
+        return getattr(cfg, "_glb_engine", None) is engine and bool(getattr(cfg, "_glb_long_attention", False)) == bool(long_attention)
     if (cfg is None or not hasattr(engine, "short_attention") or getattr(cfg, "_attn_implementation", None) != "sdpa"
             or getattr(cfg, "attn_logit_softcapping", None) or getattr(cfg, "sliding_window", None)
             or getattr(cfg, "scale_attn_by_inverse_layer_idx", False)):
@@ -145,6 +154,7 @@ def use_glb_attention(shadow, engine):
     _register_attention()
     cfg._attn_implementation = _ATTN_NAME
     cfg._glb_engine = engine
+    cfg._glb_long_attention = bool(long_attention)
     return True
 
 

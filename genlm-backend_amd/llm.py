@@ -272,7 +272,7 @@ class AsyncAmdLM(AsyncLM):
     def __init__(self, hf_model, hf_tokenizer, batch_size=20, timeout=0.02, engine=None, fuse_activations=True,
                  kv_budget_bytes=8 << 30, logprob_budget_bytes=16 << 30, auto_kv_rows=0, auto_kv_cap=64,
                  auto_kv_chunk=1, auto_kv_span=None, logprob_dtype="float32", glb_attention=True, merge_mlp=True, contract=None, gemms="library",
-                 split_gemms=True, w4_gemm="auto", score_chunk_bytes=1 << 30):
+                 split_gemms=True, w4_gemm="auto", score_chunk_bytes=1 << 30, long_attention=False):
         """The caller's `hf_model` is never modified (hf.py:114-140 leaves it alone too): with `fuse_activations` or
         `glb_attention` the forwards of this backend run on a private SHADOW of its module tree that shares every weight
         (fuse.shadow_model); `self.model` stays the caller's object.
@@ -283,6 +283,11 @@ class AsyncAmdLM(AsyncLM):
         shadow's attention goes through this library's kernels where they apply (padded
         batches of short contexts: glb_short_attention; the in-place one-token forward over KV rows: glb_slab_attention),
         everything else still runs the SDPA path.  Both False: the forwards run on `hf_model` itself.
+        long_attention (needs glb_attention; default False: no path changes): padded batches PAST glb_short_attention's range
+        (q_len * k_len > 4096, contexts of more than about 64 tokens: prompt forwards, re-encoding with or without cached
+        prefixes, whole-sequence scoring) run glb_batch_attention_tile (MFMA; float32 / bfloat16 / float16, head_dim 64 / 128;
+        DESIGN.md §35 has where it was measured ahead of SDPA with the mask and where behind) under every other condition
+        of the short path; other shapes and a backend without the kernel: SDPA as before.
         logprob_dtype: "float32" (default: every row `next_token_logprobs` returns is float32, whatever the checkpoint's
         dtype) or "model" - rows in the model's own dtype, what the reference returns (cache.py:96 keeps the dtype; for a
         bfloat16 checkpoint a third fewer bytes per materialised row: glb_log_softmax_rows' out_dtype).
@@ -319,6 +324,10 @@ class AsyncAmdLM(AsyncLM):
         if score_chunk_bytes <= 0:
             raise ValueError(f"score_chunk_bytes must be positive, got {score_chunk_bytes!r}")
         self.score_chunk_bytes = min(int(score_chunk_bytes), int(logprob_budget_bytes))
+        if not isinstance(long_attention, bool):
+            raise ValueError(f"long_attention must be True or False, got {long_attention!r}")
+        if long_attention and not glb_attention:
+            raise ValueError("long_attention needs glb_attention: the kernel is reached through this library's attention entry")
         self.model = hf_model
         self.tokenizer = hf_tokenizer
         self.device = hf_model.device
@@ -356,6 +365,7 @@ class AsyncAmdLM(AsyncLM):
         self.timer = None
         self.model.eval()
         self.glb_attention = False
+        self.long_attention = long_attention  # (in force where glb_attention is: a HIP device and a model the entry serves)
         self.fused = []
         self._net = self.model  # what this backend's forwards run on: the caller's model, or its shadow
         want_attention = bool(glb_attention) and self.device.type == "cuda"
@@ -369,7 +379,7 @@ class AsyncAmdLM(AsyncLM):
             if want_attention:
                 from .kv import use_glb_attention
 
-                self.glb_attention = use_glb_attention(self._net, self.engine)
+                self.glb_attention = use_glb_attention(self._net, self.engine, long_attention=long_attention)
         from .quant import bind as _bind_w4
 
         _bind_w4(self._net, self.engine, w4_gemm)

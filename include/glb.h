@@ -508,6 +508,30 @@ int glb_short_attention(const void *q, const int64_t q_strides[3], const void *k
                         float scale, int32_t dtype, void *out, void *hip_stream);
 
 /*
+ * glb_batch_attention_tile: glb_short_attention's contract without its bound on q_len * k_len - the padded
+ *   batches of LONG contexts: prompts, encode_ragged with or without cached prefixes in front of the keys, whole-sequence
+ *   scoring.  The same arguments: q / k / v by element strides {row, head, position} with unit inner stride, read where the
+ *   projection (or a gathered prefix) left them; mask bool / uint8 [n_rows, q_len, k_len] by byte strides (row, query), unit
+ *   key stride, nonzero = attend, a stride of 0 broadcasts that axis - any mask: right padding, left padding, a hole in the
+ *   key axis - or null: causal, key s <= t + k_len - q_len.  out [n_rows, q_len, heads, head_dim] contiguous; a query that
+ *   sees no key gives zeros.  Nothing but `out` is written; no atomics, no workspace, no allocation: fit for a captured graph.
+ *   One workgroup per (row, KV head, 64 query rows, t-major) scans the mask rows of its queries for the first and last key
+ *   any of them sees, brings the K / V tiles of that range on chip once and runs both products on MFMA
+ *   (v_mfma_f32_16x16x32_{bf16,f16}; float32 on v_mfma_f32_16x16x4f32, inputs unrounded), softmax in float32; for the 16-bit
+ *   types the probabilities are rounded to the element type as the second product's operand.  Not glb_short_attention's
+ *   bits: this kernel sums in MFMA order.
+ *   float32 / bfloat16 / float16; head_dim 64 / 128 (GLB_EUNSUPPORTED otherwise); any heads / kv_heads;
+ *   1 <= q_len <= k_len <= GLB_BATCH_ATTENTION_MAX_KEYS; n_rows * kv_heads * ceil(q_len * heads / kv_heads / 64) below 2^31;
+ *   pointers and strides of q / k / v / out multiples of 16 bytes - the mask pointer and its strides need no alignment
+ *   (strides >= 0).  GLB_EINVAL otherwise, nothing launched.
+ */
+#define GLB_BATCH_ATTENTION_MAX_KEYS 65536
+int glb_batch_attention_tile(const void *q, const int64_t q_strides[3], const void *k, const int64_t k_strides[3], const void *v,
+                             const int64_t v_strides[3], const uint8_t *mask, int64_t mask_stride_row, int64_t mask_stride_query,
+                             int64_t n_rows, int64_t heads, int64_t kv_heads, int64_t q_len, int64_t k_len, int64_t head_dim,
+                             float scale, int32_t dtype, void *out, void *hip_stream);
+
+/*
  * The same attention over a ROW-PACKED batch whose contexts share the rows of their prompt: q / k / v are
  * [n_rows, heads, head_dim] views by element strides {row, head} with unit inner stride (one projection output, read where
  * it lies), plan [n_segments][4] int32 on the device: (pre_start, pre_len, tail_start, tail_len) per segment.  The tail_len
