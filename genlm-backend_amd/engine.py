@@ -1550,6 +1550,44 @@ class HipEngine:
                                                   _DT[query.dtype], _ptr(out), _ptr(err), self._stream()))
         return out
 
+    def packed_row_map(self, plan, n_rows, max_keys, err=None):
+        """The plan of a row-packed batch as one entry per packed row (glb_packed_row_map): int32 [n_rows, 4] =
+        (seg_start, pre_start, pre_len, named), made once per forward for `packed_attention_tile`.  plan int32 [S, 4] on the
+        device as for `short_attention_packed`; max_keys: the most keys of a segment, 1 .. 65536.  A segment that is not
+        followed leaves its rows unnamed and adds to `err` (int32 [1] device; default: `error_word()`)."""
+        assert plan.dtype == torch.int32 and plan.dim() == 2 and plan.shape[1] == 4 and plan.is_contiguous()
+        self._check_dev(plan)
+        err = self.error_word() if err is None else err
+        assert err.dtype == torch.int32 and err.device == self.device
+        row_map = torch.empty((int(n_rows), 4), dtype=torch.int32, device=self.device)
+        check(self.lib.glb_packed_row_map(_ptr(plan), plan.shape[0], int(n_rows), int(max_keys), _ptr(row_map), _ptr(err),
+                                          self._stream()))
+        return row_map
+
+    def packed_attention_tile(self, query, key, value, row_map, scale, out=None):
+        """`short_attention_packed` for contexts of any length (glb_packed_attention_tile: MFMA): query
+        [M, H, Dh], key / value [M, H_kv, Dh] (unit inner stride: views of the projection output), row_map int32 [M, 4] from
+        `packed_row_map`.  Returns [M, H, Dh] (`out`, contiguous, when given); rows the map does not name are left as they
+        were.  float32 / bfloat16 / float16, head_dim 64 / 128 (`packed_attention_tile_supports`); the tile kernels'
+        accuracy, not `short_attention_packed`'s bits."""
+        M, H, Dh = query.shape
+        Hkv = key.shape[1]
+        assert key.shape == value.shape == (M, Hkv, Dh) and key.dtype == value.dtype == query.dtype
+        assert query.stride(2) == 1 and key.stride(2) == 1 and value.stride(2) == 1
+        assert row_map.dtype == torch.int32 and row_map.shape == (M, 4) and row_map.is_contiguous()
+        self._check_dev(row_map)
+        if out is None:
+            out = torch.empty((M, H, Dh), dtype=query.dtype, device=self.device)
+        assert out.shape == (M, H, Dh) and out.dtype == query.dtype and out.device == self.device and out.is_contiguous()
+        check(self.lib.glb_packed_attention_tile(_ptr(query), query.stride(0), query.stride(1), _ptr(key), key.stride(0),
+                                                 key.stride(1), _ptr(value), value.stride(0), value.stride(1), _ptr(row_map), M, H,
+                                                 Hkv, Dh, float(scale), _DT[query.dtype], _ptr(out), self._stream()))
+        return out
+
+    @staticmethod
+    def packed_attention_tile_supports(dtype, head_dim):
+        return dtype in _DT and head_dim in (64, 128)
+
     def kv_gather_rows(self, srcs, dsts, src_row_of, len_of, srcs_stable=True):
         """dsts[t][i, h, p] = srcs[t][src_row_of[i], h, p] for p < len_of[i], for every tensor pair of the two lists
         (all [rows, heads, cap, head_dim], contiguous) in ONE launch through device pointer tables

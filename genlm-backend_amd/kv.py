@@ -102,8 +102,11 @@ def _glb_attention_forward(module, query, key, value, attention_mask, dropout=0.
         if query.shape[0] != 1 or key.shape[2] != query.shape[2] or query.shape[2] != packed.n_rows or value.shape != key.shape:
             raise RuntimeError("glb_short_attention_packed: the attention module changed the shape of the packed batch")
         scale = scaling if scaling is not None else query.shape[-1] ** -0.5
-        out = packed.engine.short_attention_packed(query[0].transpose(0, 1), key[0].transpose(0, 1), value[0].transpose(0, 1),
-                                                   packed.segments, packed.max_keys, scale)
+        q, k, v = query[0].transpose(0, 1), key[0].transpose(0, 1), value[0].transpose(0, 1)
+        if packed.row_map is not None:  # encode_packed(tile=True): contexts past 32 keys, the MFMA tile kernel
+            out = packed.engine.packed_attention_tile(q, k, v, packed.row_map, scale)
+        else:
+            out = packed.engine.short_attention_packed(q, k, v, packed.segments, packed.max_keys, scale)
         packed.served += 1
         return out.unsqueeze(0), None
     eng = getattr(getattr(module, "config", None), "_glb_engine", None)
@@ -677,6 +680,7 @@ def encode_ragged(llm, batch, sel, n_sel, l_max, pad_id=0, base=None, prefixes=N
 
 # ---- the row-packed encoding: every shared prompt once per forward ----------------------------------------
 PACKED_MAX_KEYS = 32  # glb_short_attention_packed: prompt + tail tokens of a context
+PACKED_TILE_MAX_KEYS = 65536  # glb_packed_attention_tile (encode_packed(tile=True))
 
 
 class PromptGroups:
@@ -748,10 +752,13 @@ class _PackedLayer(CacheLayerMixin):
 class PackedKV(Cache):
     """The side channel of one row-packed forward: a `Cache` that stores nothing (so transformers builds no mask and looks
     for no packed sequences in the position ids) and carries the plan to the "glb" attention entry on the key tensor.
-    `segments`: int32 [G + U, 4] device, `n_rows` = M, `max_keys` <= 32; `served` counts the layers that reached the kernel."""
+    `segments`: int32 [G + U, 4] device, `n_rows` = M, `max_keys` <= 32; `served` counts the layers that reached the kernel.
+    `row_map`: int32 [M, 4] (engine.packed_row_map, made once for all layers) sends the forward to glb_packed_attention_tile,
+    and `max_keys` may then go up to PACKED_TILE_MAX_KEYS."""
 
-    def __init__(self, engine, segments, n_rows, max_keys, n_layers):
+    def __init__(self, engine, segments, n_rows, max_keys, n_layers, row_map=None):
         self.engine, self.segments, self.n_rows, self.max_keys = engine, segments, int(n_rows), int(max_keys)
+        self.row_map = row_map
         self.served = 0
         layer = _PackedLayer(self)
         super().__init__(layers=[layer] * n_layers)
@@ -768,28 +775,32 @@ class PackedEncoding:
         return self.hidden[self.last]
 
 
-def packed_supported(llm):
+def packed_supported(llm, tile=False):
     """Whether `llm._body`'s attention is served by this library's short-context kernels (the shadow points at the "glb"
-    entry with the backend's engine, a head width the kernels are built for)."""
+    entry with the backend's engine, a head width the kernels are built for).  tile: and by glb_packed_attention_tile."""
     body, eng = llm._body, llm.engine
     cfg = getattr(body, "config", None)
     if cfg is None or getattr(cfg, "_attn_implementation", None) != _ATTN_NAME or getattr(cfg, "_glb_engine", None) is not eng:
         return False
     heads = getattr(cfg, "num_attention_heads", None)
     head_dim = getattr(cfg, "head_dim", None) or (cfg.hidden_size // heads if heads else None)
+    if tile and not (hasattr(eng, "packed_attention_tile") and eng.packed_attention_tile_supports(
+            next(body.parameters()).dtype, head_dim)):
+        return False
     return bool(head_dim in (16, 32, 64, 128) and getattr(cfg, "num_hidden_layers", 0) > 0)
 
 
-def _packed_plan_arrays(llm, batch, sel, n_sel, grp, groups, n_tail_rows, native_plan=True):
+def _packed_plan_arrays(llm, batch, sel, n_sel, grp, groups, n_tail_rows, native_plan=True, key_cap=PACKED_MAX_KEYS):
     """The plan of `encode_packed` on the device: (segments int32 [G + U, 4], ids int64 [M], pos int64 [M], last int64 [U], M).
     native_plan: glb_packed_plan, two launches; False, or an engine without `packed_plan`: the torch ops below, the
-    restatement the kernel is tested against (tests/test_packed_plan_native_gpu.py) - the same arrays for every input."""
+    restatement the kernel is tested against (tests/test_packed_plan_native_gpu.py) - the same arrays for every input.
+    key_cap: the most keys of a context the attention kernel serves - positions are clamped below it."""
     eng, dev = llm.engine, llm.device
     tokens, starts, lengths = batch
     G, n_pre = len(groups.lens), groups.n_rows
     M = n_pre + int(n_tail_rows)
     max_pos = getattr(llm._body.config, "max_position_embeddings", None) or (1 << 30)
-    pos_cap = min(PACKED_MAX_KEYS, max_pos)
+    pos_cap = min(key_cap, max_pos)
     native = getattr(eng, "packed_plan", None) if native_plan else None  # (None: an engine without the kernel)
     if native is not None:
         return native(batch, sel, n_sel, grp, groups, n_tail_rows, pos_cap) + (M,)
@@ -809,7 +820,7 @@ def _packed_plan_arrays(llm, batch, sel, n_sel, grp, groups, n_tail_rows, native
     return segments, ids, pos, (tail_start + tail - 1).long().clamp_(0, M - 1), M
 
 
-def encode_packed(llm, batch, sel, n_sel, grp, groups, n_tail_rows, max_keys=PACKED_MAX_KEYS, native_plan=True):
+def encode_packed(llm, batch, sel, n_sel, grp, groups, n_tail_rows, max_keys=PACKED_MAX_KEYS, native_plan=True, tile=False):
     """Encode contexts `sel` (int32 device, its first n_sel entries) of the ragged `batch` = (tokens, starts, lengths) in one
     ROW-PACKED forward of `llm._body`: context u is prompt `grp[u]` (int32 [n_sel] device) of `groups` (PromptGroups) plus a
     tail of t_u >= 1 tokens, and the batch is [1, M]: the G prompts once, then the tails in context order - M = sum P_g +
@@ -818,17 +829,24 @@ def encode_packed(llm, batch, sel, n_sel, grp, groups, n_tail_rows, max_keys=PAC
     changes no result; attention is glb_short_attention_packed through `PackedKV`.  max_keys: the most P + t of a context
     (<= 32).  Lengths that do not match n_tail_rows, a tail < 1 or a context longer than max_keys are refused row by row in
     the kernel (engine.error_word / raise_if_failed); every index used here is clamped into range first.  native_plan: the
-    plan's four arrays come from glb_packed_plan (`_packed_plan_arrays`); False keeps the torch ops."""
+    plan's four arrays come from glb_packed_plan (`_packed_plan_arrays`); False keeps the torch ops.
+    tile: attention is glb_packed_attention_tile (MFMA) and max_keys may go up to PACKED_TILE_MAX_KEYS and the
+    model's positions; the plan becomes a row map once, for every layer.  The tile kernel's accuracy, not the short one's bits."""
     eng = llm.engine
-    if not 1 <= max_keys <= PACKED_MAX_KEYS:
-        raise ValueError(f"encode_packed serves contexts of up to {PACKED_MAX_KEYS} tokens")
+    key_cap = PACKED_MAX_KEYS
+    if tile:
+        key_cap = min(PACKED_TILE_MAX_KEYS, getattr(llm._body.config, "max_position_embeddings", None) or PACKED_TILE_MAX_KEYS)
+    if not 1 <= max_keys <= key_cap:
+        raise ValueError(f"encode_packed serves contexts of up to {key_cap} tokens")
     if n_sel < 1 or n_tail_rows < n_sel:
         raise ValueError("encode_packed: every context feeds at least one tail row")
-    if not packed_supported(llm):
-        raise RuntimeError("encode_packed: this model's attention is not served by glb_short_attention")
-    segments, ids, pos, last, M = _packed_plan_arrays(llm, batch, sel, n_sel, grp, groups, n_tail_rows, native_plan)
+    if not packed_supported(llm, tile):
+        raise RuntimeError("encode_packed: this model's attention is not served by glb_short_attention"
+                           + (" and glb_packed_attention_tile" if tile else ""))
+    segments, ids, pos, last, M = _packed_plan_arrays(llm, batch, sel, n_sel, grp, groups, n_tail_rows, native_plan, key_cap)
     ids, pos = ids.view(1, M), pos.view(1, M)
-    pkv = PackedKV(eng, segments, M, max_keys, llm._body.config.num_hidden_layers)
+    row_map = eng.packed_row_map(segments, M, max_keys) if tile else None
+    pkv = PackedKV(eng, segments, M, max_keys, llm._body.config.num_hidden_layers, row_map)
     out = llm._body(input_ids=ids, position_ids=pos, attention_mask=None, past_key_values=pkv, use_cache=True)
     if pkv.served != len(pkv.layers):
         raise RuntimeError(f"glb_short_attention_packed served {pkv.served} of {len(pkv.layers)} layers: an attention module "

@@ -22,7 +22,8 @@ import torch
 from .cache import KVPrefix
 from .engine import check_truncation
 from .fuse import SplitConv1D, split_gemm_all_rows
-from .kv import PACKED_MAX_KEYS, PrefixTable, PromptGroups, SlabKV, SlabRunner, encode_packed, encode_ragged, packed_supported
+from .kv import (PACKED_MAX_KEYS, PACKED_TILE_MAX_KEYS, PrefixTable, PromptGroups, SlabKV, SlabRunner, encode_packed, encode_ragged,
+                 packed_supported)
 from ._lib import MASK_BITS, MASK_NONE
 from .masks import ParticleMasks
 
@@ -313,8 +314,12 @@ class DeviceSIS:
         self.particle_kv = bool(use_particle_kv)
         self.share_kv = bool(share_kv) and self.particle_kv
         # the row-packed re-encoding (kv.encode_packed): every distinct prompt's rows once per step instead of once per
-        # distinct context; `_packed_ready` says per step whether it applies
+        # distinct context; `_packed_ready` says per step whether it applies.  "tile": also past the short kernel's 32 keys,
+        # where attention is glb_packed_attention_tile (the tile kernel's accuracy, so it is asked for)
+        if not isinstance(share_prompt_rows, bool) and share_prompt_rows != "tile":
+            raise ValueError(f"share_prompt_rows must be True, False or 'tile', got {share_prompt_rows!r}")
         self.share_prompt_rows = bool(share_prompt_rows)
+        self._packed_tile = share_prompt_rows == "tile"
         self.packed_steps = 0
         self._groups = self._grp0 = None
         if self.share_prompt_rows and not use_prefix_kv and not use_particle_kv and not (self.collective and world > 1):
@@ -651,7 +656,7 @@ class DeviceSIS:
             # read-back), every projection on the split kernel so that a row keeps the bits it has in the padded batch
             with split_gemm_all_rows(eng):
                 enc = encode_packed(llm, (ctx_flat, self.starts, lengths_eff), rep, U, self._grp[rep[:U].long()],
-                                    self._groups, U * self.t, max_keys=l_max)
+                                    self._groups, U * self.t, max_keys=l_max, tile=l_max > PACKED_MAX_KEYS)
             self._fwd_tokens = enc.n_rows
             self.packed_steps += 1
         else:
@@ -669,14 +674,20 @@ class DeviceSIS:
         every context is its prompt plus exactly t >= 1 tokens, none a finished particle's stub -, a context fits the
         kernel's 32 keys, the body's attention is this library's, and the padded batch would have run every projection on
         the split kernel (U * l_max rows reach the largest threshold of the body's SplitConv1D modules; a body without
-        them keeps the padded path: its library GEMMs give a row no batch-independent bits)."""
-        if self._groups is None or self.t < 1 or n_active != self.N or l_max > PACKED_MAX_KEYS or self.prefixes is not None:
+        them keeps the padded path: its library GEMMs give a row no batch-independent bits).  share_prompt_rows="tile":
+        past 32 keys too, up to the tile kernel's bound and the model's positions, where that kernel serves the body."""
+        if self._groups is None or self.t < 1 or n_active != self.N or self.prefixes is not None:
             return False
         body = self.llm._body
         ent = self.__dict__.get("_packed_body")
         if ent is None or ent[0] is not body:  # (set_lora makes the backend's shadow anew)
             rows = [m.min_rows for m in body.modules() if isinstance(m, SplitConv1D)]
-            ent = self._packed_body = (body, max(rows) if rows and packed_supported(self.llm) else None)
+            tile_cap = 0
+            if self._packed_tile and packed_supported(self.llm, tile=True):
+                tile_cap = min(PACKED_TILE_MAX_KEYS, getattr(body.config, "max_position_embeddings", None) or PACKED_TILE_MAX_KEYS)
+            ent = self._packed_body = (body, max(rows) if rows and packed_supported(self.llm) else None, tile_cap)
+        if l_max > max(PACKED_MAX_KEYS, ent[2]):
+            return False
         return ent[1] is not None and U * l_max >= ent[1]
 
     def _parity_noise(self, group_of, V):

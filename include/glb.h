@@ -552,6 +552,33 @@ int glb_short_attention_packed(const void *q, int64_t q_stride_row, int64_t q_st
                                void *hip_stream);
 
 /*
+ * The row-packed attention without the bound of 32 keys: the plan of glb_short_attention_packed, served by
+ * an MFMA tile kernel whose work is split over packed rows, in two calls.
+ * glb_packed_row_map: once per forward, the plan as one int32x4 per packed row: (seg_start, pre_start, pre_len, named) -
+ *   row_map [n_rows][4] int32 on the device, 16-byte aligned as the plan.  Every row starts unnamed; a segment with
+ *   pre_len + tail_len > max_keys, tail_len < 1, pre_len < 0 or a range outside [0, n_rows) is never followed: its rows stay
+ *   unnamed and it adds 1 to *err_word.  max_keys outside 1 .. GLB_PACKED_ATTENTION_MAX_KEYS: GLB_EINVAL, nothing launched.
+ * glb_packed_attention_tile: q / k / v / out as for glb_short_attention_packed; query row `r` sees the rows pre_start ..
+ *   pre_start + pre_len - 1 and seg_start .. r of its map entry.  One workgroup per (64 query rows row-major over packed rows,
+ *   KV head): the tails of many contexts in one block; the shared rows of a prompt are walked once per block for every query
+ *   behind them (once per distinct range in a block), the own rows as a block-diagonal causal band; both products on MFMA
+ *   (v_mfma_f32_16x16x32_{bf16,f16}; float32 on v_mfma_f32_16x16x4f32, inputs unrounded), softmax in float32.  The tile
+ *   kernels' accuracy, not glb_short_attention_packed's bits.  The map is device data: an entry that fails
+ *   0 <= seg_start <= row, pre_start >= 0, pre_len >= 0 or pre_start + pre_len <= n_rows makes its row unnamed.  Rows
+ *   that are not named are not written.  Writes `out` only; no atomics, no workspace: fit for a captured graph.
+ *   float32 / bfloat16 / float16; head_dim 64 / 128 (GLB_EUNSUPPORTED otherwise); any heads / kv_heads; pointers and
+ *   strides (>= 0) of q / k / v / out and row_map multiples of 16 bytes; n_rows * heads / kv_heads + 64 and the grid below
+ *   2^31.  GLB_EINVAL otherwise, nothing launched.
+ */
+#define GLB_PACKED_ATTENTION_MAX_KEYS 65536
+int glb_packed_row_map(const int32_t *plan, int64_t n_segments, int64_t n_rows, int64_t max_keys, int32_t *row_map,
+                       uint32_t *err_word, void *hip_stream);
+int glb_packed_attention_tile(const void *q, int64_t q_stride_row, int64_t q_stride_head, const void *k, int64_t k_stride_row,
+                              int64_t k_stride_head, const void *v, int64_t v_stride_row, int64_t v_stride_head,
+                              const int32_t *row_map, int64_t n_rows, int64_t heads, int64_t kv_heads, int64_t head_dim,
+                              float scale, int32_t dtype, void *out, void *hip_stream);
+
+/*
  * Systematic resampling of the whole population from the all-gathered log-weights (the step the all-gather of
  * README.md:108-110's weights exists for; the reference itself stops at the normalised weights).  Exact integer
  * comb over the fixed-point weights of glb_normalize_weights with one Philox draw keyed by (seed, offset):
