@@ -275,6 +275,8 @@ class HipEngine:
             self.device = torch.device("cuda", torch.cuda.current_device())
         self.lib = _OnDevice(lib, self.device.index)
         self._ws = None
+        self._prefix_ws = None  # slab_attention_prefix's partials: grow-only, its own (a captured call keeps the address)
+        self._cus = None
         self._step_ws = None
         self._imp_ws = None
         self._trie_ws = None
@@ -1483,6 +1485,51 @@ class HipEngine:
     @staticmethod
     def slab_attention_supports(dtype, head_dim):
         return dtype in _DT and head_dim in (16, 32, 64, 128)
+
+    def slab_attention_prefix_splits(self, n_rows, heads, kv_heads, prefix_cap):
+        """The split count `slab_attention_prefix(splits=0)` runs with: the smallest S in 1 .. 8 whose grid of
+        ceil(n_rows * G / 64) * kv_heads * S workgroups reaches the device's CU count, at most ceil(prefix_cap / 32) - a
+        function of host-side shapes only, so a shape always gets the same bits."""
+        if self._cus is None:
+            self._cus = torch.cuda.get_device_properties(self.device).multi_processor_count
+        blocks = -(-(n_rows * (heads // kv_heads)) // 64) * kv_heads
+        s = 1
+        while s < 8 and blocks * s < self._cus:
+            s += 1
+        return max(1, min(s, -(-prefix_cap // 32)))
+
+    def slab_attention_prefix(self, query, k_new, v_new, k_slab, v_slab, pos, prefix_k, prefix_v, prefix_len, prefix_of, scale,
+                              splits=0):
+        """`slab_attention` over rows that stand behind a prompt stored once (glb_slab_attention_prefix):
+        prefix_k / prefix_v [U, H_kv, prefix_cap, Dh] contiguous, prefix_len int32 [U], prefix_of int32 [R] (-1: no prefix).  Row
+        r attends prefix_len[prefix_of[r]] prefix positions, its own slab positions below pos[r] and the new token, which is
+        appended at pos[r]; the slabs [R, H_kv, cap, Dh] hold the tails only.  splits: 1 .. 8 shares of a prefix's keys per
+        (64 query rows, KV head), 0: `slab_attention_prefix_splits`.  float32 / bfloat16 / float16, head_dim 64 / 128
+        (`slab_attention_prefix_supports`).  Returns [R, 1, H, Dh].  The workspace stays with the engine and only grows, so a
+        captured call keeps its address."""
+        R, H, _, Dh = query.shape
+        Hkv, cap = k_slab.shape[1], k_slab.shape[2]
+        U, pcap = prefix_k.shape[0], prefix_k.shape[2]
+        assert query.stride(3) == 1 and k_new.stride(3) == 1 and v_new.stride(3) == 1 and k_slab.is_contiguous() and v_slab.is_contiguous()
+        assert k_new.dtype == v_new.dtype == query.dtype == k_slab.dtype == prefix_k.dtype == prefix_v.dtype
+        assert prefix_k.shape == prefix_v.shape == (U, Hkv, pcap, Dh) and prefix_k.is_contiguous() and prefix_v.is_contiguous()
+        assert prefix_len.dtype == prefix_of.dtype == torch.int32 and prefix_len.numel() == U and prefix_of.numel() == R
+        self._check_dev(prefix_k, prefix_v, prefix_len, prefix_of)
+        S = int(splits) if splits else self.slab_attention_prefix_splits(R, H, Hkv, pcap)
+        need = self.lib.glb_slab_attention_prefix_workspace(R, H, Dh, S)
+        if self._prefix_ws is None or self._prefix_ws.numel() < need:
+            self._prefix_ws = torch.empty(max(need, 1 << 16), dtype=torch.uint8, device=self.device)
+        out = torch.empty((R, 1, H, Dh), dtype=query.dtype, device=self.device)
+        check(self.lib.glb_slab_attention_prefix(_ptr(query), query.stride(0), query.stride(1), _ptr(k_new), k_new.stride(0),
+                                                 k_new.stride(1), _ptr(v_new), v_new.stride(0), v_new.stride(1), _ptr(k_slab),
+                                                 _ptr(v_slab), _ptr(pos), R, H, Hkv, cap, Dh, float(scale), _DT[query.dtype],
+                                                 _ptr(out), _ptr(prefix_k), _ptr(prefix_v), _ptr(prefix_len), _ptr(prefix_of), U,
+                                                 pcap, S, _ptr(self._prefix_ws), self._prefix_ws.numel(), self._stream()))
+        return out
+
+    @staticmethod
+    def slab_attention_prefix_supports(dtype, head_dim):
+        return dtype in _DT and head_dim in (64, 128)
 
     def short_attention(self, query, key, value, mask, scale):
         """Masked attention of a padded batch of short contexts (glb_short_attention).  query [U, H, Lq, Dh], key / value

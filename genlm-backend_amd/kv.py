@@ -57,6 +57,21 @@ def _kernel_serves(engine, name, pkv, body):
                 and getattr(cfg, "_attn_implementation", None) == _ATTN_NAME and getattr(cfg, "_glb_engine", None) is engine)
 
 
+def prefix_kv_refusal(llm):
+    """Why KV rows behind a stored prompt (SlabKV.set_prefix) cannot serve `llm`, or None: what `_kernel_serves` will ask of
+    "slab_attention_prefix" once the slabs exist, asked of the model before there are any."""
+    body, eng = llm._body, llm.engine
+    cfg = getattr(body, "config", None)
+    if cfg is None or getattr(cfg, "_attn_implementation", None) != _ATTN_NAME or getattr(cfg, "_glb_engine", None) is not eng:
+        return "the model's attention does not go through this backend's fused attention entry (glb_attention)"
+    heads = getattr(cfg, "num_attention_heads", None)
+    head_dim = getattr(cfg, "head_dim", None) or (cfg.hidden_size // heads if heads else None)
+    dtype = next(body.parameters()).dtype
+    if not (hasattr(eng, "slab_attention_prefix") and eng.slab_attention_prefix_supports(dtype, head_dim)):
+        return f"glb_slab_attention_prefix is not built for {dtype}, head_dim {head_dim} (float32 / bfloat16 / float16, 64 / 128)"
+    return None
+
+
 def _fused_forward(pkv, body, entry, lost, **inputs):
     """One forward of `body` over `pkv` whose attention AND append are this library's kernel `entry` (no mask: the kernel
     attends to the positions a row holds and its new ones, nothing else).  Whatever happens, the slabs are left with the
@@ -94,6 +109,10 @@ def _glb_attention_forward(module, query, key, value, attention_mask, dropout=0.
         if chunk:
             attend = getattr(o.engine, _chunk_kernel(query.shape[2]))
             return attend(query, k_new, v_new, layer.keys, layer.values, o.pos, o.n_new, scale, rows=o.rows), None
+        if getattr(o, "prefix_layers", None) is not None:  # SlabKV.set_prefix: the rows stand behind prompts stored once
+            pk, pv = o.prefix_layers[layer.idx]
+            return o.engine.slab_attention_prefix(query, k_new, v_new, layer.keys, layer.values, o.pos, pk, pv, o.prefix_len,
+                                                  o.prefix_of, scale), None
         return o.engine.slab_attention(query, k_new, v_new, layer.keys, layer.values, o.pos, scale), None
     packed = getattr(key, "_glb_packed", None)
     if packed is not None:
@@ -217,6 +236,34 @@ class SlabKV(Cache):
         super().__init__(layers=[_SlabLayer(self, i) for i in range(n_layers)])
         self._alt = None
         self._ptrs = None
+        self.prefix_layers = self.prefix_len = self.prefix_of = None  # set_prefix: the rows hold what follows a shared prompt
+
+    def set_prefix(self, layers, prefix_len, prefix_of):
+        """The rows stand behind prompts stored ONCE.  layers: [(K, V)] per layer, each [U, kv_heads, l_max,
+        head_dim] contiguous and right-padded - `encode_ragged(..., keep_kv=True).kv_layers()` as it is; prefix_len int32 [U];
+        prefix_of int32 [n]: the prompt row i stands behind, -1: none.  The rows then hold only the tokens behind the prompt:
+        `pos` counts those, a fused one-token forward attends prompt, row and new token (glb_slab_attention_prefix) and
+        `SlabForward` feeds position_ids = prefix_len[prefix_of] + pos.  Fused forwards only.  Calling it again with the same
+        `layers` (a resampling step: prefix_of follows the ancestors) rewrites prefix_len / prefix_of in place, so a captured
+        forward stays valid."""
+        if len(layers) != len(self.layers):
+            raise ValueError(f"{len(layers)} prefix layers for {len(self.layers)} slab layers")
+        prefix_len, prefix_of = prefix_len.to(torch.int32), prefix_of.to(torch.int32)
+        if prefix_len.numel() != layers[0][0].shape[0] or prefix_of.numel() != self.n:
+            raise ValueError("prefix_len names every prefix, prefix_of every row")
+        if self.prefix_layers is layers and self.prefix_len.numel() == prefix_len.numel():
+            self.prefix_len.copy_(prefix_len)
+            self.prefix_of.copy_(prefix_of)
+        else:
+            self.prefix_layers, self.prefix_len, self.prefix_of = layers, prefix_len.clone(), prefix_of.clone()
+        self._alloc_like(layers)
+
+    def position_ids(self, pos):
+        """The positions the tokens fed at `pos` have in their contexts: behind the row's prefix, if it has one."""
+        if self.prefix_layers is None:
+            return pos
+        own = self.prefix_of >= 0
+        return pos + torch.where(own, self.prefix_len[self.prefix_of.clamp_min(0).long()], torch.zeros_like(pos))
 
     # ---- forward-side helpers ----------------------------------------------------------------------------------
     def set_forward_in_place(self, pos):
@@ -256,7 +303,8 @@ class SlabKV(Cache):
             layer.values, self._alt[2 * j + 1] = self._alt[2 * j + 1], layer.values
 
     def nbytes(self):
-        return sum(t.numel() * t.element_size() for t in self._tensors(self.layers) if t is not None) * (2 if self._alt else 1)
+        own = sum(t.numel() * t.element_size() for t in self._tensors(self.layers) if t is not None) * (2 if self._alt else 1)
+        return own + sum(t.numel() * t.element_size() for kv in self.prefix_layers or () for t in kv)
 
 
 class _SharedLayer(_SlabLayer):
@@ -411,6 +459,10 @@ class SlabForward:
         # (the body is AsyncAmdLM's shadow of the model, already pointed at the "glb" attention entry when glb_attention is on;
         # a body that is not - the caller's own model, glb_attention=False - keeps appends + mask + SDPA)
         self.fused = bool(fused_attention) and _kernel_serves(pkv.engine, "slab_attention", pkv, body)
+        if getattr(pkv, "prefix_layers", None) is not None and not (
+                self.fused and _kernel_serves(pkv.engine, "slab_attention_prefix", pkv, body)):
+            raise ValueError("rows behind a stored prefix (SlabKV.set_prefix) are served by the fused forward only: "
+                             "glb_slab_attention_prefix, float32 / bfloat16 / float16, head_dim 64 / 128, the glb attention entry")
 
     def _weights_version(self):
         return sum(t._version for t in self._watched)
@@ -419,8 +471,9 @@ class SlabForward:
         pkv = self.pkv
         pkv.set_forward_in_place(pos)
         if self.fused:
+            at = pkv.position_ids(pos) if getattr(pkv, "prefix_layers", None) is not None else pos
             out = _fused_forward(pkv, self.body, "glb_slab_attention", "the new token's K / V were not appended - run this model "
-                                 "with SlabForward(fused_attention=False)", input_ids=ids, position_ids=pos.view(-1, 1).long())
+                                 "with SlabForward(fused_attention=False)", input_ids=ids, position_ids=at.view(-1, 1).long())
             return out.last_hidden_state[:, 0]
         out = self.body(input_ids=ids, position_ids=pos.view(-1, 1).long(), attention_mask=pkv.attention_mask(pos),
                         past_key_values=pkv, use_cache=True)
@@ -444,6 +497,8 @@ class SlabForward:
         # a graph belongs to the slab tensors it was captured over: every layer's addresses, shape and dtype make the key,
         # and the entry holds the tensors, so the allocator cannot hand their addresses to another slab set meanwhile
         slabs = self.pkv._tensors(self.pkv.layers)
+        if getattr(self.pkv, "prefix_layers", None) is not None:  # and to the prefix store, its lengths and the rows' prefixes
+            slabs = slabs + [t for kv in self.pkv.prefix_layers for t in kv] + [self.pkv.prefix_len, self.pkv.prefix_of]
         key = tuple((t.data_ptr(), tuple(t.shape), t.dtype) for t in slabs)
         ent = self.graphs.get(key)
         if ent is None:
@@ -475,7 +530,8 @@ class SlabForward:
             finally:
                 if gc_was_on:
                     gc.enable()
-            ent = self.graphs[key] = (g, s_ids, s_pos, hidden, slabs)
+            # (the engine's grow-only scratch of the prefix kernel rides along: the captured launches keep its address)
+            ent = self.graphs[key] = (g, s_ids, s_pos, hidden, slabs + [getattr(self.pkv.engine, "_prefix_ws", None)])
         g, s_ids, s_pos, hidden, _held = ent
         s_ids.copy_(ids)
         s_pos.copy_(pos)

@@ -23,7 +23,7 @@ from .cache import KVPrefix
 from .engine import check_truncation
 from .fuse import SplitConv1D, split_gemm_all_rows
 from .kv import (PACKED_MAX_KEYS, PACKED_TILE_MAX_KEYS, PrefixTable, PromptGroups, SlabKV, SlabRunner, encode_packed, encode_ragged,
-                 packed_supported)
+                 packed_supported, prefix_kv_refusal)
 from ._lib import MASK_BITS, MASK_NONE
 from .masks import ParticleMasks
 
@@ -191,6 +191,11 @@ class DeviceSIS:
                      rank, a row budget that is spent) are encoded from their tokens (kv.SharedSlabKV).  False: every
                      particle owns row i (kv.SlabKV), no dedup - the decode loop of DeviceSampler, whose sequences
                      never coincide.
+    share_prompt_kv  (with use_particle_kv, share_kv=False, one rank; off by default) every distinct prompt's KV is stored
+                     ONCE: step 0's encoding stays as the prefix store, a particle's row holds only the max_tokens + 1
+                     positions behind its prompt and attention reads prompt, row and new token
+                     (glb_slab_attention_prefix, DESIGN.md §37: float32 / bfloat16 / float16, head_dim 64 / 128, the fused
+                     attention entry - ValueError otherwise); resampling copies tails and re-points prefixes.
     kv_rows          row budget of the shared store (default: one per particle, which always suffices); contexts that
                      find no free row are served without their KV being kept.
     kv_in_place      with shared KV rows: the fraction of live slab rows from which a forward runs on the slab in place
@@ -226,7 +231,14 @@ class DeviceSIS:
     def __init__(self, llm, n_particles, prompt_ids, max_tokens, eos_id, seed=0, rng="philox", rank=0, world=1,
                  dist=None, use_prefix_kv=False, use_particle_kv=False, resample_ess=None, force_collectives=False,
                  share_kv=True, kv_rows=None, kv_in_place=0.75, kv_graph=True, particle_masks=None, migrate_kv=True,
-                 constraint=None, share_prompt_rows=True, proposal_temperature=None, proposal=None):
+                 constraint=None, share_prompt_rows=True, proposal_temperature=None, proposal=None, share_prompt_kv=False):
+        if share_prompt_kv:
+            why = ("it needs use_particle_kv=True" if not use_particle_kv else "it needs share_kv=False (the block-table store "
+                   "keeps whole contexts in its rows)" if share_kv else "it serves one rank (world == 1)" if world != 1
+                   else prefix_kv_refusal(llm))
+            if why:
+                raise ValueError(f"share_prompt_kv=True: {why}")
+        self.share_prompt_kv = bool(share_prompt_kv)
         if constraint is not None and particle_masks is not None:
             raise ValueError("give particle_masks (the caller's bit rows) or constraint (masks made on the device), not both")
         self._propose = proposal_temperature is not None or proposal is not None
@@ -415,6 +427,18 @@ class DeviceSIS:
         l_max = int(lens_eff.max().item())
         enc = encode_ragged(llm, (ctx_flat, self.starts, lens_eff), rep, U, l_max, keep_kv=True)
         src = enc.kv_layers()
+        if self.share_prompt_kv:  # the distinct prompts' KV is the prefix store; the rows hold what is generated behind it
+            assert rows is None and self.t == 0
+            if self.pkv is None:
+                self._kv.pkv = SlabKV(eng, N, self.max_tokens + 1, len(src))
+            old = self.pkv.prefix_layers
+            if old is not None and old[0][0].shape == src[0][0].shape:  # a new run of the same prompts: the store's addresses
+                for (k0, v0), (k, v) in zip(old, src):                    # stay, and with them the captured forwards
+                    k0.copy_(k)
+                    v0.copy_(v)
+                src = old
+            self.pkv.set_prefix(src, lens_eff[rep[:U].long()], group_of)
+            return enc, group_of, rep, U
         if self.pkv is None:
             self._kv.pkv = SlabKV(eng, N, self.cap, len(src))
         src_row = torch.where(want, group_of, torch.full_like(group_of, -1))
@@ -436,6 +460,8 @@ class DeviceSIS:
         rows = torch.arange(N, device=dev)
         pos = (self.lengths - 1).clamp_min(0)  # tokens already in the row's KV = index of the newest token
         newest = self.contexts[rows, pos.long()]
+        if self.share_prompt_kv:  # the row holds the tokens behind the prompt only (SlabForward adds the prompt's length back)
+            pos = (pos - self.prompt_len).clamp_min(0)
         ids = torch.where(self.active > 0, newest, torch.zeros_like(newest)).view(N, 1).long()
         logits = llm._lm_head(self._kv.slab_forward()(ids, pos))  # [N, V]
         self._noise_groups = None
@@ -823,6 +849,9 @@ class DeviceSIS:
             is_local = (local >= 0) & (local < N)
             src = torch.where(is_local, local, torch.full_like(local, -1))
             kv_len = (self.lengths - 1).clamp_min(0)
+            if self.share_prompt_kv:  # tails only; the particle stands behind its ancestor's prompt (one rank: all local)
+                kv_len = (kv_len - self.prompt_len).clamp_min(0)
+                self.pkv.set_prefix(self.pkv.prefix_layers, self.pkv.prefix_len, self.pkv.prefix_of[local.long()])
             self.pkv.gather(src, kv_len)
             stale = ~is_local
             if self.migrate_kv and self.collective and self.world > 1:
@@ -929,11 +958,12 @@ class DeviceSampler(DeviceSIS):
     Nothing is read back per token: the active count is fetched every `sync_every` steps."""
 
     def __init__(self, llm, prompts, max_tokens, eos_token_ids, temperature=1.0, seed=None, sync_every=4, top_k=0, top_p=1.0,
-                 min_p=0.0):
+                 min_p=0.0, share_prompt_kv=False):
         top_k, top_p, log_min_p = check_truncation(top_k, top_p, min_p)
         super().__init__(llm, len(prompts), [list(p) for p in prompts], max_tokens, eos_id=-1,
                          seed=0 if seed is None else int(seed), rng="philox", use_particle_kv=True, share_kv=False,
-                         kv_graph=max_tokens >= 64)  # (a capture costs a few dozen eager steps: long generations only)
+                         kv_graph=max_tokens >= 64,  # (a capture costs a few dozen eager steps: long generations only)
+                         share_prompt_kv=share_prompt_kv)
         self.sync_every = max(1, int(sync_every))
         self.temperature = float(temperature)
         # truncation (DESIGN.md §31): the keep set of every step's rows as bit rows, the draw under them; all off: no such call

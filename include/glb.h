@@ -493,6 +493,35 @@ int glb_slab_attention(const void *q, int64_t q_stride_row, int64_t q_stride_hea
                        int32_t dtype, void *out, void *hip_stream);
 
 /*
+ * The same one-token forward over slab rows that stand BEHIND A PROMPT STORED ONCE: the arguments of the
+ * entry above, then the prefix store - prefix_k / prefix_v [n_prefixes, kv_heads, prefix_cap, head_dim] contiguous, the slabs'
+ * dtype; prefix_len [n_prefixes] int32 on the device, 0 .. prefix_cap (read as clamped into that range); prefix_of [n_rows]
+ * int32 on the device: the prefix row r stands behind, -1: none.  Row r under query head h attends, in this order, the
+ * prefix_len[prefix_of[r]] prefix positions, its own slab positions 0 .. pos[r] - 1 and the new token, read from k_new / v_new
+ * where the projection left them and written to slab position pos[r] once per (row, KV head).  pos[r] counts the tokens
+ * behind the prefix only and cap is the tails' capacity; rotary positions are the caller's business.  out [n_rows, heads,
+ * head_dim].  A row with pos outside [0, cap), prefix_of >= n_prefixes or prefix_of < -1: NaN, nothing appended, the other
+ * rows unaffected.  A row with prefix_of = -1 gets the arithmetic of the entry above.
+ * Two launches.  A: one workgroup per (64 query rows row-major over (row, head of the group), KV head, split) walks split s's
+ * share of the 32-key tiles of every distinct prefix its rows name, both products on MFMA (v_mfma_f32_16x16x32_{bf16,f16};
+ * float32 on v_mfma_f32_16x16x4f32, inputs unrounded; 16-bit types: probabilities rounded to the element type as the second
+ * product's operand), and leaves one float32 partial (maximum, sum, unnormalised output) per (row, head, split) in the
+ * workspace.  B: one wave per (row, query head) folds the partials, walks the own positions and the new token, appends,
+ * normalises and stores.  splits 1 .. 8; workspace: the bytes the _workspace function names (0 for sizes the entry
+ * refuses), 16-byte aligned, every byte of it rewritten by every call.  float32 / bfloat16 / float16; head_dim 64 / 128
+ * (GLB_EUNSUPPORTED otherwise); any heads / kv_heads; pointers and strides multiples of 16 bytes; prefix_cap <= 2^30.  Writes
+ * out, the appended slab positions and the workspace only; no atomics, no allocation: fit for a captured graph.  GLB_EINVAL
+ * for anything else, nothing launched.
+ */
+size_t glb_slab_attention_prefix_workspace(int64_t n_rows, int64_t heads, int64_t head_dim, int32_t splits);
+int glb_slab_attention_prefix(const void *q, int64_t q_stride_row, int64_t q_stride_head, const void *k_new, int64_t k_stride_row,
+                              int64_t k_stride_head, const void *v_new, int64_t v_stride_row, int64_t v_stride_head, void *k_slab,
+                              void *v_slab, const int32_t *pos, int64_t n_rows, int64_t heads, int64_t kv_heads, int64_t cap,
+                              int64_t head_dim, float scale, int32_t dtype, void *out, const void *prefix_k, const void *prefix_v,
+                              const int32_t *prefix_len, const int32_t *prefix_of, int64_t n_prefixes, int64_t prefix_cap,
+                              int32_t splits, void *workspace, size_t workspace_bytes, void *hip_stream);
+
+/*
  * Masked attention of the padded batches of short contexts the path feeds the transformer (hf.py:232-281): for every row u,
  * query head h and query position t, softmax over the keys s it may see of q[u,h,t] . k[u,h/G,s] * scale, times v.  q / k / v
  * by element strides {row, head, position} with unit inner stride (the projections' outputs, cached prefixes in front of
