@@ -608,6 +608,9 @@ SYMBOLS = {
     "glb_slab_attention_prefix_workspace": (_sz, [_i64, _i64, _i64, _i32]),
     "glb_slab_attention_prefix": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _i64,
                                             _i64, _f32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _sz, _vp]),
+    "glb_slab_attention_fp8": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64,
+                                         _i64, _i64, _f32, _i32, _vp, _vp]),
+    "glb_kv_quantize_rows": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _i32, _vp]),
     "glb_short_attention": (C.c_int, [_vp, C.POINTER(C.c_int64), _vp, C.POINTER(C.c_int64), _vp, C.POINTER(C.c_int64), _vp, _i64, _i64,
                                       _i64, _i64, _i64, _i64, _i64, _i64, _f32, _i32, _vp, _vp]),
     "glb_batch_attention_tile": (C.c_int, [_vp, C.POINTER(C.c_int64), _vp, C.POINTER(C.c_int64), _vp, C.POINTER(C.c_int64), _vp, _i64,

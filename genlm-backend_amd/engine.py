@@ -1531,6 +1531,46 @@ class HipEngine:
     def slab_attention_prefix_supports(dtype, head_dim):
         return dtype in _DT and head_dim in (64, 128)
 
+    def slab_attention_fp8(self, query, k_new, v_new, k_codes, v_codes, k_scale, v_scale, pos, scale):
+        """`slab_attention` over rows kept in e4m3 (glb_slab_attention_fp8): k_codes / v_codes [R, H_kv, cap, Dh]
+        torch.float8_e4m3fn, k_scale / v_scale [R, H_kv, cap] float32, all contiguous; query, k_new, v_new in the model's dtype.
+        The new token is quantised, attended at its dequantised value and written to position pos[r].  float32 / bfloat16 /
+        float16, head_dim 64 / 128, H / H_kv 1 / 2 / 4 / 8.  Returns [R, 1, H, Dh]."""
+        R, H, _, Dh = query.shape
+        Hkv, cap = k_codes.shape[1], k_codes.shape[2]
+        assert query.stride(3) == 1 and k_new.stride(3) == 1 and v_new.stride(3) == 1 and k_new.dtype == v_new.dtype == query.dtype
+        assert k_codes.dtype == v_codes.dtype == torch.float8_e4m3fn and k_scale.dtype == v_scale.dtype == torch.float32
+        assert k_codes.shape == v_codes.shape == (R, Hkv, cap, Dh) and k_scale.shape == v_scale.shape == (R, Hkv, cap)
+        assert all(t.is_contiguous() for t in (k_codes, v_codes, k_scale, v_scale))
+        self._check_dev(k_codes, v_codes, k_scale, v_scale)
+        out = torch.empty((R, 1, H, Dh), dtype=query.dtype, device=self.device)
+        check(self.lib.glb_slab_attention_fp8(_ptr(query), query.stride(0), query.stride(1), _ptr(k_new), k_new.stride(0),
+                                              k_new.stride(1), _ptr(v_new), v_new.stride(0), v_new.stride(1), _ptr(k_codes),
+                                              _ptr(v_codes), _ptr(k_scale), _ptr(v_scale), _ptr(pos), R, H, Hkv, cap, Dh,
+                                              float(scale), _DT[query.dtype], _ptr(out), self._stream()))
+        return out
+
+    @staticmethod
+    def slab_attention_fp8_supports(dtype, head_dim):
+        return dtype in _DT and head_dim in (64, 128)
+
+    def kv_quantize_rows(self, srcs, dst_codes, dst_scales, src_row_of, len_of):
+        """`kv_gather_rows` into e4m3 rows (glb_kv_quantize_rows): srcs[t] [u, H_kv, l_src, Dh] in the model's dtype, dst_codes[t]
+        [rows, H_kv, cap, Dh] torch.float8_e4m3fn, dst_scales[t] [rows, H_kv, cap] float32, all contiguous - every pair of the
+        lists in ONE launch.  Row i with src_row_of[i] >= 0 takes the first len_of[i] positions of row src_row_of[i]."""
+        s0, d0 = srcs[0], dst_codes[0]
+        assert len(srcs) == len(dst_codes) == len(dst_scales)
+        assert all(t.is_contiguous() for ts in (srcs, dst_codes, dst_scales) for t in ts)
+        assert all(t.dtype == torch.float8_e4m3fn and t.shape == d0.shape for t in dst_codes)
+        assert all(t.dtype == torch.float32 and t.shape == d0.shape[:3] for t in dst_scales)
+        assert all(t.dtype == s0.dtype and t.shape == s0.shape for t in srcs) and s0.shape[1] == d0.shape[1] and s0.shape[3] == d0.shape[3]
+        assert src_row_of.dtype == len_of.dtype == torch.int32 and src_row_of.numel() == len_of.numel() == d0.shape[0]
+        self._check_dev(s0, d0, src_row_of, len_of)
+        sp = torch.tensor([t.data_ptr() for t in srcs], dtype=torch.int64, device=self.device)  # (a one-off: a forward's KV)
+        check(self.lib.glb_kv_quantize_rows(_ptr(sp), _ptr(self._ptr_table(dst_codes)), _ptr(self._ptr_table(dst_scales)), len(srcs),
+                                            s0.shape[0], d0.shape[0], d0.shape[1], d0.shape[3], s0.shape[2], d0.shape[2],
+                                            _ptr(src_row_of), _ptr(len_of), _DT[s0.dtype], self._stream()))
+
     def short_attention(self, query, key, value, mask, scale):
         """Masked attention of a padded batch of short contexts (glb_short_attention).  query [U, H, Lq, Dh], key / value
         [U, H_kv, Lk, Dh] (unit inner stride), mask: bool [U, 1, Lq, Lk] (true = attend) or None (causal).  Returns
@@ -1657,7 +1697,10 @@ class HipEngine:
         owner died does not pass for the old tensor.  Entries whose tensors are gone leave at the next miss."""
         import weakref
 
-        key = tuple(t.data_ptr() for t in tensors)
+        ptrs = tuple(t.data_ptr() for t in tensors)
+        # (views of one storage - e4m3 codes as byte pairs, scales with a unit axis: SlabKV.gather - are other tensor objects
+        # at the same addresses: an entry of their own, or the two callers would evict each other's table every call)
+        key = ptrs + (tensors[0].dtype, tensors[0].dim())
         ent = self._ptr_tables.get(key)
         if ent is not None and all(r() is t for r, t in zip(ent[1], tensors)):
             return ent[0]
@@ -1666,7 +1709,7 @@ class HipEngine:
             del self._ptr_tables[k]
         if len(self._ptr_tables) >= 64:
             self._ptr_tables.pop(next(iter(self._ptr_tables)))
-        table = torch.tensor(key, dtype=torch.int64, device=self.device)
+        table = torch.tensor(ptrs, dtype=torch.int64, device=self.device)
         self._ptr_tables[key] = (table, [weakref.ref(t) for t in tensors])
         return table
 

@@ -72,6 +72,27 @@ def prefix_kv_refusal(llm):
     return None
 
 
+KV_DTYPES = ("fp8_e4m3",)  # narrow element types of the private KV rows (SlabKV(kv_dtype=...))
+
+
+def fp8_kv_refusal(llm_or_body, engine=None):
+    """Why KV rows in e4m3 (SlabKV(kv_dtype="fp8_e4m3")) cannot serve this model, or None: the fused attention entry, an
+    element type, head size and heads per KV head glb_slab_attention_fp8 is built for.  An AsyncAmdLM, or its body and engine."""
+    body, eng = (llm_or_body._body, llm_or_body.engine) if engine is None else (llm_or_body, engine)
+    cfg = getattr(body, "config", None)
+    if cfg is None or getattr(cfg, "_attn_implementation", None) != _ATTN_NAME or getattr(cfg, "_glb_engine", None) is not eng:
+        return "the model's attention does not go through this backend's fused attention entry (glb_attention)"
+    heads = getattr(cfg, "num_attention_heads", None)
+    kv_heads = getattr(cfg, "num_key_value_heads", None) or heads
+    head_dim = getattr(cfg, "head_dim", None) or (cfg.hidden_size // heads if heads else None)
+    dtype = next(body.parameters()).dtype
+    if not (hasattr(eng, "slab_attention_fp8") and eng.slab_attention_fp8_supports(dtype, head_dim)):
+        return f"glb_slab_attention_fp8 is not built for {dtype}, head_dim {head_dim} (float32 / bfloat16 / float16, 64 / 128)"
+    if not heads or heads % kv_heads or heads // kv_heads not in (1, 2, 4, 8):
+        return f"glb_slab_attention_fp8 is not built for {heads} query heads over {kv_heads} KV heads (1, 2, 4 or 8 per KV head)"
+    return None
+
+
 def _fused_forward(pkv, body, entry, lost, **inputs):
     """One forward of `body` over `pkv` whose attention AND append are this library's kernel `entry` (no mask: the kernel
     attends to the positions a row holds and its new ones, nothing else).  Whatever happens, the slabs are left with the
@@ -109,6 +130,9 @@ def _glb_attention_forward(module, query, key, value, attention_mask, dropout=0.
         if chunk:
             attend = getattr(o.engine, _chunk_kernel(query.shape[2]))
             return attend(query, k_new, v_new, layer.keys, layer.values, o.pos, o.n_new, scale, rows=o.rows), None
+        if getattr(o, "kv_dtype", None) is not None:  # SlabKV(kv_dtype="fp8_e4m3"): codes and scales, the new token quantised
+            return o.engine.slab_attention_fp8(query, k_new, v_new, layer.keys, layer.values, layer.k_scale, layer.v_scale, o.pos,
+                                               scale), None
         if getattr(o, "prefix_layers", None) is not None:  # SlabKV.set_prefix: the rows stand behind prompts stored once
             pk, pv = o.prefix_layers[layer.idx]
             return o.engine.slab_attention_prefix(query, k_new, v_new, layer.keys, layer.values, o.pos, pk, pv, o.prefix_len,
@@ -196,6 +220,14 @@ class _SlabLayer(CacheLayerMixin):
         o = self.owner
         shape_k = (o.n, key_states.shape[1], o.cap, key_states.shape[-1])
         shape_v = (o.n, value_states.shape[1], o.cap, value_states.shape[-1])
+        if getattr(o, "kv_dtype", None) is not None:  # e4m3 codes and one float32 scale a position
+            dev = key_states.device
+            self.keys = torch.zeros(shape_k, dtype=torch.uint8, device=dev).view(torch.float8_e4m3fn)
+            self.values = torch.zeros(shape_v, dtype=torch.uint8, device=dev).view(torch.float8_e4m3fn)
+            self.k_scale = torch.zeros(shape_k[:3], dtype=torch.float32, device=dev)
+            self.v_scale = torch.zeros(shape_v[:3], dtype=torch.float32, device=dev)
+            self.is_initialized = True
+            return
         self.keys = torch.zeros(shape_k, dtype=key_states.dtype, device=key_states.device)
         self.values = torch.zeros(shape_v, dtype=value_states.dtype, device=value_states.device)
         self.is_initialized = True
@@ -208,6 +240,8 @@ class _SlabLayer(CacheLayerMixin):
             raise ValueError("SlabKV takes one new token for every particle per forward")
         if o.fused_attention:
             return self._stash(key_states, value_states)
+        if getattr(o, "kv_dtype", None) is not None:
+            raise ValueError("KV rows in fp8_e4m3 are served by the fused forward only (glb_slab_attention_fp8)")
         o.engine.kv_append(self.keys, key_states, o.pos)
         o.engine.kv_append(self.values, value_states, o.pos)
         return self.keys, self.values
@@ -229,7 +263,16 @@ class _SlabLayer(CacheLayerMixin):
 
 
 class SlabKV(Cache):
-    def __init__(self, engine, n, cap, n_layers):
+    def __init__(self, engine, n, cap, n_layers, kv_dtype=None):
+        """kv_dtype: None - the rows keep the model's element type; "fp8_e4m3" - a layer holds one-byte OCP e4m3 codes
+        (`keys` / `values`, torch.float8_e4m3fn) and one float32 scale per (row, KV head, position) (`k_scale` / `v_scale`):
+        `fill_rows` quantises, a fused one-token forward attends and appends through glb_slab_attention_fp8, `gather` carries
+        both.  Fused forwards only, no stored prefix."""
+        if kv_dtype is not None and kv_dtype not in KV_DTYPES:
+            raise ValueError(f"kv_dtype must be None or one of {KV_DTYPES}, got {kv_dtype!r}")
+        self.kv_dtype = kv_dtype
+        self._alt_scales = None
+        self._views = {}  # id(tensor) -> (tensor, its view as glb_kv_gather_rows takes it): made once, so the pointer tables stay
         self.engine, self.n, self.cap = engine, n, cap
         self.pos = None  # int32 [n] device: where this forward's token goes (= tokens already held by the row)
         self.fused_attention = False  # the running forward's attention appends (SlabForward sets it per call)
@@ -246,6 +289,8 @@ class SlabKV(Cache):
         `SlabForward` feeds position_ids = prefix_len[prefix_of] + pos.  Fused forwards only.  Calling it again with the same
         `layers` (a resampling step: prefix_of follows the ancestors) rewrites prefix_len / prefix_of in place, so a captured
         forward stays valid."""
+        if self.kv_dtype is not None:
+            raise ValueError(f"set_prefix: rows in {self.kv_dtype} stand behind no stored prefix (not built; DESIGN.md §38)")
         if len(layers) != len(self.layers):
             raise ValueError(f"{len(layers)} prefix layers for {len(self.layers)} slab layers")
         prefix_len, prefix_of = prefix_len.to(torch.int32), prefix_of.to(torch.int32)
@@ -289,7 +334,21 @@ class SlabKV(Cache):
         ([(K, V)] per layer, each [u, heads, l_src, head_dim], contiguous): fan-out of freshly encoded contexts."""
         self._alloc_like(src_layers)
         srcs = [t for kv in src_layers for t in kv]
+        if self.kv_dtype is not None:
+            self.engine.kv_quantize_rows(srcs, self._tensors(self.layers), self._scales(self.layers), src_row_of, len_of)
+            return
         self.engine.kv_gather_rows(srcs, self._tensors(self.layers), src_row_of, len_of, srcs_stable=False)
+
+    def _scales(self, which):
+        return [t for layer in which for t in (layer.k_scale, layer.v_scale)]
+
+    def _byte_view(self, t):
+        """A code or scale tensor as glb_kv_gather_rows takes it: codes as 2-byte elements of head_dim / 2, scales as 4-byte
+        elements of head_dim 1."""
+        ent = self._views.get(id(t))
+        if ent is None or ent[0] is not t:
+            ent = self._views[id(t)] = (t, t.view(torch.int16) if t.dim() == 4 else t.unsqueeze(-1))
+        return ent[1]
 
     def gather(self, src_row_of, len_of):
         """Resampling: row i becomes a copy of row src_row_of[i] (first len_of[i] positions); rows with
@@ -297,13 +356,26 @@ class SlabKV(Cache):
         cur = self._tensors(self.layers)
         if self._alt is None:
             self._alt = [torch.zeros_like(t) for t in cur]
-        self.engine.kv_gather_rows(cur, self._alt, src_row_of, len_of)
+        if self.kv_dtype is not None:  # a byte copy of codes and of scales: two launches of the same kernel
+            sc = self._scales(self.layers)
+            if self._alt_scales is None:
+                self._alt_scales = [torch.zeros_like(t) for t in sc]
+            view = self._byte_view
+            self.engine.kv_gather_rows([view(t) for t in cur], [view(t) for t in self._alt], src_row_of, len_of)
+            self.engine.kv_gather_rows([view(t) for t in sc], [view(t) for t in self._alt_scales], src_row_of, len_of)
+            for j, layer in enumerate(self.layers):
+                layer.k_scale, self._alt_scales[2 * j] = self._alt_scales[2 * j], layer.k_scale
+                layer.v_scale, self._alt_scales[2 * j + 1] = self._alt_scales[2 * j + 1], layer.v_scale
+        else:
+            self.engine.kv_gather_rows(cur, self._alt, src_row_of, len_of)
         for j, layer in enumerate(self.layers):
             layer.keys, self._alt[2 * j] = self._alt[2 * j], layer.keys
             layer.values, self._alt[2 * j + 1] = self._alt[2 * j + 1], layer.values
 
     def nbytes(self):
         own = sum(t.numel() * t.element_size() for t in self._tensors(self.layers) if t is not None) * (2 if self._alt else 1)
+        if self.kv_dtype is not None:
+            own += sum(t.numel() * 4 for ly in self.layers if ly.is_initialized for t in (ly.k_scale, ly.v_scale)) * (2 if self._alt else 1)
         return own + sum(t.numel() * t.element_size() for kv in self.prefix_layers or () for t in kv)
 
 
@@ -363,7 +435,10 @@ class SharedSlabKV(SlabKV):
     layers, K and V - into staging slabs in batch order (the PyTorch attention wants a dense [U, H, cap, Dh]), the new
     token's K / V go into the row that keeps them and beside the gathered prefix."""
 
-    def __init__(self, engine, n_rows, cap, n_layers):
+    def __init__(self, engine, n_rows, cap, n_layers, kv_dtype=None):
+        if kv_dtype is not None:
+            raise ValueError(f"SharedSlabKV: kv_dtype={kv_dtype!r} is served by private rows only (SlabKV; DESIGN.md §38)")
+        self.kv_dtype = None
         Cache.__init__(self, layers=[_SharedLayer(self, i) for i in range(n_layers)])
         self.engine, self.n, self.cap = engine, n_rows, cap
         self.pos = None
@@ -440,6 +515,11 @@ class SlabForward:
 
     def __init__(self, pkv, body, graph=True, fused_attention=True, owner=None):
         self.pkv, self.body = pkv, body
+        self.fp8 = getattr(pkv, "kv_dtype", None) is not None
+        if self.fp8:  # e4m3 rows: the fused forward or none (there is no append + mask + SDPA over codes)
+            why = "fused_attention=False" if not fused_attention else fp8_kv_refusal(body, pkv.engine)
+            if why:
+                raise ValueError(f"rows in {pkv.kv_dtype} (SlabKV(kv_dtype=...)) are served by the fused forward only: {why}")
         self.owner = owner  # the AsyncAmdLM whose `refresh_weights()` drops the captured graphs (its weights_epoch moves)
         self._owner_epoch = getattr(owner, "weights_epoch", 0)
         self.graph_ok = bool(graph) and torch.cuda.is_available()
@@ -458,6 +538,9 @@ class SlabForward:
         # goes through transformers' attention interface with plain softmax(q k^T * scale) v semantics on a HIP device
         # (the body is AsyncAmdLM's shadow of the model, already pointed at the "glb" attention entry when glb_attention is on;
         # a body that is not - the caller's own model, glb_attention=False - keeps appends + mask + SDPA)
+        if self.fp8:
+            self.fused = True
+            return
         self.fused = bool(fused_attention) and _kernel_serves(pkv.engine, "slab_attention", pkv, body)
         if getattr(pkv, "prefix_layers", None) is not None and not (
                 self.fused and _kernel_serves(pkv.engine, "slab_attention_prefix", pkv, body)):
@@ -499,6 +582,8 @@ class SlabForward:
         slabs = self.pkv._tensors(self.pkv.layers)
         if getattr(self.pkv, "prefix_layers", None) is not None:  # and to the prefix store, its lengths and the rows' prefixes
             slabs = slabs + [t for kv in self.pkv.prefix_layers for t in kv] + [self.pkv.prefix_len, self.pkv.prefix_of]
+        if getattr(self.pkv, "kv_dtype", None) is not None:  # and to the scales beside the codes
+            slabs = slabs + self.pkv._scales(self.pkv.layers)
         key = tuple((t.data_ptr(), tuple(t.shape), t.dtype) for t in slabs)
         ent = self.graphs.get(key)
         if ent is None:

@@ -1547,7 +1547,7 @@ class AsyncAmdLM(AsyncLM):
     # ---- sampling (base.py:110-179): a device-resident multi-token loop -----------------------------------------------
     @torch.no_grad()
     def batch_sample_sync(self, prompt_token_ids_list, max_tokens, eos_token_ids, temperature=1.0, seed=None,
-                          sync_every=4, top_k=0, top_p=1.0, min_p=0.0, share_prompt_kv=False):
+                          sync_every=4, top_k=0, top_p=1.0, min_p=0.0, share_prompt_kv=False, kv_dtype=None):
         """base.py:148-179.  All sequences advance together on the device (sis.DeviceSampler): per-sequence KV slabs,
         softmax(logits / temperature) -> one draw per sequence per forward by the fused step, stop on `eos_token_ids`.
         With a seed every sequence reproduces torch.multinomial under its own torch.Generator().manual_seed(seed)
@@ -1557,7 +1557,9 @@ class AsyncAmdLM(AsyncLM):
         - top-k, then the nucleus among those, and min-p against the largest probability, ties at the boundary kept
         (HipEngine.truncate_rows) - and renormalised; with a seed, torch.multinomial of exactly that.
         share_prompt_kv: every distinct prompt's KV is stored once and the sequences' rows hold their own tokens only
-        (DeviceSIS(share_prompt_kv=True))."""
+        (DeviceSIS(share_prompt_kv=True)).
+        kv_dtype: "fp8_e4m3" keeps the sequences' KV rows as e4m3 codes and per-position scales (DeviceSIS(kv_dtype=...),
+        DESIGN.md §38): a quarter to a half of the bytes, with quantisation noise."""
         from .engine import check_truncation
         from .sis import DeviceSampler
 
@@ -1569,14 +1571,14 @@ class AsyncAmdLM(AsyncLM):
         if max_tokens <= 0:
             return [[] for _ in prompt_token_ids_list]
         smp = DeviceSampler(self, prompt_token_ids_list, max_tokens, eos_token_ids, temperature, seed, sync_every=sync_every,
-                            top_k=top_k, top_p=top_p, min_p=min_p, share_prompt_kv=share_prompt_kv)
+                            top_k=top_k, top_p=top_p, min_p=min_p, share_prompt_kv=share_prompt_kv, kv_dtype=kv_dtype)
         return [[int(t) for t in row] for row in smp.generate()]
 
     async def batch_sample(self, prompt_token_ids_list, max_tokens, eos_token_ids, temperature=1.0, seed=None, top_k=0, top_p=1.0,
-                           min_p=0.0, share_prompt_kv=False):
-        """base.py:148-179; top_k, top_p, min_p, share_prompt_kv as `batch_sample_sync` takes them"""
+                           min_p=0.0, share_prompt_kv=False, kv_dtype=None):
+        """base.py:148-179; top_k, top_p, min_p, share_prompt_kv, kv_dtype as `batch_sample_sync` takes them"""
         return self.batch_sample_sync(prompt_token_ids_list, max_tokens, eos_token_ids, temperature, seed, top_k=top_k, top_p=top_p,
-                                      min_p=min_p, share_prompt_kv=share_prompt_kv)
+                                      min_p=min_p, share_prompt_kv=share_prompt_kv, kv_dtype=kv_dtype)
 
     async def sample(self, prompt_token_ids, max_tokens, eos_token_ids, temperature=1.0, seed=None, top_k=0, top_p=1.0, min_p=0.0):
         """base.py:110-146; top_k, top_p, min_p as `batch_sample_sync` takes them"""

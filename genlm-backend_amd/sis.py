@@ -22,8 +22,8 @@ import torch
 from .cache import KVPrefix
 from .engine import check_truncation
 from .fuse import SplitConv1D, split_gemm_all_rows
-from .kv import (PACKED_MAX_KEYS, PACKED_TILE_MAX_KEYS, PrefixTable, PromptGroups, SlabKV, SlabRunner, encode_packed, encode_ragged,
-                 packed_supported, prefix_kv_refusal)
+from .kv import (KV_DTYPES, PACKED_MAX_KEYS, PACKED_TILE_MAX_KEYS, PrefixTable, PromptGroups, SlabKV, SlabRunner, encode_packed, encode_ragged,
+                 fp8_kv_refusal, packed_supported, prefix_kv_refusal)
 from ._lib import MASK_BITS, MASK_NONE
 from .masks import ParticleMasks
 
@@ -196,6 +196,12 @@ class DeviceSIS:
                      positions behind its prompt and attention reads prompt, row and new token
                      (glb_slab_attention_prefix, DESIGN.md §37: float32 / bfloat16 / float16, head_dim 64 / 128, the fused
                      attention entry - ValueError otherwise); resampling copies tails and re-points prefixes.
+    kv_dtype         (with use_particle_kv, share_kv=False, share_prompt_kv=False, one rank; off by default) "fp8_e4m3": the
+                     particles' KV rows are OCP e4m3 codes plus one float32 scale per (row, KV head, position) - 0.27 of
+                     float32 rows at head_dim 64, 0.53 of 16-bit ones - quantised when the prompts' KV is fanned out and when
+                     a token is appended, read by glb_slab_attention_fp8 (float32 / bfloat16 / float16,
+                     head_dim 64 / 128, 1 / 2 / 4 / 8 query heads per KV head, the fused attention entry - ValueError
+                     otherwise).  Not exact: the rows carry quantisation noise.
     kv_rows          row budget of the shared store (default: one per particle, which always suffices); contexts that
                      find no free row are served without their KV being kept.
     kv_in_place      with shared KV rows: the fraction of live slab rows from which a forward runs on the slab in place
@@ -231,7 +237,17 @@ class DeviceSIS:
     def __init__(self, llm, n_particles, prompt_ids, max_tokens, eos_id, seed=0, rng="philox", rank=0, world=1,
                  dist=None, use_prefix_kv=False, use_particle_kv=False, resample_ess=None, force_collectives=False,
                  share_kv=True, kv_rows=None, kv_in_place=0.75, kv_graph=True, particle_masks=None, migrate_kv=True,
-                 constraint=None, share_prompt_rows=True, proposal_temperature=None, proposal=None, share_prompt_kv=False):
+                 constraint=None, share_prompt_rows=True, proposal_temperature=None, proposal=None, share_prompt_kv=False,
+                 kv_dtype=None):
+        if kv_dtype is not None:
+            why = (f"it must be None or one of {KV_DTYPES}" if kv_dtype not in KV_DTYPES
+                   else "it needs use_particle_kv=True" if not use_particle_kv
+                   else "it needs share_kv=False (the block-table store keeps the model's element type)" if share_kv
+                   else "it needs share_prompt_kv=False (rows in fp8 stand behind no stored prefix)" if share_prompt_kv
+                   else "it serves one rank (world == 1)" if world != 1 else fp8_kv_refusal(llm))
+            if why:
+                raise ValueError(f"kv_dtype={kv_dtype!r}: {why}")
+        self.kv_dtype = kv_dtype
         if share_prompt_kv:
             why = ("it needs use_particle_kv=True" if not use_particle_kv else "it needs share_kv=False (the block-table store "
                    "keeps whole contexts in its rows)" if share_kv else "it serves one rank (world == 1)" if world != 1
@@ -440,7 +456,7 @@ class DeviceSIS:
             self.pkv.set_prefix(src, lens_eff[rep[:U].long()], group_of)
             return enc, group_of, rep, U
         if self.pkv is None:
-            self._kv.pkv = SlabKV(eng, N, self.cap, len(src))
+            self._kv.pkv = SlabKV(eng, N, self.cap, len(src), kv_dtype=self.kv_dtype)
         src_row = torch.where(want, group_of, torch.full_like(group_of, -1))
         self.pkv.fill_rows(src, src_row, lens_eff)
         return enc, group_of, rep, U
@@ -958,12 +974,12 @@ class DeviceSampler(DeviceSIS):
     Nothing is read back per token: the active count is fetched every `sync_every` steps."""
 
     def __init__(self, llm, prompts, max_tokens, eos_token_ids, temperature=1.0, seed=None, sync_every=4, top_k=0, top_p=1.0,
-                 min_p=0.0, share_prompt_kv=False):
+                 min_p=0.0, share_prompt_kv=False, kv_dtype=None):
         top_k, top_p, log_min_p = check_truncation(top_k, top_p, min_p)
         super().__init__(llm, len(prompts), [list(p) for p in prompts], max_tokens, eos_id=-1,
                          seed=0 if seed is None else int(seed), rng="philox", use_particle_kv=True, share_kv=False,
                          kv_graph=max_tokens >= 64,  # (a capture costs a few dozen eager steps: long generations only)
-                         share_prompt_kv=share_prompt_kv)
+                         share_prompt_kv=share_prompt_kv, kv_dtype=kv_dtype)
         self.sync_every = max(1, int(sync_every))
         self.temperature = float(temperature)
         # truncation (DESIGN.md §31): the keep set of every step's rows as bit rows, the draw under them; all off: no such call

@@ -522,6 +522,42 @@ int glb_slab_attention_prefix(const void *q, int64_t q_stride_row, int64_t q_str
                               int32_t splits, void *workspace, size_t workspace_bytes, void *hip_stream);
 
 /*
+ * KV rows in OCP e4m3: a slab is codes [n_rows, kv_heads, cap, head_dim], one byte each, plus scales
+ * [n_rows, kv_heads, cap] float32.  The rule, for the head_dim elements x of one (row, KV head, position) as float32:
+ * amax = max |x|; s = amax / 448.0f by IEEE float32 division, 1.0f when amax == 0; code = e4m3(x / s), IEEE division, round
+ * to nearest even; the value a code stands for is float(code) * s.  Non-finite elements leave that position's contribution
+ * unspecified, and so does a position whose amax is positive but below about 448 * 2^-149: s underflows to 0, x / s is
+ * infinite and the codes are NaN (the rule as stated; torch on the CPU gives the same bits).  No address depends on K / V data.
+ *
+ * glb_slab_attention_fp8: the one-token forward of the entry two above over such rows.  Its arguments, the slabs replaced by
+ *   k_codes / v_codes / k_scale / v_scale; q, k_new, v_new (element strides (row, head), unit inner stride) and out [n_rows,
+ *   heads, head_dim] are of `dtype`, float32 / bfloat16 / float16.  Row r attends its slab positions 0 .. pos[r] - 1 and the
+ *   new token, which is quantised by the rule, attended AT ITS DEQUANTISED VALUE and written - codes and scales - to position
+ *   pos[r] once per (row, KV head): the output is attention over the slab as it stands after the call.  pos outside [0, cap):
+ *   NaN for that row, nothing written, the other rows unaffected.  One wave per (row, KV head, group of min(G, 4) query
+ *   heads), G = heads / kv_heads; float32 accumulation, the scales applied to scores and weights, never to elements.
+ *   head_dim 64 / 128 and G 1 / 2 / 4 / 8 (GLB_EUNSUPPORTED otherwise, nothing launched); q / k_new / v_new / codes / out
+ *   pointers and the strides multiples of 16 bytes.  No atomics, no allocation, no workspace: fit for a captured graph.
+ *
+ * glb_kv_quantize_rows: glb_kv_gather_rows with the rule in it - all n_tensors (layer, K|V) tensors in one launch through
+ *   device arrays of device pointers.  src[t] [n_src_rows, kv_heads, src_cap, head_dim] of `dtype`, contiguous; for every row
+ *   i < n_rows with 0 <= src_row_of[i] < n_src_rows and every p < min(len_of[i], src_cap, dst_cap), the codes and scale of
+ *   src[t][src_row_of[i], h, p, :] go to dst_codes[t][i, h, p, :] and dst_scale[t][i, h, p] (dst_cap positions a row).  Other
+ *   rows and positions are untouched.  head_dim 64 / 128 (GLB_EUNSUPPORTED otherwise); tensors 16-byte aligned.
+ *
+ * A resampling gather of such rows is a byte copy: glb_kv_gather_rows on the codes as 2-byte elements of head_dim / 2 and on
+ * the scales as 4-byte elements of head_dim 1.
+ */
+int glb_slab_attention_fp8(const void *q, int64_t q_stride_row, int64_t q_stride_head, const void *k_new, int64_t k_stride_row,
+                           int64_t k_stride_head, const void *v_new, int64_t v_stride_row, int64_t v_stride_head, void *k_codes,
+                           void *v_codes, float *k_scale, float *v_scale, const int32_t *pos, int64_t n_rows, int64_t heads,
+                           int64_t kv_heads, int64_t cap, int64_t head_dim, float scale, int32_t dtype, void *out,
+                           void *hip_stream);
+int glb_kv_quantize_rows(const void *const *src, void *const *dst_codes, float *const *dst_scale, int64_t n_tensors,
+                         int64_t n_src_rows, int64_t n_rows, int64_t kv_heads, int64_t head_dim, int64_t src_cap, int64_t dst_cap,
+                         const int32_t *src_row_of, const int32_t *len_of, int32_t dtype, void *hip_stream);
+
+/*
  * Masked attention of the padded batches of short contexts the path feeds the transformer (hf.py:232-281): for every row u,
  * query head h and query position t, softmax over the keys s it may see of q[u,h,t] . k[u,h/G,s] * scale, times v.  q / k / v
  * by element strides {row, head, position} with unit inner stride (the projections' outputs, cached prefixes in front of
